@@ -62,7 +62,16 @@ def parse_args(argv=None):
                          "fastest (staged2 = the staged pipeline in two parts, the emit pass of one beside the chain of the next)")
     ap.add_argument("--form", choices=["auto", "windowed", "fused"], default="auto",
                     help="tg_ns_homo_batched_ws form: window-ordered gather of the launch, or the fused per-batch kernel")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64): a "
+                         "fixed, seeded sample of its mini-batches (see dump_plan), at most 64 MB in all; rank 0 only, "
+                         "replicated mode only")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and args.mode != "replicated":
+        ap.error("--dump-outputs is implemented for --mode replicated only")
+    return args
 
 
 _RESULT_FD = None
@@ -286,6 +295,8 @@ def main(argv=None):
         mix = w_c = None
         candidates = None
         torch.cuda.empty_cache()
+    # which mini-batches --dump-outputs writes: fixed by the arguments (and G) alone, chosen before anything is timed
+    dump_ids = dump_plan(G, B, out.cap_nodes, out.cap_edges, len(fanout)) if args.dump_outputs and rank == 0 else None
     acc = torch.zeros(3, dtype=torch.int64, device=dev)  # sampled edges, frontier slots, launches
 
     def run(lo, hi, events=None):
@@ -417,6 +428,11 @@ def main(argv=None):
             torch, _cabi, graph, ptrs, indices, out, seeds[(i_last % n_pool) * G:(i_last % n_pool) * G + G], fanout,
             first + i_last * G, sorted({0, G // 2, G - 1}), oracle=(rank == 0))
 
+    if dump_ids is not None:
+        i_last = W + K - 1
+        dump_outputs(args.dump_outputs, out, seeds[(i_last % n_pool) * G:(i_last % n_pool) * G + G], first + i_last * G,
+                     dump_ids, len(fanout))
+
     if rank == 0 and world == 1 and not args.no_secondary:
         del out, ws
         torch.cuda.empty_cache()
@@ -465,6 +481,56 @@ def verify_step(torch, _cabi, graph, ptrs, indices, out, step_seeds, fanout, cal
             entry["equals"].append("oracle philox-mode")
         checked.append(entry)
     return checked
+
+
+DUMP_BUDGET = 64 << 20  # bytes of .npy payload --dump-outputs may write
+DUMP_SEED = 0xD0A7
+
+
+def dump_plan(G, B, cap_nodes, cap_edges, n_hops, budget=DUMP_BUDGET):
+    """-> sorted indices (within a step) of the mini-batches --dump-outputs writes: as many as fit `budget` when every one
+    of them fills its slabs to capacity, drawn by a fixed seed.  Depends on the arguments only, never on what was sampled,
+    so two builds run with the same arguments dump the same batches."""
+    import numpy as np
+    fixed = 8 * 2 * G                                                   # counts of every batch of the step
+    per_batch = 8 * (1 + B + 2 + 3 * n_hops + cap_nodes + 3 * cap_edges)  # call id, seeds, counts, layer offsets, slabs
+    n = min(G, (budget - fixed) // per_batch)
+    if n < 1:
+        raise SystemExit("bench.py: --dump-outputs: not even one mini-batch of this configuration fits %d bytes" % budget)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(G, size=n, replace=False))
+
+
+def dump_outputs(dirpath, out, step_seeds, call0, ids, n_hops):
+    """Writes what one step left in the slabs `out` as float64 .npy files under `dirpath` (ids and edge positions are
+    exact in float64 below 2^53): counts of every batch of the step ([G, 2]: sampled nodes, sampled edges) and, for the
+    batches `ids` (dump_plan), their inputs and the outputs a caller of out.batch() receives, concatenated in `ids` order:
+      batch_ids [n], call_ids [n], seeds [n, B], layer_offsets [n, hops, 3], samples [sum nodes], rows / cols /
+      edge_index [sum edges]   (batch k's part: counts[batch_ids[k]] entries)."""
+    import numpy as np
+    counts = out.counts.cpu()
+    parts = {"samples": [], "rows": [], "cols": [], "edge_index": []}
+    for j in ids:
+        got = out.batch(int(j), counts)
+        for name, t in zip(parts, got[:4]):
+            parts[name].append(t.cpu())
+    arrays = {
+        "counts": counts.numpy(),
+        "batch_ids": np.asarray(ids),
+        "call_ids": np.asarray(ids) + call0,
+        "seeds": step_seeds[list(map(int, ids))].cpu().numpy(),
+        "layer_offsets": out.layer_offsets[list(map(int, ids)), :n_hops].cpu().numpy(),
+    }
+    for name, ts in parts.items():
+        arrays[name] = np.concatenate([t.numpy() for t in ts])
+    arrays = {k: v.astype(np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (> %d)" % (total, DUMP_BUDGET))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), v)
+    sys.stderr.write("bench.py: wrote %d arrays (%d bytes, %d mini-batches of the last timed step) to %s\n"
+                     % (len(arrays), total, len(ids), dirpath))
 
 
 def partitioned_mode(args, torch, dist, _cabi, sharding, dev, world, rank, fanout):
