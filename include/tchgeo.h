@@ -150,7 +150,8 @@ TG_API int tg_ns_homo_workspace_bytes(int64_t n_batches, int64_t n_seeds, const 
                                int64_t *n_bytes);
 /* The same for a given graph: the staged pipeline's stage slots are then sized by the graph's bit widths (vertex ids and
  * tg_graph.max_degree: one 64-byte chunk per frontier vertex where the pairs {neighbour, position} fit, else two); without
- * a graph the larger size is assumed. */
+ * a graph the larger size is assumed, and under tg_ns_win_tuning.staged = 2 (AUTO) the slots are included from 2 048
+ * batches on, so that a launch whose graph has one-chunk slots can take the staged pipeline with it. */
 TG_API int tg_ns_homo_workspace_bytes_for(const tg_graph *csc, int64_t n_batches, int64_t n_seeds, const int64_t *fanout,
                                    int32_t n_hops, int64_t *n_bytes);
 /* The workspace for a launch with THIS sampler / filter configuration: the window-ordered form's for the plain samplers

@@ -79,6 +79,13 @@ extern "C" TG_API int tg_probe_ns_sol(const tg_ns_out *src, const tg_ns_out *dst
                "tg_probe_ns_sol: bad arguments");
     TG_REQUIRE(src->cap_nodes == dst->cap_nodes && src->cap_edges == dst->cap_edges && src->samples != dst->samples,
                "tg_probe_ns_sol: src and dst must be two slab sets of equal pitch");
+    // the probe's 16-byte streams (seeds, the frontier reads, rows / cols / edge_index) take one alignment for all slabs;
+    // the samplers' emit passes align each stream on its own
+    const uintptr_t mis = (uintptr_t)seeds | (uintptr_t)src->samples | (uintptr_t)src->rows | (uintptr_t)src->cols |
+                          (uintptr_t)src->edge_index | (uintptr_t)dst->samples | (uintptr_t)dst->rows | (uintptr_t)dst->cols |
+                          (uintptr_t)dst->edge_index;
+    TG_REQUIRE((mis & 15u) == 0 && ((n_seeds | src->cap_nodes | src->cap_edges) & 1) == 0,
+               "tg_probe_ns_sol: slabs must start on 16-byte boundaries (16-byte aligned bases, even pitches and seed counts)");
     hipLaunchKernelGGL(tg::ns_sol_kernel, dim3((unsigned)n_batches), dim3(256), 0, (hipStream_t)stream, *src, *dst, seeds,
                        n_seeds, n_hops, sink);
     TG_LAUNCH_CHECK();

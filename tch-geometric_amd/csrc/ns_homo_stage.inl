@@ -647,20 +647,23 @@ __device__ __forceinline__ void win_stage_emit_batch(const WinParams &p, const S
                 }
             }
             wave_lds_handoff();
-            // rows / cols / edge_index share the alignment of their addresses (equal pitch, 16-byte aligned bases); samples
-            // (offset by n_seeds, pitch cap_nodes) has its own.  The elements up to the next 64-byte boundary (head: 0 .. 7)
-            // are stored alone, the rest as 16-byte pairs, one stream after the other: every store instruction of the
+            // Each of the four streams takes its head from its own address: tg_ns_out takes four independent 8-byte aligned
+            // pointers, so rows / cols / edge_index need not share an alignment, and samples is offset by n_seeds with pitch
+            // cap_nodes.  A stream's elements up to its next 64-byte boundary (head: 0 .. 7) are stored alone, the rest as
+            // 16-byte pairs, one stream after the other: every store instruction of the
             // wavefront then covers whole aligned 64-byte chunks.  The stores are non-temporal, and a chunk that two
             // instructions share went out to memory as two partial writes: 14 % more write requests than the streams hold
             // chunks (profiles/r04/pmc_traffic_staged_bpl16384.json); aligned: emit pass 3.03 -> 2.93 ms
             // (tg_ns_win_tuning.store_align64, profiles/r04/ab_store_align64.jsonl)
             const uint32_t am = p.store_align;
-            const uint32_t head = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(rows + ea) >> 3) & am)) & am);
             const uint32_t head_s = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(samples + n_seeds + ea) >> 3) & am)) & am);
-            if ((uint32_t)lane < head && (uint32_t)lane < total && !SPLIT) {
-                __builtin_nontemporal_store(n_seeds + ea + (int64_t)lane, &rows[ea + lane]);
-                __builtin_nontemporal_store(i0 + (int64_t)slane[lane], &cols[ea + lane]);
-                __builtin_nontemporal_store((int64_t)sptr[lane], &eidx[ea + lane]);
+            const uint32_t head_r = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(rows + ea) >> 3) & am)) & am);
+            const uint32_t head_c = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(cols + ea) >> 3) & am)) & am);
+            const uint32_t head_e = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(eidx + ea) >> 3) & am)) & am);
+            if ((uint32_t)lane < total && !SPLIT) {
+                if ((uint32_t)lane < head_r) __builtin_nontemporal_store(n_seeds + ea + (int64_t)lane, &rows[ea + lane]);
+                if ((uint32_t)lane < head_c) __builtin_nontemporal_store(i0 + (int64_t)slane[lane], &cols[ea + lane]);
+                if ((uint32_t)lane < head_e) __builtin_nontemporal_store((int64_t)sptr[lane], &eidx[ea + lane]);
             }
             if ((uint32_t)lane < head_s && (uint32_t)lane < total)
                 __builtin_nontemporal_store((int64_t)sval[lane], &samples[n_seeds + ea + lane]);
@@ -673,7 +676,7 @@ __device__ __forceinline__ void win_stage_emit_batch(const WinParams &p, const S
                     __builtin_nontemporal_store((int64_t)sval[q], &samples[n_seeds + e]);
             }
             if (!SPLIT)
-            for (uint32_t q = head + 2u * lane; q < total; q += 128) { // :217
+            for (uint32_t q = head_r + 2u * lane; q < total; q += 128) { // :217
                 const int64_t e = ea + q;
                 if (q + 1 < total) {
                     i64x2 r = {n_seeds + e, n_seeds + e + 1};
@@ -682,7 +685,7 @@ __device__ __forceinline__ void win_stage_emit_batch(const WinParams &p, const S
                     __builtin_nontemporal_store(n_seeds + e, &rows[e]);
             }
             if (!SPLIT)
-            for (uint32_t q = head + 2u * lane; q < total; q += 128) {
+            for (uint32_t q = head_c + 2u * lane; q < total; q += 128) {
                 const int64_t e = ea + q;
                 if (q + 1 < total) {
                     i64x2 cc = {i0 + (int64_t)slane[q], i0 + (int64_t)slane[q + 1]};
@@ -691,7 +694,7 @@ __device__ __forceinline__ void win_stage_emit_batch(const WinParams &p, const S
                     __builtin_nontemporal_store(i0 + (int64_t)slane[q], &cols[e]);
             }
             if (!SPLIT)
-            for (uint32_t q = head + 2u * lane; q < total; q += 128) {
+            for (uint32_t q = head_e + 2u * lane; q < total; q += 128) {
                 const int64_t e = ea + q;
                 if (q + 1 < total) {
                     i64x2 x = {(int64_t)sptr[q], (int64_t)sptr[q + 1]};

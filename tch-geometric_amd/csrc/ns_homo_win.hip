@@ -372,20 +372,22 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                 // the same bytes runs at 6.7 TB/s, this kernel at 4.4: tools/probe_write_bw.py.
                 typedef long long i64x2 __attribute__((ext_vector_type(2)));
                 const int64_t ea = e_chunk;
-                // an element at an address that is not 16-byte aligned is stored alone (rows / cols / edge_index share the
-                // parity: equal pitch, 16-byte aligned bases); taken from the ADDRESS -- with an odd cap_edges the slabs of
-                // odd batches start on an odd element
-                // ... up to the next 64-byte boundary (WinParams.store_align = 7; round 3: 16-byte, = 1): from there every store
-                // instruction covers whole aligned chunks -- a chunk that two non-temporal store instructions share goes out as
-                // two partial writes
+                // the elements of a stream up to its next 64-byte boundary (WinParams.store_align = 7; round 3: 16-byte, = 1)
+                // are stored alone: from there every store instruction covers whole aligned chunks -- a chunk that two
+                // non-temporal store instructions share goes out as two partial writes.  Each stream takes its head from
+                // its own ADDRESS: with an odd cap_edges the slabs of odd batches start on an odd element, and tg_ns_out
+                // takes four independent 8-byte aligned pointers, so rows / cols / edge_index need not share an alignment
                 const uint32_t am = p.store_align;
-                const uint32_t head = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(rows + ea) >> 3) & am)) & am);
-                if ((uint32_t)lane < head && (uint32_t)lane < total) {
-                    __builtin_nontemporal_store(n_seeds + ea + (int64_t)lane, &rows[ea + lane]);
-                    __builtin_nontemporal_store(i0 + (int64_t)slane[lane], &cols[ea + lane]);
-                    __builtin_nontemporal_store(col0[c * 64 + slane[lane]] + (int64_t)spos[lane], &eidx[ea + lane]);
+                const uint32_t head_r = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(rows + ea) >> 3) & am)) & am);
+                const uint32_t head_c = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(cols + ea) >> 3) & am)) & am);
+                const uint32_t head_e = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(eidx + ea) >> 3) & am)) & am);
+                if ((uint32_t)lane < total) {
+                    if ((uint32_t)lane < head_r) __builtin_nontemporal_store(n_seeds + ea + (int64_t)lane, &rows[ea + lane]);
+                    if ((uint32_t)lane < head_c) __builtin_nontemporal_store(i0 + (int64_t)slane[lane], &cols[ea + lane]);
+                    if ((uint32_t)lane < head_e)
+                        __builtin_nontemporal_store(col0[c * 64 + slane[lane]] + (int64_t)spos[lane], &eidx[ea + lane]);
                 }
-                for (uint32_t q = head + 2u * lane; q < total; q += 128) {
+                for (uint32_t q = head_r + 2u * lane; q < total; q += 128) {
                     const int64_t e = ea + q;
                     if (q + 1 < total) {
                         i64x2 r = {n_seeds + e, n_seeds + e + 1};
@@ -393,7 +395,7 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                     } else
                         __builtin_nontemporal_store(n_seeds + e, &rows[e]);
                 }
-                for (uint32_t q = head + 2u * lane; q < total; q += 128) {
+                for (uint32_t q = head_c + 2u * lane; q < total; q += 128) {
                     const int64_t e = ea + q;
                     if (q + 1 < total) {
                         i64x2 cc = {i0 + (int64_t)slane[q], i0 + (int64_t)slane[q + 1]};
@@ -401,7 +403,7 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                     } else
                         __builtin_nontemporal_store(i0 + (int64_t)slane[q], &cols[e]);
                 }
-                for (uint32_t q = head + 2u * lane; q < total; q += 128) {
+                for (uint32_t q = head_e + 2u * lane; q < total; q += 128) {
                     const int64_t e = ea + q;
                     const int l0 = slane[q];
                     if (q + 1 < total) {
@@ -1322,9 +1324,15 @@ extern "C" int tg_ns_homo_workspace_bytes_for(const tg_graph *csc, int64_t n_bat
         TG_REQUIRE(fanout[h] >= 1 && fanout[h] <= 255, "tg_ns_homo_workspace_bytes: fanout[%d] outside [1, 255]", h);
     // the staged pipeline's stage slots (2.9 GB for the 16 384-batch bench launch with one-chunk slots) only when that
     // pipeline would be taken (tg_ns_win_tuning.staged) at the time of the query; a launch whose workspace lacks them takes
-    // the push form
+    // the push form.  Without a graph the slots are sized at two chunks (win_stage_words), which covers every graph, and
+    // under AUTO they are included from WIN_STAGED_AUTO_MIN_BATCHES on: the graph the launch brings decides whether its
+    // slots are one chunk (the staged pipeline) or not (the push one)
     const tg::WinLayout L = tg::win_layout(csc, n_batches, n_seeds, fanout, n_hops);
-    *n_bytes = (int64_t)(tg::win_staged_wanted(tg::win_tuning(), n_batches, L.stage_words) ? L.total : L.total_push);
+    const tg::WinTuning &t = tg::win_tuning();
+    const bool staged = csc ? tg::win_staged_wanted(t, n_batches, L.stage_words)
+                            : (t.staged == 2 ? n_batches >= tg::WIN_STAGED_AUTO_MIN_BATCHES && L.stage_words != 0
+                                             : t.staged != 0);
+    *n_bytes = (int64_t)(staged ? L.total : L.total_push);
     return TG_OK;
 }
 extern "C" int tg_ns_homo_workspace_bytes(int64_t n_batches, int64_t n_seeds, const int64_t *fanout, int32_t n_hops,
@@ -1361,6 +1369,9 @@ int tg_ns_homo_windowed_launch(const tg_graph *csc, const int64_t *seeds, int64_
     TG_REQUIRE(ws && ws_bytes >= (int64_t)L.total_push, "tg_ns_homo_batched_ws: workspace too small (%lld < %lld bytes)",
                (long long)ws_bytes, (long long)L.total_push);
     TG_REQUIRE(((uintptr_t)ws & 255) == 0, "tg_ns_homo_batched_ws: workspace must be 256-byte aligned");
+    // each stream's emit stores find their own 16- / 64-byte boundaries (any 8-byte aligned slab views are fine)
+    TG_REQUIRE((((uintptr_t)out->samples | (uintptr_t)out->rows | (uintptr_t)out->cols | (uintptr_t)out->edge_index) & 7u) == 0,
+               "tg_ns_homo_batched_ws: output slabs must be 8-byte aligned");
     WinParams p;
     p.store_align = win_tuning().store_align64 ? 7u : 1u;
 

@@ -1262,6 +1262,8 @@ extern "C" int tg_part_emit_slots(const tg_ns_out *out, int64_t n_batches, int64
                "tg_part_emit_slots: bad arguments");
     TG_REQUIRE(out->samples && out->rows && out->cols && out->edge_index && out->layer_offsets && out->counts,
                "tg_part_emit_slots: null output slabs");
+    TG_REQUIRE((((uintptr_t)out->samples | (uintptr_t)out->rows | (uintptr_t)out->cols | (uintptr_t)out->edge_index) & 7u) == 0,
+               "tg_part_emit_slots: output slabs must be 8-byte aligned");
     using namespace tg;
     StageBits sb;
     int W = 0;

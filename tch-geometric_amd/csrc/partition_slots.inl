@@ -243,14 +243,18 @@ __global__ void __launch_bounds__(64 * PART_SLOT_EMIT_WAVES) part_slot_emit_kern
             if (u < wave) ea += wave_tot[u];
             round_total += wave_tot[u];
         }
-        // the four streams; the elements up to the next 64-byte boundary are stored alone, the rest as 16-byte pairs: every
-        // store instruction of the wavefront then covers whole aligned 64-byte chunks (ns_homo_stage.inl's emit pass)
-        const uint32_t head = (uint32_t)((8u - (uint32_t)(((uintptr_t)(rows + ea) >> 3) & 7u)) & 7u);
+        // the four streams; a stream's elements up to its next 64-byte boundary are stored alone, the rest as 16-byte pairs:
+        // every store instruction of the wavefront then covers whole aligned 64-byte chunks (ns_homo_stage.inl's emit pass).
+        // Each stream's head comes from its own address: the four slabs of a tg_ns_out need not share an alignment
         const uint32_t head_s = (uint32_t)((8u - (uint32_t)(((uintptr_t)(samples + n_seeds + ea) >> 3) & 7u)) & 7u);
-        if ((uint32_t)lane < head && (uint32_t)lane < total) {
-            __builtin_nontemporal_store(n_seeds + ea + (int64_t)lane, &rows[ea + lane]);                       // :217
-            __builtin_nontemporal_store(i0 + (int64_t)slane[lane], &cols[ea + lane]);
-            __builtin_nontemporal_store(ebase[slane[lane]] + (int64_t)sptr[lane], &eidx[ea + lane]);
+        const uint32_t head_r = (uint32_t)((8u - (uint32_t)(((uintptr_t)(rows + ea) >> 3) & 7u)) & 7u);
+        const uint32_t head_c = (uint32_t)((8u - (uint32_t)(((uintptr_t)(cols + ea) >> 3) & 7u)) & 7u);
+        const uint32_t head_e = (uint32_t)((8u - (uint32_t)(((uintptr_t)(eidx + ea) >> 3) & 7u)) & 7u);
+        if ((uint32_t)lane < total) {
+            if ((uint32_t)lane < head_r) __builtin_nontemporal_store(n_seeds + ea + (int64_t)lane, &rows[ea + lane]); // :217
+            if ((uint32_t)lane < head_c) __builtin_nontemporal_store(i0 + (int64_t)slane[lane], &cols[ea + lane]);
+            if ((uint32_t)lane < head_e)
+                __builtin_nontemporal_store(ebase[slane[lane]] + (int64_t)sptr[lane], &eidx[ea + lane]);
         }
         if ((uint32_t)lane < head_s && (uint32_t)lane < total)
             samples[n_seeds + ea + lane] = (int64_t)sval[lane];                                               // :215 (the next hop's frontier)
@@ -262,7 +266,7 @@ __global__ void __launch_bounds__(64 * PART_SLOT_EMIT_WAVES) part_slot_emit_kern
             } else
                 samples[n_seeds + e] = (int64_t)sval[q];
         }
-        for (uint32_t q = head + 2u * lane; q < total; q += 128) {
+        for (uint32_t q = head_r + 2u * lane; q < total; q += 128) {
             const int64_t e = ea + q;
             if (q + 1 < total) {
                 i64x2 r = {n_seeds + e, n_seeds + e + 1};
@@ -270,7 +274,7 @@ __global__ void __launch_bounds__(64 * PART_SLOT_EMIT_WAVES) part_slot_emit_kern
             } else
                 __builtin_nontemporal_store(n_seeds + e, &rows[e]);
         }
-        for (uint32_t q = head + 2u * lane; q < total; q += 128) {
+        for (uint32_t q = head_c + 2u * lane; q < total; q += 128) {
             const int64_t e = ea + q;
             if (q + 1 < total) {
                 i64x2 cc = {i0 + (int64_t)slane[q], i0 + (int64_t)slane[q + 1]};
@@ -278,7 +282,7 @@ __global__ void __launch_bounds__(64 * PART_SLOT_EMIT_WAVES) part_slot_emit_kern
             } else
                 __builtin_nontemporal_store(i0 + (int64_t)slane[q], &cols[e]);
         }
-        for (uint32_t q = head + 2u * lane; q < total; q += 128) {
+        for (uint32_t q = head_e + 2u * lane; q < total; q += 128) {
             const int64_t e = ea + q;
             if (q + 1 < total) {
                 i64x2 x = {ebase[slane[q]] + (int64_t)sptr[q], ebase[slane[q + 1]] + (int64_t)sptr[q + 1]};

@@ -128,23 +128,28 @@ class NeighborLoader:
     """One launch samples `prefetch` mini-batches; while the caller consumes super-batch i, super-batch i + 1 is already
     being sampled on a side stream into the other of two slab sets (its sizes travel to pinned host memory behind the
     kernel), so neither the launch nor its one read-back sits on the consumer's path.  Launches of >= 2 048 mini-batches
-    take the window-ordered form (workspace kept by the loader)."""
+    get the window-ordered form's workspace (kept by the loader, sized for this graph's stage slots); `form` is
+    ns_homo_batched's: 0 takes that form by launch and graph size, 1 whenever the launch qualifies, 2 never."""
 
     def __init__(self, data, num_neighbors: List[int], input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
                  prefetch: int = 16, replace: bool = False, shuffle: bool = False, drop_last: bool = False,
-                 seed: int = 0, call_id0: int = 0, device="cuda"):
+                 seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0):
         self.data, self.fanout = data, [int(k) for k in num_neighbors]
         self.device = torch.device(device)
         self.batch_size, self.prefetch = int(batch_size), max(1, int(prefetch))
         self.sampler = _cabi.SAMPLER_UNIFORM_REPL if replace else _cabi.SAMPLER_UNIFORM
         self.shuffle, self.drop_last, self.seed, self.call_id0 = shuffle, drop_last, int(seed), int(call_id0)
+        self.form = int(form)               # of many-batch launches (ns_homo_batched's `form`): 0 = by launch size
         self.n_nodes = _num_nodes(data)
         self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
         # u32 shadows halve the bytes per gathered line (DESIGN.md 4.1); ids and offsets fit below 2^31 here
         small = self.n_nodes < 2 ** 31 and self.row_indices.numel() < 2 ** 31
         self._idx32 = self.row_indices.to(torch.int32) if small else None
         self._ptr32 = self.col_ptrs.to(torch.int32) if small else None
-        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, indices32=self._idx32, ptrs32=self._ptr32)
+        # the longest column (one read-back) sets the stage slots' bit widths: without it they assume n_edges, and the
+        # slots of a large graph come out two chunks wide, which the staged pipeline of many-batch launches refuses
+        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, indices32=self._idx32, ptrs32=self._ptr32,
+                                       max_degree="auto")
         nodes = torch.arange(self.n_nodes, device=self.device) if input_nodes is None else input_nodes.to(self.device)
         self.input_nodes = _checked_inputs(nodes, self.n_nodes)
         self._n_edges = int(data.edge_index.shape[1])
@@ -179,7 +184,8 @@ class NeighborLoader:
                     "free": None}
             slabs[which] = slab
         if G >= 2048 and self._ws is None:   # many batches per launch: the window-ordered form pays
-            self._ws = _cabi.ns_homo_workspace(max(G, min(self.prefetch, len(self))), B, self.fanout, self.device)
+            self._ws = _cabi.ns_homo_workspace(max(G, min(self.prefetch, len(self))), B, self.fanout, self.device,
+                                               graph=self._graph)
         cur = torch.cuda.current_stream(self.device)
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
@@ -191,7 +197,7 @@ class NeighborLoader:
             seeds = seeds.contiguous()
             out = slab["out"]
             _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
-                                  sampler=self.sampler, ws=self._ws if G >= 2048 else None)
+                                  sampler=self.sampler, ws=self._ws if G >= 2048 else None, form=self.form)
             slab["counts"][:G].copy_(out.counts[:G], non_blocking=True)
             slab["lo"][:G].copy_(out.layer_offsets[:G], non_blocking=True)
             done = torch.cuda.Event()

@@ -7,11 +7,12 @@ import torch
 
 
 def emulated_world_sample(cabi, shards, seeds, fan, seed, first_call, sampler=0, filter_mode=-1, forward=False,
-                          window=(0, 0), seeds_state=None, packed=False, slots=False):
+                          window=(0, 0), seeds_state=None, packed=False, slots=False, out=None):
     """-> (NsBatchedOut filled through tg_part_begin / requests / [count + sample | unpack + flat hop + pack] / emit,
     requests that left shard 0).  Filters / weights take the general owner path.  packed: one-word reply entries
     (TG_PART_REPLY_PACKED / _PACKED_STATE) instead of pairs / triples.  slots: the fixed-size slot replies
-    (tg_part_sample_slots / tg_part_emit_slots; unweighted, unfiltered sampling only)."""
+    (tg_part_sample_slots / tg_part_emit_slots; unweighted, unfiltered sampling only).  out: the NsBatchedOut-shaped
+    slabs to fill (default: a fresh NsBatchedOut)."""
     filtered = filter_mode != -1
     general = filtered or sampler == 2
     fmt = (4 if packed else 3) if filtered else (1 if packed else 2)     # tchgeo.h TG_PART_REPLY_*
@@ -20,7 +21,8 @@ def emulated_world_sample(cabi, shards, seeds, fan, seed, first_call, sampler=0,
     dev, world = seeds.device, len(shards)
     nb, B = seeds.shape
     H = len(fan)
-    out = cabi.NsBatchedOut(nb, B, fan, dev, with_states=filtered)
+    if out is None:
+        out = cabi.NsBatchedOut(nb, B, fan, dev, with_states=filtered)
     so, stream = out.struct(), cabi.stream_ptr(dev)
     hop_cap, cap = [], nb * B
     for k in fan:

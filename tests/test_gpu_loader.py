@@ -164,3 +164,55 @@ def test_two_live_iterators_and_an_abandoned_epoch():
     big = {id(s["out"]) for slabs in loader._pool for k, s in slabs.items() if k != "ragged"}
     rag = [s["out"] for slabs in loader._pool for k, s in slabs.items() if k == "ragged"]
     assert len(loader._pool) == 2 and len(big) <= 4 and all(r.n_batches == 1 and r.n_seeds == 500 - 7 * 64 for r in rag)
+
+
+def test_many_batch_launches_take_the_staged_pipeline(monkeypatch):
+    """A loader launch of 2 048 mini-batches runs the staged pipeline of the window-ordered form (the kernels the bench
+    figure measures): the loader's graph view carries the longest column, and its workspace is sized for that graph's
+    stage slots.  Without either, the slots of the graph come out two chunks wide or the workspace lacks them, and the
+    launch quietly takes the push pipeline.  The launch of the remaining 100 mini-batches takes neither workspace nor
+    staged pipeline.  Every checked mini-batch equals the oracle's for its (seed, call id)."""
+    from tch_geometric import _cabi
+    from tch_geometric.loader import NeighborLoader
+    from tch_geometric.transforms import Graph
+    scale, fan, B, G = 15, [15, 10], 8, 2048
+    n = 1 << scale
+    row, col = _cabi.rmat_edges(scale, n * 16, 0x10AD15, DEV)
+    ei = torch.stack([row, col]).cpu().numpy()
+    rs = np.random.default_rng(15)
+    x = rs.standard_normal((n, 4)).astype(np.float32)
+    ea = rs.standard_normal((ei.shape[1], 2)).astype(np.float32)
+    g = Graph(edge_index=torch.from_numpy(ei).to(DEV), num_nodes=n, x=torch.from_numpy(x).to(DEV),
+              edge_attr=torch.from_numpy(ea).to(DEV))
+    nodes = torch.from_numpy(rs.integers(0, n, B * 2148 + 3))
+    launches = []
+    real = _cabi.ns_homo_batched
+
+    def spy(graph, seeds, fanout, seed, call_id0, out, ws=None, form=0, **kw):
+        Gs, Bs = seeds.shape
+        launches.append((Gs, Bs, ws is not None,
+                         _cabi.ns_homo_batched_staged(graph, out, Gs, Bs, fanout, ws=ws, form=form)))
+        return real(graph, seeds, fanout, seed, call_id0, out, ws=ws, form=form, **kw)
+
+    monkeypatch.setattr(_cabi, "ns_homo_batched", spy)
+    loader = NeighborLoader(g, fan, input_nodes=nodes, batch_size=B, prefetch=G, seed=5, call_id0=70, form=1)
+    assert len(loader) == 2149
+    assert loader._graph.max_degree > 0                       # the view knows its longest column
+    ptrs, idx, perm = orc.to_csc(ei, n)
+    nodes = nodes.numpy()
+    check = {0, 1, 1000, G - 1, G, G + 50, 2147, 2148}
+    seen = 0
+    for j, b in enumerate(loader):
+        seen += 1
+        if j not in check:
+            continue
+        seeds = nodes[j * B:(j + 1) * B]
+        o = orc.ns_homo(ptrs, idx, seeds, fan, orc.rng_philox(5, 70 + j))
+        s = b.n_id.cpu().numpy()
+        assert b.call_id == 70 + j and b.batch_size == len(seeds)
+        assert np.array_equal(s, o[0]) and np.array_equal(b.edge_index.cpu().numpy(), np.stack([o[1], o[2]]))
+        assert np.array_equal(b.e_id.cpu().numpy(), perm[o[3]]) and b.layer_offsets == o[4]
+        assert np.array_equal(b.x.cpu().numpy(), x[s]) and np.array_equal(b.edge_attr.cpu().numpy(), ea[perm[o[3]]])
+    assert seen == 2149
+    assert [(Gs, Bs, w) for Gs, Bs, w, _ in launches] == [(G, B, True), (100, B, False), (1, 3, False)]
+    assert [st for *_, st in launches] == [True, False, False], "the 2 048-batch launch must take the staged pipeline"

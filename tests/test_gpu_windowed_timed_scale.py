@@ -384,3 +384,73 @@ def test_pipeline_is_chosen_by_launch_size_by_default(cabi):
         torch.cuda.synchronize()
         assert_equal_on_device(a, b)
         del a, b, ws, push_only
+
+
+def _coarse_of_window(w, n_buckets_geom):
+    """the staged sort's coarse bucket of window w (win_stage_key: window buckets are XCD-major, 8 per coarse bucket)"""
+    wq = ((n_buckets_geom + 63) & ~63) >> 3
+    return ((w & 7) * wq + (w >> 3)) >> 3, wq
+
+
+@pytest.mark.parametrize("where", ["last", "first"])
+def test_second_sort_level_reads_tables_loaded_by_other_threads(cabi, where):
+    """Guard for the second sort level's table loads (win_sort_fine_kernel; the race of 222e7db, fixed in bafeb01).
+
+    The kernel loads the vertex table (n_windows + 1 entries) and the coarse bucket starts into LDS with a 1 024-thread
+    stride loop, then looks up the first tile's coarse bucket and that bucket's window splitters.  This case makes those
+    look-ups depend on entries that OTHER threads loaded, in later rounds of the loop:
+    - 2^17 vertices, 8 in-edges each, u32 shadows, window_bytes = 1 KiB: 4 097 windows (>= 3 x 1 024, asserted from the
+      form query), so the vertex table takes five rounds of the loop;
+    - `last`: every column's neighbours lie in the last non-empty window's vertex range, so every hop-1 item falls in
+      one coarse bucket far from 0 (518 of 520), and tile 0's splitters are vertex-table entries >= 2 048 (asserted);
+    - 12 batches x 1 024 seeds, all 8 neighbours taken: 8 192 hop-1 items per batch, >= 4 tiles of 8 192 per part
+      (asserted from the outputs: counts, and every hop-1 vertex lies in the chosen range).
+    Staged pipeline, fine sub-bits 4 and 7, 1 and 3 parts; compared word for word with the fused kernel and replayed on
+    the oracle.  `first` is the mirror (every item in window 0, coarse bucket 0, the tables' first entries): the easy
+    direction, so that the construction and not luck decides."""
+    dev = torch.device(DEV)
+    n, deg, span = 1 << 17, 8, 32
+    lo_v = n - span if where == "last" else 0
+    gen = torch.Generator(device=dev).manual_seed(17)
+    col = torch.arange(n, device=dev).repeat_interleave(deg)
+    row = lo_v + torch.randint(0, span, (n * deg,), device=dev, generator=gen)
+    ptrs, idx, _ = cabi.coo_to_csx(row, col, n, n, True)
+    del row, col
+    g = cabi.graph_view(ptrs, idx, indices32=idx.to(torch.int32), ptrs32=ptrs.to(torch.int32), max_degree="auto")
+    # windows of 256 edges (1 KiB of u32 indices): the chosen span is exactly one window's vertex range
+    shift, E = 8, n * deg
+    w = (lo_v * deg) >> shift
+    assert w == ((lo_v + span) * deg - 1) >> shift and (w == 0 or ((lo_v * deg) & ((1 << shift) - 1)) == 0)
+    nb, B, fan = 12, 1024, [15, 10]
+    seeds = torch.randint(0, n, (nb, B), device=dev, generator=gen)
+    before = cabi.ns_win_tuning_set(staged=1, stage_fine=1, window_bytes=1 << 10, stage_part_min_batches=4)
+    try:
+        b = _poisoned(cabi, nb, B, fan)
+        cabi.ns_homo_batched(g, seeds, fan, 4, 800, b, form=FUSED)
+        torch.cuda.synchronize()
+        # every seed takes all 8 neighbours, every hop-1 vertex all 8 of its own: the frontier sizes are exact
+        assert bool((b.counts[:, 0] == B * (1 + deg + deg * deg)).all()) and bool((b.counts[:, 1] == B * deg * (1 + deg)).all())
+        hop1 = b.samples[:, B:B + B * deg]
+        assert bool(((hop1 >= lo_v) & (hop1 < lo_v + span)).all()), "a hop-1 vertex outside the chosen window"
+        assert nb // 3 * B * deg >= 4 * 8192                     # every part's hop-1 frontier spans >= 4 fine tiles
+        for parts in (1, 3):
+            for sub in (4, 7):
+                cabi.ns_win_tuning_set(stage_parts=parts, stage_fine_sub_bits=sub)
+                a = _poisoned(cabi, nb, B, fan)
+                ws = cabi.ns_homo_workspace(nb, B, fan, dev, staged=True, graph=g)
+                taken, n_win = cabi.ns_homo_batched_form(g, a, nb, B, fan, ws=ws, form=WINDOWED)
+                assert taken == WINDOWED and n_win >= 3 * 1024 and n_win == ((E >> shift) + 1 + 7) & ~7
+                assert cabi.ns_homo_batched_staged(g, a, nb, B, fan, ws=ws, form=WINDOWED)
+                c0, wq = _coarse_of_window(w, n_win)
+                lo0 = ((c0 * 8) % wq) * 8 + (c0 * 8) // wq              # tile 0's first splitter window
+                if where == "last":
+                    assert c0 >= 512 and lo0 >= 2048
+                else:
+                    assert c0 == 0 and lo0 == 0
+                cabi.ns_homo_batched(g, seeds, fan, 4, 800, a, ws=ws, form=WINDOWED)
+                torch.cuda.synchronize()
+                assert_equal_on_device(a, b)
+                assert_oracle(cabi, a, ptrs, idx, seeds, fan, 4, 800, (0, nb - 1))
+                del a, ws
+    finally:
+        cabi.ns_win_tuning_set(**before)
