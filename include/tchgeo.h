@@ -604,6 +604,38 @@ TG_API int tg_hgt_workspace_bytes(const tg_hgt_problem *problem, int64_t *bytes)
 TG_API int tg_hgt_sample(const tg_hgt_problem *problem, const tg_rng *rng, const tg_hgt_out *out, void *workspace,
                          int64_t workspace_bytes, void *stream);
 
+/* Batched hgt_sampling: n_calls independent calls of one problem shape in ONE launch chain (the call is the third grid
+ * dimension of every launch, so the chain is as long as a single call's).  The calls share the graphs, n_inputs,
+ * num_samples and the time range; problem->inputs[t] / input_ts[t] point at [n_calls, n_inputs[t]] row-major slabs.
+ * Call b draws with call id rng->call_id + b and equals tg_hgt_sample run alone with that call id, word for word.
+ *  - outputs: row b of every slab is call b's; only its first counts[b][...] words are written.  counts[b] holds the
+ *    node counts of the types, then the edge counts of the relations, then call b's panic flag (1 where the reference
+ *    would panic; the other calls are unaffected).
+ *  - workspace: n_calls regions at a fixed stride, nothing shared: tg_hgt_batched_workspace_bytes(p, n) =
+ *    n * tg_hgt_batched_workspace_bytes(p, 1); 8-byte aligned.  1 <= n_calls <= TG_HGT_MAX_CALLS (grid z).
+ *  - scan limit: every scan runs in one workgroup per call, so shapes past the single call's one-workgroup limit
+ *    (TG_HGT_ONE_WORKGROUP_SCAN chunks of 64 contributions in a layer or of 64 budget entries, or
+ *    TG_HGT_ONE_WORKGROUP_SCAN nodes in a type that a relation points into) are refused with TG_ERR_INVALID by all
+ *    three functions below; tg_hgt_sample takes such shapes one call at a time. */
+#define TG_HGT_MAX_CALLS 65535
+#define TG_HGT_ONE_WORKGROUP_SCAN 16384
+typedef struct {
+    int64_t *const *samples;    /* host [n_types] device slabs [n_calls, cap_nodes[t]] */
+    int64_t *const *sample_ts;  /* host [n_types], same shape */
+    const int64_t *cap_nodes;   /* host [n_types] row pitches, >= tg_hgt_batched_capacity()'s cap_nodes */
+    int64_t *const *rows;       /* host [n_rels] device slabs [n_calls, cap_edges[r]] */
+    int64_t *const *cols;       /* host [n_rels] */
+    int64_t *const *edge_index; /* host [n_rels] */
+    const int64_t *cap_edges;   /* host [n_rels] row pitches, >= tg_hgt_batched_capacity()'s cap_edges */
+    int64_t *counts;            /* device [n_calls, n_types + n_rels + 1] */
+} tg_hgt_batched_out;
+
+/* per call: cap_nodes[t] = max(n_inputs[t], 0) + the type's num_samples; cap_edges[r] = 50 * max(cap_nodes[dst], 1) */
+TG_API int tg_hgt_batched_capacity(const tg_hgt_problem *problem, int64_t *cap_nodes, int64_t *cap_edges);
+TG_API int tg_hgt_batched_workspace_bytes(const tg_hgt_problem *problem, int64_t n_calls, int64_t *bytes);
+TG_API int tg_hgt_sample_batched(const tg_hgt_problem *problem, int64_t n_calls, const tg_rng *rng,
+                                 const tg_hgt_batched_out *out, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* budget_sampling (src/algo/budget_sampling.rs:63-265; binding python.rs:486-581), one (layer, node type) at a
  * time: Budget::update + Budget::sample for every frontier node of the type (SURVEY.md 8(f) "next" row).  The host
  * appends the selected candidates in (node, slot) order.  Selected slot (j, s) lives at [j * fanout + s];

@@ -59,7 +59,28 @@ struct HgtType {
     double *bscore;
     int64_t *bm_keys, *bm_vals, bm_mask;
     HgtTypeCtr *ctr;
+    int64_t pitch; // words between two calls' rows of nodes / ts (batched form; a single call has one row)
 };
+
+// ---------------------------------------------------------------- the call dimension (tg_hgt_sample_batched)
+// A batched launch runs the calls side by side, call b = blockIdx.z.  Every array a call owns lies in its region of
+// the workspace, `ws_stride` bytes behind the previous call's; output rows lie a pitch apart; the graphs are shared.
+// A single call is the case blockIdx.z = 0: every pointer below is the one the host passed.
+__device__ __forceinline__ int64_t hgt_call_ws(int64_t ws_stride) { return (int64_t)blockIdx.z * ws_stride; }
+template <class P> __device__ __forceinline__ P *hgt_ws(P *p, int64_t off) {
+    return reinterpret_cast<P *>(reinterpret_cast<uintptr_t>(p) + (uintptr_t)off);
+}
+template <class P> __device__ __forceinline__ P *hgt_row(P *p, int64_t pitch) { return p ? p + (int64_t)blockIdx.z * pitch : p; }
+__device__ __forceinline__ HgtType hgt_type_at(HgtType y, int64_t off) {
+    y.nodes = hgt_row(y.nodes, y.pitch);
+    y.ts = hgt_row(y.ts, y.pitch);
+    y.tl_keys = hgt_ws(y.tl_keys, off), y.tl_vals = hgt_ws(y.tl_vals, off);
+    y.bkey = hgt_ws(y.bkey, off), y.bts = hgt_ws(y.bts, off), y.balive = hgt_ws(y.balive, off);
+    y.bscore = hgt_ws(y.bscore, off);
+    y.bm_keys = hgt_ws(y.bm_keys, off), y.bm_vals = hgt_ws(y.bm_vals, off);
+    y.ctr = hgt_ws(y.ctr, off);
+    return y;
+}
 
 // ---------------------------------------------------------------- small scans and fills
 // total of a flag array after its exclusive scan
@@ -83,8 +104,10 @@ __global__ void scan_total_kernel(const int64_t *__restrict__ in, const int64_t 
 }
 
 // ---------------------------------------------------------------- inputs (hgt_sampling.rs:167-180)
-__global__ void hgt_init_inputs_kernel(HgtType ty, const int64_t *__restrict__ inputs,
-                                       const int64_t *__restrict__ input_ts, int64_t n) {
+__global__ void hgt_init_inputs_kernel(HgtType ty_, const int64_t *__restrict__ inputs,
+                                       const int64_t *__restrict__ input_ts, int64_t n, int64_t ws_stride) {
+    const HgtType ty = hgt_type_at(ty_, hgt_call_ws(ws_stride));
+    inputs = hgt_row(inputs, n), input_ts = hgt_row(input_ts, n); // [n_calls, n] slabs
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t v = inputs[i];
         ty.nodes[i] = v;
@@ -343,11 +366,13 @@ __device__ __forceinline__ uint32_t *hgt_wave_radix_sort(uint32_t *a, uint32_t *
 constexpr int HGT_ACC_THREADS = 256;
 constexpr uint32_t HGT_RUN_LDS = 1024;
 constexpr int HGT_ACC_LONG_BLOCKS = 128; // workgroups at the end of accumulate's grid that take the long buckets
+constexpr int HGT_ACC_LONG_BLOCKS_BATCHED = 8; // per call of a batched launch (any number of them gives the same sums)
 __device__ __forceinline__ void hgt_accumulate_body(const HgtType &src, const uint32_t *__restrict__ bcnt,
                                                     const uint32_t *__restrict__ bwithin, const int64_t *__restrict__ trank,
                                                     uint32_t *bucket, uint32_t *bucket2, int64_t cap, int pbits,
                                                     const double *__restrict__ cinv, const int64_t *__restrict__ cts,
-                                                    const uint32_t *__restrict__ long_list, const int64_t *n_long) {
+                                                    const uint32_t *__restrict__ long_list, const int64_t *n_long,
+                                                    int long_blocks) {
     __shared__ uint32_t hist_s[HGT_ACC_THREADS / 64][256];
     __shared__ uint32_t perm_s[HGT_ACC_THREADS / 64][64];
     __shared__ double sum_s[HGT_ACC_THREADS / 64][64];
@@ -357,9 +382,9 @@ __device__ __forceinline__ void hgt_accumulate_body(const HgtType &src, const ui
     double *sbuf = sum_s[wave];
     const int64_t nbud = src.ctr->n_budget;
     const int64_t n_chunks = (min(cap, nbud) + 63) >> 6;
-    const int64_t short_blocks = (int64_t)gridDim.x - HGT_ACC_LONG_BLOCKS;
+    const int64_t short_blocks = (int64_t)gridDim.x - long_blocks;
     if ((int64_t)blockIdx.x >= short_blocks) { // the long buckets, one wavefront each
-        const int64_t n_l = *n_long, stride = (int64_t)HGT_ACC_LONG_BLOCKS * (HGT_ACC_THREADS / 64);
+        const int64_t n_l = *n_long, stride = (int64_t)long_blocks * (HGT_ACC_THREADS / 64);
         for (int64_t i = ((int64_t)blockIdx.x - short_blocks) * (HGT_ACC_THREADS / 64) + wave; i < n_l; i += stride) {
             const int64_t e2 = long_list[i];
             const uint32_t L2 = bcnt[e2];
@@ -472,16 +497,31 @@ struct HgtStep {
 };
 struct HgtSteps {
     HgtStep s[HGT_MAX_PAR];
-    int pbits; // bits of a contribution position
+    int pbits;         // bits of a contribution position
+    int long_blocks;   // workgroups at the end of accumulate's grid that take the long buckets
+    int64_t ws_stride; // bytes between two calls' workspace regions
 };
+__device__ __forceinline__ HgtStep hgt_step_at(const HgtSteps &S) {
+    HgtStep a = S.s[blockIdx.y];
+    const int64_t off = hgt_call_ws(S.ws_stride);
+    a.dst = hgt_type_at(a.dst, off), a.src = hgt_type_at(a.src, off), a.src_ctr = hgt_ws(a.src_ctr, off);
+    a.ccnt = hgt_ws(a.ccnt, off), a.coff = hgt_ws(a.coff, off), a.ckey = hgt_ws(a.ckey, off), a.cts = hgt_ws(a.cts, off);
+    a.cslot = hgt_ws(a.cslot, off), a.tmp_keys = hgt_ws(a.tmp_keys, off), a.tmp_vals = hgt_ws(a.tmp_vals, off);
+    a.flag = hgt_ws(a.flag, off), a.rank = hgt_ws(a.rank, off), a.scal = hgt_ws(a.scal, off);
+    a.tflag = hgt_ws(a.tflag, off), a.trank = hgt_ws(a.trank, off);
+    a.bcnt = hgt_ws(a.bcnt, off), a.bwithin = hgt_ws(a.bwithin, off), a.bcur = hgt_ws(a.bcur, off);
+    a.bucket = hgt_ws(a.bucket, off), a.bucket2 = hgt_ws(a.bucket2, off), a.bucket3 = hgt_ws(a.bucket3, off);
+    a.cinv = hgt_ws(a.cinv, off), a.cmask = hgt_ws(a.cmask, off);
+    return a;
+}
 __global__ void __launch_bounds__(SCAN1_THREADS) hgt_count_scan_steps_kernel(const HgtSteps S, int64_t cap) {
-    const HgtStep &a = S.s[blockIdx.y];
+    const HgtStep a = hgt_step_at(S);
     hgt_contrib_count_scan_body(a.dst, a.src_ctr, a.ptrs, a.ccnt, a.coff, cap, a.scal + 0);
 }
 // contributions; also the empty min-position map of the step's new keys and the zeroed bucket counters
 __global__ void hgt_gen_steps_kernel(const HgtSteps S, int has_timerange, int64_t tr_lo, int64_t tr_hi, int64_t cap,
                                      int64_t tmp_cap) {
-    const HgtStep &a = S.s[blockIdx.y];
+    const HgtStep a = hgt_step_at(S);
     fill2_i64_body(a.tmp_keys, tmp_cap, MAP_EMPTY, a.tmp_vals, tmp_cap, (int64_t)INT64_MAX);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.pad; i += (int64_t)gridDim.x * blockDim.x) {
         a.bcnt[i] = 0;
@@ -492,37 +532,37 @@ __global__ void hgt_gen_steps_kernel(const HgtSteps S, int has_timerange, int64_
                          a.cinv, a.cts);
 }
 __global__ void hgt_slots_steps_kernel(const HgtSteps S, int64_t tmp_mask) {
-    const HgtStep &a = S.s[blockIdx.y];
+    const HgtStep a = hgt_step_at(S);
     hgt_contrib_slots_body(a.src, a.scal + 0, a.ckey, a.cslot, a.tmp_keys, a.tmp_vals, tmp_mask);
 }
 __global__ void hgt_first_flags_steps_kernel(const HgtSteps S, int64_t tmp_mask, int64_t cap) {
-    const HgtStep &a = S.s[blockIdx.y];
+    const HgtStep a = hgt_step_at(S);
     hgt_first_flags_body(a.scal + 0, a.ckey, a.cslot, a.tmp_keys, a.tmp_vals, tmp_mask, cap, a.flag, a.cmask);
 }
 __global__ void __launch_bounds__(SCAN1_THREADS) hgt_scan1_steps_kernel(const HgtSteps S, int64_t n) {
-    const HgtStep &a = S.s[blockIdx.y];
+    const HgtStep a = hgt_step_at(S);
     hgt_scan1_body(a.flag, n, a.rank, a.scal + 1);
 }
 __global__ void hgt_new_slots_steps_kernel(const HgtSteps S, int64_t tmp_mask) {
-    const HgtStep &a = S.s[blockIdx.y];
+    const HgtStep a = hgt_step_at(S);
     hgt_new_slots_body(a.src, a.scal + 0, a.ckey, a.cslot, a.tmp_keys, a.tmp_vals, tmp_mask, a.rank, a.cmask, a.bcnt);
 }
 __global__ void hgt_bucket_offsets_steps_kernel(const HgtSteps S) {
-    const HgtStep &a = S.s[blockIdx.y];
+    const HgtStep a = hgt_step_at(S);
     hgt_bucket_offsets_body(a.src, a.bcnt, a.pad, a.bwithin, a.tflag, a.scal + 1, a.bucket2, a.scal + 3);
 }
 __global__ void __launch_bounds__(SCAN1_THREADS) hgt_bucket_scan_steps_kernel(const HgtSteps S) {
-    const HgtStep &a = S.s[blockIdx.y];
+    const HgtStep a = hgt_step_at(S);
     hgt_scan1_body(a.tflag, (a.pad + 63) >> 6, a.trank, a.scal + 2);
 }
 __global__ void hgt_bucket_scatter_steps_kernel(const HgtSteps S) {
-    const HgtStep &a = S.s[blockIdx.y];
+    const HgtStep a = hgt_step_at(S);
     hgt_bucket_scatter_body(a.scal + 0, a.cslot, a.trank, a.bwithin, a.bcur, a.bucket);
 }
 __global__ void __launch_bounds__(HGT_ACC_THREADS) hgt_accumulate_steps_kernel(const HgtSteps S) {
-    const HgtStep &a = S.s[blockIdx.y];
+    const HgtStep a = hgt_step_at(S);
     hgt_accumulate_body(a.src, a.bcnt, a.bwithin, a.trank, a.bucket, a.bucket3, a.pad, S.pbits, a.cinv, a.cts, a.bucket2,
-                        a.scal + 3);
+                        a.scal + 3, S.long_blocks);
 }
 
 // ---------------------------------------------------------------- sample_from (hgt_sampling.rs:104-135)
@@ -745,19 +785,26 @@ struct HgtSampleArgs {
     int64_t k[HGT_MULTI_TYPES];
     uint32_t *slots[HGT_MULTI_TYPES];
     double *carries[HGT_MULTI_TYPES], *wlive[HGT_MULTI_TYPES];
+    int64_t ws_stride;
 };
+// call b of a batched launch (blockIdx.z) draws with call id call_id + b
 __global__ void __launch_bounds__(SCAN1_THREADS)
     hgt_sample_layer_kernel(const HgtSampleArgs a, uint64_t seed, uint64_t call_id, int64_t layer, int first_type, int n_types,
                             int *panic) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int t = blockIdx.x;
+    const int64_t off = hgt_call_ws(a.ws_stride);
+    const HgtType ty = hgt_type_at(a.ty[t], off);
+    int64_t *const n_live = hgt_ws(a.n_live[t], off), *const live = hgt_ws(a.live[t], off);
+    int64_t *const chosen = hgt_ws(a.chosen[t], off), *const n_chosen = hgt_ws(a.n_chosen[t], off);
+    double *const wlive = hgt_ws(a.wlive[t], off);
     HGT_STAMP(0);
-    hgt_live_list_body(a.ty[t], a.live[t], a.wlive[t], a.n_live[t]);
-    hgt_reservoir_body(a.ty[t], a.n_live[t], a.live[t], a.k[t], seed, call_id, (uint64_t)(layer * n_types + first_type + t),
-                       a.chosen[t], a.n_chosen[t], panic, smem, a.carries[t], a.slots[t], a.wlive[t]);
+    hgt_live_list_body(ty, live, wlive, n_live);
+    hgt_reservoir_body(ty, n_live, live, a.k[t], seed, call_id + blockIdx.z, (uint64_t)(layer * n_types + first_type + t),
+                       chosen, n_chosen, hgt_ws(panic, off), smem, hgt_ws(a.carries[t], off), hgt_ws(a.slots[t], off), wlive);
     hgt_wg_handoff();
     HGT_STAMP(7);
-    hgt_append_body(a.ty[t], a.live[t], a.chosen[t], a.n_chosen[t]);
+    hgt_append_body(ty, live, chosen, n_chosen);
     HGT_STAMP(8);
 }
 // empty type tables and zeroed counters, all types of a call in one launch
@@ -765,8 +812,10 @@ struct HgtInitArgs {
     HgtType ty[HGT_MULTI_TYPES];
     int64_t tl_cap[HGT_MULTI_TYPES], bm_cap[HGT_MULTI_TYPES];
 };
-__global__ void hgt_init_types_kernel(const HgtInitArgs a, int64_t *scalars, int n_scalars) {
-    const HgtType &y = a.ty[blockIdx.y];
+__global__ void hgt_init_types_kernel(const HgtInitArgs a, int64_t *scalars, int n_scalars, int64_t ws_stride) {
+    const int64_t off = hgt_call_ws(ws_stride);
+    const HgtType y = hgt_type_at(a.ty[blockIdx.y], off);
+    scalars = hgt_ws(scalars, off);
     fill2_i64_body(y.tl_keys, a.tl_cap[blockIdx.y], MAP_EMPTY, y.tl_vals, a.tl_cap[blockIdx.y], (int64_t)-1);
     fill2_i64_body(y.bm_keys, a.bm_cap[blockIdx.y], MAP_EMPTY, nullptr, 0, 0);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -862,28 +911,50 @@ struct HgtEdgeRel {
     int64_t cap_n;
     uint32_t tag;
     int64_t *cand_j, *cand_ep, *kept, *off, *rows, *cols, *eidx, *n_edges;
+    int64_t edge_pitch; // words between two calls' rows of rows / cols / eidx
 };
 struct HgtEdgeRels {
     HgtEdgeRel r[HGT_EDGE_PAR];
+    int64_t ws_stride, count_pitch; // bytes between two calls' workspace regions; words between their count rows
 };
+__device__ __forceinline__ HgtEdgeRel hgt_rel_at(const HgtEdgeRels &E) {
+    HgtEdgeRel a = E.r[blockIdx.y];
+    const int64_t off = hgt_call_ws(E.ws_stride);
+    a.dst = hgt_type_at(a.dst, off), a.src = hgt_type_at(a.src, off);
+    a.cand_j = hgt_ws(a.cand_j, off), a.cand_ep = hgt_ws(a.cand_ep, off), a.kept = hgt_ws(a.kept, off), a.off = hgt_ws(a.off, off);
+    a.rows = hgt_row(a.rows, a.edge_pitch), a.cols = hgt_row(a.cols, a.edge_pitch), a.eidx = hgt_row(a.eidx, a.edge_pitch);
+    a.n_edges = hgt_row(a.n_edges, E.count_pitch);
+    return a;
+}
 __global__ void hgt_edge_candidates_rels_kernel(const HgtEdgeRels E, uint64_t seed, uint64_t call_id) {
-    const HgtEdgeRel &a = E.r[blockIdx.y];
-    hgt_edge_candidates_body(a.dst, a.src, a.ptrs, a.indices, a.cap_n, seed, call_id, a.tag, a.cand_j, a.cand_ep, a.kept);
+    const HgtEdgeRel a = hgt_rel_at(E);
+    hgt_edge_candidates_body(a.dst, a.src, a.ptrs, a.indices, a.cap_n, seed, call_id + blockIdx.z, a.tag, a.cand_j, a.cand_ep,
+                             a.kept);
 }
 __global__ void __launch_bounds__(SCAN1_THREADS) hgt_edge_scan_rels_kernel(const HgtEdgeRels E) {
-    const HgtEdgeRel &a = E.r[blockIdx.y];
+    const HgtEdgeRel a = hgt_rel_at(E);
     hgt_scan1_body(a.kept, a.cap_n, a.off, a.n_edges);
 }
 __global__ void hgt_edge_emit_rels_kernel(const HgtEdgeRels E) {
-    const HgtEdgeRel &a = E.r[blockIdx.y];
+    const HgtEdgeRel a = hgt_rel_at(E);
     hgt_edge_emit_body(a.cand_j, a.cand_ep, a.off, a.cap_n, a.rows, a.cols, a.eidx);
 }
-__global__ void hgt_finish_kernel(const HgtTypeCtr *ctr, int n_types, int64_t *n_samples, const int *panic, int *panic_out) {
+// node counts and the panic flag of every call: a single call's int32 flag (panic_out32), or a batched call's
+// count word (panic_out64, in its row of the counts block)
+__global__ void hgt_finish_kernel(const HgtTypeCtr *ctr, int n_types, int64_t *n_samples, const int *panic, int *panic_out32,
+                                  int64_t *panic_out64, int64_t ws_stride, int64_t count_pitch) {
+    const int64_t off = hgt_call_ws(ws_stride);
+    ctr = hgt_ws(ctr, off), panic = hgt_ws(panic, off), n_samples = hgt_row(n_samples, count_pitch);
     for (int t = threadIdx.x; t < n_types; t += blockDim.x) n_samples[t] = ctr[t].n_nodes;
-    if (threadIdx.x == 0) *panic_out = *panic;
+    if (threadIdx.x == 0) {
+        if (panic_out32) *panic_out32 = *panic;
+        if (panic_out64) hgt_row(panic_out64, count_pitch)[0] = (int64_t)*panic;
+    }
 }
 
 // ---------------------------------------------------------------- workspace layout
+constexpr int64_t ONE_WORKGROUP_SCAN = 16384; // elements up to which one workgroup beats the library's launches
+static_assert(ONE_WORKGROUP_SCAN == TG_HGT_ONE_WORKGROUP_SCAN, "tchgeo.h states the batched form's limit");
 struct HgtPlan {
     int T, R, H;
     std::vector<int64_t> cap_nodes, cap_budget, tl_cap, bm_cap;
@@ -994,7 +1065,9 @@ static size_t hgt_carve(const HgtPlan &pl, unsigned char *base, HgtBuffers &B) {
     return off + 256;
 }
 
-static int hgt_make_plan(const tg_hgt_problem *pb, HgtPlan &pl) {
+// library_scan: size the rocPRIM scans' temporary storage (the single call's fallback past ONE_WORKGROUP_SCAN); the
+// batched form never runs them and plans without it
+static int hgt_make_plan(const tg_hgt_problem *pb, HgtPlan &pl, bool library_scan = true) {
     pl.T = pb->n_types;
     pl.R = pb->n_rels;
     pl.H = pb->n_hops;
@@ -1037,12 +1110,15 @@ static int hgt_make_plan(const tg_hgt_problem *pb, HgtPlan &pl) {
     pl.edge_cap = pl.max_nodes * HGT_MAX_NB;
     pl.edge_lanes = std::max(1, std::min(pl.R, HGT_EDGE_PAR));
     pl.scan_cap = std::max(std::max(pl.mc_cap, pl.max_budget) / 64 + 3, pl.max_nodes + 2);
+    pl.scan_temp_bytes = 0;
+    if (library_scan) {
     hipError_t e;
     size_t sc = 0;
     e = rocprim::exclusive_scan(nullptr, sc, (int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)pl.scan_cap,
                                 rocprim::plus<int64_t>(), (hipStream_t)0, false);
     if (e != hipSuccess) return tg::fail(TG_ERR_HIP, "rocprim::exclusive_scan size query failed: %s", hipGetErrorString(e));
     pl.scan_temp_bytes = sc;
+    }
     HgtBuffers B;
     pl.total_bytes = hgt_carve(pl, nullptr, B);
     return TG_OK;
@@ -1061,17 +1137,26 @@ extern "C" int tg_hgt_workspace_bytes(const tg_hgt_problem *pb, int64_t *bytes) 
     return TG_OK;
 }
 
-extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const tg_hgt_out *out, void *workspace,
-                             int64_t workspace_bytes, void *stream_) {
-    using namespace tg;
-    TG_REQUIRE(pb && rng && out && workspace, "tg_hgt_sample: null argument");
-    TG_REQUIRE(pb->n_types >= 1 && pb->n_types <= 1024 && pb->n_rels >= 0 && pb->n_hops >= 0, "tg_hgt_sample: bad sizes");
-    hipStream_t stream = (hipStream_t)stream_;
-    HgtPlan pl;
-    int rc = hgt_make_plan(pb, pl);
-    if (rc != TG_OK) return rc;
-    TG_REQUIRE((size_t)workspace_bytes >= pl.total_bytes, "tg_hgt_sample: workspace too small (%lld < %lld)",
-               (long long)workspace_bytes, (long long)pl.total_bytes);
+namespace tg {
+
+// where one launch chain's results go: a single call's buffers (pitches 0), or a batched launch's slabs
+struct HgtDest {
+    int64_t *const *samples, *const *sample_ts, *const *rows, *const *cols, *const *eidx;
+    const int64_t *node_pitch, *edge_pitch; // [T] / [R] words between two calls' rows, or NULL: one call
+    int64_t *n_samples, *n_edges;           // the first call's node / edge counts
+    int64_t count_pitch;                    // words between two calls' counts
+    int *panic32;                           // a single call's flag, or NULL
+    int64_t *panic64;                       // the first call's flag word in the counts block, or NULL
+};
+
+// The launch chain of hgt_sampling for n_calls calls side by side (blockIdx.z = call): call b owns the workspace region
+// [b * ws_stride, (b + 1) * ws_stride) and draws with call id rng->call_id + b.  Past ONE_WORKGROUP_SCAN elements the
+// scans go through rocPRIM, which only a single call (n_calls = 1) may do.
+static int hgt_run(const tg_hgt_problem *pb, const HgtPlan &pl, int64_t n_calls, int64_t ws_stride, const tg_rng *rng,
+                   const HgtDest &out, void *workspace, hipStream_t stream) {
+    const unsigned Z = (unsigned)n_calls;
+    const bool batched = n_calls > 1 || ws_stride > 0;
+    int rc = TG_OK;
     const int T = pl.T, R = pl.R, H = pl.H;
     HgtBuffers B;
     (void)hgt_carve(pl, reinterpret_cast<unsigned char *>(workspace), B);
@@ -1079,8 +1164,9 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
     HgtTypeCtr *ctr = B.ctr;
     int *panic = B.panic;
     for (int t = 0; t < T; ++t) {
-        ty[(size_t)t].nodes = out->samples[t];
-        ty[(size_t)t].ts = out->sample_ts[t];
+        ty[(size_t)t].nodes = out.samples[t];
+        ty[(size_t)t].ts = out.sample_ts[t];
+        ty[(size_t)t].pitch = out.node_pitch ? out.node_pitch[t] : 0;
     }
 
     // ---- empty maps, zero counters: the types side by side
@@ -1095,20 +1181,22 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
             ia.bm_cap[i] = pl.bm_cap[t0 + i];
             widest = std::max(widest, std::max(ia.tl_cap[i], ia.bm_cap[i]));
         }
-        hipLaunchKernelGGL(hgt_init_types_kernel, dim3(grid_1d(widest), (unsigned)n), dim3(256), 0, stream, ia, B.scal, 8);
+        hipLaunchKernelGGL(hgt_init_types_kernel, dim3(grid_1d(widest), (unsigned)n, Z), dim3(256), 0, stream, ia, B.scal, 8,
+                           ws_stride);
     }
     TG_LAUNCH_CHECK();
 
     // exclusive scan of flag[0..n) into rank[0..n), total into *total, for the sizes one workgroup is too slow for
     auto library_scan = [&](const int64_t *flag, int64_t *rank, int64_t n, int64_t *total) -> int {
         TG_REQUIRE(n <= pl.scan_cap, "tg_hgt_sample: scan of %lld elements exceeds the plan", (long long)n);
+        TG_REQUIRE(!batched && pl.scan_temp_bytes > 0, "tg_hgt_sample_batched: scan of %lld elements past the one-workgroup limit",
+                   (long long)n);
         size_t stb = pl.scan_temp_bytes;
         TG_HIP(rocprim::exclusive_scan(B.scan_temp, stb, flag, rank, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), stream,
                                        false));
         hipLaunchKernelGGL(scan_total_kernel, dim3(1), dim3(64), 0, stream, flag, rank, n, total);
         return TG_OK;
     };
-    constexpr int64_t ONE_WORKGROUP_SCAN = 16384; // elements up to which one workgroup beats the library's launches
 
     // ---- update_budget (:27-102) for the layers of the node types `which`, in order (:47 relations in canonical order).
     // A step = (node type nt, relation r into nt); steps are dealt to ROUNDS: a step goes to the round after the last
@@ -1152,16 +1240,18 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
                 a.bcnt = sc.bcnt, a.bwithin = sc.bwithin, a.bcur = sc.bcur, a.bucket = sc.bucket, a.bucket2 = sc.bucket2;
                 a.bucket3 = sc.bucket3;
             }
+            S.long_blocks = batched ? HGT_ACC_LONG_BLOCKS_BATCHED : HGT_ACC_LONG_BLOCKS;
+            S.ws_stride = ws_stride;
             S.pbits = 1;
             while (((int64_t)1 << S.pbits) < pl.mc_cap) ++S.pbits;
-            auto g2 = [&](int64_t n) { return dim3(grid_1d(n), Y); };
-            hipLaunchKernelGGL(hgt_count_scan_steps_kernel, dim3(1, Y), dim3(SCAN1_THREADS), 0, stream, S, pl.max_layer);
+            auto g2 = [&](int64_t n) { return dim3(grid_1d(n), Y, Z); };
+            hipLaunchKernelGGL(hgt_count_scan_steps_kernel, dim3(1, Y, Z), dim3(SCAN1_THREADS), 0, stream, S, pl.max_layer);
             hipLaunchKernelGGL(hgt_gen_steps_kernel, g2(pl.mc_cap), dim3(256), 0, stream, S, pb->has_timerange, pb->tr_lo,
                                pb->tr_hi, pl.max_layer, pl.tmp_cap);
             hipLaunchKernelGGL(hgt_slots_steps_kernel, g2(pl.mc_cap), dim3(256), 0, stream, S, pl.tmp_cap - 1);
             hipLaunchKernelGGL(hgt_first_flags_steps_kernel, g2(pl.mc_cap), dim3(256), 0, stream, S, pl.tmp_cap - 1, pl.mc_cap);
             if (n_chunks <= ONE_WORKGROUP_SCAN) { // over the chunks' counts: one workgroup per step
-                hipLaunchKernelGGL(hgt_scan1_steps_kernel, dim3(1, Y), dim3(SCAN1_THREADS), 0, stream, S, n_chunks);
+                hipLaunchKernelGGL(hgt_scan1_steps_kernel, dim3(1, Y, Z), dim3(SCAN1_THREADS), 0, stream, S, n_chunks);
             } else {
                 for (unsigned y = 0; y < Y; ++y)
                     if (int rcs = library_scan(S.s[y].flag, S.s[y].rank, n_chunks, S.s[y].scal + 1)) return rcs;
@@ -1169,13 +1259,13 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
             hipLaunchKernelGGL(hgt_new_slots_steps_kernel, g2(pl.mc_cap), dim3(256), 0, stream, S, pl.tmp_cap - 1);
             hipLaunchKernelGGL(hgt_bucket_offsets_steps_kernel, g2(widest_budget), dim3(256), 0, stream, S);
             if ((widest_budget + 63) / 64 <= ONE_WORKGROUP_SCAN) { // over the budget chunks' contribution counts
-                hipLaunchKernelGGL(hgt_bucket_scan_steps_kernel, dim3(1, Y), dim3(SCAN1_THREADS), 0, stream, S);
+                hipLaunchKernelGGL(hgt_bucket_scan_steps_kernel, dim3(1, Y, Z), dim3(SCAN1_THREADS), 0, stream, S);
             } else {
                 for (unsigned y = 0; y < Y; ++y)
                     if (int rcs = library_scan(S.s[y].tflag, S.s[y].trank, (S.s[y].pad + 63) / 64, S.s[y].scal + 2)) return rcs;
             }
             hipLaunchKernelGGL(hgt_bucket_scatter_steps_kernel, g2(pl.mc_cap), dim3(256), 0, stream, S);
-            hipLaunchKernelGGL(hgt_accumulate_steps_kernel, dim3(grid_1d(widest_budget) + HGT_ACC_LONG_BLOCKS, Y),
+            hipLaunchKernelGGL(hgt_accumulate_steps_kernel, dim3(grid_1d(widest_budget) + (unsigned)S.long_blocks, Y, Z),
                                dim3(HGT_ACC_THREADS), 0, stream, S);
             TG_LAUNCH_CHECK();
         }
@@ -1187,8 +1277,8 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
         const int64_t n_in = pb->n_inputs[t];
         if (n_in > 0) {
             TG_REQUIRE(pb->inputs[t], "tg_hgt_sample: node type %d has n_inputs > 0 but no pointer", t);
-            hipLaunchKernelGGL(hgt_init_inputs_kernel, dim3(grid_1d(n_in)), dim3(256), 0, stream, ty[(size_t)t], pb->inputs[t],
-                               pb->input_ts ? pb->input_ts[t] : (const int64_t *)nullptr, n_in);
+            hipLaunchKernelGGL(hgt_init_inputs_kernel, dim3(grid_1d(n_in), 1, Z), dim3(256), 0, stream, ty[(size_t)t], pb->inputs[t],
+                               pb->input_ts ? pb->input_ts[t] : (const int64_t *)nullptr, n_in, ws_stride);
         }
     }
     TG_LAUNCH_CHECK();
@@ -1205,6 +1295,7 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
             const int n = std::min(HGT_MULTI_TYPES, T - t0);
             HgtSampleArgs sa;
             std::memset(&sa, 0, sizeof(sa));
+            sa.ws_stride = ws_stride;
             size_t lds = 8;
             for (int i = 0; i < n; ++i) {
                 const size_t t = (size_t)(t0 + i);
@@ -1214,7 +1305,7 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
                 sa.slots[i] = B.slots[t], sa.carries[i] = B.carries[t], sa.wlive[i] = B.wlive[t];
                 if (sa.k[i] > 0 && sa.k[i] <= HGT_LDS_SLOTS) lds = std::max(lds, (size_t)sa.k[i] * 4);
             }
-            hipLaunchKernelGGL(hgt_sample_layer_kernel, dim3((unsigned)n), dim3(SCAN1_THREADS), lds, stream, sa, rng->seed,
+            hipLaunchKernelGGL(hgt_sample_layer_kernel, dim3((unsigned)n, 1, Z), dim3(SCAN1_THREADS), lds, stream, sa, rng->seed,
                                rng->call_id, (int64_t)layer, t0, T, panic);
         }
         TG_LAUNCH_CHECK();
@@ -1230,6 +1321,7 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
         const int n = std::min(pl.edge_lanes, R - r0);
         HgtEdgeRels E;
         std::memset(&E, 0, sizeof(E));
+        E.ws_stride = ws_stride, E.count_pitch = out.count_pitch;
         int64_t widest = 1;
         for (int i = 0; i < n; ++i) {
             const int r = r0 + i, st = pb->rel_src[r], dt = pb->rel_dst[r];
@@ -1240,13 +1332,14 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
             a.tag = TAG_HGT | ((uint32_t)(r + 1) << 8);
             a.cand_j = B.ed[(size_t)i].cand_j, a.cand_ep = B.ed[(size_t)i].cand_ep;
             a.kept = B.ed[(size_t)i].kept, a.off = B.ed[(size_t)i].off;
-            a.rows = out->rows[r], a.cols = out->cols[r], a.eidx = out->edge_index[r], a.n_edges = out->n_edges + r;
+            a.rows = out.rows[r], a.cols = out.cols[r], a.eidx = out.eidx[r], a.n_edges = out.n_edges + r;
+            a.edge_pitch = out.edge_pitch ? out.edge_pitch[r] : 0;
             widest = std::max(widest, a.cap_n);
         }
-        const dim3 grid(grid_1d(widest * 64), (unsigned)n);
+        const dim3 grid(grid_1d(widest * 64), (unsigned)n, Z);
         hipLaunchKernelGGL(hgt_edge_candidates_rels_kernel, grid, dim3(256), 0, stream, E, rng->seed, rng->call_id);
         if (widest <= ONE_WORKGROUP_SCAN) { // over the nodes' kept-edge counts
-            hipLaunchKernelGGL(hgt_edge_scan_rels_kernel, dim3(1, (unsigned)n), dim3(SCAN1_THREADS), 0, stream, E);
+            hipLaunchKernelGGL(hgt_edge_scan_rels_kernel, dim3(1, (unsigned)n, Z), dim3(SCAN1_THREADS), 0, stream, E);
         } else {
             for (int i = 0; i < n; ++i)
                 if (int rcs = library_scan(E.r[i].kept, E.r[i].off, E.r[i].cap_n, E.r[i].n_edges)) return rcs;
@@ -1254,7 +1347,8 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
         hipLaunchKernelGGL(hgt_edge_emit_rels_kernel, grid, dim3(256), 0, stream, E);
         TG_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(hgt_finish_kernel, dim3(1), dim3(256), 0, stream, ctr, T, out->n_samples, panic, out->panic);
+    hipLaunchKernelGGL(hgt_finish_kernel, dim3(1, 1, Z), dim3(256), 0, stream, ctr, T, out.n_samples, panic, out.panic32,
+                       out.panic64, ws_stride, out.count_pitch);
     TG_LAUNCH_CHECK();
 #ifdef TG_HGT_STAMPS
     {
@@ -1270,4 +1364,123 @@ extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const 
     }
 #endif
     return TG_OK;
+}
+
+} // namespace tg
+
+
+extern "C" int tg_hgt_sample(const tg_hgt_problem *pb, const tg_rng *rng, const tg_hgt_out *out, void *workspace,
+                             int64_t workspace_bytes, void *stream_) {
+    using namespace tg;
+    TG_REQUIRE(pb && rng && out && workspace, "tg_hgt_sample: null argument");
+    TG_REQUIRE(pb->n_types >= 1 && pb->n_types <= 1024 && pb->n_rels >= 0 && pb->n_hops >= 0, "tg_hgt_sample: bad sizes");
+    HgtPlan pl;
+    int rc = hgt_make_plan(pb, pl);
+    if (rc != TG_OK) return rc;
+    TG_REQUIRE((size_t)workspace_bytes >= pl.total_bytes, "tg_hgt_sample: workspace too small (%lld < %lld)",
+               (long long)workspace_bytes, (long long)pl.total_bytes);
+    HgtDest d{};
+    d.samples = out->samples, d.sample_ts = out->sample_ts;
+    d.rows = out->rows, d.cols = out->cols, d.eidx = out->edge_index;
+    d.n_samples = out->n_samples, d.n_edges = out->n_edges, d.panic32 = out->panic;
+    return hgt_run(pb, pl, 1, 0, rng, d, workspace, (hipStream_t)stream_);
+}
+
+// ---------------------------------------------------------------- the batched form
+namespace tg {
+// the per-call plan of a batched launch and the bytes between two calls' workspace regions
+static int hgt_batched_plan(const tg_hgt_problem *pb, const char *who, HgtPlan &pl, int64_t *stride) {
+    TG_REQUIRE(pb && pb->n_inputs && pb->num_samples && (pb->n_rels == 0 || (pb->rel_src && pb->rel_dst && pb->graphs)),
+               "%s: null argument", who);
+    TG_REQUIRE(pb->n_types >= 1 && pb->n_types <= 1024 && pb->n_rels >= 0 && pb->n_hops >= 0, "%s: bad sizes", who);
+    for (int r = 0; r < pb->n_rels; ++r)
+        TG_REQUIRE(pb->rel_src[r] >= 0 && pb->rel_src[r] < pb->n_types && pb->rel_dst[r] >= 0 && pb->rel_dst[r] < pb->n_types,
+                   "%s: relation %d has a bad node type", who, r);
+    int rc = hgt_make_plan(pb, pl, false);
+    if (rc != TG_OK) return rc;
+    // every scan of the chain runs in one workgroup per call (the single call's rocPRIM fallback would be launches per call)
+    const int64_t contrib_chunks = (pl.mc_cap + 63) / 64, budget_chunks = (pl.max_budget + 63) / 64;
+    TG_REQUIRE(contrib_chunks <= ONE_WORKGROUP_SCAN,
+               "%s: %lld samples in one layer exceed the one-workgroup scan limit (%lld chunks of 64 contributions)", who,
+               (long long)pl.max_layer, (long long)ONE_WORKGROUP_SCAN);
+    TG_REQUIRE(budget_chunks <= ONE_WORKGROUP_SCAN,
+               "%s: a budget of %lld entries exceeds the one-workgroup scan limit (%lld chunks of 64 entries)", who,
+               (long long)pl.max_budget, (long long)ONE_WORKGROUP_SCAN);
+    for (int r = 0; r < pb->n_rels; ++r)
+        TG_REQUIRE(pl.cap_nodes[pb->rel_dst[r]] <= ONE_WORKGROUP_SCAN,
+                   "%s: node type %d holds up to %lld nodes, past the one-workgroup scan limit of %lld", who, pb->rel_dst[r],
+                   (long long)pl.cap_nodes[pb->rel_dst[r]], (long long)ONE_WORKGROUP_SCAN);
+    *stride = (int64_t)((pl.total_bytes + 255) & ~(size_t)255);
+    return TG_OK;
+}
+} // namespace tg
+
+extern "C" int tg_hgt_batched_capacity(const tg_hgt_problem *pb, int64_t *cap_nodes, int64_t *cap_edges) {
+    using namespace tg;
+    TG_REQUIRE(cap_nodes && (!pb || pb->n_rels == 0 || cap_edges), "tg_hgt_batched_capacity: null argument");
+    HgtPlan pl;
+    int64_t stride = 0;
+    int rc = hgt_batched_plan(pb, "tg_hgt_batched_capacity", pl, &stride);
+    if (rc != TG_OK) return rc;
+    for (int t = 0; t < pl.T; ++t) cap_nodes[t] = pl.cap_nodes[t];
+    for (int r = 0; r < pl.R; ++r) cap_edges[r] = HGT_MAX_NB * std::max<int64_t>(pl.cap_nodes[pb->rel_dst[r]], 1);
+    return TG_OK;
+}
+
+extern "C" int tg_hgt_batched_workspace_bytes(const tg_hgt_problem *pb, int64_t n_calls, int64_t *bytes) {
+    using namespace tg;
+    TG_REQUIRE(bytes, "tg_hgt_batched_workspace_bytes: null argument");
+    TG_REQUIRE(n_calls >= 1 && n_calls <= TG_HGT_MAX_CALLS, "tg_hgt_batched_workspace_bytes: n_calls = %lld outside [1, %d]",
+               (long long)n_calls, TG_HGT_MAX_CALLS);
+    HgtPlan pl;
+    int64_t stride = 0;
+    int rc = hgt_batched_plan(pb, "tg_hgt_batched_workspace_bytes", pl, &stride);
+    if (rc != TG_OK) return rc;
+    *bytes = n_calls * stride;
+    return TG_OK;
+}
+
+extern "C" int tg_hgt_sample_batched(const tg_hgt_problem *pb, int64_t n_calls, const tg_rng *rng,
+                                     const tg_hgt_batched_out *out, void *workspace, int64_t workspace_bytes, void *stream_) {
+    using namespace tg;
+    const char *who = "tg_hgt_sample_batched";
+    TG_REQUIRE(rng && out && workspace && out->counts, "%s: null argument", who);
+    TG_REQUIRE(n_calls >= 1 && n_calls <= TG_HGT_MAX_CALLS, "%s: n_calls = %lld outside [1, %d]", who, (long long)n_calls,
+               TG_HGT_MAX_CALLS);
+    HgtPlan pl;
+    int64_t stride = 0;
+    int rc = hgt_batched_plan(pb, who, pl, &stride);
+    if (rc != TG_OK) return rc;
+    TG_REQUIRE(workspace_bytes >= n_calls * stride, "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes,
+               (long long)(n_calls * stride));
+    TG_REQUIRE((((uintptr_t)workspace | (uintptr_t)out->counts) & 7u) == 0, "%s: workspace and counts must be 8-byte aligned",
+               who);
+    const int T = pl.T, R = pl.R;
+    TG_REQUIRE(out->samples && out->sample_ts && out->cap_nodes &&
+                   (R == 0 || (out->rows && out->cols && out->edge_index && out->cap_edges)),
+               "%s: null output array", who);
+    for (int t = 0; t < T; ++t) {
+        TG_REQUIRE(out->cap_nodes[t] >= pl.cap_nodes[t], "%s: samples slab of type %d too small (pitch %lld < %lld)", who, t,
+                   (long long)out->cap_nodes[t], (long long)pl.cap_nodes[t]);
+        TG_REQUIRE(pl.cap_nodes[t] == 0 || (out->samples[t] && out->sample_ts[t]), "%s: null samples slab of type %d", who, t);
+        TG_REQUIRE((((uintptr_t)out->samples[t] | (uintptr_t)out->sample_ts[t]) & 7u) == 0,
+                   "%s: samples slabs of type %d must be 8-byte aligned", who, t);
+        TG_REQUIRE(pb->n_inputs[t] <= 0 || (pb->inputs && pb->inputs[t]), "%s: null inputs of type %d", who, t);
+    }
+    for (int r = 0; r < R; ++r) {
+        const int64_t need = HGT_MAX_NB * std::max<int64_t>(pl.cap_nodes[pb->rel_dst[r]], 1);
+        TG_REQUIRE(pb->graphs[r].ptrs && (pb->graphs[r].indices || pb->graphs[r].n_edges == 0), "%s: null graph of relation %d",
+                   who, r);
+        TG_REQUIRE(out->cap_edges[r] >= need, "%s: edge slabs of relation %d too small (pitch %lld < %lld)", who, r,
+                   (long long)out->cap_edges[r], (long long)need);
+        TG_REQUIRE(out->rows[r] && out->cols[r] && out->edge_index[r], "%s: null edge slab of relation %d", who, r);
+        TG_REQUIRE((((uintptr_t)out->rows[r] | (uintptr_t)out->cols[r] | (uintptr_t)out->edge_index[r]) & 7u) == 0,
+                   "%s: edge slabs of relation %d must be 8-byte aligned", who, r);
+    }
+    HgtDest d{};
+    d.samples = out->samples, d.sample_ts = out->sample_ts, d.node_pitch = out->cap_nodes;
+    d.rows = out->rows, d.cols = out->cols, d.eidx = out->edge_index, d.edge_pitch = out->cap_edges;
+    d.count_pitch = T + R + 1;
+    d.n_samples = out->counts, d.n_edges = out->counts + T, d.panic64 = out->counts + T + R;
+    return hgt_run(pb, pl, n_calls, stride, rng, d, workspace, (hipStream_t)stream_);
 }

@@ -32,7 +32,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_ns_win_stage_timing", "tg_ns_win_stage_times", "tg_probe_ns_sol",
            "tg_debug_bounds_set_flag", "tg_part_sample_workspace_bytes", "tg_part_sample_ws",
            "tg_part_sample_order_thresholds", "tg_ns_homo_batched_pipeline", "tg_graph_max_degree",
-           "tg_ns_homo_workspace_bytes_for", "tg_ns_homo_batched_workspace_bytes"]
+           "tg_ns_homo_workspace_bytes_for", "tg_ns_homo_batched_workspace_bytes", "tg_hgt_batched_capacity",
+           "tg_hgt_batched_workspace_bytes", "tg_hgt_sample_batched"]
 
 
 class TgGraph(C.Structure):
@@ -388,6 +389,105 @@ class NsHeteroBatched:
         rng = TgRng(seed, call_id)
         check(lib.tg_ns_hetero_batched(C.byref(self.problem), C.c_int64(self.nb), C.byref(rng), C.byref(self.out),
                                        stream_ptr(self.dev)))
+
+
+class TgHgtProblem(C.Structure):
+    _fields_ = [("n_types", C.c_int32), ("n_rels", C.c_int32), ("n_hops", C.c_int32), ("has_timerange", C.c_int32),
+                ("rel_src", C.POINTER(C.c_int32)), ("rel_dst", C.POINTER(C.c_int32)), ("graphs", C.POINTER(TgGraph)),
+                ("inputs", C.POINTER(C.c_void_p)), ("input_ts", C.POINTER(C.c_void_p)), ("n_inputs", C.POINTER(C.c_int64)),
+                ("num_samples", C.POINTER(C.c_int64)), ("tr_lo", C.c_int64), ("tr_hi", C.c_int64)]
+
+
+class TgHgtBatchedOut(C.Structure):
+    _fields_ = [("samples", C.POINTER(C.c_void_p)), ("sample_ts", C.POINTER(C.c_void_p)), ("cap_nodes", C.POINTER(C.c_int64)),
+                ("rows", C.POINTER(C.c_void_p)), ("cols", C.POINTER(C.c_void_p)), ("edge_index", C.POINTER(C.c_void_p)),
+                ("cap_edges", C.POINTER(C.c_int64)), ("counts", C.c_void_p)]
+
+
+def hgt_problem(n_types, rels, n_inputs, num_samples, n_hops, inputs=None, input_ts=None, timerange=None):
+    """A tg_hgt_problem.  rels: list of (src type index, dst type index, ptrs, indices, row timestamps or None);
+    n_inputs: per type (< 0: no entry in `inputs`); num_samples: per type a list of n_hops quotas, or None (no entry);
+    inputs / input_ts: per type a device tensor or None (input_ts None: no input timestamps at all)."""
+    T, R = n_types, len(rels)
+    p = TgHgtProblem()
+    p.n_types, p.n_rels, p.n_hops = T, R, n_hops
+    rel_src = (C.c_int32 * max(R, 1))(*[r[0] for r in rels])
+    rel_dst = (C.c_int32 * max(R, 1))(*[r[1] for r in rels])
+    graphs = (TgGraph * max(R, 1))()
+    for i, r in enumerate(rels):
+        graphs[i] = graph_view(r[2], r[3], timestamps=r[4] if len(r) > 4 else None)
+    ns = (C.c_int64 * max(T * n_hops, 1))(*[int(q[h]) if q is not None else -1 for q in num_samples for h in range(n_hops)])
+    n_in = (C.c_int64 * T)(*[int(x) for x in n_inputs])
+    vp = lambda ts: (C.c_void_p * T)(*[None if x is None or x.numel() == 0 else x.data_ptr() for x in ts])
+    ins = vp(inputs if inputs is not None else [None] * T)
+    its = vp(input_ts) if input_ts is not None else None
+    p.rel_src, p.rel_dst, p.graphs, p.n_inputs, p.num_samples = rel_src, rel_dst, graphs, n_in, ns
+    p.inputs = ins
+    p.input_ts = its if its is not None else C.POINTER(C.c_void_p)()
+    if timerange is not None:
+        p.has_timerange, p.tr_lo, p.tr_hi = 1, int(timerange[0]), int(timerange[1])
+    p._keep = (rels, inputs, input_ts, rel_src, rel_dst, graphs, ns, n_in, ins, its)
+    return p
+
+
+def hgt_batched_capacity(problem):
+    """-> (cap_nodes [T], cap_edges [R]) of one call (tg_hgt_batched_capacity)."""
+    cn, ce = (C.c_int64 * problem.n_types)(), (C.c_int64 * max(problem.n_rels, 1))()
+    check(lib.tg_hgt_batched_capacity(C.byref(problem), cn, ce))
+    return list(cn), list(ce)[:problem.n_rels]
+
+
+def hgt_batched_workspace_bytes(problem, n_calls):
+    nbytes = C.c_int64(0)
+    check(lib.tg_hgt_batched_workspace_bytes(C.byref(problem), C.c_int64(n_calls), C.byref(nbytes)))
+    return nbytes.value
+
+
+class HgtBatched:
+    """Problem description, output slabs and workspace of tg_hgt_sample_batched: n_calls hgt_sampling calls of one shape
+    per launch chain.  inputs / input_ts: per node type a [n_calls, n_inputs] tensor or None (no entry in `inputs`);
+    num_samples: per type a list of n_hops quotas or None; rels as in hgt_problem.  pad: extra words per slab row (the
+    pitches then exceed the capacities).  Call b of run(seed, call_id) equals hgt_sampling with call id call_id + b."""
+
+    def __init__(self, n_types, rels, inputs, num_samples, n_hops, n_calls, device, input_ts=None, timerange=None, pad=0):
+        T, R = n_types, len(rels)
+        self.T, self.R, self.H, self.nc, self.dev = T, R, n_hops, int(n_calls), device
+        n_in = [-1 if x is None else int(x.shape[1]) for x in inputs]
+        flat = lambda xs: [None if x is None else x.reshape(n_calls, -1).contiguous() for x in xs]
+        self.inputs = flat(inputs)
+        self.input_ts = flat(input_ts) if input_ts is not None else None
+        self.problem = hgt_problem(T, rels, n_in, num_samples, n_hops, self.inputs, self.input_ts, timerange)
+        self.cap_nodes, self.cap_edges = hgt_batched_capacity(self.problem)
+        o = dict(dtype=torch.int64, device=device)
+        self.node_pitch = [c + pad if c + pad > 0 else 1 for c in self.cap_nodes]
+        self.edge_pitch = [c + pad for c in self.cap_edges]
+        self.samples = [torch.empty((n_calls, p), **o) for p in self.node_pitch]
+        self.sample_ts = [torch.empty((n_calls, p), **o) for p in self.node_pitch]
+        self.rows = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
+        self.cols = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
+        self.edge_index = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
+        self.counts = torch.zeros((n_calls, T + R + 1), **o)
+        self.workspace_bytes = hgt_batched_workspace_bytes(self.problem, n_calls)
+        self.workspace = torch.empty(self.workspace_bytes // 8 + 1, **o)
+        vp = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
+        i64 = lambda xs: (C.c_int64 * max(len(xs), 1))(*xs)
+        self._arrays = [vp(self.samples), vp(self.sample_ts), i64(self.node_pitch), vp(self.rows), vp(self.cols),
+                        vp(self.edge_index), i64(self.edge_pitch)]
+        self.out = TgHgtBatchedOut(*self._arrays, self.counts.data_ptr())
+
+    def run(self, seed, call_id):
+        rng = TgRng(seed, call_id)
+        check(lib.tg_hgt_sample_batched(C.byref(self.problem), C.c_int64(self.nc), C.byref(rng), C.byref(self.out),
+                                        ptr(self.workspace), C.c_int64(self.workspace_bytes), stream_ptr(self.dev)))
+
+    def call(self, b, counts=None):
+        """Call b's results -> (samples [T], sample_ts [T], rows [R], cols [R], edge_index [R], panic) trimmed to its
+        counts (counts: the counts block already read back, else it is read here)."""
+        c = (self.counts[b].tolist() if counts is None else [int(x) for x in counts[b]])
+        T, R = self.T, self.R
+        return ([self.samples[t][b, :c[t]] for t in range(T)], [self.sample_ts[t][b, :c[t]] for t in range(T)],
+                [self.rows[r][b, :c[T + r]] for r in range(R)], [self.cols[r][b, :c[T + r]] for r in range(R)],
+                [self.edge_index[r][b, :c[T + r]] for r in range(R)], c[T + R])
 
 
 BIAS = {"uniform": 0, "linear": 1, "exponential": 2}

@@ -364,3 +364,140 @@ class HeteroNeighborLoader:
             yield from self._emit(nodes[start * B:(start + G) * B].reshape(G, B), batch0 + start)
         if not self.drop_last and n_full * B < nodes.numel():
             yield from self._emit(nodes[n_full * B:].reshape(1, -1), batch0 + n_full)
+
+
+class HGTLoader:
+    """HGT budget sampling (hgt_sampling) as a loader: seeds of ONE node type, `prefetch` mini-batches per
+    tg_hgt_sample_batched launch chain, one read-back of the counts per launch, per-type / per-relation slabs flattened
+    by tg_compact_rows, node attributes gathered per type and edge attributes per relation through the ingest
+    permutation (as HeteroNeighborLoader).  num_samples: one list of per-hop quotas for every node type (as
+    HGTSamplerTransform) or a dict per type.  temporal=True uses the edge stores' int64 `timestamps` as row timestamps,
+    `input_timestamps` (one per input node) as the seeds' timestamps and `timerange` = [lo, hi).
+
+    Mini-batch j of the epoch equals hgt_sampling for (seed, call_id0 + j); every epoch draws fresh call ids.  A
+    launch's workspace is prefetch x tg_hgt_batched_workspace_bytes(one call): prefetch is clamped so that it stays
+    within `max_workspace_bytes` (default 4 GiB; at least one mini-batch per launch)."""
+
+    def __init__(self, data, num_samples, input_type: str, input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
+                 prefetch: int = 64, temporal: bool = False, input_timestamps: Optional[Tensor] = None, timerange=None,
+                 drop_last: bool = False, seed: int = 0, call_id0: int = 0, max_workspace_bytes: int = 4 << 30,
+                 device="cuda"):
+        self.data, self.device = data, torch.device(device)
+        self.node_types, self.edge_types = list(data.node_types), list(data.edge_types)
+        self.input_type, self.batch_size = input_type, int(batch_size)
+        self.drop_last, self.seed, self.call_id0 = drop_last, int(seed), int(call_id0)
+        if isinstance(num_samples, dict):
+            self.num_samples = {k: [int(x) for x in v] for k, v in num_samples.items()}
+            self.n_hops = max((len(v) for v in self.num_samples.values()), default=0)
+        else:
+            self.n_hops = len(num_samples)
+            self.num_samples = {nt: [int(x) for x in num_samples] for nt in self.node_types}
+        for nt, v in self.num_samples.items():
+            if len(v) < self.n_hops:
+                raise ValueError("num_samples[%s] is shorter than the number of hops" % nt)
+        self.col_ptrs, self.row_indices, self.perm = to_hetero_csc(data, self.device)
+        self.temporal, self.timerange = temporal, (None if timerange is None else (int(timerange[0]), int(timerange[1])))
+        self._tix = {t: i for i, t in enumerate(self.node_types)}
+        rts = {}
+        if temporal:  # timestamps follow the CSC edge order
+            rts = {rel_key(et): _cabi.gather_rows(data[et].timestamps.to(self.device).to(torch.int64),
+                                                  self.perm[rel_key(et)])[0] for et in self.edge_types}
+        self._rels = [(self._tix[et[0]], self._tix[et[2]], self.col_ptrs[rel_key(et)], self.row_indices[rel_key(et)],
+                       rts.get(rel_key(et))) for et in self.edge_types]
+        n_in = _num_nodes(data[input_type])
+        nodes = torch.arange(n_in, device=self.device) if input_nodes is None else input_nodes.to(self.device)
+        self.input_nodes = _checked_inputs(nodes, n_in)
+        self.input_ts = None
+        if temporal:
+            if input_timestamps is None:
+                raise ValueError("temporal=True needs input_timestamps (one per input node)")
+            self.input_ts = input_timestamps.to(self.device).reshape(-1).to(torch.int64)
+            if self.input_ts.numel() != self.input_nodes.numel():
+                raise ValueError("input_timestamps must have one entry per input node")
+        per_call = _cabi.hgt_batched_workspace_bytes(self._problem(self.batch_size), 1)
+        self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // per_call))
+        self.epoch = 0
+        self._node_attrs = {t: [(k, v.to(self.device)) for k, v in _tensor_items(data[t])
+                                if v.dim() > 0 and v.shape[0] == _num_nodes(data[t])] for t in self.node_types}
+        self._edge_attrs = {}
+        for et in self.edge_types:
+            n_e = int(data[et].edge_index.shape[1])
+            self._edge_attrs[et] = [(k, v.to(self.device)) for k, v in _tensor_items(data[et])
+                                    if k != "edge_index" and v.dim() > 0 and v.shape[0] == n_e]
+
+    def _num_samples(self):
+        return [self.num_samples.get(nt) for nt in self.node_types]
+
+    def _problem(self, n_seeds):
+        """A host-only problem of the loader's shape (sizes the workspace; nothing is launched)."""
+        n_in = [n_seeds if nt == self.input_type else -1 for nt in self.node_types]
+        return _cabi.hgt_problem(len(self.node_types), self._rels, n_in, self._num_samples(), self.n_hops)
+
+    def __len__(self) -> int:
+        n = self.input_nodes.numel()
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def _emit(self, seeds: Tensor, seeds_ts: Optional[Tensor], first_batch: int) -> Iterator[HeteroGraph]:
+        G, B = seeds.shape
+        T, R = len(self.node_types), len(self.edge_types)
+        it = self._tix[self.input_type]
+        inputs = [None] * T
+        inputs[it] = seeds.contiguous()
+        input_ts = None
+        if seeds_ts is not None:
+            input_ts = [None] * T
+            input_ts[it] = seeds_ts.contiguous()
+        hb = _cabi.HgtBatched(T, self._rels, inputs, self._num_samples(), self.n_hops, G, self.device,
+                              input_ts=input_ts, timerange=self.timerange if self.temporal else None)
+        hb.run(self.seed, self.call_id0 + first_batch)
+        counts = hb.counts.cpu()                                # the launch's only read-back
+        panicked = [b for b in range(G) if int(counts[b, T + R]) != 0]
+        if panicked:
+            raise RuntimeError("HGTLoader: mini-batch %d: a weight sum was not positive, or a node type that owns a budget "
+                               "has no num_samples entry (the reference panics here)" % (first_batch + panicked[0]))
+        rows_of = lambda table, index: _cabi.gather_rows(table, index)[0]
+        node_parts, ts_parts, attr_parts = {}, {}, {}
+        for t, nt in enumerate(self.node_types):
+            lens = counts[:, t].tolist()
+            flat = _cabi.compact_rows(hb.samples[t], hb.counts[:, t], sum(lens))
+            node_parts[nt] = (torch.split(flat, lens), lens)
+            ts_parts[nt] = torch.split(_cabi.compact_rows(hb.sample_ts[t], hb.counts[:, t], sum(lens)), lens)
+            attr_parts[nt] = {k: torch.split(rows_of(v, flat), lens) for k, v in self._node_attrs[nt]}
+        edge_parts = {}
+        for r, et in enumerate(self.edge_types):
+            lens = counts[:, T + r].tolist()
+            tot = sum(lens)
+            fr = _cabi.compact_rows(hb.rows[r], hb.counts[:, T + r], tot)
+            fc = _cabi.compact_rows(hb.cols[r], hb.counts[:, T + r], tot)
+            fe = rows_of(self.perm[rel_key(et)], _cabi.compact_rows(hb.edge_index[r], hb.counts[:, T + r], tot))
+            edge_parts[et] = (torch.split(torch.stack([fr, fc]), lens, dim=1), torch.split(fe, lens),
+                              {k: torch.split(rows_of(v, fe), lens) for k, v in self._edge_attrs[et]})
+        for b in range(G):
+            g = HeteroGraph()
+            for nt in self.node_types:
+                st = g[nt]
+                st.n_id, st.num_nodes = node_parts[nt][0][b], node_parts[nt][1][b]
+                for k, parts in attr_parts[nt].items():
+                    setattr(st, k, parts[b])
+            g[self.input_type].batch_size = B
+            for et in self.edge_types:
+                st = g[et]
+                st.edge_index, st.e_id = edge_parts[et][0][b], edge_parts[et][1][b]
+                for k, parts in edge_parts[et][2].items():
+                    setattr(st, k, parts[b])
+            g.samples_timestamps = {nt: ts_parts[nt][b] for nt in self.node_types}
+            g.call_id = self.call_id0 + first_batch + b
+            yield g
+
+    def __iter__(self) -> Iterator[HeteroGraph]:
+        nodes, ts, B = self.input_nodes, self.input_ts, self.batch_size
+        batch0 = self.epoch * len(self)                         # fresh draws every epoch (see NeighborLoader)
+        self.epoch += 1
+        n_full = nodes.numel() // B
+        for start in range(0, n_full, self.prefetch):
+            G = min(self.prefetch, n_full - start)
+            sl = slice(start * B, (start + G) * B)
+            yield from self._emit(nodes[sl].reshape(G, B), None if ts is None else ts[sl].reshape(G, B), batch0 + start)
+        if not self.drop_last and n_full * B < nodes.numel():
+            yield from self._emit(nodes[n_full * B:].reshape(1, -1), None if ts is None else ts[n_full * B:].reshape(1, -1),
+                                  batch0 + n_full)
