@@ -8,6 +8,9 @@ throughput therefore does not depend on how many steps the caller asks for.
 N > 1: one process per GPU (torchrun), CSC replicated, every rank samples its own K steps with no
 data-path collective (weak scaling); the only collectives are the barrier / MAX / SUM of the timing
 protocol.  Prints ONE JSON line on rank 0.
+A plain run does only what the headline needs: set-up (graph, seeds, the placement / pipeline pick), warm-up, the timed
+steps, --dump-outputs, the line.  `--full` adds the rest to the same line: the check of the last timed step against the
+fused kernel and the oracle, two launches in flight, the secondary configurations and the CPU baseline.
 """
 import argparse
 import json
@@ -32,11 +35,15 @@ def parse_args(argv=None):
     ap.add_argument("--fanout", type=str, default="15,10")
     ap.add_argument("--batches-per-step", "--batches-per-launch", dest="batches_per_step", type=int, default=16384,
                     help="independent 1024-seed mini-batches sampled by the one launch of a step")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU work of the cpu_baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short runs of BASELINE cfg3 / cfg4")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also verify the last timed step, time two launches in flight, run the "
+                         "secondary configurations and the CPU baseline (a plain run does none of these)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target CPU work of the cpu_baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the short runs of BASELINE cfg3 / cfg4")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the (untimed) check of batches of the last timed step against the fused kernel and the oracle")
+                    help="--full: skip the (untimed) check of batches of the last timed step against the fused kernel and "
+                         "the oracle")
     ap.add_argument("--idx32", type=int, default=1, help="also keep a u32 shadow of `indices` for the gathers")
     ap.add_argument("--ptr32", type=int, default=1, help="also keep a u32 shadow of `ptrs`")
     ap.add_argument("--placements", type=int, default=2,
@@ -268,7 +275,7 @@ def main(argv=None):
         # beside the line (never part of `value`): the same launches with TWO in flight, one per placement on its own
         # stream -- what a caller that prefetches the next super-batch gets
         in_flight = None
-        if n_c >= 2:
+        if args.full and n_c >= 2:
             side = [torch.cuda.Stream(device=dev) for _ in range(2)]
             cur = torch.cuda.current_stream(dev)
             for timed in (False, True):
@@ -399,6 +406,7 @@ def main(argv=None):
             "sampled_edges_per_mini_batch": edges_all / (K * world * G),
             "graph_build_s": round(t_build, 2),
             "form": args.form,
+            "full": args.full,
             "gpu_state_before_timed_region": gpu_state0,
             "gpu_state_after_timed_region": gpu_state1,
         },
@@ -422,7 +430,7 @@ def main(argv=None):
 
     # ---- what was timed is checked (untimed): batches of the LAST timed step, as they lie in the slabs, against the
     # fused per-batch kernel (another code path, on the device) and against the CPU oracle in philox-mode (the checker)
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         i_last = W + K - 1
         result["config"]["verified_batches"] = verify_step(
             torch, _cabi, graph, ptrs, indices, out, seeds[(i_last % n_pool) * G:(i_last % n_pool) * G + G], fanout,
@@ -433,7 +441,7 @@ def main(argv=None):
         dump_outputs(args.dump_outputs, out, seeds[(i_last % n_pool) * G:(i_last % n_pool) * G + G], first + i_last * G,
                      dump_ids, len(fanout))
 
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         del out, ws
         torch.cuda.empty_cache()
         result["secondary"] = secondary_configs(torch, _cabi, dev, args.cpu_seconds)
@@ -446,7 +454,7 @@ def main(argv=None):
                 torch, _cabi, ptrs, indices, dev, B, fanout, n_nodes, first)
         except Exception as e:  # noqa: BLE001
             result["secondary"]["mode2_partitioned_one_rank_4096_batches"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, ptrs, indices, seeds[:min(int(seeds.shape[0]), 16384)], fanout)
     if rank == 0:
         print_result(result)

@@ -63,12 +63,13 @@ def test_plain_spelling_really_starts_ranks():
     """`python bench.py --gpus 2` end to end: torchrun starts two ranks.  Without a GPU each dies for lack of one (the HIP
     library / device is missing) -- the launcher itself must have worked: non-zero exit, no result line, and the ranks'
     error mentions the device or library, not the old 'launch N>1 through torch.distributed.run' refusal.  With a GPU the
-    two rehearsal ranks (both on cuda:0, gloo) run to the end and rank 0's ONE result line, for two GPUs, is relayed."""
+    two rehearsal ranks (both on cuda:0, gloo) run to the end, each checking its last timed step (--full), and rank 0's
+    ONE result line, for two GPUs, is relayed."""
     import torch
     env = dict(os.environ, TG_BENCH_REHEARSE="1")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--scale", "10", "--batches-per-step", "4", "--no-secondary", "--no-cpu-baseline"],
+                        "--scale", "10", "--batches-per-step", "4", "--full", "--no-secondary", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600)
     if torch.cuda.is_available():
         assert p.returncode == 0, p.stderr[-2000:]
