@@ -695,6 +695,32 @@ TG_API int tg_budget_workspace_bytes(const tg_budget_problem *problem, int64_t *
 TG_API int tg_budget_sample(const tg_budget_problem *problem, const tg_rng *rng, const tg_budget_out *out, void *workspace,
                             int64_t workspace_bytes, void *stream);
 
+/* Batched budget_sampling: n_calls independent calls of one problem shape in ONE launch chain (the call is the third grid
+ * dimension of every launch, so the chain is as long as a single call's).  The calls share the graphs, n_inputs,
+ * num_neighbors and the temporal filter; problem->inputs[t] / input_ts[t] point at [n_calls, n_inputs[t]] row-major slabs.
+ * Call b draws with call id rng->call_id + b and equals tg_budget_sample run alone with that call id, word for word.
+ *  - outputs: row b of every slab is call b's; only its first counts[b][...] words are written.  counts[b] holds the
+ *    node counts of the types, then the edge counts of the relations (budget sampling never panics on the device).
+ *  - capacities: tg_budget_capacity's, per call.
+ *  - workspace: n_calls regions at a fixed stride, nothing shared: tg_budget_batched_workspace_bytes(p, n) =
+ *    n * tg_budget_batched_workspace_bytes(p, 1) (= n * tg_budget_workspace_bytes(p)); 8-byte aligned.
+ *    1 <= n_calls <= TG_BUDGET_MAX_CALLS (grid z).
+ *  - limits: tg_budget_sample's (<= 8 node types, <= 16 relations, num_neighbors <= 64).  Shapes past them and bad
+ *    arguments are refused with TG_ERR_INVALID before anything is launched. */
+#define TG_BUDGET_MAX_CALLS 65535
+typedef struct {
+    int64_t *const *samples, *const *sample_ts;             /* host [n_types] device slabs [n_calls, pitch_nodes[t]] */
+    const int64_t *pitch_nodes;                             /* host [n_types], >= tg_budget_capacity()'s cap_nodes */
+    int64_t *const *rows, *const *cols, *const *edge_index; /* host [n_rels] device slabs [n_calls, pitch_edges[r]] */
+    const int64_t *pitch_edges;                             /* host [n_rels], >= tg_budget_capacity()'s cap_edges */
+    int64_t *counts;                                        /* device [n_calls, n_types + n_rels] */
+} tg_budget_batched_out;
+
+TG_API int tg_budget_batched_workspace_bytes(const tg_budget_problem *problem, int64_t n_calls, int64_t *bytes);
+TG_API int tg_budget_sample_batched(const tg_budget_problem *problem, int64_t n_calls, const tg_rng *rng,
+                                    const tg_budget_batched_out *out, void *workspace, int64_t workspace_bytes,
+                                    void *stream);
+
 /* ---- synthetic inputs of the measurement harness ---- */
 
 /* R-MAT edge list: n_edges edges over 2^scale vertices, (a,b,c,d) =

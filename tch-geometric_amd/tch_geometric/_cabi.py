@@ -33,7 +33,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_debug_bounds_set_flag", "tg_part_sample_workspace_bytes", "tg_part_sample_ws",
            "tg_part_sample_order_thresholds", "tg_ns_homo_batched_pipeline", "tg_graph_max_degree",
            "tg_ns_homo_workspace_bytes_for", "tg_ns_homo_batched_workspace_bytes", "tg_hgt_batched_capacity",
-           "tg_hgt_batched_workspace_bytes", "tg_hgt_sample_batched"]
+           "tg_hgt_batched_workspace_bytes", "tg_hgt_sample_batched", "tg_budget_batched_workspace_bytes",
+           "tg_budget_sample_batched"]
 
 
 class TgGraph(C.Structure):
@@ -488,6 +489,124 @@ class HgtBatched:
         return ([self.samples[t][b, :c[t]] for t in range(T)], [self.sample_ts[t][b, :c[t]] for t in range(T)],
                 [self.rows[r][b, :c[T + r]] for r in range(R)], [self.cols[r][b, :c[T + r]] for r in range(R)],
                 [self.edge_index[r][b, :c[T + r]] for r in range(R)], c[T + R])
+
+
+class TgBudgetProblem(C.Structure):
+    _fields_ = [("n_types", C.c_int32), ("n_rels", C.c_int32), ("n_hops", C.c_int32), ("filter_on", C.c_int32),
+                ("forward", C.c_int32), ("relative", C.c_int32), ("win_lo", C.c_int64), ("win_hi", C.c_int64),
+                ("rel_src", C.POINTER(C.c_int32)), ("rel_dst", C.POINTER(C.c_int32)), ("graphs", C.POINTER(TgGraph)),
+                ("num_neighbors", C.POINTER(C.c_int64)), ("inputs", C.POINTER(C.c_void_p)),
+                ("input_ts", C.POINTER(C.c_void_p)), ("n_inputs", C.POINTER(C.c_int64))]
+
+
+class TgBudgetBatchedOut(C.Structure):
+    _fields_ = [("samples", C.POINTER(C.c_void_p)), ("sample_ts", C.POINTER(C.c_void_p)),
+                ("pitch_nodes", C.POINTER(C.c_int64)), ("rows", C.POINTER(C.c_void_p)), ("cols", C.POINTER(C.c_void_p)),
+                ("edge_index", C.POINTER(C.c_void_p)), ("pitch_edges", C.POINTER(C.c_int64)), ("counts", C.c_void_p)]
+
+
+def budget_problem(n_types, rels, n_inputs, num_neighbors, n_hops, inputs=None, input_ts=None, window=None, forward=False,
+                   relative=False):
+    """A tg_budget_problem.  rels: list of (src type index, dst type index, ptrs, indices, row timestamps or None);
+    n_inputs: per type; num_neighbors: per type a list of n_hops quotas; inputs / input_ts: per type a device tensor or
+    None (input_ts None: no input timestamps at all); window = (lo, hi) turns the temporal filter on (python.rs:541-548)."""
+    T, R = n_types, len(rels)
+    p = TgBudgetProblem()
+    p.n_types, p.n_rels, p.n_hops = T, R, n_hops
+    rel_src = (C.c_int32 * max(R, 1))(*[r[0] for r in rels])
+    rel_dst = (C.c_int32 * max(R, 1))(*[r[1] for r in rels])
+    graphs = (TgGraph * max(R, 1))()
+    for i, r in enumerate(rels):
+        graphs[i] = graph_view(r[2], r[3], timestamps=r[4] if len(r) > 4 else None)
+    nn = (C.c_int64 * max(T * n_hops, 1))(*[int(q[h]) for q in num_neighbors for h in range(n_hops)])
+    n_in = (C.c_int64 * T)(*[int(x) for x in n_inputs])
+    vp = lambda ts: (C.c_void_p * T)(*[None if x is None or x.numel() == 0 else x.data_ptr() for x in ts])
+    ins = vp(inputs if inputs is not None else [None] * T)
+    its = vp(input_ts) if input_ts is not None else None
+    p.rel_src, p.rel_dst, p.graphs, p.n_inputs, p.num_neighbors = rel_src, rel_dst, graphs, n_in, nn
+    p.inputs = ins
+    p.input_ts = its if its is not None else C.POINTER(C.c_void_p)()
+    if window is not None:
+        p.filter_on, p.forward, p.relative = 1, int(bool(forward)), int(bool(relative))
+        p.win_lo, p.win_hi = int(window[0]), int(window[1])
+    p._keep = (rels, inputs, input_ts, rel_src, rel_dst, graphs, nn, n_in, ins, its)
+    return p
+
+
+def budget_capacity(problem):
+    """-> (cap_nodes [T], cap_edges [R]) of one call (tg_budget_capacity: the worst case of every list)."""
+    cn, ce = (C.c_int64 * problem.n_types)(), (C.c_int64 * max(problem.n_rels, 1))()
+    check(lib.tg_budget_capacity(C.byref(problem), cn, ce))
+    return list(cn), list(ce)[:problem.n_rels]
+
+
+def budget_batched_workspace_bytes(problem, n_calls):
+    nbytes = C.c_int64(0)
+    check(lib.tg_budget_batched_workspace_bytes(C.byref(problem), C.c_int64(n_calls), C.byref(nbytes)))
+    return nbytes.value
+
+
+def budget_batched_pitches(problem, pad=0):
+    """Row pitches of BudgetBatched's slabs: the capacity + pad words, at least one."""
+    cap_n, cap_e = budget_capacity(problem)
+    return [max(c + pad, 1) for c in cap_n], [max(c + pad, 1) for c in cap_e]
+
+
+def budget_batched_bytes(problem, n_calls, pad=0):
+    """Device bytes of one launch as BudgetBatched allocates it: the workspace, the output slabs (sized for the worst case,
+    far above typical counts) and the counts."""
+    pn, pe = budget_batched_pitches(problem, pad)
+    words = 2 * sum(pn) + 3 * sum(pe) + len(pn) + len(pe)
+    return budget_batched_workspace_bytes(problem, n_calls) + 8 * n_calls * words
+
+
+class BudgetBatched:
+    """Problem description, output slabs and workspace of tg_budget_sample_batched: n_calls budget_sampling calls of one
+    shape per launch chain.  inputs / input_ts: per node type a [n_calls, n_inputs] tensor or None (no inputs);
+    num_neighbors: per type a list of n_hops quotas; rels as in budget_problem.  pad: extra words per slab row (the pitches
+    then exceed the capacities).  Call b of run(seed, call_id) equals budget_sampling with call id call_id + b."""
+
+    def __init__(self, n_types, rels, inputs, num_neighbors, n_hops, n_calls, device, input_ts=None, window=None,
+                 forward=False, relative=False, pad=0):
+        T, R = n_types, len(rels)
+        self.T, self.R, self.H, self.nc, self.dev = T, R, n_hops, int(n_calls), device
+        n_in = [0 if x is None else int(x.shape[-1]) for x in inputs]
+        flat = lambda xs: [None if x is None else x.reshape(n_calls, n_in[t]).contiguous() for t, x in enumerate(xs)]
+        self.inputs = flat(inputs)
+        self.input_ts = flat(input_ts) if input_ts is not None else None
+        self.problem = budget_problem(T, rels, n_in, num_neighbors, n_hops, self.inputs, self.input_ts, window, forward,
+                                      relative)
+        self.cap_nodes, self.cap_edges = budget_capacity(self.problem)
+        self.node_pitch, self.edge_pitch = budget_batched_pitches(self.problem, pad)
+        o = dict(dtype=torch.int64, device=device)
+        self.samples = [torch.empty((n_calls, p), **o) for p in self.node_pitch]
+        self.sample_ts = [torch.empty((n_calls, p), **o) for p in self.node_pitch]
+        self.rows = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
+        self.cols = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
+        self.edge_index = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
+        self.counts = torch.zeros((n_calls, T + R), **o)
+        self.workspace_bytes = budget_batched_workspace_bytes(self.problem, n_calls)
+        self.workspace = torch.empty(self.workspace_bytes // 8 + 1, **o)
+        self.launch_bytes = budget_batched_bytes(self.problem, n_calls, pad)
+        vp = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
+        i64 = lambda xs: (C.c_int64 * max(len(xs), 1))(*xs)
+        self._arrays = [vp(self.samples), vp(self.sample_ts), i64(self.node_pitch), vp(self.rows), vp(self.cols),
+                        vp(self.edge_index), i64(self.edge_pitch)]
+        self.out = TgBudgetBatchedOut(*self._arrays, self.counts.data_ptr())
+
+    def run(self, seed, call_id):
+        rng = TgRng(seed, call_id)
+        check(lib.tg_budget_sample_batched(C.byref(self.problem), C.c_int64(self.nc), C.byref(rng), C.byref(self.out),
+                                           ptr(self.workspace), C.c_int64(self.workspace_bytes), stream_ptr(self.dev)))
+
+    def call(self, b, counts=None):
+        """Call b's results -> (samples [T], sample_ts [T], rows [R], cols [R], edge_index [R]) trimmed to its counts
+        (counts: the counts block already read back, else it is read here)."""
+        c = (self.counts[b].tolist() if counts is None else [int(x) for x in counts[b]])
+        T, R = self.T, self.R
+        return ([self.samples[t][b, :c[t]] for t in range(T)], [self.sample_ts[t][b, :c[t]] for t in range(T)],
+                [self.rows[r][b, :c[T + r]] for r in range(R)], [self.cols[r][b, :c[T + r]] for r in range(R)],
+                [self.edge_index[r][b, :c[T + r]] for r in range(R)])
 
 
 BIAS = {"uniform": 0, "linear": 1, "exponential": 2}

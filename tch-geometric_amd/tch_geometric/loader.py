@@ -501,3 +501,167 @@ class HGTLoader:
         if not self.drop_last and n_full * B < nodes.numel():
             yield from self._emit(nodes[n_full * B:].reshape(1, -1), None if ts is None else ts[n_full * B:].reshape(1, -1),
                                   batch0 + n_full)
+
+
+def _flat_rows(slab: Tensor, lens: Tensor, total: int) -> Tensor:
+    """tg_compact_rows, or an empty tensor when the rows hold nothing (the library refuses a null destination)."""
+    if total == 0:
+        return torch.empty(0, dtype=torch.int64, device=slab.device)
+    return _cabi.compact_rows(slab, lens, total)
+
+
+class BudgetLoader:
+    """Temporal heterogeneous budget sampling (budget_sampling) as a loader: seeds of ONE node type, `prefetch`
+    mini-batches per tg_budget_sample_batched launch chain, one read-back of the counts per launch, per-type /
+    per-relation slabs flattened by tg_compact_rows, node attributes gathered per type and edge attributes per relation.
+    num_neighbors: one list of per-hop quotas for every node type or a dict per type.  temporal=True uses the edge
+    stores' int64 `timestamps` as row timestamps and `input_timestamps` (one per input node) as the seeds' timestamps;
+    `window` = [lo, hi) turns the temporal filter on, with `forward` / `relative` as in budget_sampling.
+
+    The operator's edge_index is the neighbour's index inside its CSC column (a quirk kept from the reference,
+    budget_sampling.rs:116), so e_id = perm[col_ptrs[n_id_dst[col]] + edge_index], computed on the device.
+
+    Mini-batch j of the epoch equals budget_sampling for (seed, call_id0 + j); every epoch draws fresh call ids.  A
+    launch's device memory is prefetch x (workspace + output slabs + counts of one call): the slabs are sized for the
+    worst case and dominate, so prefetch is clamped to keep both within `max_workspace_bytes` (default 4 GiB; at least
+    one mini-batch per launch)."""
+
+    def __init__(self, data, num_neighbors, input_type: str, input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
+                 prefetch: int = 64, temporal: bool = False, input_timestamps: Optional[Tensor] = None, window=None,
+                 forward: bool = False, relative: bool = False, drop_last: bool = False, seed: int = 0, call_id0: int = 0,
+                 max_workspace_bytes: int = 4 << 30, device="cuda"):
+        self.data, self.device = data, torch.device(device)
+        self.node_types, self.edge_types = list(data.node_types), list(data.edge_types)
+        self.input_type, self.batch_size = input_type, int(batch_size)
+        self.drop_last, self.seed, self.call_id0 = drop_last, int(seed), int(call_id0)
+        if isinstance(num_neighbors, dict):
+            nn = {k: [int(x) for x in v] for k, v in num_neighbors.items()}
+            self.n_hops = max((len(v) for v in nn.values()), default=0)
+        else:
+            self.n_hops = len(num_neighbors)
+            nn = {nt: [int(x) for x in num_neighbors] for nt in self.node_types}
+        for nt in self.node_types:
+            if self.n_hops and nt not in nn:
+                raise ValueError("num_neighbors has no entry for node type %s (budget_sampling panics here)" % nt)
+            if self.n_hops and len(nn[nt]) < self.n_hops:
+                raise ValueError("num_neighbors[%s] is shorter than the number of hops" % nt)
+        self.num_neighbors = [nn[nt][:self.n_hops] if self.n_hops else [] for nt in self.node_types]
+        self.window = None if window is None else (int(window[0]), int(window[1]))
+        self.forward, self.relative = bool(forward), bool(relative)
+        self.col_ptrs, self.row_indices, self.perm = to_hetero_csc(data, self.device)
+        self.temporal = temporal
+        self._tix = {t: i for i, t in enumerate(self.node_types)}
+        rts = {}
+        if temporal:  # timestamps follow the CSC edge order
+            rts = {rel_key(et): _cabi.gather_rows(data[et].timestamps.to(self.device).to(torch.int64),
+                                                  self.perm[rel_key(et)])[0] for et in self.edge_types}
+        self._rels = [(self._tix[et[0]], self._tix[et[2]], self.col_ptrs[rel_key(et)], self.row_indices[rel_key(et)],
+                       rts.get(rel_key(et))) for et in self.edge_types]
+        n_in = _num_nodes(data[input_type])
+        nodes = torch.arange(n_in, device=self.device) if input_nodes is None else input_nodes.to(self.device)
+        self.input_nodes = _checked_inputs(nodes, n_in)
+        self.input_ts = None
+        if temporal:
+            if input_timestamps is None:
+                raise ValueError("temporal=True needs input_timestamps (one per input node)")
+            self.input_ts = input_timestamps.to(self.device).reshape(-1).to(torch.int64)
+            if self.input_ts.numel() != self.input_nodes.numel():
+                raise ValueError("input_timestamps must have one entry per input node")
+        per_call = _cabi.budget_batched_bytes(self._problem(self.batch_size), 1)
+        self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // per_call))
+        self.epoch = 0
+        self._launch = {}                                       # (calls, seeds per call) -> BudgetBatched
+        self._node_attrs = {t: [(k, v.to(self.device)) for k, v in _tensor_items(data[t])
+                                if v.dim() > 0 and v.shape[0] == _num_nodes(data[t])] for t in self.node_types}
+        self._edge_attrs = {}
+        for et in self.edge_types:
+            n_e = int(data[et].edge_index.shape[1])
+            self._edge_attrs[et] = [(k, v.to(self.device)) for k, v in _tensor_items(data[et])
+                                    if k != "edge_index" and v.dim() > 0 and v.shape[0] == n_e]
+
+    def _problem(self, n_seeds):
+        """A host-only problem of the loader's shape (sizes a launch; nothing is launched)."""
+        n_in = [n_seeds if nt == self.input_type else 0 for nt in self.node_types]
+        return _cabi.budget_problem(len(self.node_types), self._rels, n_in, self.num_neighbors, self.n_hops)
+
+    def __len__(self) -> int:
+        n = self.input_nodes.numel()
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def _emit(self, seeds: Tensor, seeds_ts: Optional[Tensor], first_batch: int) -> Iterator[HeteroGraph]:
+        G, B = seeds.shape
+        T = len(self.node_types)
+        it = self._tix[self.input_type]
+        inputs = [None] * T
+        inputs[it] = seeds.contiguous()
+        input_ts = None
+        if seeds_ts is not None:
+            input_ts = [None] * T
+            input_ts[it] = seeds_ts.contiguous()
+        bb = self._launch.get((G, B))
+        if bb is None:  # full launches reuse one set of slabs; a shorter last launch gets its own, freed after use
+            bb = _cabi.BudgetBatched(T, self._rels, [None if x is None else x.clone() for x in inputs], self.num_neighbors,
+                                     self.n_hops, G, self.device,
+                                     input_ts=None if input_ts is None else [None if x is None else x.clone() for x in input_ts],
+                                     window=self.window, forward=self.forward, relative=self.relative)
+            if G == self.prefetch and B == self.batch_size:
+                self._launch = {(G, B): bb}
+        else:
+            bb.inputs[it].copy_(seeds)
+            if seeds_ts is not None:
+                bb.input_ts[it].copy_(seeds_ts)
+        bb.run(self.seed, self.call_id0 + first_batch)
+        counts = bb.counts.cpu()                                # the launch's only read-back
+        rows_of = lambda table, index: _cabi.gather_rows(table, index)[0]
+        node_parts, ts_parts, attr_parts, flat_nodes, node_off = {}, {}, {}, [], []
+        for t, nt in enumerate(self.node_types):
+            lens = counts[:, t].tolist()
+            flat = _flat_rows(bb.samples[t], bb.counts[:, t], sum(lens))
+            flat_nodes.append(flat)
+            node_off.append(torch.cumsum(bb.counts[:, t], 0) - bb.counts[:, t])   # where call b's nodes start in `flat`
+            node_parts[nt] = (torch.split(flat, lens), lens)
+            ts_parts[nt] = torch.split(_flat_rows(bb.sample_ts[t], bb.counts[:, t], sum(lens)), lens)
+            attr_parts[nt] = {k: torch.split(rows_of(v, flat), lens) for k, v in self._node_attrs[nt]}
+        edge_parts = {}
+        for r, et in enumerate(self.edge_types):
+            key, d = rel_key(et), self._tix[et[2]]
+            ne = bb.counts[:, T + r]
+            lens = counts[:, T + r].tolist()
+            tot = sum(lens)
+            fr = _flat_rows(bb.rows[r], ne, tot)
+            fc = _flat_rows(bb.cols[r], ne, tot)
+            fi = _flat_rows(bb.edge_index[r], ne, tot)
+            # e_id: the destination's node id -> its column start in the CSC -> + index inside the column -> COO edge id
+            w = rows_of(flat_nodes[d], fc + torch.repeat_interleave(node_off[d], ne, output_size=tot))
+            fe = rows_of(self.perm[key], rows_of(self.col_ptrs[key], w) + fi)
+            edge_parts[et] = (torch.split(torch.stack([fr, fc]), lens, dim=1), torch.split(fe, lens),
+                              {k: torch.split(rows_of(v, fe), lens) for k, v in self._edge_attrs[et]})
+        for b in range(G):
+            g = HeteroGraph()
+            for nt in self.node_types:
+                st = g[nt]
+                st.n_id, st.num_nodes = node_parts[nt][0][b], node_parts[nt][1][b]
+                for k, parts in attr_parts[nt].items():
+                    setattr(st, k, parts[b])
+            g[self.input_type].batch_size = B
+            for et in self.edge_types:
+                st = g[et]
+                st.edge_index, st.e_id = edge_parts[et][0][b], edge_parts[et][1][b]
+                for k, parts in edge_parts[et][2].items():
+                    setattr(st, k, parts[b])
+            g.samples_timestamps = {nt: ts_parts[nt][b] for nt in self.node_types}
+            g.call_id = self.call_id0 + first_batch + b
+            yield g
+
+    def __iter__(self) -> Iterator[HeteroGraph]:
+        nodes, ts, B = self.input_nodes, self.input_ts, self.batch_size
+        batch0 = self.epoch * len(self)                         # fresh draws every epoch (see NeighborLoader)
+        self.epoch += 1
+        n_full = nodes.numel() // B
+        for start in range(0, n_full, self.prefetch):
+            G = min(self.prefetch, n_full - start)
+            sl = slice(start * B, (start + G) * B)
+            yield from self._emit(nodes[sl].reshape(G, B), None if ts is None else ts[sl].reshape(G, B), batch0 + start)
+        if not self.drop_last and n_full * B < nodes.numel():
+            yield from self._emit(nodes[n_full * B:].reshape(1, -1), None if ts is None else ts[n_full * B:].reshape(1, -1),
+                                  batch0 + n_full)
