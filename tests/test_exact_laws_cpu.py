@@ -1,0 +1,358 @@
+"""The closed-form laws of exact_laws.py against exhaustive enumeration of the reference's loops (rational arithmetic), the
+oracle's philox-mode (the counter-addressed restatements the kernels share) against those laws on long columns, and the
+power of the test against named wrong laws at the sample sizes tests/test_gpu_exact_laws.py uses."""
+from collections import Counter
+from fractions import Fraction
+from itertools import product
+
+import numpy as np
+import pytest
+import torch
+
+import exact_laws as L
+import orc
+from exact_laws import N_NEG, N_WALK, n_outcomes
+from test_reservoir_equivalence import law_reference_loop, law_tickets
+
+
+# ---------------------------------------------------------------- closed forms == enumeration
+def _slot_marginals(law_counter, n, k):
+    M = np.zeros((k, n))
+    for dst, p in law_counter.items():
+        for s, v in enumerate(dst):
+            M[s, v] += float(p)
+    return M
+
+
+def _pair(law_counter, n, s, t):
+    J = np.zeros((n, n))
+    for dst, p in law_counter.items():
+        J[dst[s], dst[t]] += float(p)
+    return J
+
+
+def _binned_pair(J, law, edges):
+    """fold an exact [n, n] joint law of two slots into ReservoirLaw.pair_table's categories"""
+    cat = np.searchsorted(edges, np.arange(law.n), side="right")
+    m = len(edges) - 1
+    T = np.zeros((m + 1, m + 1))
+    np.add.at(T, (cat[:, None].repeat(law.n, 1), cat[None, :].repeat(law.n, 0)), J)
+    return T
+
+
+def law_weighted_loop(w, k):
+    """sampling.rs:28-55 enumerated: candidate i >= k is taken with probability w_i / W_i, then writes slot
+    U[0, k)."""
+    w = [Fraction(x) for x in w]
+    n = len(w)
+    law = Counter({tuple(range(k)): Fraction(1)})
+    W = sum(w[:k])
+    for i in range(k, n):
+        W += w[i]
+        t = w[i] / W
+        nxt = Counter()
+        for dst, p in law.items():
+            nxt[dst] += p * (1 - t)
+            for j in range(k):
+                d = list(dst)
+                d[j] = i
+                nxt[tuple(d)] += p * t / k
+        law = nxt
+    return law
+
+
+def law_chunked_one_slot(raw_pos):
+    """orc_reservoir_one_chunked enumerated over its chunk draws: a chunk with m eligible candidates after M takes the
+    slot with probability m / (M + m) and holds each of its m with probability 1 / m."""
+    n = len(raw_pos)
+    P = [Fraction(0)] * n
+    P[0] = Fraction(1)
+    seen, i = 0, 1
+    while i < n:
+        j = i
+        while j < n and raw_pos[j] >> 6 == raw_pos[i] >> 6:
+            j += 1
+        m = j - i
+        t = Fraction(1) if seen == 0 else Fraction(m, seen + m)
+        P = [x * (1 - t) for x in P[:i]] + [t / m] * m + P[j:]
+        seen += m
+        i = j
+    return P
+
+
+@pytest.mark.parametrize("n,k", [(2, 1), (5, 1), (4, 2), (6, 2), (7, 3), (8, 3), (7, 5)])
+def test_uniform_closed_form_equals_enumeration(n, k):
+    ref = law_reference_loop(n, k)
+    assert law_tickets(n, k) == ref
+    law = L.uniform_law(n, k)
+    M = _slot_marginals(ref, n, k)
+    for s in range(k):
+        assert np.allclose(law.marginal(s), M[s], atol=1e-14, rtol=0)
+    if k >= 2:
+        edges = np.arange(k, n + 1)                                        # one bin per later position: exact pairs
+        for s, t in ((0, 1), (1, 0), (0, k - 1)):
+            assert np.allclose(law.pair_table(edges), _binned_pair(_pair(ref, n, s, t), law, edges), atol=1e-14, rtol=0)
+        coarse = np.array([k, (k + n + 1) // 2, n]) if n - k > 1 else np.array([k, n])
+        assert np.allclose(law.pair_table(coarse), _binned_pair(_pair(ref, n, 0, 1), law, coarse), atol=1e-14, rtol=0)
+
+
+@pytest.mark.parametrize("w,k", [([1, 2, 3, 4, 5, 6], 2), ([3, 0, 1, 0, 7, 2, 5], 2), ([1, 5, 0, 2, 9], 1),
+                                 ([0, 2, 1e-3, 0, 6, 1, 4], 3), ([1, 1, 1, 1, 1, 1, 1], 3)])
+def test_weighted_closed_form_equals_enumeration(w, k):
+    ref = law_weighted_loop(w, k)
+    n = len(w)
+    law = L.weighted_law(w, k)
+    M = _slot_marginals(ref, n, k)
+    for s in range(k):
+        assert np.allclose(law.marginal(s), M[s], atol=1e-13, rtol=0)
+    zero = [p for p in range(k, n) if w[p] == 0]
+    assert all(M[:, p].sum() == 0 for p in zero) and all(law.marginal(0)[p] == 0 for p in zero)
+    if k >= 2:
+        edges = np.arange(k, n + 1)
+        for s, t in ((0, 1), (k - 1, 0)):
+            assert np.allclose(law.pair_table(edges), _binned_pair(_pair(ref, n, s, t), law, edges), atol=1e-13, rtol=0)
+
+
+@pytest.mark.parametrize("raw", [[0], [3, 9], list(range(10)), [5, 70, 71, 200, 300], [0, 63, 64, 65, 127, 128, 1000],
+                                 [70, 71, 72, 500, 4999]])
+def test_one_slot_laws_equal_enumeration(raw):
+    n = len(raw)
+    exact = law_chunked_one_slot(raw)
+    assert sum(exact) == 1
+    assert np.allclose(L.one_slot_walk_law(n), [float(x) for x in exact], atol=1e-15, rtol=0)
+    assert np.allclose(L.one_slot_chunked_law(raw), L.one_slot_walk_law(n), atol=1e-15, rtol=0)
+    if n <= 8:                                                           # the literal loop with k = 1
+        lit = law_reference_loop(n, 1) if n > 1 else Counter({(0,): Fraction(1)})
+        assert [float(lit.get((c,), 0)) for c in range(n)] == pytest.approx(L.one_slot_walk_law(n), abs=1e-15)
+
+
+def test_negative_item_law_equals_enumeration():
+    size, tries = 6, 3
+    adm = np.array([0, 1, 1, 0, 1, 0], dtype=bool)
+    P = [Fraction(0)] * (size + 1)
+    for ws in product(range(size), repeat=tries):                        # every draw sequence, equally likely
+        hit = next((w for w in ws if adm[w]), None)
+        P[size if hit is None else hit] += Fraction(1, size ** tries)
+    assert np.allclose(L.negative_item_law(size, adm, tries), [float(x) for x in P], atol=1e-15, rtol=0)
+
+
+def test_node2vec_law_is_the_rejection_loop_fixed_point():
+    """the loop's law: P(v) = sum_r (1 - A)^r acc_v / deg = acc_v / (deg A), A the mean acceptance (exact)"""
+    ptrs = np.array([0, 1, 5, 6, 8, 9])
+    col = np.array([1, 0, 2, 2, 3, 4, 0, 1, 1])                          # vertex 1's row: 0, 2, 2, 3 (a multiplicity)
+    law = L.node2vec_step_law(ptrs, col, 1, 0, 0.5, 4.0)
+    p0, p1, p2 = L.node2vec_probs(0.5, 4.0)
+    acc = np.array([p0, p2, p2, p1])                                     # 0 = prev; 3 -> 0 is an edge; 2 -> 0 is not
+    assert np.allclose(law, acc / acc.sum())
+
+
+# ---------------------------------------------------------------- the oracle's philox-mode on long columns
+def _hub(n):
+    return np.array([0, n], dtype=np.int64), np.zeros(n, dtype=np.int64)
+
+
+N_CPU = 1 << 16
+
+
+@pytest.mark.parametrize("n,k", [(18, 17), (64, 17), (1000, 33), (70000, 65), (1000, 129)])
+def test_oracle_uniform_reservoir_follows_the_exact_law(n, k):
+    N = N_CPU if k < 100 else N_CPU // 4
+    ptrs, idx = _hub(n)
+    o = orc.ns_homo(ptrs, idx, np.zeros(N, dtype=np.int64), [k], orc.rng_philox(0xE1, 3))
+    E = torch.from_numpy(o[3].reshape(N, k))
+    assert L.check_reservoir(E, L.uniform_law(n, k), "oracle uniform k=%d n=%d" % (k, n)) > 0
+
+
+def test_oracle_replacement_follows_the_exact_law():
+    n, k = 1000, 33
+    ptrs, idx = _hub(n)
+    o = orc.ns_homo(ptrs, idx, np.zeros(N_CPU, dtype=np.int64), [k], orc.rng_philox(0xE2, 3), sampler=1)
+    L.check_reservoir(torch.from_numpy(o[3].reshape(N_CPU, k)), L.ReplacementLaw(n, k), "oracle replacement", replace=True)
+
+
+def weights_wide(n, seed):
+    """weights 1e-6 .. 1e6 (log-uniform) with zeros interleaved; the first candidate positive (the reference panics on
+    an empty running sum)"""
+    rs = np.random.default_rng(seed)
+    w = 10.0 ** rs.uniform(-6, 6, n)
+    w[rs.random(n) < 0.25] = 0.0
+    w[0] = 1.0
+    return w
+
+
+@pytest.mark.parametrize("n,k", [(65, 5), (5000, 5), (5000, 64), (513, 1)])
+def test_oracle_weighted_reservoir_follows_the_exact_law(n, k):
+    ptrs, idx = _hub(n)
+    w = weights_wide(n, n + k)
+    o = orc.ns_homo(ptrs, idx, np.zeros(N_CPU, dtype=np.int64), [k], orc.rng_philox(0xE3, 3), sampler=2, weights=w)
+    E = torch.from_numpy(o[3].reshape(N_CPU, k))
+    L.check_reservoir(E, L.weighted_law(w, k), "oracle weighted k=%d n=%d" % (k, n), zero_pos=torch.from_numpy(w == 0))
+
+
+def test_oracle_filtered_weighted_reservoir_follows_the_law_on_the_admitted_subsequence():
+    n, k = 5000, 5
+    rs = np.random.default_rng(9)
+    ts = rs.integers(0, 90, n)
+    w = weights_wide(n, 77)
+    adm = (ts >= 10) & (ts <= 40)                                        # FILTER_STATIC: the window is inclusive
+    ptrs, idx = _hub(n)
+    o = orc.ns_homo(ptrs, idx, np.zeros(N_CPU, dtype=np.int64), [k], orc.rng_philox(0xE4, 3), sampler=2, weights=w,
+                    filter_mode=0, window=(10, 40), timestamps=ts, inputs_state=np.zeros(N_CPU, dtype=np.int64))
+    rank = np.full(n, -1)
+    rank[adm] = np.arange(adm.sum())
+    E = torch.from_numpy(rank[o[3].reshape(N_CPU, k)])
+    wa = w[adm]
+    L.check_reservoir(E, L.weighted_law(wa, k), "oracle filtered weighted", zero_pos=torch.from_numpy(wa == 0))
+
+
+def walk_row(length, pattern):
+    """admissible raw positions of a tempo-walk row: 'scatter' (about a third), 'edges' (first admissible candidate in
+    chunk 1, empty chunks between, one in the last chunk and around every chunk boundary)"""
+    if pattern == "all":
+        return np.arange(length)
+    if pattern == "scatter":
+        return np.flatnonzero(np.random.default_rng(length).random(length) < 0.35)
+    pos = {64, length - 1}
+    for c in range(1, (length - 1) // 64 + 1):
+        if c % 3 != 2:                                                   # every third chunk stays empty
+            pos |= {64 * c - 1, 64 * c, 64 * c + 1} if c > 1 else {64, 65}
+    return np.array(sorted(p for p in pos if 64 <= p < length))
+
+
+def tempo_graph(length, adm):
+    """vertex 0's CSR row: `length` out-edges to vertices 1..length, edge time 10 where admissible, 100 elsewhere"""
+    ptrs = np.zeros(length + 2, dtype=np.int64)
+    ptrs[1:] = length
+    idx = np.arange(1, length + 1, dtype=np.int64)
+    ets = np.full(length, 100, dtype=np.int64)
+    ets[adm] = 10
+    return ptrs, idx, np.full(length + 1, -1, dtype=np.int64), ets
+
+
+@pytest.mark.parametrize("length,pattern", [(2, "all"), (65, "edges"), (129, "edges"), (5000, "edges"), (5000, "scatter")])
+def test_oracle_chunked_walk_step_follows_the_exact_law(length, pattern):
+    adm = walk_row(length, pattern)
+    ptrs, idx, nts, ets = tempo_graph(length, adm)
+    st = np.zeros(N_CPU, dtype=np.int64)
+    w, _ = orc.tempo_random_walk(ptrs, idx, nts, ets, st, np.full(N_CPU, 5, dtype=np.int64), 2, (0, 20),
+                                 orc.rng_philox(0xE5, 1))
+    rank = np.full(length + 1, -1)
+    rank[adm + 1] = np.arange(adm.size)
+    L.chi2_gof(np.bincount(rank[w[:, 1]], minlength=adm.size), L.one_slot_walk_law(adm.size), "oracle tempo walk")
+
+
+def node2vec_graph(row):
+    """start S = 0 -> hub H = 1 only; H's row of `row` entries: S once, vertices 2..9 (which have S in their rows:
+    distance 1) twice each, the rest distance-2 vertices; so step 2 (prev = S, cur = H) sees all three cases"""
+    near = list(range(2, 10))
+    far = list(range(10, 10 + row - 1 - 2 * len(near)))
+    n = far[-1] + 1
+    rows = {0: [1], 1: sorted([0] + near * 2 + far)}
+    for v in near:
+        rows[v] = [0, 1]
+    for v in far:
+        rows[v] = [1]
+    ptrs = np.zeros(n + 1, dtype=np.int64)
+    ptrs[1:] = np.cumsum([len(rows[v]) for v in range(n)])
+    col = np.concatenate([rows[v] for v in range(n)]).astype(np.int64)
+    return ptrs, col, n
+
+
+def test_oracle_node2vec_step_follows_the_exact_law():
+    ptrs, col, n = node2vec_graph(100)
+    w = orc.random_walk(ptrs, col, np.zeros(N_CPU, dtype=np.int64), 2, 0.5, 4.0, orc.rng_philox(0xE6, 1))
+    assert np.all(w[:, 1] == 1)
+    law = L.node2vec_step_law(ptrs, col, 1, 0, 0.5, 4.0)
+    P = np.bincount(col[ptrs[1]:ptrs[2]], weights=law, minlength=n)
+    L.chi2_gof(np.bincount(w[:, 2], minlength=n), P / P.sum(), "oracle node2vec step 2")
+
+
+@pytest.mark.parametrize("bias", ["uniform", "linear", "exponential"])
+def test_oracle_biased_step_follows_the_exact_law(bias):
+    row = 65
+    times = 5 + np.random.default_rng(2).permutation(row)                # distinct times >= the start time 5
+    times[[0, np.argmin(times)]] = times[[np.argmin(times), 0]]          # candidate 0 weighs > 0 (else the reference panics)
+    ptrs = np.zeros(row + 2, dtype=np.int64)
+    ptrs[1:] = row
+    idx = np.arange(1, row + 1, dtype=np.int64)
+    w, _ = orc.biased_tempo_random_walk(ptrs, idx, np.full(row + 1, -1), times, np.zeros(N_CPU, dtype=np.int64),
+                                        np.full(N_CPU, 5, dtype=np.int64), 2, bias, True, 1, orc.rng_philox(0xE7, 1))
+    L.chi2_gof(np.bincount(w[:, 1] - 1, minlength=row), L.biased_step_law(times, 5, bias), "oracle biased " + bias)
+
+
+def test_oracle_negative_item_follows_the_exact_law():
+    size, tries = 1000, 3
+    rs = np.random.default_rng(5)
+    row = np.sort(rs.choice(size, size // 2, replace=False))
+    ptrs = np.zeros(size + 1, dtype=np.int64)
+    ptrs[1:] = row.size                                                  # vertex 0 holds the row
+    B, k = N_CPU // 8, 8
+    s, r, c, _ = orc.neg_homo(ptrs, row, (size, size), np.zeros(B, dtype=np.int64), k, tries, orc.rng_philox(0xE8, 1))
+    got = np.bincount(s[c], minlength=size + 1)
+    got[size] = B * k - c.size
+    adm = np.ones(size, dtype=bool)
+    adm[row] = False
+    adm[0] = False
+    L.chi2_gof(got, L.negative_item_law(size, adm, tries), "oracle negatives")
+
+
+# ---------------------------------------------------------------- power against named wrong laws, negative controls
+def _reject(counts, probs):
+    with pytest.raises(AssertionError):
+        L.chi2_gof(counts, probs, "wrong law")
+
+
+def test_power_uniform_without_the_quirk():
+    """j from 0..=i instead of 0..i: at the GPU file's k = 16, n = 64 the own-position marginal moves 15/63 -> 16/64"""
+    n, k = 64, 16
+    N = n_outcomes(k)
+    right, wrong = L.uniform_law(n, k).marginal(0), L.uniform_law(n, k, quirk=False).marginal(0)
+    assert L.power(wrong, right, N) >= 0.999
+    _reject(np.random.default_rng(1).multinomial(N, wrong), right)
+    L.chi2_gof(np.random.default_rng(1).multinomial(N, right), right, "right law")
+    n, k = 2, 1                                                          # k = 1, n = 2: the quirk always takes candidate 1
+    assert L.power(L.uniform_law(n, k, quirk=False).marginal(0), L.uniform_law(n, k).marginal(0), n_outcomes(1)) >= 0.999
+
+
+def test_power_weighted_with_the_previous_running_sum():
+    n, k = 5000, 5
+    w = weights_wide(n, n + k)
+    N = n_outcomes(k)
+    right, wrong = L.weighted_law(w, k).marginal(0), L.weighted_law(w, k, shift=True).marginal(0)
+    assert L.power(wrong, right, N) >= 0.999
+    _reject(np.random.default_rng(2).multinomial(N, wrong), right)
+    L.chi2_gof(np.random.default_rng(2).multinomial(N, right), right, "right law")
+
+
+def test_power_chunked_walk_step_off_by_one():
+    adm = walk_row(5000, "edges")
+    right, wrong = L.one_slot_walk_law(adm.size), L.one_slot_chunked_law(adm, off_by_one=True)
+    assert L.power(wrong, right, N_WALK) >= 0.999
+    _reject(np.random.default_rng(3).multinomial(N_WALK, wrong), right)
+    L.chi2_gof(np.random.default_rng(3).multinomial(N_WALK, right), right, "right law")
+
+
+def test_power_node2vec_p_q_swapped():
+    ptrs, col, n = node2vec_graph(100)
+    right, wrong = L.node2vec_step_law(ptrs, col, 1, 0, 0.5, 4.0), L.node2vec_step_law(ptrs, col, 1, 0, 4.0, 0.5)
+    assert L.power(wrong, right, N_WALK) >= 0.999
+    _reject(np.random.default_rng(4).multinomial(N_WALK, wrong), right)
+
+
+def test_power_negative_tries_off_by_one():
+    size = 1000
+    adm = np.ones(size, dtype=bool)
+    adm[: size // 2] = False
+    right, wrong = L.negative_item_law(size, adm, 3), L.negative_item_law(size, adm, 2)
+    assert L.power(wrong, right, N_NEG) >= 0.999
+    _reject(np.random.default_rng(5).multinomial(N_NEG, wrong), right)
+
+
+def test_power_of_a_biased_slot_at_k_129():
+    """slot 128 of 129 holding the 64 positions of one chunk 20 % too often"""
+    n, k = 1000, 129
+    right = L.uniform_law(n, k).marginal(128)
+    wrong = right.copy()
+    wrong[192:256] *= 1.2
+    wrong[k:] *= (1 - wrong[128]) / wrong[k:].sum()
+    assert L.power(wrong, right, n_outcomes(k)) >= 0.999
