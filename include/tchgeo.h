@@ -573,6 +573,47 @@ TG_API int tg_neg_workspace_bytes(const tg_neg_problem *problem, int64_t *bytes)
 TG_API int tg_neg_sample(const tg_neg_problem *problem, const tg_rng *rng, const tg_neg_out *out, void *workspace,
                          void *stream);
 
+/* Batched negative sampling: n_calls independent calls of one problem shape in ONE launch.  The calls share the graphs,
+ * n_inputs, num_neg and try_count; problem->inputs[t] points at an [n_calls, n_inputs[t]] row-major slab.  Call b draws
+ * with call id rng->call_id + b and equals tg_neg_sample run alone with that call id, word for word.
+ *  - form: where a call's state (32-bit candidates, local ids, one hash table over inputs and new nodes) fits the LDS of
+ *    a workgroup, ONE workgroup runs ONE whole call and only the CSR look-ups and the output stores touch global memory
+ *    (form 1, "fused").  Otherwise (too many items or inputs, node counts or CSR rows of 2^32 and more, more than 16 node
+ *    types, a device with less LDS) the same entry point runs tg_neg_sample's kernels call by call on the caller's
+ *    stream (form 0): same outputs, tg_neg_sample's speed.  tg_neg_batched_form tells which: lds_limit_bytes > 0 is taken
+ *    as the workgroup's LDS limit and no device is touched, <= 0 asks the current device (what tg_neg_sample_batched
+ *    does); *lds_bytes = what the fused kernel asks for (0 where 32-bit ids do not do).
+ *  - inputs must be valid node ids of their type (>= 0, below the row count of every relation that leaves the type), as for
+ *    tg_neg_sample; the fused form keeps ids in 32 bits, so ids outside [0, 2^32) would be merged there (the host
+ *    surfaces check the range before they launch).
+ *  - outputs: row b of every slab is call b's; only its first counts[b][...] words are written.  counts[b] holds the node
+ *    counts of the types, then the edge counts of the relations.  panic[b] = 1 where the reference would panic in call b
+ *    (inbound row out of range, negative_sampling.rs:113); that call's rows are then unspecified, every other call is
+ *    unaffected.
+ *  - capacities (tg_neg_batched_capacity), per call: tg_neg_out's, max(n_inputs[t], 0) + total items for a type,
+ *    n_inputs[src] * num_neg for a relation.  Pitches must be at least these.
+ *  - workspace: none for the fused form (0 bytes, the pointer may be NULL), tg_neg_workspace_bytes for the other (the
+ *    calls run one after the other in it); 8-byte aligned.  1 <= n_calls <= TG_NEG_MAX_CALLS.
+ *  - bad arguments (null, n_calls, more than 32 relations, negative counts, a type with inputs and no outgoing
+ *    relation, short pitches, short workspace) are refused with TG_ERR_INVALID before anything is launched.  Nothing
+ *    synchronises. */
+#define TG_NEG_MAX_CALLS 65535
+typedef struct {
+    int64_t *const *samples;    /* host [n_types] device slabs [n_calls, pitch_nodes[t]] */
+    const int64_t *pitch_nodes; /* host [n_types], >= tg_neg_batched_capacity()'s cap_nodes */
+    int64_t *const *rows;       /* host [n_rels] device slabs [n_calls, pitch_edges[r]] */
+    int64_t *const *cols;
+    const int64_t *pitch_edges; /* host [n_rels], >= tg_neg_batched_capacity()'s cap_edges */
+    int64_t *counts;            /* device [n_calls, n_types + n_rels] */
+    int32_t *panic;             /* device [n_calls] */
+} tg_neg_batched_out;
+
+TG_API int tg_neg_batched_capacity(const tg_neg_problem *problem, int64_t *cap_nodes, int64_t *cap_edges);
+TG_API int tg_neg_batched_form(const tg_neg_problem *problem, int64_t lds_limit_bytes, int32_t *form, int64_t *lds_bytes);
+TG_API int tg_neg_batched_workspace_bytes(const tg_neg_problem *problem, int64_t n_calls, int64_t *bytes);
+TG_API int tg_neg_sample_batched(const tg_neg_problem *problem, int64_t n_calls, const tg_rng *rng,
+                                 const tg_neg_batched_out *out, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* hgt_sampling (src/algo/hgt_sampling.rs:138-278; binding python.rs:399-482).  Host arrays are indexed by node
  * type (`node_types` order) and relation (`edge_types` order); graphs are CSC, graphs[r].timestamps is the
  * relation's row_timestamps or NULL.  All state lives in the caller's workspace; nothing synchronises. */

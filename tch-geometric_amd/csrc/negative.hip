@@ -341,3 +341,5 @@ extern "C" int tg_neg_sample(const tg_neg_problem *pb, const tg_rng *rng, const 
     TG_HIP(hipMemcpyAsync(out->panic, panic, sizeof(int), hipMemcpyDeviceToDevice, stream));
     return TG_OK;
 }
+
+#include "negative_batched.inl" // tg_neg_sample_batched: one workgroup per call

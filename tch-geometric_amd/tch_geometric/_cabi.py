@@ -34,7 +34,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_part_sample_order_thresholds", "tg_ns_homo_batched_pipeline", "tg_graph_max_degree",
            "tg_ns_homo_workspace_bytes_for", "tg_ns_homo_batched_workspace_bytes", "tg_hgt_batched_capacity",
            "tg_hgt_batched_workspace_bytes", "tg_hgt_sample_batched", "tg_budget_batched_workspace_bytes",
-           "tg_budget_sample_batched"]
+           "tg_budget_sample_batched", "tg_neg_batched_capacity", "tg_neg_batched_form", "tg_neg_batched_workspace_bytes",
+           "tg_neg_sample_batched"]
 
 
 class TgGraph(C.Structure):
@@ -607,6 +608,131 @@ class BudgetBatched:
         return ([self.samples[t][b, :c[t]] for t in range(T)], [self.sample_ts[t][b, :c[t]] for t in range(T)],
                 [self.rows[r][b, :c[T + r]] for r in range(R)], [self.cols[r][b, :c[T + r]] for r in range(R)],
                 [self.edge_index[r][b, :c[T + r]] for r in range(R)])
+
+
+class TgNegProblem(C.Structure):
+    _fields_ = [("n_types", C.c_int32), ("n_rels", C.c_int32), ("homogeneous", C.c_int32), ("inbound", C.c_int32),
+                ("rel_src", C.POINTER(C.c_int32)), ("rel_dst", C.POINTER(C.c_int32)), ("graphs", C.POINTER(TgGraph)),
+                ("node_count", C.POINTER(C.c_int64)), ("inputs", C.POINTER(C.c_void_p)), ("n_inputs", C.POINTER(C.c_int64)),
+                ("num_neg", C.c_int64), ("try_count", C.c_int64)]
+
+
+class TgNegBatchedOut(C.Structure):
+    _fields_ = [("samples", C.POINTER(C.c_void_p)), ("pitch_nodes", C.POINTER(C.c_int64)), ("rows", C.POINTER(C.c_void_p)),
+                ("cols", C.POINTER(C.c_void_p)), ("pitch_edges", C.POINTER(C.c_int64)), ("counts", C.c_void_p),
+                ("panic", C.c_void_p)]
+
+
+TG_NEG_MAX_CALLS = 65535
+NEG_LDS_160K = 160 * 1024   # a gfx950 workgroup's LDS limit, for form queries that touch no device
+
+
+def neg_problem(n_types, rels, n_inputs, num_neg, try_count, inputs=None, inbound=False, homogeneous=False):
+    """A tg_neg_problem.  rels: list of (src type index, dst type index, CSR ptrs, CSR indices, node_count) with
+    node_count = the size of the range the negatives are drawn from (sizes[rel][1]); n_inputs: per type, < 0 where the type
+    has no entry in `inputs`; inputs: per type a device tensor ([n_calls, n_inputs] for the batched form) or None."""
+    T, R = n_types, len(rels)
+    p = TgNegProblem()
+    p.n_types, p.n_rels, p.homogeneous, p.inbound = T, R, int(bool(homogeneous)), int(bool(inbound))
+    rel_src = (C.c_int32 * max(R, 1))(*[r[0] for r in rels])
+    rel_dst = (C.c_int32 * max(R, 1))(*[r[1] for r in rels])
+    graphs = (TgGraph * max(R, 1))()
+    for i, r in enumerate(rels):
+        graphs[i] = graph_view(r[2], r[3])
+    node_count = (C.c_int64 * max(R, 1))(*[int(r[4]) for r in rels])
+    n_in = (C.c_int64 * max(T, 1))(*[int(x) for x in n_inputs])
+    ins = (C.c_void_p * max(T, 1))(*[None if x is None or x.numel() == 0 else x.data_ptr()
+                                     for x in (inputs if inputs is not None else [None] * T)])
+    p.rel_src, p.rel_dst, p.graphs, p.node_count, p.inputs, p.n_inputs = rel_src, rel_dst, graphs, node_count, ins, n_in
+    p.num_neg, p.try_count = int(num_neg), int(try_count)
+    p._keep = (rels, inputs, rel_src, rel_dst, graphs, node_count, n_in, ins)
+    return p
+
+
+def neg_batched_capacity(problem):
+    """-> (cap_nodes [T], cap_edges [R]) of one call: max(n_inputs[t], 0) + total items; n_inputs[src] * num_neg."""
+    cn, ce = (C.c_int64 * max(problem.n_types, 1))(), (C.c_int64 * max(problem.n_rels, 1))()
+    check(lib.tg_neg_batched_capacity(C.byref(problem), cn, ce))
+    return list(cn)[:problem.n_types], list(ce)[:problem.n_rels]
+
+
+def neg_batched_form(problem, lds_limit_bytes=0):
+    """-> (form, lds_bytes): 1 = one workgroup runs one whole call in LDS, 0 = call by call; the LDS the fused kernel asks
+    for.  lds_limit_bytes > 0: taken as the workgroup's limit, no device is touched; otherwise the current device is asked."""
+    form, nbytes = C.c_int32(-1), C.c_int64(0)
+    check(lib.tg_neg_batched_form(C.byref(problem), C.c_int64(lds_limit_bytes), C.byref(form), C.byref(nbytes)))
+    return form.value, nbytes.value
+
+
+def neg_batched_workspace_bytes(problem, n_calls):
+    nbytes = C.c_int64(0)
+    check(lib.tg_neg_batched_workspace_bytes(C.byref(problem), C.c_int64(n_calls), C.byref(nbytes)))
+    return nbytes.value
+
+
+def neg_batched_pitches(problem, pad=0):
+    """Row pitches of NegBatched's slabs: the capacity + pad words, at least one."""
+    cap_n, cap_e = neg_batched_capacity(problem)
+    return [max(c + pad, 1) for c in cap_n], [max(c + pad, 1) for c in cap_e]
+
+
+def neg_batched_bytes(problem, n_calls, pad=0):
+    """Device bytes of one launch as NegBatched allocates it: workspace, output slabs, counts and panic words."""
+    pn, pe = neg_batched_pitches(problem, pad)
+    words = sum(pn) + 2 * sum(pe) + len(pn) + len(pe) + 1
+    return neg_batched_workspace_bytes(problem, n_calls) + 8 * n_calls * words
+
+
+class NegBatched:
+    """Problem description, input and output slabs and workspace of tg_neg_sample_batched: n_calls negative-sampling calls of
+    one shape per launch.  inputs: per node type a [n_calls, n_inputs] tensor or None (no entry in `inputs`); rels as in
+    neg_problem.  pad: extra words per slab row (the pitches then exceed the capacities).  Call b of run(seed, call_id)
+    equals the single operator with call id call_id + b.  counts and panic share one tensor (`state`, [n_calls, T + R + 1],
+    the panic word last), so one read-back fetches both."""
+
+    def __init__(self, n_types, rels, inputs, num_neg, try_count, n_calls, device, inbound=False, homogeneous=False, pad=0):
+        T, R = n_types, len(rels)
+        self.T, self.R, self.nc, self.dev = T, R, int(n_calls), device
+        n_in = [-1 if x is None else int(x.shape[-1]) for x in inputs]
+        self.inputs = [None if x is None else x.reshape(n_calls, n_in[t]).contiguous() for t, x in enumerate(inputs)]
+        self.problem = neg_problem(T, rels, n_in, num_neg, try_count, self.inputs, inbound, homogeneous)
+        self.cap_nodes, self.cap_edges = neg_batched_capacity(self.problem)
+        self.node_pitch, self.edge_pitch = neg_batched_pitches(self.problem, pad)
+        self.form, self.lds_bytes = neg_batched_form(self.problem)
+        o = dict(dtype=torch.int64, device=device)
+        self.samples = [torch.empty((n_calls, p), **o) for p in self.node_pitch]
+        self.rows = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
+        self.cols = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
+        # counts [n_calls, T + R] first (its own contiguous block, as the C ABI wants it), the panic words behind it
+        self.state = torch.zeros(n_calls * (T + R + 1), **o)
+        self.counts = self.state[:n_calls * (T + R)].view(n_calls, T + R)
+        self.panic = self.state[n_calls * (T + R):].view(torch.int32)[:n_calls]
+        self.workspace_bytes = neg_batched_workspace_bytes(self.problem, n_calls)
+        self.workspace = torch.empty(self.workspace_bytes // 8 + 1, **o)
+        self.launch_bytes = neg_batched_bytes(self.problem, n_calls, pad)
+        vp = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
+        i64 = lambda xs: (C.c_int64 * max(len(xs), 1))(*xs)
+        self._arrays = [vp(self.samples), i64(self.node_pitch), vp(self.rows), vp(self.cols), i64(self.edge_pitch)]
+        self.out = TgNegBatchedOut(*self._arrays, self.counts.data_ptr(), self.panic.data_ptr())
+
+    def run(self, seed, call_id):
+        rng = TgRng(seed, call_id)
+        check(lib.tg_neg_sample_batched(C.byref(self.problem), C.c_int64(self.nc), C.byref(rng), C.byref(self.out),
+                                        ptr(self.workspace), C.c_int64(self.workspace_bytes), stream_ptr(self.dev)))
+
+    def read_state(self):
+        """ONE read-back -> (counts [n_calls, T + R], panic [n_calls]) as host tensors."""
+        h = self.state.cpu()
+        n = self.nc * (self.T + self.R)
+        return h[:n].view(self.nc, self.T + self.R), h[n:].view(torch.int32)[:self.nc]
+
+    def call(self, b, counts=None):
+        """Call b's results -> (samples [T], rows [R], cols [R]) trimmed to its counts (counts: the counts block already
+        read back, else it is read here)."""
+        c = (self.counts[b].tolist() if counts is None else [int(x) for x in counts[b]])
+        T, R = self.T, self.R
+        return ([self.samples[t][b, :c[t]] for t in range(T)], [self.rows[r][b, :c[T + r]] for r in range(R)],
+                [self.cols[r][b, :c[T + r]] for r in range(R)])
 
 
 BIAS = {"uniform": 0, "linear": 1, "exponential": 2}

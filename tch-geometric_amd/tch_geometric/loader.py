@@ -665,3 +665,134 @@ class BudgetLoader:
         if not self.drop_last and n_full * B < nodes.numel():
             yield from self._emit(nodes[n_full * B:].reshape(1, -1), None if ts is None else ts[n_full * B:].reshape(1, -1),
                                   batch0 + n_full)
+
+
+class NegativeLoader:
+    """Negative sampling (negative_sample_neighbors_homogenous / _heterogenous) as a loader: `prefetch` mini-batches per
+    tg_neg_sample_batched launch (one workgroup runs one whole mini-batch in LDS where its shape fits, tchgeo.h), ONE
+    read-back per launch (counts and panic words together), slabs flattened by tg_compact_rows and node attributes gathered
+    once per launch and split.
+
+    Homogeneous `data`: yields what NegativeSamplerTransform returns for the mini-batch's inputs (n_id, num_nodes,
+    neg_edge_index, batch_size, node attributes gathered by n_id) plus `call_id`.  Heterogeneous `data`: the seeds are of ONE
+    node type (`input_type`); yields a HeteroGraph with the same fields per node type and neg_edge_index per relation, as
+    the transform does for inputs = {input_type: seeds}.
+
+    Mini-batch j of epoch e equals the transform for (seed, call_id0 + e * len(loader) + j).  Where the reference would
+    panic in a mini-batch (inbound, a drawn row out of range; negative_sampling.rs:113) the transform's RuntimeError is
+    raised when that mini-batch is reached, not earlier.  A launch's device memory is the workspace plus prefetch x the
+    slabs of one call; prefetch is clamped to keep it within `max_workspace_bytes` (at least one mini-batch per launch)."""
+
+    PANIC = ("inbound negative sampling indexed a CSR row out of range (the reference panics here, "
+             "negative_sampling.rs:113)")
+
+    def __init__(self, data, num_neg: int, try_count: int, input_nodes: Optional[Tensor] = None,
+                 input_type: Optional[str] = None, batch_size: int = 1024, prefetch: int = 256, inbound: bool = False,
+                 drop_last: bool = False, seed: int = 0, call_id0: int = 0, max_workspace_bytes: int = 4 << 30, device="cuda"):
+        self.data, self.device = data, torch.device(device)
+        self.num_neg, self.try_count, self.inbound = int(num_neg), int(try_count), bool(inbound)
+        if self.num_neg < 0 or self.try_count < 0:
+            raise ValueError("num_neg and try_count must be >= 0")
+        self.batch_size, self.drop_last, self.seed, self.call_id0 = int(batch_size), drop_last, int(seed), int(call_id0)
+        self.hetero = hasattr(data, "node_types") and hasattr(data, "edge_types")
+        if self.hetero:
+            self.node_types, self.edge_types = list(data.node_types), list(data.edge_types)
+            if input_type not in self.node_types:
+                raise ValueError("input_type must name one of the node types %s" % self.node_types)
+            tix = {t: i for i, t in enumerate(self.node_types)}
+            self._rels = []
+            for et in self.edge_types:
+                size = (_num_nodes(data[et[0]]), _num_nodes(data[et[2]]))
+                if size[1] < 1:
+                    raise ValueError("relation %s has an empty destination range" % (et,))
+                ptrs, idx, _ = _host.to_csr(data[et].edge_index.to(self.device), size)
+                self._rels.append((tix[et[0]], tix[et[2]], ptrs, idx, size[1]))
+            self._it = tix[input_type]
+            stores = [data[t] for t in self.node_types]
+        else:
+            self.node_types, self.edge_types, input_type = [None], [None], None
+            self.inbound = False                                    # the homogeneous operator has no inbound form (the transform ignores it)
+            n = _num_nodes(data)
+            ptrs, idx, _ = _host.to_csr(data.edge_index.to(self.device), n)
+            self._rels, self._it = [(0, 0, ptrs, idx, n)], 0
+            stores = [data]
+        self.input_type = input_type
+        n_in = _num_nodes(stores[self._it])
+        nodes = torch.arange(n_in, device=self.device) if input_nodes is None else input_nodes.to(self.device)
+        self.input_nodes = _checked_inputs(nodes, n_in)             # an input indexes the CSR rows of its type unchecked
+        self._node_attrs = []
+        for store in stores:
+            n = _num_nodes(store)
+            self._node_attrs.append([(k, v.to(self.device)) for k, v in _tensor_items(store)
+                                     if k != "edge_index" and v.dim() > 0 and v.shape[0] == n])
+        per_call = max(1, _cabi.neg_batched_bytes(self._problem(self.batch_size), 1))
+        self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // per_call, _cabi.TG_NEG_MAX_CALLS))
+        self.epoch = 0
+        self._launch = {}                                           # (calls, seeds per call) -> NegBatched
+
+    def _problem(self, n_seeds):
+        """A host-only problem of the loader's shape (sizes a launch; nothing is launched)."""
+        n_in = [n_seeds if t == self._it else -1 for t in range(len(self.node_types))]
+        return _cabi.neg_problem(len(self.node_types), self._rels, n_in, self.num_neg, self.try_count, None, self.inbound,
+                                 not self.hetero)
+
+    def __len__(self) -> int:
+        n = self.input_nodes.numel()
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def _emit(self, seeds: Tensor, first_batch: int):
+        G, B = seeds.shape
+        T = len(self.node_types)
+        nb = self._launch.get((G, B))
+        if nb is None:  # full launches reuse one set of slabs; a shorter last launch gets its own, freed after use
+            inputs = [None] * T
+            inputs[self._it] = seeds.clone()
+            nb = _cabi.NegBatched(T, self._rels, inputs, self.num_neg, self.try_count, G, self.device, self.inbound,
+                                  not self.hetero)
+            if G == self.prefetch and B == self.batch_size:
+                self._launch = {(G, B): nb}
+        else:
+            nb.inputs[self._it].copy_(seeds)
+        nb.run(self.seed, self.call_id0 + first_batch)
+        counts, panic = nb.read_state()                             # the launch's only read-back
+        node_parts, attr_parts = [], []
+        for t in range(T):
+            lens = counts[:, t].tolist()
+            flat = _flat_rows(nb.samples[t], nb.counts[:, t], sum(lens))
+            node_parts.append((torch.split(flat, lens), lens))
+            attr_parts.append({k: torch.split(_cabi.gather_rows(v, flat)[0], lens) for k, v in self._node_attrs[t]})
+        edge_parts = []
+        for r in range(len(self._rels)):
+            ne, lens = nb.counts[:, T + r], counts[:, T + r].tolist()
+            tot = sum(lens)
+            rc = torch.stack([_flat_rows(nb.rows[r], ne, tot), _flat_rows(nb.cols[r], ne, tot)])
+            edge_parts.append(torch.split(rc, lens, dim=1))
+        for b in range(G):
+            if int(panic[b]) != 0:
+                raise RuntimeError(self.PANIC)
+            if not self.hetero:
+                g = Graph(num_nodes=node_parts[0][1][b], n_id=node_parts[0][0][b], neg_edge_index=edge_parts[0][b], batch_size=B)
+                for k, parts in attr_parts[0].items():
+                    setattr(g, k, parts[b])
+            else:
+                g = HeteroGraph()
+                for t, nt in enumerate(self.node_types):
+                    st = g[nt]
+                    st.n_id, st.num_nodes, st.batch_size = node_parts[t][0][b], node_parts[t][1][b], B if t == self._it else 0
+                    for k, parts in attr_parts[t].items():
+                        setattr(st, k, parts[b])
+                for r, et in enumerate(self.edge_types):
+                    g[et].neg_edge_index = edge_parts[r][b]
+            g.call_id = self.call_id0 + first_batch + b
+            yield g
+
+    def __iter__(self):
+        nodes, B = self.input_nodes, self.batch_size
+        batch0 = self.epoch * len(self)                             # fresh draws every epoch (see NeighborLoader)
+        self.epoch += 1
+        n_full = nodes.numel() // B
+        for start in range(0, n_full, self.prefetch):
+            G = min(self.prefetch, n_full - start)
+            yield from self._emit(nodes[start * B:(start + G) * B].reshape(G, B), batch0 + start)
+        if not self.drop_last and n_full * B < nodes.numel():
+            yield from self._emit(nodes[n_full * B:].reshape(1, -1), batch0 + n_full)
