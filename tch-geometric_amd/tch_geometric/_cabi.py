@@ -138,6 +138,28 @@ def graph_sizing(n_major, n_edges, max_degree=0):
     return g
 
 
+def _rel_arrays(rels, timestamps=False):
+    """rels (src type index, dst type index, ptrs, indices, ...) -> the (rel_src, rel_dst, graphs) arrays of a typed
+    problem.  timestamps: r[4] holds the relation's row timestamps or None (the hgt and budget problems; elsewhere r[4]
+    means something else)."""
+    R = len(rels)
+    rel_src = (C.c_int32 * max(R, 1))(*[r[0] for r in rels])
+    rel_dst = (C.c_int32 * max(R, 1))(*[r[1] for r in rels])
+    graphs = (TgGraph * max(R, 1))()
+    for i, r in enumerate(rels):
+        graphs[i] = graph_view(r[2], r[3], timestamps=r[4] if timestamps and len(r) > 4 else None)
+    return rel_src, rel_dst, graphs
+
+
+def _vp(tensors):
+    """One pointer per tensor (per node type, or per slab), null for None and for a tensor without elements."""
+    return (C.c_void_p * max(len(tensors), 1))(*[None if x is None or x.numel() == 0 else x.data_ptr() for x in tensors])
+
+
+def _i64(xs):
+    return (C.c_int64 * max(len(xs), 1))(*[int(x) for x in xs])
+
+
 def ns_homo_capacity(n_seeds, fanout):
     cn, ce = C.c_int64(0), C.c_int64(0)
     fan = (C.c_int64 * max(len(fanout), 1))(*fanout)
@@ -359,15 +381,10 @@ class NsHeteroBatched:
         T, R = n_types, len(rels)
         self.T, self.R, self.H, self.nb, self.dev = T, R, n_hops, n_batches, device
         self._keep = [rels, inputs]
-        self.rel_src = (C.c_int32 * max(R, 1))(*[r[0] for r in rels])
-        self.rel_dst = (C.c_int32 * max(R, 1))(*[r[1] for r in rels])
-        self.graphs = (TgGraph * max(R, 1))()
-        for i, r in enumerate(rels):
-            self.graphs[i] = graph_view(r[2], r[3])
-        flat = [int(k) for r in rels for k in r[4]]
-        self.fanout = (C.c_int64 * max(len(flat), 1))(*flat)
-        self.n_inputs = (C.c_int64 * T)(*[0 if x is None else int(x.shape[1]) for x in inputs])
-        self.inputs = (C.c_void_p * T)(*[None if x is None else x.data_ptr() for x in inputs])
+        self.rel_src, self.rel_dst, self.graphs = _rel_arrays(rels)
+        self.fanout = _i64([k for r in rels for k in r[4]])
+        self.n_inputs = _i64([0 if x is None else x.shape[1] for x in inputs])
+        self.inputs = _vp(inputs)
         self.problem = TgHetProblem(T, R, n_hops, sampler, self.rel_src, self.rel_dst, self.graphs, self.fanout,
                                     self.inputs, self.n_inputs)
         self.cap_nodes, self.cap_edges = (C.c_int64 * T)(), (C.c_int64 * max(R, 1))()
@@ -380,10 +397,9 @@ class NsHeteroBatched:
         self.layer_offsets = torch.zeros((n_batches, max(R, 1), max(n_hops, 1), 3), **o)
         self.counts = torch.zeros((n_batches, T + R), **o)
         # the slabs are allocated with at least one column; tell the library their true pitch
-        self.cap_nodes_alloc = (C.c_int64 * T)(*[max(self.cap_nodes[t], 1) for t in range(T)])
-        self.cap_edges_alloc = (C.c_int64 * max(R, 1))(*[max(self.cap_edges[r], 1) for r in range(R)])
-        vp = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
-        self._ptrs = [vp(self.samples), vp(self.rows), vp(self.cols), vp(self.edge_index)]
+        self.cap_nodes_alloc = _i64([max(self.cap_nodes[t], 1) for t in range(T)])
+        self.cap_edges_alloc = _i64([max(self.cap_edges[r], 1) for r in range(R)])
+        self._ptrs = [_vp(self.samples), _vp(self.rows), _vp(self.cols), _vp(self.edge_index)]
         self.out = TgHetOut(self._ptrs[0], self.cap_nodes_alloc, self._ptrs[1], self._ptrs[2], self._ptrs[3],
                             self.cap_edges_alloc, self.layer_offsets.data_ptr(), self.counts.data_ptr())
 
@@ -406,29 +422,105 @@ class TgHgtBatchedOut(C.Structure):
                 ("cap_edges", C.POINTER(C.c_int64)), ("counts", C.c_void_p)]
 
 
+def _typed_problem(p, n_types, rels, n_inputs, inputs, input_ts=None, timestamps=False, **arrays):
+    """Fills what the hgt, budget and negative problem structs share -- the type and relation counts, the relation
+    arrays, the per-type inputs (and input timestamps, where the struct has them and the caller gives some) -- and the
+    further ctypes arrays in `arrays`, by field name.  The struct only borrows all of it: p._keep holds it alive."""
+    p.n_types, p.n_rels = n_types, len(rels)
+    rel = _rel_arrays(rels, timestamps)
+    p.rel_src, p.rel_dst, p.graphs = rel
+    ins, n_in = _vp(inputs if inputs is not None else [None] * n_types), _i64(n_inputs)
+    p.inputs, p.n_inputs = ins, n_in
+    its = _vp(input_ts) if input_ts is not None else None
+    if its is not None:
+        p.input_ts = its
+    for field, array in arrays.items():
+        setattr(p, field, array)
+    p._keep = (rels, inputs, input_ts, rel, ins, n_in, its, arrays)
+    return p
+
+
+def _call_major(tensors, n_calls, missing):
+    """Per-type inputs of a batched launch as contiguous [n_calls, n_inputs] tensors -> (tensors, n_inputs per type);
+    `missing` is the n_inputs of a type without an entry."""
+    n_in = [missing if x is None else int(x.shape[-1]) for x in tensors]
+    return [None if x is None else x.reshape(n_calls, n_in[t]).contiguous() for t, x in enumerate(tensors)], n_in
+
+
+class _Batched:
+    """The output slabs, counts and workspace of a batched typed operator (hgt, budget, negative): n_calls calls of one
+    shape per launch.  A subclass names its per-node-type and per-relation slab lists, the state words each call has
+    behind its T + R counts, the out struct (slab pointers, node pitches, slab pointers, edge pitches, counts[, ...] in
+    that order) and the library's capacity / workspace / launch functions; this class allocates the slabs with row pitch
+    capacity + pad (at least one word), the state block and the workspace, and gives run() and call()."""
+    NODE_SLABS, EDGE_SLABS, TAIL = ("samples", "sample_ts"), ("rows", "cols", "edge_index"), 0
+    OUT = LAUNCH = capacity = workspace_bytes_of = None
+
+    @classmethod
+    def pitches(cls, problem, pad=0):
+        """Row pitches (per type, per relation) of the slabs: the capacity + pad words, at least one."""
+        cap_n, cap_e = cls.capacity(problem)
+        return [max(c + pad, 1) for c in cap_n], [max(c + pad, 1) for c in cap_e]
+
+    @classmethod
+    def bytes_of(cls, problem, n_calls, pad=0):
+        """Device bytes of one launch as this class allocates it: the workspace, the output slabs (sized for the worst
+        case) and the state block."""
+        return cls.workspace_bytes_of(problem, n_calls) + 8 * n_calls * cls._call_words(*cls.pitches(problem, pad))
+
+    @classmethod
+    def _call_words(cls, node_pitch, edge_pitch):
+        """int64 words of one call: its row in every slab, its T + R counts and its tail words"""
+        return (len(cls.NODE_SLABS) * sum(node_pitch) + len(cls.EDGE_SLABS) * sum(edge_pitch) + len(node_pitch) +
+                len(edge_pitch) + cls.TAIL)
+
+    def __init__(self, problem, n_calls, device, pad=0):
+        T, R, n = problem.n_types, problem.n_rels, int(n_calls)
+        self.problem, self.T, self.R, self.nc, self.dev = problem, T, R, n, device
+        self.cap_nodes, self.cap_edges = self.capacity(problem)
+        self.node_pitch, self.edge_pitch = self.pitches(problem, pad)
+        o = dict(dtype=torch.int64, device=device)
+        self._arrays = []
+        for names, pitch in ((self.NODE_SLABS, self.node_pitch), (self.EDGE_SLABS, self.edge_pitch)):
+            for name in names:
+                setattr(self, name, [torch.empty((n, p), **o) for p in pitch])
+                self._arrays.append(_vp(getattr(self, name)))
+            self._arrays.append(_i64(pitch))
+        self.state = torch.zeros(n * (T + R + self.TAIL), **o)
+        self.workspace_bytes = self.workspace_bytes_of(problem, n)
+        self.workspace = torch.empty(self.workspace_bytes // 8 + 1, **o)
+        self.launch_bytes = self.workspace_bytes + 8 * n * self._call_words(self.node_pitch, self.edge_pitch)
+        self.out = self.OUT(*self._arrays, *self._state_fields())
+
+    def _state_fields(self):
+        """Cuts `state` into what the library writes -> the out struct's fields behind the pitches.  Here: one
+        [n_calls, T + R + TAIL] counts block (a call's tail words are the last columns of its row)."""
+        self.counts = self.state.view(self.nc, -1)
+        return (self.counts.data_ptr(),)
+
+    def run(self, seed, call_id):
+        rng = TgRng(seed, call_id)
+        check(self.LAUNCH(C.byref(self.problem), C.c_int64(self.nc), C.byref(rng), C.byref(self.out), ptr(self.workspace),
+                          C.c_int64(self.workspace_bytes), stream_ptr(self.dev)))
+
+    def call(self, b, counts=None):
+        """Call b's results trimmed to its counts -> one list per node slab ([T]), one per edge slab ([R]), then the tail
+        words of its counts row (counts: the counts block already read back, else it is read here)."""
+        c = (self.counts[b].tolist() if counts is None else [int(x) for x in counts[b]])
+        T, R = self.T, self.R
+        return (tuple([getattr(self, k)[t][b, :c[t]] for t in range(T)] for k in self.NODE_SLABS) +
+                tuple([getattr(self, k)[r][b, :c[T + r]] for r in range(R)] for k in self.EDGE_SLABS) + tuple(c[T + R:]))
+
+
 def hgt_problem(n_types, rels, n_inputs, num_samples, n_hops, inputs=None, input_ts=None, timerange=None):
     """A tg_hgt_problem.  rels: list of (src type index, dst type index, ptrs, indices, row timestamps or None);
     n_inputs: per type (< 0: no entry in `inputs`); num_samples: per type a list of n_hops quotas, or None (no entry);
     inputs / input_ts: per type a device tensor or None (input_ts None: no input timestamps at all)."""
-    T, R = n_types, len(rels)
-    p = TgHgtProblem()
-    p.n_types, p.n_rels, p.n_hops = T, R, n_hops
-    rel_src = (C.c_int32 * max(R, 1))(*[r[0] for r in rels])
-    rel_dst = (C.c_int32 * max(R, 1))(*[r[1] for r in rels])
-    graphs = (TgGraph * max(R, 1))()
-    for i, r in enumerate(rels):
-        graphs[i] = graph_view(r[2], r[3], timestamps=r[4] if len(r) > 4 else None)
-    ns = (C.c_int64 * max(T * n_hops, 1))(*[int(q[h]) if q is not None else -1 for q in num_samples for h in range(n_hops)])
-    n_in = (C.c_int64 * T)(*[int(x) for x in n_inputs])
-    vp = lambda ts: (C.c_void_p * T)(*[None if x is None or x.numel() == 0 else x.data_ptr() for x in ts])
-    ins = vp(inputs if inputs is not None else [None] * T)
-    its = vp(input_ts) if input_ts is not None else None
-    p.rel_src, p.rel_dst, p.graphs, p.n_inputs, p.num_samples = rel_src, rel_dst, graphs, n_in, ns
-    p.inputs = ins
-    p.input_ts = its if its is not None else C.POINTER(C.c_void_p)()
+    ns = _i64([q[h] if q is not None else -1 for q in num_samples for h in range(n_hops)])
+    p = _typed_problem(TgHgtProblem(), n_types, rels, n_inputs, inputs, input_ts, timestamps=True, num_samples=ns)
+    p.n_hops = n_hops
     if timerange is not None:
         p.has_timerange, p.tr_lo, p.tr_hi = 1, int(timerange[0]), int(timerange[1])
-    p._keep = (rels, inputs, input_ts, rel_src, rel_dst, graphs, ns, n_in, ins, its)
     return p
 
 
@@ -445,51 +537,22 @@ def hgt_batched_workspace_bytes(problem, n_calls):
     return nbytes.value
 
 
-class HgtBatched:
+class HgtBatched(_Batched):
     """Problem description, output slabs and workspace of tg_hgt_sample_batched: n_calls hgt_sampling calls of one shape
     per launch chain.  inputs / input_ts: per node type a [n_calls, n_inputs] tensor or None (no entry in `inputs`);
     num_samples: per type a list of n_hops quotas or None; rels as in hgt_problem.  pad: extra words per slab row (the
-    pitches then exceed the capacities).  Call b of run(seed, call_id) equals hgt_sampling with call id call_id + b."""
+    pitches then exceed the capacities).  Call b of run(seed, call_id) equals hgt_sampling with call id call_id + b;
+    call(b) -> (samples [T], sample_ts [T], rows [R], cols [R], edge_index [R], panic): the panic word is the last
+    column of `counts` ([n_calls, T + R + 1])."""
+    TAIL, OUT, LAUNCH = 1, TgHgtBatchedOut, lib.tg_hgt_sample_batched
+    capacity, workspace_bytes_of = staticmethod(hgt_batched_capacity), staticmethod(hgt_batched_workspace_bytes)
 
     def __init__(self, n_types, rels, inputs, num_samples, n_hops, n_calls, device, input_ts=None, timerange=None, pad=0):
-        T, R = n_types, len(rels)
-        self.T, self.R, self.H, self.nc, self.dev = T, R, n_hops, int(n_calls), device
-        n_in = [-1 if x is None else int(x.shape[1]) for x in inputs]
-        flat = lambda xs: [None if x is None else x.reshape(n_calls, -1).contiguous() for x in xs]
-        self.inputs = flat(inputs)
-        self.input_ts = flat(input_ts) if input_ts is not None else None
-        self.problem = hgt_problem(T, rels, n_in, num_samples, n_hops, self.inputs, self.input_ts, timerange)
-        self.cap_nodes, self.cap_edges = hgt_batched_capacity(self.problem)
-        o = dict(dtype=torch.int64, device=device)
-        self.node_pitch = [c + pad if c + pad > 0 else 1 for c in self.cap_nodes]
-        self.edge_pitch = [c + pad for c in self.cap_edges]
-        self.samples = [torch.empty((n_calls, p), **o) for p in self.node_pitch]
-        self.sample_ts = [torch.empty((n_calls, p), **o) for p in self.node_pitch]
-        self.rows = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
-        self.cols = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
-        self.edge_index = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
-        self.counts = torch.zeros((n_calls, T + R + 1), **o)
-        self.workspace_bytes = hgt_batched_workspace_bytes(self.problem, n_calls)
-        self.workspace = torch.empty(self.workspace_bytes // 8 + 1, **o)
-        vp = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
-        i64 = lambda xs: (C.c_int64 * max(len(xs), 1))(*xs)
-        self._arrays = [vp(self.samples), vp(self.sample_ts), i64(self.node_pitch), vp(self.rows), vp(self.cols),
-                        vp(self.edge_index), i64(self.edge_pitch)]
-        self.out = TgHgtBatchedOut(*self._arrays, self.counts.data_ptr())
-
-    def run(self, seed, call_id):
-        rng = TgRng(seed, call_id)
-        check(lib.tg_hgt_sample_batched(C.byref(self.problem), C.c_int64(self.nc), C.byref(rng), C.byref(self.out),
-                                        ptr(self.workspace), C.c_int64(self.workspace_bytes), stream_ptr(self.dev)))
-
-    def call(self, b, counts=None):
-        """Call b's results -> (samples [T], sample_ts [T], rows [R], cols [R], edge_index [R], panic) trimmed to its
-        counts (counts: the counts block already read back, else it is read here)."""
-        c = (self.counts[b].tolist() if counts is None else [int(x) for x in counts[b]])
-        T, R = self.T, self.R
-        return ([self.samples[t][b, :c[t]] for t in range(T)], [self.sample_ts[t][b, :c[t]] for t in range(T)],
-                [self.rows[r][b, :c[T + r]] for r in range(R)], [self.cols[r][b, :c[T + r]] for r in range(R)],
-                [self.edge_index[r][b, :c[T + r]] for r in range(R)], c[T + R])
+        self.H = n_hops
+        self.inputs, n_in = _call_major(inputs, n_calls, -1)
+        self.input_ts = _call_major(input_ts, n_calls, -1)[0] if input_ts is not None else None
+        super().__init__(hgt_problem(n_types, rels, n_in, num_samples, n_hops, self.inputs, self.input_ts, timerange),
+                         n_calls, device, pad)
 
 
 class TgBudgetProblem(C.Structure):
@@ -511,26 +574,12 @@ def budget_problem(n_types, rels, n_inputs, num_neighbors, n_hops, inputs=None, 
     """A tg_budget_problem.  rels: list of (src type index, dst type index, ptrs, indices, row timestamps or None);
     n_inputs: per type; num_neighbors: per type a list of n_hops quotas; inputs / input_ts: per type a device tensor or
     None (input_ts None: no input timestamps at all); window = (lo, hi) turns the temporal filter on (python.rs:541-548)."""
-    T, R = n_types, len(rels)
-    p = TgBudgetProblem()
-    p.n_types, p.n_rels, p.n_hops = T, R, n_hops
-    rel_src = (C.c_int32 * max(R, 1))(*[r[0] for r in rels])
-    rel_dst = (C.c_int32 * max(R, 1))(*[r[1] for r in rels])
-    graphs = (TgGraph * max(R, 1))()
-    for i, r in enumerate(rels):
-        graphs[i] = graph_view(r[2], r[3], timestamps=r[4] if len(r) > 4 else None)
-    nn = (C.c_int64 * max(T * n_hops, 1))(*[int(q[h]) for q in num_neighbors for h in range(n_hops)])
-    n_in = (C.c_int64 * T)(*[int(x) for x in n_inputs])
-    vp = lambda ts: (C.c_void_p * T)(*[None if x is None or x.numel() == 0 else x.data_ptr() for x in ts])
-    ins = vp(inputs if inputs is not None else [None] * T)
-    its = vp(input_ts) if input_ts is not None else None
-    p.rel_src, p.rel_dst, p.graphs, p.n_inputs, p.num_neighbors = rel_src, rel_dst, graphs, n_in, nn
-    p.inputs = ins
-    p.input_ts = its if its is not None else C.POINTER(C.c_void_p)()
+    nn = _i64([q[h] for q in num_neighbors for h in range(n_hops)])
+    p = _typed_problem(TgBudgetProblem(), n_types, rels, n_inputs, inputs, input_ts, timestamps=True, num_neighbors=nn)
+    p.n_hops = n_hops
     if window is not None:
         p.filter_on, p.forward, p.relative = 1, int(bool(forward)), int(bool(relative))
         p.win_lo, p.win_hi = int(window[0]), int(window[1])
-    p._keep = (rels, inputs, input_ts, rel_src, rel_dst, graphs, nn, n_in, ins, its)
     return p
 
 
@@ -547,67 +596,26 @@ def budget_batched_workspace_bytes(problem, n_calls):
     return nbytes.value
 
 
-def budget_batched_pitches(problem, pad=0):
-    """Row pitches of BudgetBatched's slabs: the capacity + pad words, at least one."""
-    cap_n, cap_e = budget_capacity(problem)
-    return [max(c + pad, 1) for c in cap_n], [max(c + pad, 1) for c in cap_e]
-
-
-def budget_batched_bytes(problem, n_calls, pad=0):
-    """Device bytes of one launch as BudgetBatched allocates it: the workspace, the output slabs (sized for the worst case,
-    far above typical counts) and the counts."""
-    pn, pe = budget_batched_pitches(problem, pad)
-    words = 2 * sum(pn) + 3 * sum(pe) + len(pn) + len(pe)
-    return budget_batched_workspace_bytes(problem, n_calls) + 8 * n_calls * words
-
-
-class BudgetBatched:
+class BudgetBatched(_Batched):
     """Problem description, output slabs and workspace of tg_budget_sample_batched: n_calls budget_sampling calls of one
     shape per launch chain.  inputs / input_ts: per node type a [n_calls, n_inputs] tensor or None (no inputs);
     num_neighbors: per type a list of n_hops quotas; rels as in budget_problem.  pad: extra words per slab row (the pitches
-    then exceed the capacities).  Call b of run(seed, call_id) equals budget_sampling with call id call_id + b."""
+    then exceed the capacities).  Call b of run(seed, call_id) equals budget_sampling with call id call_id + b; call(b) ->
+    (samples [T], sample_ts [T], rows [R], cols [R], edge_index [R]).  The slabs are sized for the worst case, far above
+    typical counts, and are most of launch_bytes."""
+    OUT, LAUNCH = TgBudgetBatchedOut, lib.tg_budget_sample_batched
+    capacity, workspace_bytes_of = staticmethod(budget_capacity), staticmethod(budget_batched_workspace_bytes)
 
     def __init__(self, n_types, rels, inputs, num_neighbors, n_hops, n_calls, device, input_ts=None, window=None,
                  forward=False, relative=False, pad=0):
-        T, R = n_types, len(rels)
-        self.T, self.R, self.H, self.nc, self.dev = T, R, n_hops, int(n_calls), device
-        n_in = [0 if x is None else int(x.shape[-1]) for x in inputs]
-        flat = lambda xs: [None if x is None else x.reshape(n_calls, n_in[t]).contiguous() for t, x in enumerate(xs)]
-        self.inputs = flat(inputs)
-        self.input_ts = flat(input_ts) if input_ts is not None else None
-        self.problem = budget_problem(T, rels, n_in, num_neighbors, n_hops, self.inputs, self.input_ts, window, forward,
-                                      relative)
-        self.cap_nodes, self.cap_edges = budget_capacity(self.problem)
-        self.node_pitch, self.edge_pitch = budget_batched_pitches(self.problem, pad)
-        o = dict(dtype=torch.int64, device=device)
-        self.samples = [torch.empty((n_calls, p), **o) for p in self.node_pitch]
-        self.sample_ts = [torch.empty((n_calls, p), **o) for p in self.node_pitch]
-        self.rows = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
-        self.cols = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
-        self.edge_index = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
-        self.counts = torch.zeros((n_calls, T + R), **o)
-        self.workspace_bytes = budget_batched_workspace_bytes(self.problem, n_calls)
-        self.workspace = torch.empty(self.workspace_bytes // 8 + 1, **o)
-        self.launch_bytes = budget_batched_bytes(self.problem, n_calls, pad)
-        vp = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
-        i64 = lambda xs: (C.c_int64 * max(len(xs), 1))(*xs)
-        self._arrays = [vp(self.samples), vp(self.sample_ts), i64(self.node_pitch), vp(self.rows), vp(self.cols),
-                        vp(self.edge_index), i64(self.edge_pitch)]
-        self.out = TgBudgetBatchedOut(*self._arrays, self.counts.data_ptr())
+        self.H = n_hops
+        self.inputs, n_in = _call_major(inputs, n_calls, 0)
+        self.input_ts = _call_major(input_ts, n_calls, 0)[0] if input_ts is not None else None
+        super().__init__(budget_problem(n_types, rels, n_in, num_neighbors, n_hops, self.inputs, self.input_ts, window,
+                                        forward, relative), n_calls, device, pad)
 
-    def run(self, seed, call_id):
-        rng = TgRng(seed, call_id)
-        check(lib.tg_budget_sample_batched(C.byref(self.problem), C.c_int64(self.nc), C.byref(rng), C.byref(self.out),
-                                           ptr(self.workspace), C.c_int64(self.workspace_bytes), stream_ptr(self.dev)))
 
-    def call(self, b, counts=None):
-        """Call b's results -> (samples [T], sample_ts [T], rows [R], cols [R], edge_index [R]) trimmed to its counts
-        (counts: the counts block already read back, else it is read here)."""
-        c = (self.counts[b].tolist() if counts is None else [int(x) for x in counts[b]])
-        T, R = self.T, self.R
-        return ([self.samples[t][b, :c[t]] for t in range(T)], [self.sample_ts[t][b, :c[t]] for t in range(T)],
-                [self.rows[r][b, :c[T + r]] for r in range(R)], [self.cols[r][b, :c[T + r]] for r in range(R)],
-                [self.edge_index[r][b, :c[T + r]] for r in range(R)])
+budget_batched_pitches, budget_batched_bytes = BudgetBatched.pitches, BudgetBatched.bytes_of
 
 
 class TgNegProblem(C.Structure):
@@ -631,21 +639,9 @@ def neg_problem(n_types, rels, n_inputs, num_neg, try_count, inputs=None, inboun
     """A tg_neg_problem.  rels: list of (src type index, dst type index, CSR ptrs, CSR indices, node_count) with
     node_count = the size of the range the negatives are drawn from (sizes[rel][1]); n_inputs: per type, < 0 where the type
     has no entry in `inputs`; inputs: per type a device tensor ([n_calls, n_inputs] for the batched form) or None."""
-    T, R = n_types, len(rels)
-    p = TgNegProblem()
-    p.n_types, p.n_rels, p.homogeneous, p.inbound = T, R, int(bool(homogeneous)), int(bool(inbound))
-    rel_src = (C.c_int32 * max(R, 1))(*[r[0] for r in rels])
-    rel_dst = (C.c_int32 * max(R, 1))(*[r[1] for r in rels])
-    graphs = (TgGraph * max(R, 1))()
-    for i, r in enumerate(rels):
-        graphs[i] = graph_view(r[2], r[3])
-    node_count = (C.c_int64 * max(R, 1))(*[int(r[4]) for r in rels])
-    n_in = (C.c_int64 * max(T, 1))(*[int(x) for x in n_inputs])
-    ins = (C.c_void_p * max(T, 1))(*[None if x is None or x.numel() == 0 else x.data_ptr()
-                                     for x in (inputs if inputs is not None else [None] * T)])
-    p.rel_src, p.rel_dst, p.graphs, p.node_count, p.inputs, p.n_inputs = rel_src, rel_dst, graphs, node_count, ins, n_in
+    p = _typed_problem(TgNegProblem(), n_types, rels, n_inputs, inputs, node_count=_i64([r[4] for r in rels]))
+    p.homogeneous, p.inbound = int(bool(homogeneous)), int(bool(inbound))
     p.num_neg, p.try_count = int(num_neg), int(try_count)
-    p._keep = (rels, inputs, rel_src, rel_dst, graphs, node_count, n_in, ins)
     return p
 
 
@@ -670,55 +666,28 @@ def neg_batched_workspace_bytes(problem, n_calls):
     return nbytes.value
 
 
-def neg_batched_pitches(problem, pad=0):
-    """Row pitches of NegBatched's slabs: the capacity + pad words, at least one."""
-    cap_n, cap_e = neg_batched_capacity(problem)
-    return [max(c + pad, 1) for c in cap_n], [max(c + pad, 1) for c in cap_e]
-
-
-def neg_batched_bytes(problem, n_calls, pad=0):
-    """Device bytes of one launch as NegBatched allocates it: workspace, output slabs, counts and panic words."""
-    pn, pe = neg_batched_pitches(problem, pad)
-    words = sum(pn) + 2 * sum(pe) + len(pn) + len(pe) + 1
-    return neg_batched_workspace_bytes(problem, n_calls) + 8 * n_calls * words
-
-
-class NegBatched:
+class NegBatched(_Batched):
     """Problem description, input and output slabs and workspace of tg_neg_sample_batched: n_calls negative-sampling calls of
     one shape per launch.  inputs: per node type a [n_calls, n_inputs] tensor or None (no entry in `inputs`); rels as in
     neg_problem.  pad: extra words per slab row (the pitches then exceed the capacities).  Call b of run(seed, call_id)
-    equals the single operator with call id call_id + b.  counts and panic share one tensor (`state`, [n_calls, T + R + 1],
-    the panic word last), so one read-back fetches both."""
+    equals the single operator with call id call_id + b; call(b) -> (samples [T], rows [R], cols [R]).  counts and panic
+    share one tensor (`state`, n_calls x (T + R + 1) words, the panic words last), so one read-back fetches both."""
+    NODE_SLABS, EDGE_SLABS, TAIL = ("samples",), ("rows", "cols"), 1
+    OUT, LAUNCH = TgNegBatchedOut, lib.tg_neg_sample_batched
+    capacity, workspace_bytes_of = staticmethod(neg_batched_capacity), staticmethod(neg_batched_workspace_bytes)
 
     def __init__(self, n_types, rels, inputs, num_neg, try_count, n_calls, device, inbound=False, homogeneous=False, pad=0):
-        T, R = n_types, len(rels)
-        self.T, self.R, self.nc, self.dev = T, R, int(n_calls), device
-        n_in = [-1 if x is None else int(x.shape[-1]) for x in inputs]
-        self.inputs = [None if x is None else x.reshape(n_calls, n_in[t]).contiguous() for t, x in enumerate(inputs)]
-        self.problem = neg_problem(T, rels, n_in, num_neg, try_count, self.inputs, inbound, homogeneous)
-        self.cap_nodes, self.cap_edges = neg_batched_capacity(self.problem)
-        self.node_pitch, self.edge_pitch = neg_batched_pitches(self.problem, pad)
-        self.form, self.lds_bytes = neg_batched_form(self.problem)
-        o = dict(dtype=torch.int64, device=device)
-        self.samples = [torch.empty((n_calls, p), **o) for p in self.node_pitch]
-        self.rows = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
-        self.cols = [torch.empty((n_calls, p), **o) for p in self.edge_pitch]
-        # counts [n_calls, T + R] first (its own contiguous block, as the C ABI wants it), the panic words behind it
-        self.state = torch.zeros(n_calls * (T + R + 1), **o)
-        self.counts = self.state[:n_calls * (T + R)].view(n_calls, T + R)
-        self.panic = self.state[n_calls * (T + R):].view(torch.int32)[:n_calls]
-        self.workspace_bytes = neg_batched_workspace_bytes(self.problem, n_calls)
-        self.workspace = torch.empty(self.workspace_bytes // 8 + 1, **o)
-        self.launch_bytes = neg_batched_bytes(self.problem, n_calls, pad)
-        vp = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
-        i64 = lambda xs: (C.c_int64 * max(len(xs), 1))(*xs)
-        self._arrays = [vp(self.samples), i64(self.node_pitch), vp(self.rows), vp(self.cols), i64(self.edge_pitch)]
-        self.out = TgNegBatchedOut(*self._arrays, self.counts.data_ptr(), self.panic.data_ptr())
+        self.inputs, n_in = _call_major(inputs, n_calls, -1)
+        problem = neg_problem(n_types, rels, n_in, num_neg, try_count, self.inputs, inbound, homogeneous)
+        self.form, self.lds_bytes = neg_batched_form(problem)
+        super().__init__(problem, n_calls, device, pad)
 
-    def run(self, seed, call_id):
-        rng = TgRng(seed, call_id)
-        check(lib.tg_neg_sample_batched(C.byref(self.problem), C.c_int64(self.nc), C.byref(rng), C.byref(self.out),
-                                        ptr(self.workspace), C.c_int64(self.workspace_bytes), stream_ptr(self.dev)))
+    def _state_fields(self):
+        # counts [n_calls, T + R] first (its own contiguous block, as the C ABI wants it), the panic words behind it
+        n = self.nc * (self.T + self.R)
+        self.counts = self.state[:n].view(self.nc, self.T + self.R)
+        self.panic = self.state[n:].view(torch.int32)[:self.nc]
+        return self.counts.data_ptr(), self.panic.data_ptr()
 
     def read_state(self):
         """ONE read-back -> (counts [n_calls, T + R], panic [n_calls]) as host tensors."""
@@ -726,13 +695,8 @@ class NegBatched:
         n = self.nc * (self.T + self.R)
         return h[:n].view(self.nc, self.T + self.R), h[n:].view(torch.int32)[:self.nc]
 
-    def call(self, b, counts=None):
-        """Call b's results -> (samples [T], rows [R], cols [R]) trimmed to its counts (counts: the counts block already
-        read back, else it is read here)."""
-        c = (self.counts[b].tolist() if counts is None else [int(x) for x in counts[b]])
-        T, R = self.T, self.R
-        return ([self.samples[t][b, :c[t]] for t in range(T)], [self.rows[r][b, :c[T + r]] for r in range(R)],
-                [self.cols[r][b, :c[T + r]] for r in range(R)])
+
+neg_batched_pitches, neg_batched_bytes = NegBatched.pitches, NegBatched.bytes_of
 
 
 BIAS = {"uniform": 0, "linear": 1, "exponential": 2}

@@ -8,6 +8,11 @@ every mini-batch equals what `neighbor_sampling_homogenous` returns for that (se
 out as lazily built views of that `SuperBatch` (or the super-batch itself: `NeighborLoader.super_batches()`).
 Everything stays in HBM; the host learns only the per-batch sizes (one read-back per launch, taken from pinned memory
 behind a launch that runs one super-batch ahead on a side stream).
+
+The typed-graph loaders (HeteroNeighborLoader, HGTLoader, BudgetLoader, NegativeLoader) are one program, _TypedLoader:
+`prefetch` mini-batches of one node type's seeds per launch of a batched operator, one read-back of the counts, every
+slab flattened and split per mini-batch, attributes gathered once per launch.  Each loader adds only its operator's
+launch object and a few hooks (e_id, extras, panics).  They run on the caller's stream, launch by launch.
 """
 from typing import Iterator, List, Optional
 
@@ -16,7 +21,8 @@ from torch import Tensor
 
 from . import _cabi
 from . import tch_geometric as _host
-from .transforms import Graph, HeteroGraph, _attr_kind, _num_nodes, _tensor_items, rel_key, to_csc, to_hetero_csc
+from .transforms import (Graph, HeteroGraph, _attr_kind, _is_hetero, _num_nodes, _tensor_items, rel_key, to_csc,
+                         to_hetero_csc)
 
 
 def _checked_inputs(nodes: Tensor, n_nodes: int) -> Tensor:
@@ -26,6 +32,26 @@ def _checked_inputs(nodes: Tensor, n_nodes: int) -> Tensor:
     if nodes.numel() and (int(nodes.min()) < 0 or int(nodes.max()) >= n_nodes):
         raise IndexError("input_nodes outside [0, %d)" % n_nodes)
     return nodes
+
+
+def _epoch_plan(n: int, batch_size: int, prefetch: int, drop_last: bool):
+    """An epoch over n inputs as launches [(start, n_batches, batch_width)]: a launch samples the inputs
+    [start, start + n_batches * batch_width) as n_batches mini-batches, the first of them mini-batch start // batch_size
+    of the epoch.  Full mini-batches go `prefetch` to a launch; the ragged last one (dropped under drop_last) is a launch of
+    its own."""
+    n_full = n // batch_size
+    plan = [(first * batch_size, min(prefetch, n_full - first), batch_size) for first in range(0, n_full, prefetch)]
+    if not drop_last and n_full * batch_size < n:
+        plan.append((n_full * batch_size, 1, n - n_full * batch_size))
+    return plan
+
+
+class _Loader:
+    """What every loader here has: input_nodes, batch_size, drop_last -> the number of mini-batches of an epoch."""
+
+    def __len__(self) -> int:
+        n = self.input_nodes.numel()
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
 
 class SuperBatch:
@@ -124,7 +150,7 @@ class MiniBatch:
         return [(k, views[i]) for k, i in self._sb._index.items()] + [("e_id", self.e_id)]
 
 
-class NeighborLoader:
+class NeighborLoader(_Loader):
     """One launch samples `prefetch` mini-batches; while the caller consumes super-batch i, super-batch i + 1 is already
     being sampled on a side stream into the other of two slab sets (its sizes travel to pinned host memory behind the
     kernel), so neither the launch nor its one read-back sits on the consumer's path.  Launches of >= 2 048 mini-batches
@@ -164,10 +190,6 @@ class NeighborLoader:
         self._ws = None
         self._side = None
         self.epoch = 0
-
-    def __len__(self) -> int:
-        n = self.input_nodes.numel()
-        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     # ---- stage 1 (side stream): sample G mini-batches into slab set `which`, sizes -> pinned host memory
     def _sample(self, slabs, which, seeds: Tensor, first_batch: int):
@@ -244,17 +266,12 @@ class NeighborLoader:
             gen = torch.Generator(device=self.device)
             gen.manual_seed(self.seed * 1000003 + epoch)
             nodes = nodes[torch.randperm(nodes.numel(), device=self.device, generator=gen)]
-        B, n = self.batch_size, nodes.numel()
-        n_full = n // B
+        B = self.batch_size
         # every epoch draws afresh, as the reference's global stream does (utils/random.rs:19-22): mini-batch j of
         # epoch e uses call id call_id0 + e * len(self) + j -- reproducible for a fixed (seed, epoch)
         batch0 = epoch * len(self)
-        work = []
-        for start in range(0, n_full, self.prefetch):
-            G = min(self.prefetch, n_full - start)
-            work.append((nodes[start * B:(start + G) * B].reshape(G, B), batch0 + start))
-        if not self.drop_last and n_full * B < n:               # ragged last mini-batch: its own launch
-            work.append((nodes[n_full * B:].reshape(1, -1), batch0 + n_full))
+        work = [(nodes[start:start + G * width].reshape(G, width), batch0 + start // B)
+                for start, G, width in _epoch_plan(nodes.numel(), B, self.prefetch, self.drop_last)]
         # this iterator's own slabs (two iterators alive at once -- zip(loader, loader), a restart after an abandoned
         # epoch -- must not sample into each other's); they go back to the pool when the iterator ends or is dropped
         slabs = self._pool.pop() if self._pool else {}
@@ -277,96 +294,225 @@ class NeighborLoader:
             yield from sb
 
 
-class HeteroNeighborLoader:
-    """The heterogeneous counterpart: seeds of ONE node type, `prefetch` mini-batches per tg_ns_hetero_batched launch
-    (all hops and relations fused, default samplers), per-type / per-relation slabs flattened by tg_compact_rows, node
-    attributes gathered per type, edge attributes per relation through the ingest permutation.  Mini-batch j of the
-    epoch equals neighbor_sampling_heterogenous for (seed, call_id0 + j)."""
+def _flat_rows(slab: Tensor, lens: Tensor, total: int) -> Tensor:
+    """tg_compact_rows, or an empty tensor when the rows hold nothing (the library refuses a null destination)."""
+    if total == 0:
+        return torch.empty(0, dtype=torch.int64, device=slab.device)
+    return _cabi.compact_rows(slab, lens, total)
+
+
+def _rows_of(table: Tensor, index: Tensor) -> Tensor:
+    return _cabi.gather_rows(table, index)[0]                       # the ids come from a sampler: no range read-back
+
+
+def _fill_store(st, b: int, fields, attrs):
+    """Mini-batch b's part of a node type's or a relation's launch-wide fields and attributes, set on its store."""
+    for k, parts in fields:
+        if parts is not None:
+            setattr(st, k, parts[b])
+    for k, parts in attrs.items():
+        setattr(st, k, parts[b])
+
+
+class _TypedLoader(_Loader):
+    """The program the typed-graph loaders share: seeds of ONE node type, `prefetch` mini-batches per launch of a batched
+    operator, ONE read-back per launch, every per-type / per-relation slab flattened by tg_compact_rows and split per
+    mini-batch, node attributes gathered per type by n_id and edge attributes per relation by e_id, one graph per
+    mini-batch.  Mini-batch j of epoch e draws with call id call_id0 + e * len(loader) + j.  A subclass builds the launch
+    object (_new_launch) and may say how its state is read back, what e_id is, what else a mini-batch carries and when a
+    panic is raised."""
+    EDGE_FIELD = "edge_index"       # the name of a relation's [2, E] tensor on a mini-batch
+    REUSE_SLABS = False             # True: full launches copy their seeds into one kept launch object
+    SAMPLE_TS = False               # True: the launch has sample_ts slabs, split into `ts_parts`
+    input_ts = None
+
+    def __init__(self, data, input_type, input_nodes, batch_size, drop_last, seed, call_id0, device, edge_attrs=True):
+        self.data, self.device = data, torch.device(device)
+        self.batch_size, self.drop_last, self.seed, self.call_id0 = int(batch_size), drop_last, int(seed), int(call_id0)
+        self.hetero = _is_hetero(data)
+        if self.hetero:
+            self.node_types, self.edge_types = list(data.node_types), list(data.edge_types)
+            if input_type not in self.node_types:
+                raise ValueError("input_type must name one of the node types %s" % self.node_types)
+            stores = [data[t] for t in self.node_types]
+        else:                                                       # one unnamed node type, one unnamed relation
+            self.node_types, self.edge_types, input_type, stores = [None], [None], None, [data]
+        self.input_type = input_type
+        self._tix = {t: i for i, t in enumerate(self.node_types)}
+        self._it = self._tix[input_type]
+        n_in = _num_nodes(stores[self._it])
+        nodes = torch.arange(n_in, device=self.device) if input_nodes is None else input_nodes.to(self.device)
+        self.input_nodes = _checked_inputs(nodes, n_in)             # an input indexes the rows of its type unchecked
+        self._node_attrs = [self._attrs_of(st, _num_nodes(st)) for st in stores]
+        self._edge_attrs = [self._attrs_of(data[et], int(data[et].edge_index.shape[1])) if edge_attrs else []
+                            for et in self.edge_types]
+        self.epoch = 0
+        self._launch = {}                                           # (calls, seeds per call) -> the kept launch object
+
+    def _attrs_of(self, store, n):
+        """The tensors of a store that have one row per node (per edge), on the device."""
+        return [(k, v.to(self.device)) for k, v in _tensor_items(store)
+                if k != "edge_index" and v.dim() > 0 and v.shape[0] == n]
+
+    def _quotas(self, quotas, name):
+        """Per-hop quotas, one list for every node type or a dict per type -> (dict per type, number of hops)."""
+        if isinstance(quotas, dict):
+            per_type = {k: [int(x) for x in v] for k, v in quotas.items()}
+            n_hops = max((len(v) for v in per_type.values()), default=0)
+        else:
+            n_hops = len(quotas)
+            per_type = {nt: [int(x) for x in quotas] for nt in self.node_types}
+        for nt, v in per_type.items():
+            if len(v) < n_hops:
+                raise ValueError("%s[%s] is shorter than the number of hops" % (name, nt))
+        return per_type, n_hops
+
+    def _csc_rels(self, fifth):
+        """Ingests every relation as a CSC (col_ptrs, row_indices, perm: CSC position -> COO edge id) -> the operators'
+        `rels` tuples, with fifth(edge type) as their fifth entry."""
+        self.col_ptrs, self.row_indices, self.perm = to_hetero_csc(self.data, self.device)
+        return [(self._tix[et[0]], self._tix[et[2]], self.col_ptrs[rel_key(et)], self.row_indices[rel_key(et)], fifth(et))
+                for et in self.edge_types]
+
+    # ---- what a subclass fills in
+    def _new_launch(self, inputs, input_ts, n_calls):
+        """-> the _cabi launch object (problem, slabs, run) for n_calls mini-batches; inputs / input_ts: per node type a
+        [n_calls, seeds] tensor or None (input_ts None: no timestamps)."""
+        raise NotImplementedError
+
+    def _read_back(self, slabs):
+        """The launch's only read-back -> (host counts [n_calls, >= T + R], what _decorate and _check_panic want)."""
+        return slabs.counts.cpu(), None
+
+    def _e_id(self, slabs, r, cols, n_edges, total, flat_nodes):
+        """COO edge ids of relation r's sampled edges, flat over the launch; None: the mini-batches carry no e_id.  Here
+        the operator's edge_index is a CSC position, so e_id = perm[edge_index]."""
+        return _rows_of(self.perm[rel_key(self.edge_types[r])], _flat_rows(slabs.edge_index[r], n_edges, total))
+
+    def _decorate(self, g, b, n_seeds, state, ts_parts):
+        """The loader's own extras on mini-batch b of the launch."""
+
+    def _check_panic(self, counts, state, first_batch, b):
+        """Raises where the reference would have panicked.  Called with b = None after the read-back, before any
+        mini-batch of the launch is handed out, and with every b before that mini-batch is."""
+
+    # ---- the skeleton
+    def _launch_for(self, seeds: Tensor, seeds_ts: Optional[Tensor]):
+        G, B = seeds.shape
+        per_type = lambda x: None if x is None else [x if t == self._it else None for t in range(len(self.node_types))]
+        if not self.REUSE_SLABS:
+            return self._new_launch(per_type(seeds.contiguous()),
+                                    per_type(None if seeds_ts is None else seeds_ts.contiguous()), G)
+        slabs = self._launch.get((G, B))
+        if slabs is None:  # full launches reuse one set of slabs; a shorter last launch gets its own, freed after use
+            slabs = self._new_launch(per_type(seeds.clone()), per_type(None if seeds_ts is None else seeds_ts.clone()), G)
+            if G == self.prefetch and B == self.batch_size:
+                self._launch = {(G, B): slabs}
+        else:
+            slabs.inputs[self._it].copy_(seeds)
+            if seeds_ts is not None:
+                slabs.input_ts[self._it].copy_(seeds_ts)
+        return slabs
+
+    def _graph_of(self, b, n_seeds, node_parts, edge_parts):
+        g = HeteroGraph()
+        for nt, (fields, attrs) in zip(self.node_types, node_parts):
+            _fill_store(g[nt], b, fields, attrs)
+        g[self.input_type].batch_size = n_seeds
+        for et, (fields, attrs) in zip(self.edge_types, edge_parts):
+            _fill_store(g[et], b, fields, attrs)
+        return g
+
+    def _emit(self, seeds: Tensor, seeds_ts: Optional[Tensor], first_batch: int):
+        G, B = seeds.shape
+        T = len(self.node_types)
+        slabs = self._launch_for(seeds, seeds_ts)
+        slabs.run(self.seed, self.call_id0 + first_batch)
+        counts, state = self._read_back(slabs)
+        self._check_panic(counts, state, first_batch, None)
+        flat_nodes, ts_parts, node_parts, edge_parts = [], [], [], []
+        for t in range(T):
+            n, lens = slabs.counts[:, t], counts[:, t].tolist()
+            flat = _flat_rows(slabs.samples[t], n, sum(lens))
+            flat_nodes.append(flat)
+            if self.SAMPLE_TS:
+                ts_parts.append(torch.split(_flat_rows(slabs.sample_ts[t], n, sum(lens)), lens))
+            node_parts.append(((("n_id", torch.split(flat, lens)), ("num_nodes", lens)),
+                               {k: torch.split(_rows_of(v, flat), lens) for k, v in self._node_attrs[t]}))
+        for r in range(len(self.edge_types)):
+            n, lens = slabs.counts[:, T + r], counts[:, T + r].tolist()
+            tot = sum(lens)
+            fr, fc = _flat_rows(slabs.rows[r], n, tot), _flat_rows(slabs.cols[r], n, tot)
+            fe = self._e_id(slabs, r, fc, n, tot, flat_nodes)
+            edge_parts.append((((self.EDGE_FIELD, torch.split(torch.stack([fr, fc]), lens, dim=1)),
+                                ("e_id", None if fe is None else torch.split(fe, lens))),
+                               {k: torch.split(_rows_of(v, fe), lens) for k, v in self._edge_attrs[r]}))
+        for b in range(G):
+            self._check_panic(counts, state, first_batch, b)
+            g = self._graph_of(b, B, node_parts, edge_parts)
+            self._decorate(g, b, B, state, ts_parts)
+            g.call_id = self.call_id0 + first_batch + b
+            yield g
+
+    def __iter__(self):
+        nodes, ts, B = self.input_nodes, self.input_ts, self.batch_size
+        batch0 = self.epoch * len(self)                             # fresh draws every epoch (see NeighborLoader)
+        self.epoch += 1
+        for start, G, width in _epoch_plan(nodes.numel(), B, self.prefetch, self.drop_last):
+            sl = slice(start, start + G * width)
+            yield from self._emit(nodes[sl].reshape(G, width), None if ts is None else ts[sl].reshape(G, width),
+                                  batch0 + start // B)
+
+
+class _TemporalInputs:
+    """What HGTLoader and BudgetLoader add to _TypedLoader alike: temporal=True takes the edge stores' int64 `timestamps`
+    as row timestamps and `input_timestamps` (one per input node) as the seeds' timestamps; the operators return a
+    timestamp per sampled node, handed out per node type as the mini-batch's samples_timestamps."""
+    SAMPLE_TS = True
+
+    def _init_temporal(self, temporal, input_timestamps):
+        """-> self.temporal, self._rels (CSC, with row timestamps in CSC edge order when temporal), self.input_ts"""
+        self.temporal = temporal
+        self._rels = self._csc_rels(lambda et: _rows_of(self.data[et].timestamps.to(self.device).to(torch.int64),
+                                                        self.perm[rel_key(et)]) if temporal else None)
+        if temporal:
+            if input_timestamps is None:
+                raise ValueError("temporal=True needs input_timestamps (one per input node)")
+            self.input_ts = input_timestamps.to(self.device).reshape(-1).to(torch.int64)
+            if self.input_ts.numel() != self.input_nodes.numel():
+                raise ValueError("input_timestamps must have one entry per input node")
+
+    def _decorate(self, g, b, n_seeds, state, ts_parts):
+        g.samples_timestamps = {nt: ts_parts[t][b] for t, nt in enumerate(self.node_types)}
+
+
+class HeteroNeighborLoader(_TypedLoader):
+    """The heterogeneous counterpart of NeighborLoader: seeds of ONE node type, `prefetch` mini-batches per
+    tg_ns_hetero_batched launch (all hops and relations fused, default samplers), per-type / per-relation slabs flattened
+    by tg_compact_rows, node attributes gathered per type, edge attributes per relation through the ingest permutation.
+    Mini-batch j of the epoch equals neighbor_sampling_heterogenous for (seed, call_id0 + j)."""
 
     def __init__(self, data, num_neighbors: List[int], input_type: str, input_nodes: Optional[Tensor] = None,
                  batch_size: int = 1024, prefetch: int = 16, replace: bool = False, drop_last: bool = False, seed: int = 0,
                  call_id0: int = 0, device="cuda"):
-        self.data, self.fanout, self.device = data, [int(k) for k in num_neighbors], torch.device(device)
-        self.node_types, self.edge_types = list(data.node_types), list(data.edge_types)
-        self.input_type, self.batch_size, self.prefetch = input_type, int(batch_size), max(1, int(prefetch))
+        super().__init__(data, input_type, input_nodes, batch_size, drop_last, seed, call_id0, device)
+        self.fanout, self.prefetch = [int(k) for k in num_neighbors], max(1, int(prefetch))
         self.sampler = _cabi.SAMPLER_UNIFORM_REPL if replace else _cabi.SAMPLER_UNIFORM
-        self.drop_last, self.seed, self.call_id0 = drop_last, int(seed), int(call_id0)
-        self.col_ptrs, self.row_indices, self.perm = to_hetero_csc(data, self.device)
-        tix = {t: i for i, t in enumerate(self.node_types)}
-        self._tix = tix
-        self._rels = [(tix[et[0]], tix[et[2]], self.col_ptrs[rel_key(et)], self.row_indices[rel_key(et)], self.fanout)
-                      for et in self.edge_types]
-        n_in = _num_nodes(data[input_type])
-        nodes = torch.arange(n_in, device=self.device) if input_nodes is None else input_nodes.to(self.device)
-        self.input_nodes = _checked_inputs(nodes, n_in)
-        self.epoch = 0
-        self._node_attrs = {t: [(k, v.to(self.device)) for k, v in _tensor_items(data[t])
-                                if v.dim() > 0 and v.shape[0] == _num_nodes(data[t])] for t in self.node_types}
-        self._edge_attrs = {}
-        for et in self.edge_types:
-            n_e = int(data[et].edge_index.shape[1])
-            self._edge_attrs[et] = [(k, v.to(self.device)) for k, v in _tensor_items(data[et])
-                                    if k != "edge_index" and v.dim() > 0 and v.shape[0] == n_e]
+        self._rels = self._csc_rels(lambda et: self.fanout)
 
-    def __len__(self) -> int:
-        n = self.input_nodes.numel()
-        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+    def _new_launch(self, inputs, input_ts, n_calls):
+        return _cabi.NsHeteroBatched(len(self.node_types), self._rels, inputs, len(self.fanout), n_calls, self.device,
+                                     sampler=self.sampler)
 
-    def _emit(self, seeds: Tensor, first_batch: int) -> Iterator[HeteroGraph]:
-        G, B = seeds.shape
-        T, R, H = len(self.node_types), len(self.edge_types), len(self.fanout)
-        inputs = [None] * T
-        inputs[self._tix[self.input_type]] = seeds.contiguous()
-        hb = _cabi.NsHeteroBatched(T, self._rels, inputs, H, G, self.device, sampler=self.sampler)
-        hb.run(self.seed, self.call_id0 + first_batch)
-        counts = hb.counts.cpu()                                # the launch's only read-back
-        lo = hb.layer_offsets.cpu().tolist()
-        rows_of = lambda table, index: _cabi.gather_rows(table, index)[0]
-        node_parts, attr_parts = {}, {}
-        for t, nt in enumerate(self.node_types):
-            lens = counts[:, t].tolist()
-            flat = _cabi.compact_rows(hb.samples[t], hb.counts[:, t], sum(lens))
-            node_parts[nt] = (torch.split(flat, lens), lens)
-            attr_parts[nt] = {k: torch.split(rows_of(v, flat), lens) for k, v in self._node_attrs[nt]}
-        edge_parts = {}
+    def _read_back(self, slabs):
+        return slabs.counts.cpu(), slabs.layer_offsets.cpu().tolist()
+
+    def _decorate(self, g, b, n_seeds, state, ts_parts):
         for r, et in enumerate(self.edge_types):
-            lens = counts[:, T + r].tolist()
-            tot = sum(lens)
-            fr = _cabi.compact_rows(hb.rows[r], hb.counts[:, T + r], tot)
-            fc = _cabi.compact_rows(hb.cols[r], hb.counts[:, T + r], tot)
-            fe = rows_of(self.perm[rel_key(et)], _cabi.compact_rows(hb.edge_index[r], hb.counts[:, T + r], tot))
-            edge_parts[et] = (torch.split(torch.stack([fr, fc]), lens, dim=1), torch.split(fe, lens),
-                              {k: torch.split(rows_of(v, fe), lens) for k, v in self._edge_attrs[et]})
-        for b in range(G):
-            g = HeteroGraph()
-            for nt in self.node_types:
-                st = g[nt]
-                st.n_id, st.num_nodes = node_parts[nt][0][b], node_parts[nt][1][b]
-                for k, parts in attr_parts[nt].items():
-                    setattr(st, k, parts[b])
-            g[self.input_type].batch_size = B
-            for r, et in enumerate(self.edge_types):
-                st = g[et]
-                st.edge_index, st.e_id = edge_parts[et][0][b], edge_parts[et][1][b]
-                st.layer_offsets = [tuple(x) for x in lo[b][r][:H]]
-                for k, parts in edge_parts[et][2].items():
-                    setattr(st, k, parts[b])
-            g.call_id = self.call_id0 + first_batch + b
-            yield g
-
-    def __iter__(self) -> Iterator[HeteroGraph]:
-        nodes, B = self.input_nodes, self.batch_size
-        batch0 = self.epoch * len(self)                         # fresh draws every epoch (see NeighborLoader)
-        self.epoch += 1
-        n_full = nodes.numel() // B
-        for start in range(0, n_full, self.prefetch):
-            G = min(self.prefetch, n_full - start)
-            yield from self._emit(nodes[start * B:(start + G) * B].reshape(G, B), batch0 + start)
-        if not self.drop_last and n_full * B < nodes.numel():
-            yield from self._emit(nodes[n_full * B:].reshape(1, -1), batch0 + n_full)
+            g[et].layer_offsets = [tuple(x) for x in state[b][r][:len(self.fanout)]]
 
 
-class HGTLoader:
+class HGTLoader(_TemporalInputs, _TypedLoader):
     """HGT budget sampling (hgt_sampling) as a loader: seeds of ONE node type, `prefetch` mini-batches per
     tg_hgt_sample_batched launch chain, one read-back of the counts per launch, per-type / per-relation slabs flattened
     by tg_compact_rows, node attributes gathered per type and edge attributes per relation through the ingest
@@ -382,48 +528,12 @@ class HGTLoader:
                  prefetch: int = 64, temporal: bool = False, input_timestamps: Optional[Tensor] = None, timerange=None,
                  drop_last: bool = False, seed: int = 0, call_id0: int = 0, max_workspace_bytes: int = 4 << 30,
                  device="cuda"):
-        self.data, self.device = data, torch.device(device)
-        self.node_types, self.edge_types = list(data.node_types), list(data.edge_types)
-        self.input_type, self.batch_size = input_type, int(batch_size)
-        self.drop_last, self.seed, self.call_id0 = drop_last, int(seed), int(call_id0)
-        if isinstance(num_samples, dict):
-            self.num_samples = {k: [int(x) for x in v] for k, v in num_samples.items()}
-            self.n_hops = max((len(v) for v in self.num_samples.values()), default=0)
-        else:
-            self.n_hops = len(num_samples)
-            self.num_samples = {nt: [int(x) for x in num_samples] for nt in self.node_types}
-        for nt, v in self.num_samples.items():
-            if len(v) < self.n_hops:
-                raise ValueError("num_samples[%s] is shorter than the number of hops" % nt)
-        self.col_ptrs, self.row_indices, self.perm = to_hetero_csc(data, self.device)
-        self.temporal, self.timerange = temporal, (None if timerange is None else (int(timerange[0]), int(timerange[1])))
-        self._tix = {t: i for i, t in enumerate(self.node_types)}
-        rts = {}
-        if temporal:  # timestamps follow the CSC edge order
-            rts = {rel_key(et): _cabi.gather_rows(data[et].timestamps.to(self.device).to(torch.int64),
-                                                  self.perm[rel_key(et)])[0] for et in self.edge_types}
-        self._rels = [(self._tix[et[0]], self._tix[et[2]], self.col_ptrs[rel_key(et)], self.row_indices[rel_key(et)],
-                       rts.get(rel_key(et))) for et in self.edge_types]
-        n_in = _num_nodes(data[input_type])
-        nodes = torch.arange(n_in, device=self.device) if input_nodes is None else input_nodes.to(self.device)
-        self.input_nodes = _checked_inputs(nodes, n_in)
-        self.input_ts = None
-        if temporal:
-            if input_timestamps is None:
-                raise ValueError("temporal=True needs input_timestamps (one per input node)")
-            self.input_ts = input_timestamps.to(self.device).reshape(-1).to(torch.int64)
-            if self.input_ts.numel() != self.input_nodes.numel():
-                raise ValueError("input_timestamps must have one entry per input node")
+        super().__init__(data, input_type, input_nodes, batch_size, drop_last, seed, call_id0, device)
+        self.num_samples, self.n_hops = self._quotas(num_samples, "num_samples")
+        self.timerange = None if timerange is None else (int(timerange[0]), int(timerange[1]))
+        self._init_temporal(temporal, input_timestamps)
         per_call = _cabi.hgt_batched_workspace_bytes(self._problem(self.batch_size), 1)
         self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // per_call))
-        self.epoch = 0
-        self._node_attrs = {t: [(k, v.to(self.device)) for k, v in _tensor_items(data[t])
-                                if v.dim() > 0 and v.shape[0] == _num_nodes(data[t])] for t in self.node_types}
-        self._edge_attrs = {}
-        for et in self.edge_types:
-            n_e = int(data[et].edge_index.shape[1])
-            self._edge_attrs[et] = [(k, v.to(self.device)) for k, v in _tensor_items(data[et])
-                                    if k != "edge_index" and v.dim() > 0 and v.shape[0] == n_e]
 
     def _num_samples(self):
         return [self.num_samples.get(nt) for nt in self.node_types]
@@ -433,84 +543,21 @@ class HGTLoader:
         n_in = [n_seeds if nt == self.input_type else -1 for nt in self.node_types]
         return _cabi.hgt_problem(len(self.node_types), self._rels, n_in, self._num_samples(), self.n_hops)
 
-    def __len__(self) -> int:
-        n = self.input_nodes.numel()
-        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+    def _new_launch(self, inputs, input_ts, n_calls):
+        return _cabi.HgtBatched(len(self.node_types), self._rels, inputs, self._num_samples(), self.n_hops, n_calls,
+                                self.device, input_ts=input_ts, timerange=self.timerange if self.temporal else None)
 
-    def _emit(self, seeds: Tensor, seeds_ts: Optional[Tensor], first_batch: int) -> Iterator[HeteroGraph]:
-        G, B = seeds.shape
-        T, R = len(self.node_types), len(self.edge_types)
-        it = self._tix[self.input_type]
-        inputs = [None] * T
-        inputs[it] = seeds.contiguous()
-        input_ts = None
-        if seeds_ts is not None:
-            input_ts = [None] * T
-            input_ts[it] = seeds_ts.contiguous()
-        hb = _cabi.HgtBatched(T, self._rels, inputs, self._num_samples(), self.n_hops, G, self.device,
-                              input_ts=input_ts, timerange=self.timerange if self.temporal else None)
-        hb.run(self.seed, self.call_id0 + first_batch)
-        counts = hb.counts.cpu()                                # the launch's only read-back
-        panicked = [b for b in range(G) if int(counts[b, T + R]) != 0]
-        if panicked:
-            raise RuntimeError("HGTLoader: mini-batch %d: a weight sum was not positive, or a node type that owns a budget "
-                               "has no num_samples entry (the reference panics here)" % (first_batch + panicked[0]))
-        rows_of = lambda table, index: _cabi.gather_rows(table, index)[0]
-        node_parts, ts_parts, attr_parts = {}, {}, {}
-        for t, nt in enumerate(self.node_types):
-            lens = counts[:, t].tolist()
-            flat = _cabi.compact_rows(hb.samples[t], hb.counts[:, t], sum(lens))
-            node_parts[nt] = (torch.split(flat, lens), lens)
-            ts_parts[nt] = torch.split(_cabi.compact_rows(hb.sample_ts[t], hb.counts[:, t], sum(lens)), lens)
-            attr_parts[nt] = {k: torch.split(rows_of(v, flat), lens) for k, v in self._node_attrs[nt]}
-        edge_parts = {}
-        for r, et in enumerate(self.edge_types):
-            lens = counts[:, T + r].tolist()
-            tot = sum(lens)
-            fr = _cabi.compact_rows(hb.rows[r], hb.counts[:, T + r], tot)
-            fc = _cabi.compact_rows(hb.cols[r], hb.counts[:, T + r], tot)
-            fe = rows_of(self.perm[rel_key(et)], _cabi.compact_rows(hb.edge_index[r], hb.counts[:, T + r], tot))
-            edge_parts[et] = (torch.split(torch.stack([fr, fc]), lens, dim=1), torch.split(fe, lens),
-                              {k: torch.split(rows_of(v, fe), lens) for k, v in self._edge_attrs[et]})
-        for b in range(G):
-            g = HeteroGraph()
-            for nt in self.node_types:
-                st = g[nt]
-                st.n_id, st.num_nodes = node_parts[nt][0][b], node_parts[nt][1][b]
-                for k, parts in attr_parts[nt].items():
-                    setattr(st, k, parts[b])
-            g[self.input_type].batch_size = B
-            for et in self.edge_types:
-                st = g[et]
-                st.edge_index, st.e_id = edge_parts[et][0][b], edge_parts[et][1][b]
-                for k, parts in edge_parts[et][2].items():
-                    setattr(st, k, parts[b])
-            g.samples_timestamps = {nt: ts_parts[nt][b] for nt in self.node_types}
-            g.call_id = self.call_id0 + first_batch + b
-            yield g
-
-    def __iter__(self) -> Iterator[HeteroGraph]:
-        nodes, ts, B = self.input_nodes, self.input_ts, self.batch_size
-        batch0 = self.epoch * len(self)                         # fresh draws every epoch (see NeighborLoader)
-        self.epoch += 1
-        n_full = nodes.numel() // B
-        for start in range(0, n_full, self.prefetch):
-            G = min(self.prefetch, n_full - start)
-            sl = slice(start * B, (start + G) * B)
-            yield from self._emit(nodes[sl].reshape(G, B), None if ts is None else ts[sl].reshape(G, B), batch0 + start)
-        if not self.drop_last and n_full * B < nodes.numel():
-            yield from self._emit(nodes[n_full * B:].reshape(1, -1), None if ts is None else ts[n_full * B:].reshape(1, -1),
-                                  batch0 + n_full)
+    def _check_panic(self, counts, state, first_batch, b):
+        if b is None:                                               # the whole launch, before any mini-batch is handed out
+            word = len(self.node_types) + len(self.edge_types)
+            panicked = [j for j in range(counts.shape[0]) if int(counts[j, word]) != 0]
+            if panicked:
+                raise RuntimeError("HGTLoader: mini-batch %d: a weight sum was not positive, or a node type that owns a "
+                                   "budget has no num_samples entry (the reference panics here)"
+                                   % (first_batch + panicked[0]))
 
 
-def _flat_rows(slab: Tensor, lens: Tensor, total: int) -> Tensor:
-    """tg_compact_rows, or an empty tensor when the rows hold nothing (the library refuses a null destination)."""
-    if total == 0:
-        return torch.empty(0, dtype=torch.int64, device=slab.device)
-    return _cabi.compact_rows(slab, lens, total)
-
-
-class BudgetLoader:
+class BudgetLoader(_TemporalInputs, _TypedLoader):
     """Temporal heterogeneous budget sampling (budget_sampling) as a loader: seeds of ONE node type, `prefetch`
     mini-batches per tg_budget_sample_batched launch chain, one read-back of the counts per launch, per-type /
     per-relation slabs flattened by tg_compact_rows, node attributes gathered per type and edge attributes per relation.
@@ -524,154 +571,50 @@ class BudgetLoader:
     Mini-batch j of the epoch equals budget_sampling for (seed, call_id0 + j); every epoch draws fresh call ids.  A
     launch's device memory is prefetch x (workspace + output slabs + counts of one call): the slabs are sized for the
     worst case and dominate, so prefetch is clamped to keep both within `max_workspace_bytes` (default 4 GiB; at least
-    one mini-batch per launch)."""
+    one mini-batch per launch).  Full launches reuse one set of slabs."""
+    REUSE_SLABS = True
 
     def __init__(self, data, num_neighbors, input_type: str, input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
                  prefetch: int = 64, temporal: bool = False, input_timestamps: Optional[Tensor] = None, window=None,
                  forward: bool = False, relative: bool = False, drop_last: bool = False, seed: int = 0, call_id0: int = 0,
                  max_workspace_bytes: int = 4 << 30, device="cuda"):
-        self.data, self.device = data, torch.device(device)
-        self.node_types, self.edge_types = list(data.node_types), list(data.edge_types)
-        self.input_type, self.batch_size = input_type, int(batch_size)
-        self.drop_last, self.seed, self.call_id0 = drop_last, int(seed), int(call_id0)
-        if isinstance(num_neighbors, dict):
-            nn = {k: [int(x) for x in v] for k, v in num_neighbors.items()}
-            self.n_hops = max((len(v) for v in nn.values()), default=0)
-        else:
-            self.n_hops = len(num_neighbors)
-            nn = {nt: [int(x) for x in num_neighbors] for nt in self.node_types}
+        super().__init__(data, input_type, input_nodes, batch_size, drop_last, seed, call_id0, device)
+        nn, self.n_hops = self._quotas(num_neighbors, "num_neighbors")
         for nt in self.node_types:
             if self.n_hops and nt not in nn:
                 raise ValueError("num_neighbors has no entry for node type %s (budget_sampling panics here)" % nt)
-            if self.n_hops and len(nn[nt]) < self.n_hops:
-                raise ValueError("num_neighbors[%s] is shorter than the number of hops" % nt)
         self.num_neighbors = [nn[nt][:self.n_hops] if self.n_hops else [] for nt in self.node_types]
         self.window = None if window is None else (int(window[0]), int(window[1]))
         self.forward, self.relative = bool(forward), bool(relative)
-        self.col_ptrs, self.row_indices, self.perm = to_hetero_csc(data, self.device)
-        self.temporal = temporal
-        self._tix = {t: i for i, t in enumerate(self.node_types)}
-        rts = {}
-        if temporal:  # timestamps follow the CSC edge order
-            rts = {rel_key(et): _cabi.gather_rows(data[et].timestamps.to(self.device).to(torch.int64),
-                                                  self.perm[rel_key(et)])[0] for et in self.edge_types}
-        self._rels = [(self._tix[et[0]], self._tix[et[2]], self.col_ptrs[rel_key(et)], self.row_indices[rel_key(et)],
-                       rts.get(rel_key(et))) for et in self.edge_types]
-        n_in = _num_nodes(data[input_type])
-        nodes = torch.arange(n_in, device=self.device) if input_nodes is None else input_nodes.to(self.device)
-        self.input_nodes = _checked_inputs(nodes, n_in)
-        self.input_ts = None
-        if temporal:
-            if input_timestamps is None:
-                raise ValueError("temporal=True needs input_timestamps (one per input node)")
-            self.input_ts = input_timestamps.to(self.device).reshape(-1).to(torch.int64)
-            if self.input_ts.numel() != self.input_nodes.numel():
-                raise ValueError("input_timestamps must have one entry per input node")
+        self._init_temporal(temporal, input_timestamps)
         per_call = _cabi.budget_batched_bytes(self._problem(self.batch_size), 1)
         self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // per_call))
-        self.epoch = 0
-        self._launch = {}                                       # (calls, seeds per call) -> BudgetBatched
-        self._node_attrs = {t: [(k, v.to(self.device)) for k, v in _tensor_items(data[t])
-                                if v.dim() > 0 and v.shape[0] == _num_nodes(data[t])] for t in self.node_types}
-        self._edge_attrs = {}
-        for et in self.edge_types:
-            n_e = int(data[et].edge_index.shape[1])
-            self._edge_attrs[et] = [(k, v.to(self.device)) for k, v in _tensor_items(data[et])
-                                    if k != "edge_index" and v.dim() > 0 and v.shape[0] == n_e]
 
     def _problem(self, n_seeds):
         """A host-only problem of the loader's shape (sizes a launch; nothing is launched)."""
         n_in = [n_seeds if nt == self.input_type else 0 for nt in self.node_types]
         return _cabi.budget_problem(len(self.node_types), self._rels, n_in, self.num_neighbors, self.n_hops)
 
-    def __len__(self) -> int:
-        n = self.input_nodes.numel()
-        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+    def _new_launch(self, inputs, input_ts, n_calls):
+        return _cabi.BudgetBatched(len(self.node_types), self._rels, inputs, self.num_neighbors, self.n_hops, n_calls,
+                                   self.device, input_ts=input_ts, window=self.window, forward=self.forward,
+                                   relative=self.relative)
 
-    def _emit(self, seeds: Tensor, seeds_ts: Optional[Tensor], first_batch: int) -> Iterator[HeteroGraph]:
-        G, B = seeds.shape
-        T = len(self.node_types)
-        it = self._tix[self.input_type]
-        inputs = [None] * T
-        inputs[it] = seeds.contiguous()
-        input_ts = None
-        if seeds_ts is not None:
-            input_ts = [None] * T
-            input_ts[it] = seeds_ts.contiguous()
-        bb = self._launch.get((G, B))
-        if bb is None:  # full launches reuse one set of slabs; a shorter last launch gets its own, freed after use
-            bb = _cabi.BudgetBatched(T, self._rels, [None if x is None else x.clone() for x in inputs], self.num_neighbors,
-                                     self.n_hops, G, self.device,
-                                     input_ts=None if input_ts is None else [None if x is None else x.clone() for x in input_ts],
-                                     window=self.window, forward=self.forward, relative=self.relative)
-            if G == self.prefetch and B == self.batch_size:
-                self._launch = {(G, B): bb}
-        else:
-            bb.inputs[it].copy_(seeds)
-            if seeds_ts is not None:
-                bb.input_ts[it].copy_(seeds_ts)
-        bb.run(self.seed, self.call_id0 + first_batch)
-        counts = bb.counts.cpu()                                # the launch's only read-back
-        rows_of = lambda table, index: _cabi.gather_rows(table, index)[0]
-        node_parts, ts_parts, attr_parts, flat_nodes, node_off = {}, {}, {}, [], []
-        for t, nt in enumerate(self.node_types):
-            lens = counts[:, t].tolist()
-            flat = _flat_rows(bb.samples[t], bb.counts[:, t], sum(lens))
-            flat_nodes.append(flat)
-            node_off.append(torch.cumsum(bb.counts[:, t], 0) - bb.counts[:, t])   # where call b's nodes start in `flat`
-            node_parts[nt] = (torch.split(flat, lens), lens)
-            ts_parts[nt] = torch.split(_flat_rows(bb.sample_ts[t], bb.counts[:, t], sum(lens)), lens)
-            attr_parts[nt] = {k: torch.split(rows_of(v, flat), lens) for k, v in self._node_attrs[nt]}
-        edge_parts = {}
-        for r, et in enumerate(self.edge_types):
-            key, d = rel_key(et), self._tix[et[2]]
-            ne = bb.counts[:, T + r]
-            lens = counts[:, T + r].tolist()
-            tot = sum(lens)
-            fr = _flat_rows(bb.rows[r], ne, tot)
-            fc = _flat_rows(bb.cols[r], ne, tot)
-            fi = _flat_rows(bb.edge_index[r], ne, tot)
-            # e_id: the destination's node id -> its column start in the CSC -> + index inside the column -> COO edge id
-            w = rows_of(flat_nodes[d], fc + torch.repeat_interleave(node_off[d], ne, output_size=tot))
-            fe = rows_of(self.perm[key], rows_of(self.col_ptrs[key], w) + fi)
-            edge_parts[et] = (torch.split(torch.stack([fr, fc]), lens, dim=1), torch.split(fe, lens),
-                              {k: torch.split(rows_of(v, fe), lens) for k, v in self._edge_attrs[et]})
-        for b in range(G):
-            g = HeteroGraph()
-            for nt in self.node_types:
-                st = g[nt]
-                st.n_id, st.num_nodes = node_parts[nt][0][b], node_parts[nt][1][b]
-                for k, parts in attr_parts[nt].items():
-                    setattr(st, k, parts[b])
-            g[self.input_type].batch_size = B
-            for et in self.edge_types:
-                st = g[et]
-                st.edge_index, st.e_id = edge_parts[et][0][b], edge_parts[et][1][b]
-                for k, parts in edge_parts[et][2].items():
-                    setattr(st, k, parts[b])
-            g.samples_timestamps = {nt: ts_parts[nt][b] for nt in self.node_types}
-            g.call_id = self.call_id0 + first_batch + b
-            yield g
-
-    def __iter__(self) -> Iterator[HeteroGraph]:
-        nodes, ts, B = self.input_nodes, self.input_ts, self.batch_size
-        batch0 = self.epoch * len(self)                         # fresh draws every epoch (see NeighborLoader)
-        self.epoch += 1
-        n_full = nodes.numel() // B
-        for start in range(0, n_full, self.prefetch):
-            G = min(self.prefetch, n_full - start)
-            sl = slice(start * B, (start + G) * B)
-            yield from self._emit(nodes[sl].reshape(G, B), None if ts is None else ts[sl].reshape(G, B), batch0 + start)
-        if not self.drop_last and n_full * B < nodes.numel():
-            yield from self._emit(nodes[n_full * B:].reshape(1, -1), None if ts is None else ts[n_full * B:].reshape(1, -1),
-                                  batch0 + n_full)
+    def _e_id(self, slabs, r, cols, n_edges, total, flat_nodes):
+        # the destination's node id -> its column start in the CSC -> + index inside the column -> COO edge id
+        et = self.edge_types[r]
+        key, d = rel_key(et), self._tix[et[2]]
+        n_dst = slabs.counts[:, d]
+        node_off = torch.cumsum(n_dst, 0) - n_dst                   # where call b's nodes start in flat_nodes[d]
+        w = _rows_of(flat_nodes[d], cols + torch.repeat_interleave(node_off, n_edges, output_size=total))
+        return _rows_of(self.perm[key], _rows_of(self.col_ptrs[key], w) + _flat_rows(slabs.edge_index[r], n_edges, total))
 
 
-class NegativeLoader:
+class NegativeLoader(_TypedLoader):
     """Negative sampling (negative_sample_neighbors_homogenous / _heterogenous) as a loader: `prefetch` mini-batches per
     tg_neg_sample_batched launch (one workgroup runs one whole mini-batch in LDS where its shape fits, tchgeo.h), ONE
     read-back per launch (counts and panic words together), slabs flattened by tg_compact_rows and node attributes gathered
-    once per launch and split.
+    once per launch and split.  Full launches reuse one set of slabs.
 
     Homogeneous `data`: yields what NegativeSamplerTransform returns for the mini-batch's inputs (n_id, num_nodes,
     neg_edge_index, batch_size, node attributes gathered by n_id) plus `call_id`.  Heterogeneous `data`: the seeds are of ONE
@@ -682,6 +625,7 @@ class NegativeLoader:
     panic in a mini-batch (inbound, a drawn row out of range; negative_sampling.rs:113) the transform's RuntimeError is
     raised when that mini-batch is reached, not earlier.  A launch's device memory is the workspace plus prefetch x the
     slabs of one call; prefetch is clamped to keep it within `max_workspace_bytes` (at least one mini-batch per launch)."""
+    EDGE_FIELD, REUSE_SLABS = "neg_edge_index", True
 
     PANIC = ("inbound negative sampling indexed a CSR row out of range (the reference panics here, "
              "negative_sampling.rs:113)")
@@ -689,46 +633,26 @@ class NegativeLoader:
     def __init__(self, data, num_neg: int, try_count: int, input_nodes: Optional[Tensor] = None,
                  input_type: Optional[str] = None, batch_size: int = 1024, prefetch: int = 256, inbound: bool = False,
                  drop_last: bool = False, seed: int = 0, call_id0: int = 0, max_workspace_bytes: int = 4 << 30, device="cuda"):
-        self.data, self.device = data, torch.device(device)
-        self.num_neg, self.try_count, self.inbound = int(num_neg), int(try_count), bool(inbound)
+        self.num_neg, self.try_count = int(num_neg), int(try_count)
         if self.num_neg < 0 or self.try_count < 0:
             raise ValueError("num_neg and try_count must be >= 0")
-        self.batch_size, self.drop_last, self.seed, self.call_id0 = int(batch_size), drop_last, int(seed), int(call_id0)
-        self.hetero = hasattr(data, "node_types") and hasattr(data, "edge_types")
+        super().__init__(data, input_type, input_nodes, batch_size, drop_last, seed, call_id0, device, edge_attrs=False)
+        # the homogeneous operator has no inbound form (the transform ignores the flag)
+        self.inbound = bool(inbound) and self.hetero
         if self.hetero:
-            self.node_types, self.edge_types = list(data.node_types), list(data.edge_types)
-            if input_type not in self.node_types:
-                raise ValueError("input_type must name one of the node types %s" % self.node_types)
-            tix = {t: i for i, t in enumerate(self.node_types)}
             self._rels = []
             for et in self.edge_types:
                 size = (_num_nodes(data[et[0]]), _num_nodes(data[et[2]]))
                 if size[1] < 1:
                     raise ValueError("relation %s has an empty destination range" % (et,))
                 ptrs, idx, _ = _host.to_csr(data[et].edge_index.to(self.device), size)
-                self._rels.append((tix[et[0]], tix[et[2]], ptrs, idx, size[1]))
-            self._it = tix[input_type]
-            stores = [data[t] for t in self.node_types]
+                self._rels.append((self._tix[et[0]], self._tix[et[2]], ptrs, idx, size[1]))
         else:
-            self.node_types, self.edge_types, input_type = [None], [None], None
-            self.inbound = False                                    # the homogeneous operator has no inbound form (the transform ignores it)
             n = _num_nodes(data)
             ptrs, idx, _ = _host.to_csr(data.edge_index.to(self.device), n)
-            self._rels, self._it = [(0, 0, ptrs, idx, n)], 0
-            stores = [data]
-        self.input_type = input_type
-        n_in = _num_nodes(stores[self._it])
-        nodes = torch.arange(n_in, device=self.device) if input_nodes is None else input_nodes.to(self.device)
-        self.input_nodes = _checked_inputs(nodes, n_in)             # an input indexes the CSR rows of its type unchecked
-        self._node_attrs = []
-        for store in stores:
-            n = _num_nodes(store)
-            self._node_attrs.append([(k, v.to(self.device)) for k, v in _tensor_items(store)
-                                     if k != "edge_index" and v.dim() > 0 and v.shape[0] == n])
+            self._rels = [(0, 0, ptrs, idx, n)]
         per_call = max(1, _cabi.neg_batched_bytes(self._problem(self.batch_size), 1))
         self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // per_call, _cabi.TG_NEG_MAX_CALLS))
-        self.epoch = 0
-        self._launch = {}                                           # (calls, seeds per call) -> NegBatched
 
     def _problem(self, n_seeds):
         """A host-only problem of the loader's shape (sizes a launch; nothing is launched)."""
@@ -736,63 +660,30 @@ class NegativeLoader:
         return _cabi.neg_problem(len(self.node_types), self._rels, n_in, self.num_neg, self.try_count, None, self.inbound,
                                  not self.hetero)
 
-    def __len__(self) -> int:
-        n = self.input_nodes.numel()
-        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+    def _new_launch(self, inputs, input_ts, n_calls):
+        return _cabi.NegBatched(len(self.node_types), self._rels, inputs, self.num_neg, self.try_count, n_calls,
+                                self.device, self.inbound, not self.hetero)
 
-    def _emit(self, seeds: Tensor, first_batch: int):
-        G, B = seeds.shape
-        T = len(self.node_types)
-        nb = self._launch.get((G, B))
-        if nb is None:  # full launches reuse one set of slabs; a shorter last launch gets its own, freed after use
-            inputs = [None] * T
-            inputs[self._it] = seeds.clone()
-            nb = _cabi.NegBatched(T, self._rels, inputs, self.num_neg, self.try_count, G, self.device, self.inbound,
-                                  not self.hetero)
-            if G == self.prefetch and B == self.batch_size:
-                self._launch = {(G, B): nb}
-        else:
-            nb.inputs[self._it].copy_(seeds)
-        nb.run(self.seed, self.call_id0 + first_batch)
-        counts, panic = nb.read_state()                             # the launch's only read-back
-        node_parts, attr_parts = [], []
-        for t in range(T):
-            lens = counts[:, t].tolist()
-            flat = _flat_rows(nb.samples[t], nb.counts[:, t], sum(lens))
-            node_parts.append((torch.split(flat, lens), lens))
-            attr_parts.append({k: torch.split(_cabi.gather_rows(v, flat)[0], lens) for k, v in self._node_attrs[t]})
-        edge_parts = []
-        for r in range(len(self._rels)):
-            ne, lens = nb.counts[:, T + r], counts[:, T + r].tolist()
-            tot = sum(lens)
-            rc = torch.stack([_flat_rows(nb.rows[r], ne, tot), _flat_rows(nb.cols[r], ne, tot)])
-            edge_parts.append(torch.split(rc, lens, dim=1))
-        for b in range(G):
-            if int(panic[b]) != 0:
-                raise RuntimeError(self.PANIC)
-            if not self.hetero:
-                g = Graph(num_nodes=node_parts[0][1][b], n_id=node_parts[0][0][b], neg_edge_index=edge_parts[0][b], batch_size=B)
-                for k, parts in attr_parts[0].items():
-                    setattr(g, k, parts[b])
-            else:
-                g = HeteroGraph()
-                for t, nt in enumerate(self.node_types):
-                    st = g[nt]
-                    st.n_id, st.num_nodes, st.batch_size = node_parts[t][0][b], node_parts[t][1][b], B if t == self._it else 0
-                    for k, parts in attr_parts[t].items():
-                        setattr(st, k, parts[b])
-                for r, et in enumerate(self.edge_types):
-                    g[et].neg_edge_index = edge_parts[r][b]
-            g.call_id = self.call_id0 + first_batch + b
-            yield g
+    def _read_back(self, slabs):
+        return slabs.read_state()                                   # counts and panic words in one read-back
 
-    def __iter__(self):
-        nodes, B = self.input_nodes, self.batch_size
-        batch0 = self.epoch * len(self)                             # fresh draws every epoch (see NeighborLoader)
-        self.epoch += 1
-        n_full = nodes.numel() // B
-        for start in range(0, n_full, self.prefetch):
-            G = min(self.prefetch, n_full - start)
-            yield from self._emit(nodes[start * B:(start + G) * B].reshape(G, B), batch0 + start)
-        if not self.drop_last and n_full * B < nodes.numel():
-            yield from self._emit(nodes[n_full * B:].reshape(1, -1), batch0 + n_full)
+    def _e_id(self, slabs, r, cols, n_edges, total, flat_nodes):
+        return None                                                 # a negative edge is no edge of the graph
+
+    def _check_panic(self, counts, state, first_batch, b):
+        if b is not None and int(state[b]) != 0:                    # when the panicking mini-batch is reached
+            raise RuntimeError(self.PANIC)
+
+    def _graph_of(self, b, n_seeds, node_parts, edge_parts):
+        if self.hetero:
+            return super()._graph_of(b, n_seeds, node_parts, edge_parts)
+        g = Graph()                                                 # the homogeneous form: one flat container
+        _fill_store(g, b, *node_parts[0])
+        _fill_store(g, b, *edge_parts[0])
+        g.batch_size = n_seeds
+        return g
+
+    def _decorate(self, g, b, n_seeds, state, ts_parts):
+        if self.hetero:                                             # as the transform: every node type says how many seeds
+            for t, nt in enumerate(self.node_types):
+                g[nt].batch_size = n_seeds if t == self._it else 0
