@@ -813,6 +813,45 @@ TG_API int tg_ns_homo_compact(const tg_ns_out *out, int64_t n_batches, const int
                               int64_t *flat_samples, int64_t *flat_rows, int64_t *flat_cols, int64_t *flat_edge_index,
                               void *stream);
 
+/* ---- per-batch node dedup and relabel of the tg_ns_homo_batched slabs ------------------------------------------------
+ * The sampler returns a forest: a vertex reached along two paths has two slots in `samples`.  This operator makes, for
+ * every batch b independently (n = counts[b][0] nodes, m = counts[b][1] edges), what a PyG-style consumer expects:
+ *   nodes[b]        the distinct values of samples[b][:n], ordered by the position of their FIRST occurrence (distinct
+ *                   seeds therefore stay first, in order)
+ *   inverse[b][p]   index in nodes[b] of samples[b][p], p < n: nodes[inverse] == samples          (may be NULL)
+ *   rows[b][e], cols[b][e] = inverse[in.rows[b][e]], inverse[in.cols[b][e]], e < m; edges are not merged
+ *   counts[b]       {n_unique, m}: the layout of tg_ns_out.counts
+ *   layer_nodes[b][h], h < n_hops: unique nodes among the first in.layer_offsets[b][h][0] positions, the node count known
+ *                   when hop h starts (h = 0: the unique seeds)                                    (may be NULL)
+ * Pitches are in.cap_nodes (nodes, inverse), in.cap_edges (rows, cols), 2 (counts), n_hops (layer_nodes).  Words past
+ * n_unique / n / m are not written; in.edge_index is not touched.  out.rows / out.cols may be in.rows / in.cols.  A
+ * tg_ns_out with samples = nodes, rows, cols, counts of this struct goes straight into tg_ns_homo_compact.
+ * Every id is in [0, id_bound): id_bound <= 2^31 takes 32-bit hash keys, else 64-bit ones.  `form`: 0 auto, 1 one
+ * workgroup runs one batch with its table in LDS (where a table of 2^k >= 4/3 cap_nodes slots fits: cap_nodes <= 12 288
+ * with 32-bit keys in 160 KiB), 2 a grid over all batches' positions with the per-batch tables in `workspace` (cleared
+ * inside the call).  Outputs depend on neither the form nor the workspace size: a workspace of at least bytes_min and
+ * less than bytes runs the batches in rounds of as many tables as fit.  Bad arguments are refused with TG_ERR_INVALID
+ * before anything is launched; the call does not synchronise and reads nothing back. */
+typedef struct {
+    int64_t *nodes;
+    int64_t *inverse;     /* or NULL */
+    int64_t *rows;
+    int64_t *cols;
+    int64_t *counts;
+    int64_t *layer_nodes; /* or NULL */
+} tg_ns_unique_out;
+/* Which form an auto call takes: *form = 1 (LDS) or 2 (flat); *lds_bytes = the LDS the LDS form asks for.
+ * lds_limit_bytes > 0 is taken as the workgroup's LDS limit and no device is touched; <= 0 asks the current device. */
+TG_API int tg_ns_homo_unique_form(int64_t cap_nodes, int64_t id_bound, int64_t lds_limit_bytes, int32_t *form,
+                                  int64_t *lds_bytes);
+/* *bytes_min = the flat form's workspace of ONE batch, *bytes = what an auto call wants for all n_batches at once:
+ * n_batches * bytes_min, or 0 where auto takes the LDS form on the current device. */
+TG_API int tg_ns_homo_unique_workspace_bytes(int64_t cap_nodes, int64_t id_bound, int64_t n_batches, int64_t *bytes,
+                                             int64_t *bytes_min);
+TG_API int tg_ns_homo_unique(const tg_ns_out *in, int64_t n_batches, int64_t n_seeds, int32_t n_hops, int64_t id_bound,
+                             const tg_ns_unique_out *out, void *workspace, int64_t workspace_bytes, int32_t form,
+                             void *stream);
+
 /* Ragged rows of an int64 slab -> one flat array: dst[offsets[r] + i] = src[r * pitch + i] for
  * i < lens[r * lens_stride] (lens, offsets: device arrays).  The per-type / per-relation slabs of
  * tg_ns_hetero_batched are flattened with it (tch_geometric/loader.py). */

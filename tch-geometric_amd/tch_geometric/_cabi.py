@@ -35,7 +35,7 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_ns_homo_workspace_bytes_for", "tg_ns_homo_batched_workspace_bytes", "tg_hgt_batched_capacity",
            "tg_hgt_batched_workspace_bytes", "tg_hgt_sample_batched", "tg_budget_batched_workspace_bytes",
            "tg_budget_sample_batched", "tg_neg_batched_capacity", "tg_neg_batched_form", "tg_neg_batched_workspace_bytes",
-           "tg_neg_sample_batched"]
+           "tg_neg_sample_batched", "tg_ns_homo_unique_form", "tg_ns_homo_unique_workspace_bytes", "tg_ns_homo_unique"]
 
 
 class TgGraph(C.Structure):
@@ -786,6 +786,95 @@ def ns_homo_compact(out, n_batches, counts_host, stacked=False):
     check(lib.tg_ns_homo_compact(C.byref(so), C.c_int64(n_batches), ptr(off[0]), ptr(off[1]), ptr(fs), ptr(fr), ptr(fc),
                                  ptr(fe), stream_ptr(dev)))
     return (fs, rc, fe) if stacked else (fs, fr, fc, fe)
+
+
+class TgNsUniqueOut(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("inverse", C.c_void_p), ("rows", C.c_void_p), ("cols", C.c_void_p),
+                ("counts", C.c_void_p), ("layer_nodes", C.c_void_p)]
+
+
+def ns_homo_unique_form(cap_nodes, id_bound, lds_limit_bytes=0):
+    """-> (form, lds_bytes, bound): the form an auto tg_ns_homo_unique call takes for slabs of pitch cap_nodes (1 = one
+    workgroup per batch with the table in LDS, 2 = flat over all batches' positions), the LDS the LDS form asks for, and
+    the largest cap_nodes that still takes the LDS form under the same limit (found by bisection over the same query).
+    lds_limit_bytes > 0: taken as the workgroup's limit, no device is touched; otherwise the current device is asked."""
+    def ask(cn):
+        form, nbytes = C.c_int32(-1), C.c_int64(0)
+        check(lib.tg_ns_homo_unique_form(C.c_int64(cn), C.c_int64(id_bound), C.c_int64(lds_limit_bytes), C.byref(form),
+                                         C.byref(nbytes)))
+        return form.value, nbytes.value
+    form, nbytes = ask(cap_nodes)
+    lo, hi = -1, 1 << 30                      # the form is monotone in cap_nodes: LDS up to the bound, flat above
+    if ask(hi)[0] == 1:
+        lo = hi
+    while hi - lo > 1 and lo != hi:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if ask(mid)[0] == 1 else (lo, mid)
+    return form, nbytes, lo
+
+
+def ns_homo_unique_workspace_bytes(cap_nodes, id_bound, n_batches):
+    """-> (bytes, bytes_min): what an auto call wants for all batches at once (0 where it takes the LDS form) and the
+    flat form's workspace of one batch (the least a flat call runs with, round by round)."""
+    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_ns_homo_unique_workspace_bytes(C.c_int64(cap_nodes), C.c_int64(id_bound), C.c_int64(n_batches),
+                                                C.byref(nbytes), C.byref(bmin)))
+    return nbytes.value, bmin.value
+
+
+def ns_homo_unique_workspace(cap_nodes, id_bound, n_batches, device, form=0):
+    """The workspace of ns_homo_unique for n_batches batches at once as an int64 tensor; None where the call takes none
+    (the LDS form).  form=2 sizes it for the flat form whatever auto would take."""
+    nbytes, bmin = ns_homo_unique_workspace_bytes(cap_nodes, id_bound, n_batches)
+    if form == 2:
+        nbytes = bmin * n_batches
+    return torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device) if nbytes > 0 and form != 1 else None
+
+
+class NsUniqueOut:
+    """Output slabs of tg_ns_homo_unique for the slabs `src` (an NsBatchedOut or another object with its fields): nodes,
+    inverse [n_batches, cap_nodes], rows, cols [n_batches, cap_edges] (src's own under in_place), counts [n_batches, 2],
+    layer_nodes [n_batches, n_hops].  struct() is a tg_ns_out view (samples = nodes, the relabelled rows / cols, src's
+    edge_index and layer_offsets, the unique counts) that ns_homo_compact accepts."""
+
+    def __init__(self, src, in_place=False, with_inverse=True):
+        self.src, self.n_batches, self.n_seeds, self.n_hops = src, src.samples.shape[0], src.n_seeds, src.n_hops
+        o = dict(dtype=torch.int64, device=src.samples.device)
+        self.samples = self.nodes = torch.empty_like(src.samples)
+        self.inverse = torch.empty_like(src.samples) if with_inverse else None
+        self.rows = src.rows if in_place else torch.empty_like(src.rows)
+        self.cols = src.cols if in_place else torch.empty_like(src.cols)
+        self.edge_index, self.layer_offsets, self.states = src.edge_index, src.layer_offsets, None
+        self.counts = torch.zeros((self.n_batches, 2), **o)
+        self.layer_nodes = torch.zeros((self.n_batches, max(self.n_hops, 1)), **o)[:, :self.n_hops]
+        self.cap_nodes, self.cap_edges = src.samples.shape[1], src.rows.shape[1]
+
+    struct = NsBatchedOut.struct
+    batch = NsBatchedOut.batch
+
+    def unique_struct(self):
+        u = TgNsUniqueOut()
+        u.nodes, u.rows, u.cols, u.counts = self.nodes.data_ptr(), self.rows.data_ptr(), self.cols.data_ptr(), self.counts.data_ptr()
+        u.inverse = self.inverse.data_ptr() if self.inverse is not None else None
+        u.layer_nodes = self.layer_nodes.data_ptr() if self.n_hops else None
+        return u
+
+
+def ns_homo_unique(out, n_batches, id_bound, form=0, ws=None, in_place=False, result=None, with_inverse=True):
+    """Per-batch node dedup and relabel of the first n_batches batches of `out` (an NsBatchedOut, or a NsUniqueOut-like
+    object with samples / rows / cols / layer_offsets / counts slabs): tg_ns_homo_unique on the current stream, no host
+    synchronisation.  id_bound: every id is in [0, id_bound).  form: 0 auto, 1 LDS, 2 flat; ws: the workspace
+    (ns_homo_unique_workspace), allocated here when the call needs one and none is given; in_place: the relabelled rows /
+    cols replace out's.  result: an NsUniqueOut of an earlier call on the same slabs, reused.  -> the NsUniqueOut."""
+    res = result if result is not None else NsUniqueOut(out, in_place, with_inverse)
+    if ws is None:
+        ws = ns_homo_unique_workspace(out.samples.shape[1], id_bound, n_batches, out.samples.device, form)
+    si, su = out.struct(), res.unique_struct()
+    check(lib.tg_ns_homo_unique(C.byref(si), C.c_int64(n_batches), C.c_int64(out.n_seeds), C.c_int32(out.n_hops),
+                                C.c_int64(id_bound), C.byref(su), ptr(ws), C.c_int64(ws.numel() * 8 if ws is not None else 0),
+                                C.c_int32(form), stream_ptr(out.samples.device)))
+    res._ws = ws                              # the launch borrows it: alive as long as the result
+    return res
 
 
 def compact_rows(slab, lens, total):

@@ -58,11 +58,12 @@ class SuperBatch:
     """`prefetch` mini-batches sampled by ONE launch, as flat batch-major device tensors plus per-batch offsets -- the unit
     the loader really works in.  `n_id` [sum nodes], `edge_index` [2, sum edges] (batch-local numbering), `e_id`
     [sum edges] (COO edge ids of the source graph), one flat tensor per node / edge attribute, `node_ptr` / `edge_ptr`
-    (python lists, length G + 1), `layer_offsets` [G][hops] triples, `call_id0`.  Iterating (or indexing) yields the
+    (python lists, length G + 1), `layer_offsets` [G][hops] triples, `call_id0`; from a `unique=True` loader also
+    `layer_nodes` [G][hops] (unique nodes known when a hop starts; else None).  Iterating (or indexing) yields the
     mini-batches as `MiniBatch` views; a consumer that can take the whole super-batch (a model over a batch of
     sub-graphs with `ptr` offsets) pays no per-mini-batch host work at all."""
     __slots__ = ("n_id", "edge_index", "_e_id", "_e_ptr", "_perm", "node_attrs", "edge_attrs", "node_ptr", "edge_ptr",
-                 "layer_offsets", "batch_size", "call_id0", "n_hops", "_views", "_index")
+                 "layer_offsets", "layer_nodes", "seed_counts", "batch_size", "call_id0", "n_hops", "_views", "_index")
 
     @property
     def e_id(self):
@@ -119,7 +120,19 @@ class MiniBatch:
 
     num_nodes = property(lambda self: self._sb.node_ptr[self._j + 1] - self._sb.node_ptr[self._j])
     num_edges = property(lambda self: self._sb.edge_ptr[self._j + 1] - self._sb.edge_ptr[self._j])
-    batch_size = property(lambda self: self._sb.batch_size)
+
+    @property
+    def batch_size(self):
+        """the seeds of the mini-batch; under unique=True the distinct ones (they lead n_id)"""
+        sc = self._sb.seed_counts
+        return self._sb.batch_size if sc is None else sc[self._j]
+
+    @property
+    def layer_nodes(self):
+        """unique=True: [hops] unique nodes among the positions known when hop h starts ([0] = the unique seeds)"""
+        ln = self._sb.layer_nodes
+        return None if ln is None else list(ln[self._j][:self._sb.n_hops])
+
     call_id = property(lambda self: self._sb.call_id0 + self._j)
     layer_offsets = property(lambda self: [tuple(x) for x in self._sb.layer_offsets[self._j][:self._sb.n_hops]])
 
@@ -155,17 +168,25 @@ class NeighborLoader(_Loader):
     being sampled on a side stream into the other of two slab sets (its sizes travel to pinned host memory behind the
     kernel), so neither the launch nor its one read-back sits on the consumer's path.  Launches of >= 2 048 mini-batches
     get the window-ordered form's workspace (kept by the loader, sized for this graph's stage slots); `form` is
-    ns_homo_batched's: 0 takes that form by launch and graph size, 1 whenever the launch qualifies, 2 never."""
+    ns_homo_batched's: 0 takes that form by launch and graph size, 1 whenever the launch qualifies, 2 never.
+
+    unique=True hands out PyG-style mini-batches: tg_ns_homo_unique runs behind the sampler on the side stream, `n_id`
+    lists each node once (first occurrence first, so the distinct seeds lead), `edge_index` is numbered against it (edges
+    are not merged), node attributes are gathered per unique node; `e_id` and the edge attributes are the forest's.
+    `batch_size` is the unique-seed count, `layer_nodes[h]` the unique nodes known when hop h starts; `layer_offsets`
+    stays the forest's."""
 
     def __init__(self, data, num_neighbors: List[int], input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
                  prefetch: int = 16, replace: bool = False, shuffle: bool = False, drop_last: bool = False,
-                 seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0):
+                 seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0, unique: bool = False):
         self.data, self.fanout = data, [int(k) for k in num_neighbors]
         self.device = torch.device(device)
         self.batch_size, self.prefetch = int(batch_size), max(1, int(prefetch))
         self.sampler = _cabi.SAMPLER_UNIFORM_REPL if replace else _cabi.SAMPLER_UNIFORM
         self.shuffle, self.drop_last, self.seed, self.call_id0 = shuffle, drop_last, int(seed), int(call_id0)
         self.form = int(form)               # of many-batch launches (ns_homo_batched's `form`): 0 = by launch size
+        self.unique = bool(unique)
+        self._unique_ws = None              # the dedup's tables (flat form), sized once for a full launch
         self.n_nodes = _num_nodes(data)
         self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
         # u32 shadows halve the bytes per gathered line (DESIGN.md 4.1); ids and offsets fit below 2^31 here
@@ -204,6 +225,9 @@ class NeighborLoader(_Loader):
                     "counts": torch.empty((cap, 2), dtype=torch.int64).pin_memory(),
                     "lo": torch.empty((cap, max(H, 1), 3), dtype=torch.int64).pin_memory(),
                     "free": None}
+            if self.unique:
+                slab["uniq"] = _cabi.NsUniqueOut(slab["out"], in_place=True, with_inverse=False)
+                slab["ln"] = torch.empty((cap, max(H, 1)), dtype=torch.int64).pin_memory()
             slabs[which] = slab
         if G >= 2048 and self._ws is None:   # many batches per launch: the window-ordered form pays
             self._ws = _cabi.ns_homo_workspace(max(G, min(self.prefetch, len(self))), B, self.fanout, self.device,
@@ -220,7 +244,16 @@ class NeighborLoader(_Loader):
             out = slab["out"]
             _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
                                   sampler=self.sampler, ws=self._ws if G >= 2048 else None, form=self.form)
-            slab["counts"][:G].copy_(out.counts[:G], non_blocking=True)
+            sizes = out
+            if self.unique:                  # dedup + relabel directly behind the sampler; the host reads the unique counts
+                sizes = uniq = slab["uniq"]
+                need, least = _cabi.ns_homo_unique_workspace_bytes(out.cap_nodes, self.n_nodes, out.n_batches)
+                if need and (self._unique_ws is None or self._unique_ws.numel() * 8 < least):
+                    self._unique_ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=self.device)
+                _cabi.ns_homo_unique(out, G, self.n_nodes, ws=self._unique_ws if need else None, result=uniq)
+                if H:
+                    slab["ln"][:G].copy_(uniq.layer_nodes[:G], non_blocking=True)
+            slab["counts"][:G].copy_(sizes.counts[:G], non_blocking=True)
             slab["lo"][:G].copy_(out.layer_offsets[:G], non_blocking=True)
             done = torch.cuda.Event()
             done.record(side)
@@ -236,7 +269,8 @@ class NeighborLoader(_Loader):
         cur.wait_event(done)
         counts = slab["counts"][:G]
         n_nodes, n_edges = counts[:, 0].tolist(), counts[:, 1].tolist()
-        n_id, edge_index, e_ptr = _cabi.ns_homo_compact(out, G, counts, stacked=True)   # copies: the slabs go back to the sampler
+        src = slab["uniq"] if self.unique else out                 # unique: the deduplicated, relabelled view of the slabs
+        n_id, edge_index, e_ptr = _cabi.ns_homo_compact(src, G, counts, stacked=True)   # copies: the slabs go back to the sampler
         free = torch.cuda.Event()
         free.record(cur)
         slab["free"] = free
@@ -254,6 +288,11 @@ class NeighborLoader(_Loader):
             ptr_e.append(e)
         sb.node_ptr, sb.edge_ptr = ptr_n, ptr_e
         sb.layer_offsets = slab["lo"][:G].tolist()
+        sb.layer_nodes = sb.seed_counts = None
+        if self.unique:
+            H = len(self.fanout)
+            sb.layer_nodes = slab["ln"][:G, :H].tolist()
+            sb.seed_counts = [ln[0] for ln in sb.layer_nodes] if H else n_nodes
         sb.batch_size, sb.call_id0, sb.n_hops = B, self.call_id0 + first_batch, len(self.fanout)
         return sb
 

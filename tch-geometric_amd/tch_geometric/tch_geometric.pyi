@@ -7,7 +7,12 @@ Limits the reference does not have: per-hop fan-out at most 4096 for the unweigh
 1024 under a temporal filter or the weighted sampler (ValueError beyond; the C ABI's batched launch tg_ns_homo_batched
 takes fan-outs up to 255 and 8 hops, TG_MAX_HOPS: the operators route larger fan-outs to the flat per-hop kernels and
 deeper calls hop by hop); heterogeneous sampling at most 8 node types / 16 relations in the fused launch (more fall back
-to one launch per relation and hop)."""
+to one launch per relation and hop).
+
+neighbor_sampling_homogenous returns the reference's forest (a vertex reached along two paths holds two slots of
+`samples`, rows[e] == n_seeds + e).  The PyG-style form -- each node once, edges numbered against that list -- is made
+behind it, not inside it: transforms.unique_nodes(samples, rows, cols) -> (nodes, rows_u, cols_u, inverse) for one call
+(tg_ns_homo_unique, csrc/ns_unique.hip), loader.NeighborLoader(..., unique=True) for mini-batches."""
 from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor

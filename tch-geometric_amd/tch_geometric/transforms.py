@@ -152,6 +152,49 @@ def filter_hetero_data(data, samples: Dict[str, Tensor], rows, cols, edge_index,
     return out
 
 
+class _OneCallSlabs:
+    """One call's (samples, rows, cols) as the single-batch slabs tg_ns_homo_unique reads."""
+
+    def __init__(self, samples: Tensor, rows: Tensor, cols: Tensor):
+        n, m, dev = samples.numel(), rows.numel(), samples.device
+        pad = lambda x: (x if x.numel() else torch.zeros(1, dtype=torch.int64, device=dev)).contiguous().view(1, -1)
+        self.samples, self.rows, self.cols = pad(samples), pad(rows), pad(cols)
+        self.edge_index = self.rows
+        self.layer_offsets = torch.zeros((1, 1, 3), dtype=torch.int64, device=dev)
+        self.counts = torch.tensor([[n, m]], dtype=torch.int64).to(dev)
+        self.states, self.n_seeds, self.n_hops = None, 0, 0
+
+    struct = _cabi.NsBatchedOut.struct
+
+
+def unique_nodes(samples: Tensor, rows: Tensor, cols: Tensor, id_bound: Optional[int] = None):
+    """Node dedup and relabel of ONE sampled batch (what neighbor_sampling_homogenous returns: a forest, a vertex reached
+    along two paths holds two slots) -> (nodes, rows_u, cols_u, inverse): `nodes` lists each value of `samples` once, in
+    order of first occurrence (distinct seeds stay first, in order), nodes[inverse] == samples, rows_u = inverse[rows],
+    cols_u = inverse[cols]; edges are not merged.  Device tensors run tg_ns_homo_unique (csrc/ns_unique.hip; one read-back
+    of the unique count); CPU tensors take a torch implementation of the same rule.  id_bound: every id is in
+    [0, id_bound) (at most 2^31 takes 32-bit hash keys); None assumes nothing beyond non-negative int64 ids."""
+    for t in (samples, rows, cols):
+        if t.dtype != torch.int64:
+            raise ValueError("Tensor must be a is of invalid type. Expected Int64 but got %s" % t.dtype)
+    samples, rows, cols = samples.reshape(-1), rows.reshape(-1), cols.reshape(-1)
+    if rows.numel() != cols.numel():
+        raise ValueError("rows and cols differ in length")
+    if not samples.is_cuda:
+        n = samples.numel()
+        values, inv = torch.unique(samples, return_inverse=True)
+        first = torch.full((values.numel(),), n, dtype=torch.int64).scatter_reduce_(0, inv, torch.arange(n), "amin")
+        order = torch.argsort(first)
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(order.numel())
+        inverse = rank[inv]
+        return values[order], inverse[rows], inverse[cols], inverse
+    slabs = _OneCallSlabs(samples, rows.to(samples.device), cols.to(samples.device))
+    u = _cabi.ns_homo_unique(slabs, 1, (1 << 62) if id_bound is None else int(id_bound))
+    n_unique, m = int(u.counts[0, 0]), rows.numel()
+    return u.nodes[0, :n_unique], u.rows[0, :m], u.cols[0, :m], u.inverse[0, :samples.numel()]
+
+
 def _is_hetero(data) -> bool:
     return hasattr(data, "node_types") and hasattr(data, "edge_types")
 
