@@ -1057,7 +1057,8 @@ extern "C" int tg_ns_hop_scan(const tg_graph *csc, const tg_hop_in *in, const tg
                               int64_t workspace_bytes, int64_t group_cap, void *stream_) {
     using namespace tg;
     TG_REQUIRE(csc && csc->ptrs && in && flt && rng && out && status, "tg_ns_hop_scan: null argument");
-    TG_REQUIRE(csc->timestamps, "tg_ns_hop_scan: the graph has no edge timestamps");
+    // a graph without edges has no per-edge arrays, and none is touched (as in tg_ns_hop_segments)
+    TG_REQUIRE(csc->timestamps || csc->n_edges == 0, "tg_ns_hop_scan: the graph has no edge timestamps");
     TG_REQUIRE(in->sampler == TG_SAMPLER_UNIFORM || in->sampler == TG_SAMPLER_UNIFORM_REPL,
                "tg_ns_hop_scan: only the unweighted samplers");
     TG_REQUIRE(flt->filter_mode >= TG_FILTER_STATIC && flt->filter_mode <= TG_FILTER_DYNAMIC, "tg_ns_hop_scan: bad filter");
@@ -1076,10 +1077,11 @@ extern "C" int tg_ns_hop_weighted(const tg_graph *csc, const tg_hop_in *in, cons
                                   int64_t workspace_bytes, void *stream_) {
     using namespace tg;
     TG_REQUIRE(csc && csc->ptrs && in && rng && out && status, "tg_ns_hop_weighted: null argument");
-    TG_REQUIRE(csc->weights, "tg_ns_hop_weighted: the graph has no edge weights");
+    const bool no_edges = csc->n_edges == 0; // an empty graph: its per-edge arrays are never touched
+    TG_REQUIRE(csc->weights || no_edges, "tg_ns_hop_weighted: the graph has no edge weights");
     const int filter_mode = flt ? flt->filter_mode : TG_FILTER_NONE;
     TG_REQUIRE(filter_mode >= TG_FILTER_NONE && filter_mode <= TG_FILTER_DYNAMIC, "tg_ns_hop_weighted: bad filter");
-    TG_REQUIRE(filter_mode == TG_FILTER_NONE || (csc->timestamps && flt->states && states_out),
+    TG_REQUIRE(filter_mode == TG_FILTER_NONE || ((csc->timestamps || no_edges) && flt->states && states_out),
                "tg_ns_hop_weighted: the filter needs edge timestamps and states");
     HsCall c{};
     c.seg[0] = HsSeg{csc->ptrs, csc->indices, csc->timestamps, csc->weights, 0, in->fanout, in->rng_tag ? in->rng_tag : TG_TAG_NS_HOMO};
@@ -1095,10 +1097,11 @@ extern "C" int tg_ns_hop_weighted_groups(const tg_graph *csc, const tg_hop_in *i
                                          int64_t workspace_bytes, int64_t group_cap, void *stream_) {
     using namespace tg;
     TG_REQUIRE(csc && csc->ptrs && in && rng && out && status, "tg_ns_hop_weighted_groups: null argument");
-    TG_REQUIRE(csc->weights, "tg_ns_hop_weighted_groups: the graph has no edge weights");
+    const bool no_edges = csc->n_edges == 0; // an empty graph: its per-edge arrays are never touched
+    TG_REQUIRE(csc->weights || no_edges, "tg_ns_hop_weighted_groups: the graph has no edge weights");
     const int filter_mode = flt ? flt->filter_mode : TG_FILTER_NONE;
     TG_REQUIRE(filter_mode >= TG_FILTER_NONE && filter_mode <= TG_FILTER_DYNAMIC, "tg_ns_hop_weighted_groups: bad filter");
-    TG_REQUIRE(filter_mode == TG_FILTER_NONE || (csc->timestamps && flt->states && states_out),
+    TG_REQUIRE(filter_mode == TG_FILTER_NONE || ((csc->timestamps || no_edges) && flt->states && states_out),
                "tg_ns_hop_weighted_groups: the filter needs edge timestamps and states");
     HsCall c{};
     c.seg[0] = HsSeg{csc->ptrs, csc->indices, csc->timestamps, csc->weights, 0, in->fanout, in->rng_tag ? in->rng_tag : TG_TAG_NS_HOMO};
