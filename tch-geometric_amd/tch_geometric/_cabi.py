@@ -618,6 +618,39 @@ class BudgetBatched(_Batched):
 budget_batched_pitches, budget_batched_bytes = BudgetBatched.pitches, BudgetBatched.bytes_of
 
 
+class TgBudgetLayerIn(C.Structure):
+    _fields_ = [("graphs", C.POINTER(TgGraph)), ("rel_ids", C.POINTER(C.c_int32)), ("n_rels", C.c_int32),
+                ("node_type", C.c_int32), ("fanout", C.c_int32), ("filter_on", C.c_int32), ("forward", C.c_int32),
+                ("relative", C.c_int32), ("win_lo", C.c_int64), ("win_hi", C.c_int64), ("nodes", C.c_void_p),
+                ("nodes_ts", C.c_void_p), ("n_front", C.c_int64), ("id_base", C.c_int64)]
+
+
+class TgBudgetLayerOut(C.Structure):
+    _fields_ = [("sel_v", C.c_void_p), ("sel_ts", C.c_void_p), ("sel_rel", C.c_void_p), ("sel_i", C.c_void_p)]
+
+
+def budget_layer(rels, rel_ids, node_type, fanout, nodes, nodes_ts, seed, call_id, id_base=0, window=None, forward=False,
+                 relative=False):
+    """tg_budget_layer: Budget::update + Budget::sample for every frontier node of one node type, one (layer, type)
+    step.  rels: the relations INTO the type as (src type index, dst type index, ptrs, indices, row timestamps or None),
+    rel_ids their indices in the caller's relation list; nodes / nodes_ts: [n_front] device tensors.
+    -> (sel_v, sel_ts, sel_rel, sel_i), each [n_front, fanout]; sel_rel < 0 marks an empty slot."""
+    n = nodes.numel()
+    _, _, graphs = _rel_arrays(rels, timestamps=True)
+    lin = TgBudgetLayerIn()
+    lin.graphs, lin.rel_ids, lin.n_rels = graphs, (C.c_int32 * max(len(rels), 1))(*rel_ids), len(rels)
+    lin.node_type, lin.fanout = node_type, fanout
+    if window is not None:
+        lin.filter_on, lin.forward, lin.relative = 1, int(bool(forward)), int(bool(relative))
+        lin.win_lo, lin.win_hi = int(window[0]), int(window[1])
+    lin.nodes, lin.nodes_ts, lin.n_front, lin.id_base = nodes.data_ptr(), nodes_ts.data_ptr(), n, id_base
+    sel = [torch.empty((n, fanout), dtype=torch.int64, device=nodes.device) for _ in range(4)]
+    out = TgBudgetLayerOut(*[x.data_ptr() for x in sel])
+    rng = TgRng(seed, call_id)
+    check(lib.tg_budget_layer(C.byref(lin), C.byref(rng), C.byref(out), stream_ptr(nodes.device)))
+    return tuple(sel)
+
+
 class TgNegProblem(C.Structure):
     _fields_ = [("n_types", C.c_int32), ("n_rels", C.c_int32), ("homogeneous", C.c_int32), ("inbound", C.c_int32),
                 ("rel_src", C.POINTER(C.c_int32)), ("rel_dst", C.POINTER(C.c_int32)), ("graphs", C.POINTER(TgGraph)),

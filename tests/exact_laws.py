@@ -328,6 +328,74 @@ def default_slots(k):
     return sorted({0, 1, k // 2, k - 1, *BOUNDARY_SLOTS} & set(range(k)))
 
 
+class ReservoirTally:
+    """check_reservoir over outcomes that arrive in chunks: add() asserts a chunk's structure and adds its counts (on
+    the chunk's device), finish() runs the chi-square tests over all N outcomes.  Arguments as check_reservoir's."""
+
+    def __init__(self, N, k, law, what, replace=False, zero_pos=None, slots=None, positions=None, pairs=None, pair_bins=24):
+        n = law.n
+        self.N, self.k, self.law, self.what, self.replace, self.zero_pos, self.seen = N, k, law, what, replace, zero_pos, 0
+        self.slots = list(default_slots(k) if slots is None else slots)
+        self.positions = [] if replace else list(sorted({k, (k + n) // 2, n - 1}) if positions is None else positions)
+        self.pairs = []
+        if k >= 2:
+            nb = int(min(pair_bins, max(1, np.sqrt(N / MIN_EXPECTED) - 1), n - law.tail0))
+            self.edges = law.tail_bins(nb)
+            self.m = len(self.edges) - 1
+            self.pairs = [(a, b) for a, b in (((0, 1), (0, k - 1), (k // 2, k - 1)) if pairs is None else pairs) if a != b]
+        self.cnt = {}
+
+    def _acc(self, key, t):
+        self.cnt[key] = t if key not in self.cnt else self.cnt[key] + t
+
+    def add(self, E):
+        import torch
+        what, k, n, replace = self.what, self.k, self.law.n, self.replace
+        assert E.shape[1] == k
+        assert int(((E < 0) | (E >= n)).sum()) == 0, "%s: ranks outside [0, n)" % what
+        if not replace:
+            ar = torch.arange(k, device=E.device)
+            assert int(((E < k) & (E != ar)).sum()) == 0, "%s: a slot holds an earlier candidate other than its own" % what
+            if k > 1:
+                srt = E.sort(1).values
+                assert int((srt[:, 1:] == srt[:, :-1]).sum()) == 0, "%s: a candidate twice in one outcome" % what
+        if self.zero_pos is not None:
+            hit = self.zero_pos[E] & (E >= (0 if replace else k))
+            assert int(hit.sum()) == 0, "%s: a zero-probability candidate was sampled" % what
+        for s in dict.fromkeys(self.slots):                  # a slot, rank or pair listed twice is counted once
+            self._acc(("slot", s), torch.bincount(E[:, s], minlength=n))
+        for q in dict.fromkeys(self.positions):
+            self._acc(("pos", q), (E == q).sum(0))
+        if self.pairs:
+            et = torch.as_tensor(self.edges, device=E.device)
+            m = self.m
+            for a, b in dict.fromkeys(self.pairs):
+                ca = torch.bucketize(E[:, a].contiguous(), et, right=True)
+                cb = torch.bucketize(E[:, b].contiguous(), et, right=True)
+                self._acc(("pair", a, b), torch.bincount(ca * (m + 1) + cb, minlength=(m + 1) ** 2))
+        self.seen += E.shape[0]
+        return self
+
+    def finish(self):
+        what, k, law, N = self.what, self.k, self.law, self.N
+        assert self.seen == N, "%s: %d of %d outcomes counted" % (what, self.seen, N)
+        tests = 0
+        for s in self.slots:
+            tests += chi2_gof(self.cnt[("slot", s)].cpu().numpy(), law.marginal(s), "%s slot %d" % (what, s))[1] > 0
+        for q in self.positions:
+            held = self.cnt[("pos", q)].cpu().numpy()
+            pq = law.marginal(0)[q]
+            probs = np.concatenate([np.full(k, pq), [max(0.0, 1.0 - k * pq)]])
+            probs /= probs.sum()
+            tests += chi2_gof(np.concatenate([held, [N - held.sum()]]), probs, "%s which slot holds rank %d" % (what, q))[1] > 0
+        if self.pairs:
+            T = law.pair_table(self.edges)
+            for a, b in self.pairs:
+                joint = self.cnt[("pair", a, b)].cpu().numpy()
+                tests += chi2_gof(joint, (T / T.sum()).ravel(), "%s slots (%d, %d)" % (what, a, b))[1] > 0
+        return tests
+
+
 def check_reservoir(E, law, what, replace=False, zero_pos=None, slots=None, positions=None, pairs=None, pair_bins=24):
     """One-sample tests of N sampled outcomes E ([N, k] int64 torch tensor of candidate ranks, any device; counted where
     it lives) against `law` (ReservoirLaw, or ReplacementLaw with replace=True):
@@ -337,44 +405,264 @@ def check_reservoir(E, law, what, replace=False, zero_pos=None, slots=None, posi
       - each rank of `positions` (>= k, without replacement): which slot holds it, or none -- exclusive events;
       - each pair of `pairs`: the joint law of the two slots' (own / tail bin) categories.
     -> number of chi-square tests run (dof > 0)."""
-    import torch
     N, k = E.shape
-    n = law.n
-    assert int(((E < 0) | (E >= n)).sum()) == 0, "%s: ranks outside [0, n)" % what
-    if not replace:
-        ar = torch.arange(k, device=E.device)
-        assert int(((E < k) & (E != ar)).sum()) == 0, "%s: a slot holds an earlier candidate other than its own" % what
-        if k > 1:
-            srt = E.sort(1).values
-            assert int((srt[:, 1:] == srt[:, :-1]).sum()) == 0, "%s: a candidate twice in one outcome" % what
-    if zero_pos is not None:
-        hit = zero_pos[E] & (E >= (0 if replace else k))
-        assert int(hit.sum()) == 0, "%s: a zero-probability candidate was sampled" % what
-    tests = 0
+    return ReservoirTally(N, k, law, what, replace, zero_pos, slots, positions, pairs, pair_bins).add(E).finish()
+
+
+# ---------------------------------------------------------------- the typed samplers: hgt_sampling, budget_sampling
+# Derived from src/algo/hgt_sampling.rs and src/algo/budget_sampling.rs alone.  Canonical order (the reference's HashMap
+# order is not reproducible): relations in `edge_types` order, samples in list order, neighbours in column order.
+TYPED_MAX_NB = 50                                                       # MAX_NEIGHBORS (hgt_sampling.rs:10, budget_sampling.rs:10)
+
+
+def hgt_budget_weights(contribs, sampled=(), budget=None):
+    """`BudgetDict::update_budget` (hgt_sampling.rs:27-102) for ONE source node type, restated literally: `contribs` is
+    the list of (col_ptrs, row_indices, samples) of the relations out of that type, in canonical order; every sample w
+    contributes the first min(deg, 50) entries of its column (:72: the reservoir over 0..min(len, 50) into 50 slots takes
+    them all, in order, without a draw), each adding inv_deg = 1 / min(deg, 50) with a sequential f64 `+=` (:96) unless
+    the neighbour is in `sampled` (:80).  `budget` (an insertion-ordered dict key -> score) is continued when given.
+    -> (keys in insertion order [n] int64, score ** 2 [n] f64 -- the weights of sample_from, :110 -- and the dict)"""
+    sampled = set(int(v) for v in sampled)
+    budget = {} if budget is None else budget
+    for ptrs, indices, samples in contribs:
+        for w in samples:
+            lo, hi = int(ptrs[w]), int(ptrs[w + 1])
+            if hi == lo:
+                continue                                                # :60
+            cnt = min(hi - lo, TYPED_MAX_NB)
+            inv_deg = 1.0 / float(cnt)
+            for i in range(cnt):
+                v = int(indices[lo + i])
+                if v in sampled:
+                    continue
+                budget[v] = budget.get(v, 0.0) + inv_deg                # python floats are f64: the same rounding chain
+    keys = np.fromiter(budget.keys(), dtype=np.int64, count=len(budget))
+    score = np.fromiter(budget.values(), dtype=np.float64, count=len(budget))
+    return keys, score * score, budget
+
+
+def hgt_layer_law(w, k):
+    """One layer of `BudgetDict::sample_from` (hgt_sampling.rs:104-135) over a budget of n live entries with weights w
+    (insertion order): it IS reservoir_sampling_weighted (sampling.rs:28-55) with k slots, so the law is
+    weighted_law(w, k) -- no new maths.  Ranks are positions among the LIVE entries (a removed entry is gone from the
+    HashMap, :220).  n <= k takes every entry in order with no draw: there is no law then (-> None) and slot s holds
+    entry s."""
+    w = np.asarray(w, dtype=np.float64)
+    if w.size <= k:
+        return None
+    return weighted_law(w, k)
+
+
+def _csc(columns, n_cols):
+    """CSC of {column: list of row ids} -> (ptrs [n_cols + 1], indices)"""
+    ptrs = np.zeros(n_cols + 1, dtype=np.int64)
+    for c, rows in columns.items():
+        ptrs[c + 1] = len(rows)
+    ptrs = np.cumsum(ptrs)
+    idx = np.concatenate([np.asarray(columns[c], dtype=np.int64) for c in sorted(columns)] or [np.zeros(0, dtype=np.int64)])
+    return ptrs, idx
+
+
+def hgt_heavy_ranks(n):
+    """ranks of hgt_wide_graph's heavy entries: one early, then at 30 %, 55 % and 80 % of the budget"""
+    return sorted({r for r in (1, (3 * n) // 10, (11 * n) // 20, (4 * n) // 5) if 1 <= r < n})
+
+
+def hgt_wide_graph(n, seed):
+    """An HGT budget of exactly n entries with wide, known weights.  Types a (inputs) and b, one relation b -> a.  The
+    inputs' columns have 1..50 entries: some fresh b nodes and some shared with earlier columns (early ranks more often),
+    so scores run from 1/50 up and many entries have two or more contributions; the entries of hgt_heavy_ranks(n) are
+    also the only neighbour of a few further inputs each (score += 1 per input: several units, the square is of the order
+    of all the weight before them -- where a mis-carried running sum shows).  b's node ids are a permutation: an id is not
+    its rank.  -> dict(node_types, edge_types, ptrs, indices, inputs {"a": ids}, keys [n], w [n], rank_of [n_b])"""
+    rs = np.random.default_rng(seed)
+    n_b = n + 7
+    ids = rs.permutation(n_b)[:n]                                       # node id of rank r
+    heavy = hgt_heavy_ranks(n)
+    columns, made, pending = [], 0, []
+    while made < n:
+        length = int(rs.integers(1, TYPED_MAX_NB + 1))
+        fresh = min(n - made, length if made == 0 else int(rs.integers((length + 1) // 2, length + 1)))
+        old = min(length - fresh, made)
+        col = list(range(made, made + fresh))                          # fresh entries in rank order: label = rank
+        if old:
+            pick = np.unique((rs.random(3 * old) ** 2 * made).astype(np.int64))[:old]
+            for v in pick.tolist():                                     # shared ones anywhere between them
+                col.insert(int(rs.integers(0, len(col) + 1)), v)
+        columns.append(col)
+        for h in heavy:
+            if made <= h < made + fresh:
+                pending.append(h)
+        made += fresh
+        for h in pending:                                               # after its first appearance: columns of one entry
+            columns += [[h]] * max(2, int(np.ceil(np.sqrt(0.05 * h))))
+        pending = []
+    m = len(columns)
+    ptrs, idx = _csc({c: ids[np.asarray(col)] for c, col in enumerate(columns)}, m)
+    inputs = np.arange(m, dtype=np.int64)
+    keys, w, _ = hgt_budget_weights([(ptrs, idx, inputs)])
+    assert keys.size == n and np.unique(keys).size == n
+    rank_of = np.full(n_b, -1, dtype=np.int64)
+    rank_of[keys] = np.arange(n)
+    return dict(node_types=["a", "b"], edge_types=[("b", "r", "a")], ptrs={"b__r__a": ptrs}, indices={"b__r__a": idx},
+                inputs={"a": inputs}, keys=keys, w=w, rank_of=rank_of, n_b=n_b)
+
+
+def hgt_dead_prefix_graph(n0, n1, seed, fan=TYPED_MAX_NB):
+    """The dead-prefix case: relations b -> a and b -> b.  Layer 0 (quota >= n0) takes the whole budget of n0 entries --
+    no draw: slot s holds entry s, all n0 die -- and layer 1 samples from the n1 FRESH entries the b -> b columns of those
+    n0 samples contribute (columns also list layer-0 nodes: already sampled, skipped, :80), which sit behind n0 dead ones.
+    Its law is weighted_law over the n1 live entries.  -> dict as hgt_wide_graph, with keys0 (layer 0, in order), keys / w /
+    rank_of of layer 1's live entries, and w_dead (the n0 dead entries' old weights: named wrong law (c))."""
+    rs = np.random.default_rng(seed)
+    n_b = n0 + n1 + 5
+    ids = rs.permutation(n_b)
+    first, second = ids[:n0], ids[n0:n0 + n1]
+    m = -(-n0 // fan)
+    cols_a = {c: first[c * fan:(c + 1) * fan] for c in range(m)}
+    pa, ia = _csc(cols_a, m)
+    heavy = hgt_heavy_ranks(n1)[1:] if n0 >= 20 else []                  # each: three columns of that one entry, score += 3
+    M = n0 - 3 * len(heavy)                                             # the other columns share the n1 fresh entries evenly
+    assert n1 <= 40 * M
+    cols_b, made, normal, pending = {}, 0, 0, []
+    for v in first:
+        if pending:
+            cols_b[int(v)] = [second[pending.pop()]]
+            continue
+        fresh = n1 // M + (1 if normal < n1 % M else 0)
+        normal += 1
+        col = list(second[made:made + fresh]) + list(rs.choice(first, min(n0, int(rs.integers(0, 5))), replace=False))
+        if made:
+            col += list(rs.choice(second[:made], min(made, int(rs.integers(0, 4))), replace=False))
+        cols_b[int(v)] = [col[i] for i in rs.permutation(len(col))]
+        pending = [h for h in heavy if made <= h < made + fresh for _ in range(3)]
+        made += fresh
+    assert made == n1 and not pending
+    pb, ib = _csc(cols_b, n_b)
+    inputs = np.arange(m, dtype=np.int64)
+    keys0, w0, bud = hgt_budget_weights([(pa, ia, inputs)])
+    assert np.array_equal(keys0, first)
+    for v in keys0:                                                     # :220 the samples leave the budget
+        del bud[int(v)]
+    keys, w, _ = hgt_budget_weights([(pb, ib, keys0)], sampled=keys0, budget=bud)
+    assert keys.size == n1 and np.unique(keys).size == n1
+    rank_of = np.full(n_b, -1, dtype=np.int64)
+    rank_of[keys] = np.arange(n1)
+    return dict(node_types=["a", "b"], edge_types=[("b", "r", "a"), ("b", "s", "b")],
+                ptrs={"b__r__a": pa, "b__s__b": pb}, indices={"b__r__a": ia, "b__s__b": ib}, inputs={"a": inputs},
+                keys0=keys0, keys=keys, w=w, w_dead=w0, rank_of=rank_of, n_b=n_b)
+
+
+def hgt_edge_graph(deg, n_hubs):
+    """The HGT edge phase (hgt_sampling.rs:254-267): one type, one relation a -> a.  Inputs = a pool of `deg` nodes
+    (0..deg-1, empty columns) followed by n_hubs hubs, each hub's column the whole pool in order; num_hops = 0.  Every
+    source is a sampled node, so hub i pushes exactly min(deg, 50) edges, in slot order, and edge_index - ptrs[hub] is
+    the slot's column position: its law is uniform_law(deg, 50) (deg > 50), quirk included.
+    -> (node_types, edge_types, ptrs, indices, inputs, hub_ptrs [n_hubs])"""
+    n = deg + n_hubs
+    ptrs = np.zeros(n + 1, dtype=np.int64)
+    ptrs[deg + 1:] = deg * np.arange(1, n_hubs + 1)
+    idx = np.tile(np.arange(deg, dtype=np.int64), n_hubs)
+    return ["a"], [("a", "r", "a")], {"a__r__a": ptrs}, {"a__r__a": idx}, np.arange(n, dtype=np.int64), ptrs[deg:n].copy()
+
+
+def budget_hub_graph(lengths, window=None, seed=0):
+    """budget_sampling's `Budget::sample` (budget_sampling.rs:128-152) over one hub's candidate list.  Types a (the hub,
+    node 0) and b; len(lengths) relations b -> a, relation r's column of the hub `lengths[r]` long (0: the relation is
+    skipped, :90).  The list is the concatenation, relations in order, of every column's first 50 entries (:100) that pass
+    the filter; its law is uniform_law(n, k), quirk included, n the list's length.  The admitted entry of list rank q has
+    node id q; every other column entry (past the prefix, or filtered out) has an id >= n.  window = (lo, hi): row
+    timestamps 0..89 at random and the hub at time 100 with forward = False, so an entry is admitted iff lo <= 100 - t <
+    hi (:20-29).  -> dict(node_types, edge_types, ptrs, indices, row_ts or None, n, hub_ts)"""
+    rs = np.random.default_rng(seed)
+    R = len(lengths)
+    rels = [("b", "r%02d" % r, "a") for r in range(R)]
+    ts = [rs.integers(0, 90, L_) for L_ in lengths] if window is not None else None
+    adm = []
+    for r, L_ in enumerate(lengths):
+        a = np.zeros(L_, dtype=bool)
+        a[:TYPED_MAX_NB] = True
+        if window is not None:
+            a &= (100 - ts[r] >= window[0]) & (100 - ts[r] < window[1])
+        adm.append(a)
+    n = int(sum(a.sum() for a in adm))
+    ptrs, indices, row_ts, q, spare = {}, {}, {}, 0, n
+    for r, L_ in enumerate(lengths):
+        key = "b__r%02d__a" % r
+        ids = np.empty(L_, dtype=np.int64)
+        na = int(adm[r].sum())
+        ids[adm[r]] = np.arange(q, q + na)
+        ids[~adm[r]] = np.arange(spare, spare + L_ - na)
+        q, spare = q + na, spare + L_ - na
+        ptrs[key], indices[key] = np.array([0, L_], dtype=np.int64), ids
+        if ts is not None:
+            row_ts[key] = ts[r].astype(np.int64)
+    return dict(node_types=["a", "b"], edge_types=rels, ptrs=ptrs, indices=indices, row_ts=row_ts if ts is not None else None,
+                n=n, hub_ts=100)
+
+
+BUDGET_LISTS = {                                                        # list length n -> column lengths of the relations
+    2: [1, 1], 6: [3, 0, 3], 51: [57, 1], 64: [50, 14], 65: [70, 0, 15], 100: [50, 64], 150: [50, 51, 100],
+    800: [50 + (7 * r) % 30 for r in range(16)],
+}
+BUDGET_K = (1, 5, 50, 63, 64)
+BUDGET_FILTERED = dict(lengths=[60, 55, 70], window=(20, 70), k=5)     # three relations, about half of 150 admitted
+EDGE_DEGS = (51, 64, 65, 1000, 70000)
+
+
+def reservoir_power(wrong, right, N, slots=None, positions=()):
+    """The chance that check_reservoir rejects N outcomes drawn from the law `wrong` when it tests against `right`: at
+    least that of its most powerful single test -- a slot's marginal (slots: default_slots) or which slot holds one rank
+    of `positions`."""
+    k = right.k
+    best = 0.0
     for s in (default_slots(k) if slots is None else slots):
-        cnt = torch.bincount(E[:, s], minlength=n).cpu().numpy()
-        tests += chi2_gof(cnt, law.marginal(s), "%s slot %d" % (what, s))[1] > 0
-    if not replace:
-        for q in (sorted({k, (k + n) // 2, n - 1}) if positions is None else positions):
-            held = (E == q).sum(0).cpu().numpy()
-            pq = law.marginal(0)[q]
-            probs = np.concatenate([np.full(k, pq), [max(0.0, 1.0 - k * pq)]])
-            probs /= probs.sum()
-            tests += chi2_gof(np.concatenate([held, [N - held.sum()]]), probs, "%s which slot holds rank %d" % (what, q))[1] > 0
-    if k >= 2:
-        nb = int(min(pair_bins, max(1, np.sqrt(N / MIN_EXPECTED) - 1), n - law.tail0))
-        edges = law.tail_bins(nb)
-        m = len(edges) - 1
-        T = law.pair_table(edges)
-        et = torch.as_tensor(edges, device=E.device)
-        for a, b in (((0, 1), (0, k - 1), (k // 2, k - 1)) if pairs is None else pairs):
-            if a == b:
-                continue
-            ca = torch.bucketize(E[:, a].contiguous(), et, right=True)
-            cb = torch.bucketize(E[:, b].contiguous(), et, right=True)
-            joint = torch.bincount(ca * (m + 1) + cb, minlength=(m + 1) ** 2).cpu().numpy()
-            tests += chi2_gof(joint, (T / T.sum()).ravel(), "%s slots (%d, %d)" % (what, a, b))[1] > 0
-    return tests
+        best = max(best, power(wrong.marginal(s), right.marginal(s), N))
+        if best >= 1.0 - 1e-12:
+            return best
+    for q in positions:
+        pr, pw = right.marginal(0)[q], wrong.marginal(0)[q]
+        a = np.concatenate([np.full(k, pr), [max(0.0, 1.0 - k * pr)]])
+        b = np.concatenate([np.full(k, pw), [max(0.0, 1.0 - k * pw)]])
+        best = max(best, power(b / b.sum(), a / a.sum(), N))
+    return best
+
+
+# sample sizes of tests/test_gpu_exact_laws_typed.py; tests/test_exact_laws_cpu.py asserts their power
+HGT_CASES = [(1, 2), (2, 65), (3, 64), (63, 257), (64, 257), (65, 257), (191, 4097), (1000, 4097)]
+HGT_LARGE = [(16, 65537), (8193, 12288)]                                # second tile of chunk totals; global slot table
+HGT_DEAD = (100, 300, 7)                                                # n0, n1, k1
+HGT_SURFACE_CALLS = 4096                                                # single calls of the (2, 65) case
+BUDGET_FILTERED_OUTCOMES = 1 << 17
+# (n, k, N): BUDGET_LISTS x BUDGET_K with k < n, N the smallest power of two at which reservoir_power against the law
+# without the quirk reaches 0.999 (the quirk moves a slot's own-position marginal from (k-1)/(n-1) to k/n: the larger k and
+# n, the more outcomes it takes); the GPU tests run them in launches of bounded size
+BUDGET_CASES = [(2, 1, 1 << 12), (6, 1, 1 << 12), (6, 5, 1 << 14),
+                (51, 1, 1 << 12), (51, 5, 1 << 15), (51, 50, 1 << 23),
+                (64, 1, 1 << 12), (64, 5, 1 << 16), (64, 50, 1 << 21), (64, 63, 1 << 24),
+                (65, 1, 1 << 12), (65, 5, 1 << 16), (65, 50, 1 << 21), (65, 63, 1 << 24), (65, 64, 1 << 25),
+                (100, 1, 1 << 12), (100, 5, 1 << 17), (100, 50, 1 << 21), (100, 63, 1 << 21), (100, 64, 1 << 21),
+                (150, 1, 1 << 12), (150, 5, 1 << 17), (150, 50, 1 << 21), (150, 63, 1 << 22), (150, 64, 1 << 22),
+                (800, 1, 1 << 13), (800, 5, 1 << 21), (800, 50, 1 << 24), (800, 63, 1 << 25), (800, 64, 1 << 25)]
+# hubs of the edge phase: deg 51..1000 reach 0.999 against the law without the quirk; at deg 70 000 that law is out of
+# reach (1/69 999 against 1/70 000), see test_power_budget_and_edge_phase_without_the_quirk
+EDGE_OUTCOMES = {51: 1 << 23, 64: 1 << 21, 65: 1 << 21, 1000: 1 << 25, 70000: 1 << 15}
+
+
+def hgt_outcomes(k, n):
+    """calls of an HGT sample_from case: 2^16 for the small budgets, 2^14 from n = 4097 on, 2^12 for the two large ones
+    (each at least what reservoir_power needs against the named wrong laws)"""
+    return 1 << (16 if n <= 300 else 14 if n <= 4097 else 12)
+
+
+def hgt_slots(k):
+    """default slots (slot k - 1 among them); the global-slot-table case looks at five marginals only"""
+    return [0, 1, 4096, 8191, 8192] if k == 8193 else default_slots(k)
+
+
+def hgt_positions(k, n):
+    """the heavy entries behind the first k, and the last entry"""
+    return sorted({h for h in hgt_heavy_ranks(n) if h >= k} | {n - 1})
 
 
 # ---------------------------------------------------------------- sample sizes of tests/test_gpu_exact_laws.py

@@ -1,6 +1,8 @@
 """The closed-form laws of exact_laws.py against exhaustive enumeration of the reference's loops (rational arithmetic), the
 oracle's philox-mode (the counter-addressed restatements the kernels share) against those laws on long columns, and the
-power of the test against named wrong laws at the sample sizes tests/test_gpu_exact_laws.py uses."""
+power of the test against named wrong laws at the sample sizes tests/test_gpu_exact_laws.py and
+tests/test_gpu_exact_laws_typed.py use.  The typed samplers (hgt_sampling, budget_sampling) have their enumeration, oracle and
+power tests here as well."""
 from collections import Counter
 from fractions import Fraction
 from itertools import product
@@ -296,6 +298,136 @@ def test_oracle_negative_item_follows_the_exact_law():
     L.chi2_gof(got, L.negative_item_law(size, adm, tries), "oracle negatives")
 
 
+# ---------------------------------------------------------------- the typed samplers: hgt_sampling, budget_sampling
+def test_hgt_budget_weights_and_layer_law_equal_enumeration():
+    """a0's column b3 b1 b4, a1's b1 b5, a2's b2 b4 b6 b0: seven entries in first-contribution order, b1 and b4 with
+    two contributions (scores by hand, hgt_sampling.rs:73,96); sample_from's loop enumerated over its accept and slot
+    choices (weights score^2 as exact rationals of the f64 values)"""
+    ptrs, idx = np.array([0, 3, 5, 9]), np.array([3, 1, 4, 1, 5, 2, 4, 6, 0])
+    keys, w, _ = L.hgt_budget_weights([(ptrs, idx, [0, 1, 2])])
+    assert keys.tolist() == [3, 1, 4, 5, 2, 6, 0]
+    hand = [Fraction(1, 3), Fraction(1, 3) + Fraction(1, 2), Fraction(1, 3) + Fraction(1, 4), Fraction(1, 2),
+            Fraction(1, 4), Fraction(1, 4), Fraction(1, 4)]
+    assert np.allclose(w, [float(x * x) for x in hand], rtol=1e-15, atol=0)
+    keys_s, w_s, _ = L.hgt_budget_weights([(ptrs, idx, [0, 1, 2])], sampled=[1, 6])     # :80 sampled ones are skipped
+    assert keys_s.tolist() == [3, 4, 5, 2, 0] and np.allclose(w_s, w[[0, 2, 3, 4, 6]], rtol=0, atol=0)
+    for k in (1, 2, 3):
+        ref = law_weighted_loop(w, k)
+        law = L.hgt_layer_law(w, k)
+        M = _slot_marginals(ref, 7, k)
+        for s in range(k):
+            assert np.allclose(law.marginal(s), M[s], atol=1e-13, rtol=0)
+        if k >= 2:
+            edges = np.arange(k, 8)
+            assert np.allclose(law.pair_table(edges), _binned_pair(_pair(ref, 7, 0, k - 1), law, edges), atol=1e-13, rtol=0)
+    assert L.hgt_layer_law(w, 7) is None and L.hgt_layer_law(w, 9) is None            # n <= k: every entry, in order
+
+
+def test_hgt_dead_prefix_law_equals_enumeration():
+    """the dead-prefix builder at toy size: layer 0 takes its 3 entries, layer 1's 6 live entries get their weights from
+    the b -> b columns of those 3 alone (recomputed here from the columns), and the law over them is the loop's"""
+    g = L.hgt_dead_prefix_graph(3, 6, 1, fan=2)
+    pb, ib = g["ptrs"]["b__s__b"], g["indices"]["b__s__b"]
+    assert len(g["keys0"]) == 3 and len(g["keys"]) == 6 and not set(g["keys0"]) & set(g["keys"])
+    score, order = {}, []
+    for v in g["keys0"]:
+        col = ib[pb[v]:pb[v + 1]]
+        for u in col[:50]:
+            if u in g["keys0"]:
+                continue
+            if u not in score:
+                order.append(u)
+            score[u] = score.get(u, Fraction(0)) + Fraction(1, min(len(col), 50))
+    assert order == g["keys"].tolist()
+    assert np.allclose(g["w"], [float(score[u] ** 2) for u in order], rtol=1e-14, atol=0)
+    assert len(set(g["w"])) > 1
+    for k in (1, 2):
+        ref = law_weighted_loop(g["w"], k)
+        law = L.hgt_layer_law(g["w"], k)
+        M = _slot_marginals(ref, 6, k)
+        for s in range(k):
+            assert np.allclose(law.marginal(s), M[s], atol=1e-13, rtol=0)
+
+
+def test_typed_builders_have_the_promised_shape():
+    g = L.hgt_wide_graph(257, 357)
+    P = g["ptrs"]["b__r__a"]
+    lens = np.diff(P)
+    assert lens.min() == 1 and lens.max() == 50 and g["w"].min() < 1e-3 and g["w"].max() > 4.0
+    idx = g["indices"]["b__r__a"]
+    assert np.bincount(idx).max() >= 3                                  # entries with several contributions
+    assert all(len(set(idx[P[c]:P[c + 1]])) == lens[c] for c in range(lens.size))       # distinct inside a column
+    assert np.array_equal(g["rank_of"][g["keys"]], np.arange(257)) and not np.array_equal(g["keys"], np.arange(257))
+    for n, lengths in L.BUDGET_LISTS.items():
+        assert L.budget_hub_graph(lengths)["n"] == n == sum(min(x, 50) for x in lengths)
+    f = L.budget_hub_graph(L.BUDGET_FILTERED["lengths"], L.BUDGET_FILTERED["window"], 3)
+    assert L.BUDGET_FILTERED["k"] < 40 < f["n"] < 110                   # a known, proper subset is admitted
+
+
+def _hgt_oracle_ranks(g, quotas, N, seed):
+    """N oracle calls (philox-mode, call id = outcome) -> [N, last quota] ranks of the last layer's samples"""
+    hops, k = len(quotas), quotas[-1]
+    ns = {"a": list(quotas), "b": list(quotas)}
+    E = np.empty((N, k), dtype=np.int64)
+    first = None
+    for c in range(N):
+        s = orc.hgt(g["node_types"], g["edge_types"], g["ptrs"], g["indices"], None, g["inputs"], None, ns, hops,
+                    orc.rng_philox(seed, c))[0]["b"]
+        if first is None:
+            first = s[:len(s) - k].copy()
+        assert len(s) == len(first) + k and np.array_equal(s[:len(first)], first)
+        E[c] = g["rank_of"][s[len(first):]]
+    return E, first
+
+
+@pytest.mark.parametrize("k,n", [(2, 65), (5, 257)])
+def test_oracle_hgt_sample_from_follows_the_exact_law(k, n):
+    g = L.hgt_wide_graph(n, 100 + n)
+    E, _ = _hgt_oracle_ranks(g, [k], N_CPU, 0xE9)
+    L.check_reservoir(torch.from_numpy(E), L.hgt_layer_law(g["w"], k), "oracle hgt k=%d n=%d" % (k, n), zero_pos=None,
+                      positions=[h for h in L.hgt_heavy_ranks(n) if h >= k] + [n - 1])
+
+
+def test_oracle_hgt_dead_prefix_follows_the_exact_law():
+    g = L.hgt_dead_prefix_graph(100, 300, 5)
+    E, first = _hgt_oracle_ranks(g, [128, 7], N_CPU // 4, 0xEA)
+    assert np.array_equal(first, g["keys0"])                            # layer 0: slot s holds entry s, no draw
+    L.check_reservoir(torch.from_numpy(E), L.hgt_layer_law(g["w"], 7), "oracle hgt dead prefix", zero_pos=None)
+
+
+@pytest.mark.parametrize("deg", [51, 65])
+def test_oracle_hgt_edge_phase_follows_the_exact_law(deg):
+    nt, et, P, I, inputs, hub_ptrs = L.hgt_edge_graph(deg, N_CPU)
+    o = orc.hgt(nt, et, P, I, None, {"a": inputs}, None, {"a": []}, 0, orc.rng_philox(0xEB, 2))
+    rows, cols, eidx = o[2]["a__r__a"], o[3]["a__r__a"], o[4]["a__r__a"]
+    assert np.array_equal(cols, np.repeat(deg + np.arange(N_CPU), 50))  # 50 edges per hub, every source a sampled node
+    E = eidx.reshape(N_CPU, 50) - hub_ptrs[:, None]
+    assert np.array_equal(rows.reshape(N_CPU, 50), E)                   # the pool node's local id is its column position
+    L.check_reservoir(torch.from_numpy(E), L.uniform_law(deg, 50), "oracle hgt edges deg=%d" % deg)
+
+
+def _budget_oracle_ranks(g, k, N, seed, window=None):
+    its = {"a": np.full(N, g["hub_ts"], dtype=np.int64)} if window is not None else None
+    o = orc.budget(g["node_types"], g["edge_types"], g["ptrs"], g["indices"], g["row_ts"], {"a": np.zeros(N, dtype=np.int64)},
+                   its, {"a": [k], "b": [k]}, 1, orc.rng_philox(seed, 4), window=window, forward=False, relative=False)
+    assert len(o[0]["b"]) == N * k
+    return o[0]["b"].reshape(N, k)
+
+
+@pytest.mark.parametrize("n,k", [(65, 5), (65, 64), (150, 5), (150, 50)])
+def test_oracle_budget_sample_follows_the_exact_law(n, k):
+    g = L.budget_hub_graph(L.BUDGET_LISTS[n])
+    E = _budget_oracle_ranks(g, k, N_CPU, 0xEC)
+    L.check_reservoir(torch.from_numpy(E), L.uniform_law(n, k), "oracle budget k=%d n=%d" % (k, n))
+
+
+def test_oracle_filtered_budget_follows_the_law_on_the_admitted_subsequence():
+    f = L.BUDGET_FILTERED
+    g = L.budget_hub_graph(f["lengths"], f["window"], 3)
+    E = _budget_oracle_ranks(g, f["k"], N_CPU, 0xED, window=f["window"])
+    L.check_reservoir(torch.from_numpy(E), L.uniform_law(g["n"], f["k"]), "oracle budget filtered")
+
+
 # ---------------------------------------------------------------- power against named wrong laws, negative controls
 def _reject(counts, probs):
     with pytest.raises(AssertionError):
@@ -356,3 +488,67 @@ def test_power_of_a_biased_slot_at_k_129():
     wrong[192:256] *= 1.2
     wrong[k:] *= (1 - wrong[128]) / wrong[k:].sum()
     assert L.power(wrong, right, n_outcomes(k)) >= 0.999
+
+
+# ---------------------------------------------------------------- the typed samplers' sample sizes
+def _hgt_wrongs(w, k, n):
+    """named wrong laws (a) weights score instead of score^2 and, for n <= 4097, (b) the previous candidate's running sum"""
+    wrongs = [L.weighted_law(np.sqrt(w), k)]
+    if n <= 4097:
+        wrongs.append(L.weighted_law(w, k, shift=True))
+    return wrongs
+
+
+@pytest.mark.parametrize("k,n", L.HGT_CASES + L.HGT_LARGE)
+def test_power_hgt_score_not_squared_and_previous_running_sum(k, n):
+    g = L.hgt_wide_graph(n, 100 + n)
+    right = L.hgt_layer_law(g["w"], k)
+    N = L.hgt_outcomes(k, n)
+    slots, positions = L.hgt_slots(k), L.hgt_positions(k, n)
+    for wrong in _hgt_wrongs(g["w"], k, n):
+        assert L.reservoir_power(wrong, right, N, slots, positions) >= 0.999
+
+
+def test_power_hgt_surface_loop():
+    """the (2, 65) case through single calls of the operator surface: HGT_SURFACE_CALLS outcomes reach the bound too"""
+    g = L.hgt_wide_graph(65, 165)
+    right = L.hgt_layer_law(g["w"], 2)
+    for wrong in _hgt_wrongs(g["w"], 2, 65):
+        assert L.reservoir_power(wrong, right, L.HGT_SURFACE_CALLS, L.hgt_slots(2), L.hgt_positions(2, 65)) >= 0.999
+
+
+def test_power_hgt_dead_entries_kept_alive():
+    """(c): the law over all n0 + n1 entries, the dead ones with their old weights -- it samples dead entries, which the
+    right law (ranks among the live ones) holds at probability zero"""
+    n0, n1, k = L.HGT_DEAD
+    g = L.hgt_dead_prefix_graph(n0, n1, 5)
+    right, wrong = L.hgt_layer_law(g["w"], k), L.weighted_law(np.concatenate([g["w_dead"], g["w"]]), k)
+    N = L.hgt_outcomes(k, n1)
+    for s in (0, k - 1):
+        live = np.concatenate([np.zeros(n0), right.marginal(s)])
+        assert L.power(wrong.marginal(s), live, N) >= 0.999
+    for w2 in _hgt_wrongs(g["w"], k, n1):                               # (a) and (b) hold for this case as well
+        assert L.reservoir_power(w2, right, N, L.hgt_slots(k), L.hgt_positions(k, n1)) >= 0.999
+
+
+def test_power_budget_and_edge_phase_without_the_quirk():
+    """(d) uniform_law(n, k, quirk=False).  The quirk moves a slot's own-position marginal from (k-1)/(n-1) to k/n and
+    every later position from 1/(n-1) to 1/n: the noncentrality per outcome is about (n-k)^2 / (n^2 (n-1) (k-1)) + 1/n^2
+    and fades with growing k and n, so the outcome counts grow to 2^25 (budget n = 800 at k = 63, 64; the edge phase, whose k
+    is 50, at deg 1000).  Every budget case of BUDGET_LISTS x BUDGET_K and the edge phase up to deg 1000 reach the bound.
+    At deg 70 000 no count does (1/69 999 against 1/70 000: more than 10^9 outcomes); that case runs EDGE_OUTCOMES[70000]
+    outcomes against the law all the same, and what it can see is an error in the width of a position -- the wrong law below
+    cuts positions to 16 bits."""
+    assert {(n, k) for n, k, _ in L.BUDGET_CASES} == {(n, k) for n in L.BUDGET_LISTS for k in L.BUDGET_K if k < n}
+    for n, k, N in L.BUDGET_CASES:
+        assert L.reservoir_power(L.uniform_law(n, k, quirk=False), L.uniform_law(n, k), N) >= 0.999, (n, k, N)
+    f = L.BUDGET_FILTERED
+    n = L.budget_hub_graph(f["lengths"], f["window"], 3)["n"]
+    assert L.reservoir_power(L.uniform_law(n, f["k"], quirk=False), L.uniform_law(n, f["k"]), L.BUDGET_FILTERED_OUTCOMES) >= 0.999
+    for deg in (51, 64, 65, 1000):
+        assert L.reservoir_power(L.uniform_law(deg, 50, quirk=False), L.uniform_law(deg, 50), L.EDGE_OUTCOMES[deg]) >= 0.999, deg
+    right = L.uniform_law(70000, 50).marginal(49)
+    wrong = right.copy()
+    wrong[1 << 16:] = 0.0                                               # a position cut to 16 bits: nothing past 65 535
+    wrong[50:] *= (1 - wrong[49]) / wrong[50:].sum()
+    assert L.power(wrong, right, L.EDGE_OUTCOMES[70000]) >= 0.999
