@@ -852,6 +852,69 @@ TG_API int tg_ns_homo_unique(const tg_ns_out *in, int64_t n_batches, int64_t n_s
                              const tg_ns_unique_out *out, void *workspace, int64_t workspace_bytes, int32_t form,
                              void *stream);
 
+/* ---- per-batch, per-type node dedup and relabel of the typed slabs (tg_ns_hetero_batched's layout) ---------------------
+ * tg_ns_homo_unique with a type dimension.  Input: per node type t a `samples` slab [n_batches * pitch_nodes[t]], per
+ * relation r `rows` / `cols` slabs [n_batches * pitch_edges[r]] -- rows index positions of samples[rel_src[r]], cols
+ * positions of samples[rel_dst[r]] -- and counts[b * counts_stride ..] = {len(samples[t]) for t..., len(edges r) for
+ * r...}, counts_stride >= n_types + n_rels (tg_ns_hetero_batched: exactly that; layouts whose rows carry tail words pass
+ * their own stride).  For every batch b and type t independently (n = counts[b][t], clamped to the pitch):
+ *   nodes[t][b]        the distinct values of samples[t][b][:n] in order of FIRST occurrence (distinct seeds stay first)
+ *   inverse[t][b][p]   index of samples[t][b][p] in nodes[t][b]       (the array, or single entries of it, may be NULL)
+ * and for every relation r (m = counts[b][n_types + r], clamped):
+ *   rows[r][b][e] = inverse[rel_src[r]][in.rows[r][b][e]], cols[r][b][e] = inverse[rel_dst[r]][in.cols[r][b][e]], e < m;
+ *                      an end that is no position of its list gives -1; edges are not merged
+ *   counts[b * counts_stride ..] = {n_unique[t]..., m[r]...}; the words of a row past n_types + n_rels are not written
+ *   seed_counts[b * n_types + t]  distinct values among the first min(n_inputs[t], n) positions: the unique seeds
+ *                                                                                                      (may be NULL)
+ * Words past n_unique / n / m of an output row are not written; the sampler's edge_index slabs are no argument.  out.rows /
+ * out.cols may be in.rows / in.cols (in place); out.counts is not in.counts.  Array-of-pointer fields, pitches, rel_src /
+ * rel_dst, n_inputs and id_bound are HOST arrays; what the pointers inside point to is device memory.
+ * Every id of type t is in [0, id_bound[t]): id_bound[t] <= 2^31 takes 32-bit hash keys for that type, else 64-bit ones.
+ * `form`: 0 auto, 1 LDS, 2 flat.  LDS: one workgroup runs one batch, type after type through one table area sized for the
+ * type that needs most (2^k >= 4/3 pitch slots of key + u32), with a u16 word per position of EVERY type kept in LDS, so
+ * the relabel of every relation reads only LDS and the edge slabs; it needs max_t(slots[t] * (key bytes[t] + 4)) +
+ * 2 * sum_t(pitch_nodes[t] rounded up to 8) + 256 bytes and every pitch <= 32 768.  Flat: a grid over (tile of positions,
+ * batch, type) with one table, one slot word per position and one count per tile for every type of a batch in `workspace`
+ * (cleared inside the call).  Outputs depend on neither the form nor the workspace size: a workspace of at least
+ * bytes_min and less than bytes runs the batches in rounds of as many as fit.  Limits: n_types in [1,
+ * TG_HET_MAX_TYPES], n_rels in [0, TG_HET_MAX_RELS], pitches in [0, 2^30], rel_src / rel_dst in [0, n_types).  Bad
+ * arguments are refused with TG_ERR_INVALID before anything is launched; the call does not synchronise and reads nothing
+ * back. */
+typedef struct {
+    int32_t n_types, n_rels;
+    const int32_t *rel_src;            /* [n_rels] type whose list `rows` index */
+    const int32_t *rel_dst;            /* [n_rels] type whose list `cols` index */
+    const int64_t *const *samples;     /* [n_types] device slabs [n_batches * pitch_nodes[t]] */
+    const int64_t *pitch_nodes;        /* [n_types] */
+    const int64_t *const *rows;        /* [n_rels] device slabs [n_batches * pitch_edges[r]] */
+    const int64_t *const *cols;
+    const int64_t *pitch_edges;        /* [n_rels] */
+    const int64_t *counts;             /* device [n_batches * counts_stride] */
+    int64_t counts_stride;
+    const int64_t *n_inputs;           /* [n_types] seeds per batch (as tg_het_problem; <= 0: none); NULL without seed_counts */
+    const int64_t *id_bound;           /* [n_types] */
+} tg_ns_typed_in;
+
+typedef struct {
+    int64_t *const *nodes;             /* [n_types] device slabs, pitch_nodes */
+    int64_t *const *inverse;           /* [n_types] or NULL */
+    int64_t *const *rows;              /* [n_rels] device slabs, pitch_edges */
+    int64_t *const *cols;
+    int64_t *counts;                   /* device [n_batches * counts_stride] */
+    int64_t *seed_counts;              /* device [n_batches * n_types], or NULL */
+} tg_ns_typed_unique_out;
+/* Which form an auto call takes: *form = 1 (LDS) or 2 (flat); *lds_bytes = the LDS the LDS form asks for.
+ * lds_limit_bytes > 0 is taken as the workgroup's LDS limit and no device is touched; <= 0 asks the current device. */
+TG_API int tg_ns_typed_unique_form(int32_t n_types, const int64_t *pitch_nodes, const int64_t *id_bound,
+                                   int64_t lds_limit_bytes, int32_t *form, int64_t *lds_bytes);
+/* *bytes_min = the flat form's workspace of ONE batch (every type's table, slot words and tile counts), *bytes = what an
+ * auto call wants for all n_batches at once: n_batches * bytes_min, or 0 where auto takes the LDS form on the current
+ * device. */
+TG_API int tg_ns_typed_unique_workspace_bytes(int32_t n_types, const int64_t *pitch_nodes, const int64_t *id_bound,
+                                              int64_t n_batches, int64_t *bytes, int64_t *bytes_min);
+TG_API int tg_ns_typed_unique(const tg_ns_typed_in *in, int64_t n_batches, const tg_ns_typed_unique_out *out,
+                              void *workspace, int64_t workspace_bytes, int32_t form, void *stream);
+
 /* Ragged rows of an int64 slab -> one flat array: dst[offsets[r] + i] = src[r * pitch + i] for
  * i < lens[r * lens_stride] (lens, offsets: device arrays).  The per-type / per-relation slabs of
  * tg_ns_hetero_batched are flattened with it (tch_geometric/loader.py). */

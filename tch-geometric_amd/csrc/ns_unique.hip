@@ -18,64 +18,10 @@
 //   Tables, the per-position slot words and the tile counts of a batch sit in the workspace.
 // Every probe loop is capped at the table size: an id outside [0, id_bound) ends it instead of spinning.
 #include <algorithm>
-#include <atomic>
 
-#include "tg_host.h"
-#include "tg_map.h"
+#include "ns_unique.h"
 
 namespace tg {
-
-constexpr int NSU_THREADS = 1024;       // LDS form: the widest workgroup
-constexpr int NSU_MAX_PER_THREAD = 32;  // positions a thread owns in the LDS form's scan: its flags are one 32-bit mask
-constexpr int64_t NSU_LDS_MAX_NODES = (int64_t)NSU_THREADS * NSU_MAX_PER_THREAD; // 32 768: slots and local ids fit u16
-constexpr int NSU_STATIC_LDS = 256;     // wave totals (upper bound)
-constexpr int NSU_TILE_THREADS = 256;   // flat form: a block owns a tile of positions, a thread NSU_PER consecutive ones
-constexpr int NSU_PER = 4;
-constexpr int NSU_TILE = NSU_TILE_THREADS * NSU_PER;
-constexpr int NSU_EDGE_PER = 8;         // edges a thread relabels
-constexpr int NSU_EDGE_TILE = NSU_TILE_THREADS * NSU_EDGE_PER;
-constexpr int64_t NSU_MAX_NODES = (int64_t)1 << 30; // positions and slots are 31-bit words
-constexpr int64_t NSU_ROUND_MAX = 32768;            // batches per round (grid.y)
-constexpr uint32_t NSU_FLAG = 0x80000000u;          // flat form: bit 31 of a position's slot word = first occurrence
-constexpr uint32_t NSU_UNSEEN = 0xFFFFFFFFu;
-
-typedef unsigned int nsu_k32;
-typedef unsigned long long nsu_k64;
-
-template <typename K> __device__ __forceinline__ K nsu_empty() { return (K)~(K)0; } // no id: ids are in [0, id_bound)
-__device__ __forceinline__ uint32_t nsu_hash(nsu_k32 key, uint32_t mask, uint32_t shift) {
-    return (key * 0x9E3779B1u) >> shift;
-}
-__device__ __forceinline__ uint32_t nsu_hash(nsu_k64 key, uint32_t mask, uint32_t shift) {
-    return (uint32_t)map_hash((int64_t)key) & mask;
-}
-// claims (or finds) the slot of `key`; at most one pass over the table
-template <typename K> __device__ __forceinline__ uint32_t nsu_insert(K *keys, uint32_t mask, uint32_t shift, K key) {
-    uint32_t s = nsu_hash(key, mask, shift);
-    for (uint32_t i = 0; i <= mask; ++i) {
-        const K prev = atomicCAS(&keys[s], nsu_empty<K>(), key);
-        if (prev == nsu_empty<K>() || prev == key) break;
-        s = (s + 1) & mask;
-    }
-    return s;
-}
-
-// exclusive prefix of `cnt` over the threads of the workgroup in thread order, *total = the sum.  Every thread calls it.
-__device__ __forceinline__ uint32_t nsu_scan(uint32_t cnt, uint32_t *s_wave, uint32_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    const uint32_t incl = wave_inclusive_scan_u32_dpp(cnt);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t carry = 0, sum = 0;
-    for (int w = 0; w < n_waves; ++w) {
-        const uint32_t v = s_wave[w];
-        sum += v;
-        if (w < wave) carry += v;
-    }
-    __syncthreads(); // s_wave is free again
-    *total = sum;
-    return carry + incl - cnt;
-}
 
 struct NsuArgs {
     const int64_t *samples, *rows, *cols, *layer_offsets, *counts; // batch 0 of the round
@@ -88,12 +34,6 @@ struct NsuArgs {
     int64_t batch_bytes, vals_off, slot_off, tile_off;
     int32_t n_node_tiles, inv_tiles;
 };
-
-__device__ __forceinline__ int64_t nsu_clamp(int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-// the local id an edge end `r` (a position) maps to; -1 where r is no position of the batch (a contract violation)
-template <typename Lookup> __device__ __forceinline__ int64_t nsu_end(int64_t r, int64_t n, Lookup lookup) {
-    return (uint64_t)r < (uint64_t)n ? (int64_t)lookup(r) : -1;
-}
 
 // ---- LDS form ------------------------------------------------------------------------------------------------------------
 template <typename K> __global__ void __launch_bounds__(NSU_THREADS) nsu_lds_kernel(const NsuArgs a) {
@@ -328,8 +268,6 @@ struct NsuPlan {
     int64_t n_node_tiles, vals_off, slot_off, tile_off, batch_bytes; // flat form: a batch's part of the workspace
 };
 
-static inline int64_t nsu_r256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
 static int nsu_plan(int64_t cap_nodes, int64_t id_bound, const char *who, NsuPlan &pl) {
     TG_REQUIRE(cap_nodes >= 0 && cap_nodes <= NSU_MAX_NODES, "%s: cap_nodes = %lld outside [0, 2^30]", who, (long long)cap_nodes);
     TG_REQUIRE(id_bound >= 1, "%s: id_bound = %lld, at least 1 expected", who, (long long)id_bound);
@@ -346,22 +284,6 @@ static int nsu_plan(int64_t cap_nodes, int64_t id_bound, const char *who, NsuPla
     return TG_OK;
 }
 
-// LDS a workgroup may ask for on the current device (0: no device)
-static int64_t nsu_device_lds_limit() {
-    static std::atomic<int64_t> cached[64]; // zero-initialised; a race only repeats the query
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    if (dev >= 0 && dev < 64 && cached[dev] > 0) return cached[dev];
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    if (dev >= 0 && dev < 64) cached[dev] = v;
-    return v;
-}
 static inline bool nsu_fits(const NsuPlan &pl, int64_t lds_limit) { return pl.lds_ok && pl.lds_bytes <= lds_limit; }
 
 template <typename K> static int nsu_launch_lds(const NsuArgs &a, const NsuPlan &pl, hipStream_t stream) {

@@ -35,7 +35,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_ns_homo_workspace_bytes_for", "tg_ns_homo_batched_workspace_bytes", "tg_hgt_batched_capacity",
            "tg_hgt_batched_workspace_bytes", "tg_hgt_sample_batched", "tg_budget_batched_workspace_bytes",
            "tg_budget_sample_batched", "tg_neg_batched_capacity", "tg_neg_batched_form", "tg_neg_batched_workspace_bytes",
-           "tg_neg_sample_batched", "tg_ns_homo_unique_form", "tg_ns_homo_unique_workspace_bytes", "tg_ns_homo_unique"]
+           "tg_neg_sample_batched", "tg_ns_homo_unique_form", "tg_ns_homo_unique_workspace_bytes", "tg_ns_homo_unique",
+           "tg_ns_typed_unique_form", "tg_ns_typed_unique_workspace_bytes", "tg_ns_typed_unique"]
 
 
 class TgGraph(C.Structure):
@@ -906,6 +907,116 @@ def ns_homo_unique(out, n_batches, id_bound, form=0, ws=None, in_place=False, re
     check(lib.tg_ns_homo_unique(C.byref(si), C.c_int64(n_batches), C.c_int64(out.n_seeds), C.c_int32(out.n_hops),
                                 C.c_int64(id_bound), C.byref(su), ptr(ws), C.c_int64(ws.numel() * 8 if ws is not None else 0),
                                 C.c_int32(form), stream_ptr(out.samples.device)))
+    res._ws = ws                              # the launch borrows it: alive as long as the result
+    return res
+
+
+class TgNsTypedIn(C.Structure):
+    _fields_ = [("n_types", C.c_int32), ("n_rels", C.c_int32), ("rel_src", C.POINTER(C.c_int32)),
+                ("rel_dst", C.POINTER(C.c_int32)), ("samples", C.POINTER(C.c_void_p)), ("pitch_nodes", C.POINTER(C.c_int64)),
+                ("rows", C.POINTER(C.c_void_p)), ("cols", C.POINTER(C.c_void_p)), ("pitch_edges", C.POINTER(C.c_int64)),
+                ("counts", C.c_void_p), ("counts_stride", C.c_int64), ("n_inputs", C.POINTER(C.c_int64)),
+                ("id_bound", C.POINTER(C.c_int64))]
+
+
+class TgNsTypedUniqueOut(C.Structure):
+    _fields_ = [("nodes", C.POINTER(C.c_void_p)), ("inverse", C.POINTER(C.c_void_p)), ("rows", C.POINTER(C.c_void_p)),
+                ("cols", C.POINTER(C.c_void_p)), ("counts", C.c_void_p), ("seed_counts", C.c_void_p)]
+
+
+def ns_typed_unique_form(pitch_nodes, id_bounds, lds_limit_bytes=0):
+    """-> (form, lds_bytes): the form an auto tg_ns_typed_unique call takes for node slabs of these pitches (1 = one
+    workgroup per batch with the table and every type's per-position words in LDS, 2 = flat over all batches' positions)
+    and the LDS the LDS form asks for.  lds_limit_bytes > 0: taken as the workgroup's limit, no device is touched;
+    otherwise the current device is asked."""
+    form, nbytes = C.c_int32(-1), C.c_int64(0)
+    check(lib.tg_ns_typed_unique_form(C.c_int32(len(pitch_nodes)), _i64(pitch_nodes), _i64(id_bounds),
+                                      C.c_int64(lds_limit_bytes), C.byref(form), C.byref(nbytes)))
+    return form.value, nbytes.value
+
+
+def ns_typed_unique_workspace_bytes(pitch_nodes, id_bounds, n_batches):
+    """-> (bytes, bytes_min): what an auto call wants for all batches at once (0 where it takes the LDS form) and the
+    flat form's workspace of one batch (the least a flat call runs with, round by round)."""
+    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_ns_typed_unique_workspace_bytes(C.c_int32(len(pitch_nodes)), _i64(pitch_nodes), _i64(id_bounds),
+                                                 C.c_int64(n_batches), C.byref(nbytes), C.byref(bmin)))
+    return nbytes.value, bmin.value
+
+
+class NsTypedUniqueOut:
+    """Output slabs of tg_ns_typed_unique for the typed slabs `src` (an NsHeteroBatched, or another object with its
+    fields: T, R, rel_src, rel_dst, n_inputs, per-type `samples`, per-relation `rows` / `cols` / `edge_index`, `counts`
+    [n_batches, >= T + R]): per type nodes and inverse, per relation rows and cols (src's own under in_place), counts (src's
+    row pitch, the unique node counts and the edge counts) and seed_counts [n_batches, T].  counts and seed_counts share one
+    tensor (`state`), so read_state() fetches both in one read-back.  It reads like the slabs it was made from -- samples
+    (= nodes), rows, cols, edge_index, counts, layer_offsets -- so a loader flattens either."""
+
+    def __init__(self, src, in_place=False, with_inverse=True):
+        self.T, self.R, self.in_place = src.T, src.R, in_place
+        self.nb, self.stride = src.counts.shape[0], src.counts.shape[1]
+        self.samples = self.nodes = [torch.empty_like(x) for x in src.samples]
+        self.inverse = [torch.empty_like(x) for x in src.samples] if with_inverse else None
+        self.rows = self.cols = None
+        self.rebind(src)
+        self.state = torch.zeros(self.nb * (self.stride + self.T), dtype=torch.int64, device=src.counts.device)
+        self.counts = self.state[:self.nb * self.stride].view(self.nb, self.stride)
+        self.seed_counts = self.state[self.nb * self.stride:].view(self.nb, self.T)
+        self._ws = None
+
+    def rebind(self, src):
+        """Takes other source slabs of the same shapes: nodes, inverse and the state tensor are kept (every word a launch
+        hands out is written by that launch), and so are rows / cols unless they are the source's own (in_place)."""
+        if [x.shape for x in src.samples] != [x.shape for x in self.nodes] or src.counts.shape != (self.nb, self.stride):
+            raise ValueError("NsTypedUniqueOut.rebind: the slabs differ in shape")
+        self.src = src
+        if self.in_place or self.rows is None:
+            self.rows = src.rows if self.in_place else [torch.empty_like(x) for x in src.rows]
+            self.cols = src.cols if self.in_place else [torch.empty_like(x) for x in src.cols]
+        self.edge_index, self.layer_offsets = src.edge_index, getattr(src, "layer_offsets", None)
+        return self
+
+    def read_state(self):
+        """ONE read-back -> (counts [n_batches, stride], seed_counts [n_batches, T]) as host tensors."""
+        h = self.state.cpu()
+        n = self.nb * self.stride
+        return h[:n].view(self.nb, self.stride), h[n:].view(self.nb, self.T)
+
+    def structs(self, id_bounds):
+        """-> (tg_ns_typed_in, tg_ns_typed_unique_out); the arrays they borrow stay alive on self."""
+        src = self.src
+        pitch_n, pitch_e = _i64([x.shape[1] for x in src.samples]), _i64([x.shape[1] for x in src.rows])
+        arrays = [_vp(src.samples), _vp(src.rows), _vp(src.cols), _vp(self.nodes), _vp(self.rows), _vp(self.cols),
+                  _vp(self.inverse) if self.inverse is not None else None, pitch_n, pitch_e, _i64(id_bounds),
+                  _i64(list(src.n_inputs)[:self.T])]
+        rel = [(C.c_int32 * max(self.R, 1))(*list(x)[:self.R]) for x in (src.rel_src, src.rel_dst)]
+        arrays += rel
+        si = TgNsTypedIn(self.T, self.R, rel[0], rel[1], arrays[0], pitch_n, arrays[1], arrays[2], pitch_e,
+                         src.counts.data_ptr(), self.stride, arrays[10], arrays[9])
+        so = TgNsTypedUniqueOut(arrays[3], arrays[6], arrays[4], arrays[5], self.counts.data_ptr(),
+                                self.seed_counts.data_ptr())
+        self._arrays = arrays
+        return si, so
+
+
+def ns_typed_unique(slabs, n_batches, id_bounds, form=0, ws=None, in_place=False, result=None, with_inverse=True):
+    """Per-batch, per-type node dedup and relabel of the first n_batches batches of the typed slabs `slabs` (an
+    NsHeteroBatched or a look-alike, see NsTypedUniqueOut): tg_ns_typed_unique on the current stream, no host
+    synchronisation.  id_bounds: per node type, every id of the type is in [0, id_bounds[t]).  form: 0 auto, 1 LDS, 2 flat;
+    ws: the workspace (an int64 tensor of ns_typed_unique_workspace_bytes), allocated here when the call needs one and none
+    is given.  result: a NsTypedUniqueOut on the same slabs (else one is made from in_place / with_inverse).
+    -> the NsTypedUniqueOut."""
+    res = result if result is not None else NsTypedUniqueOut(slabs, in_place, with_inverse)
+    dev = slabs.counts.device
+    if ws is None and form != 1:
+        pitches = [x.shape[1] for x in slabs.samples]
+        nbytes, bmin = ns_typed_unique_workspace_bytes(pitches, id_bounds, n_batches)
+        if form == 2:
+            nbytes = bmin * n_batches
+        ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev) if nbytes > 0 else None
+    si, so = res.structs(id_bounds)
+    check(lib.tg_ns_typed_unique(C.byref(si), C.c_int64(n_batches), C.byref(so), ptr(ws),
+                                 C.c_int64(ws.numel() * 8 if ws is not None else 0), C.c_int32(form), stream_ptr(dev)))
     res._ws = ws                              # the launch borrows it: alive as long as the result
     return res
 

@@ -419,6 +419,12 @@ class _TypedLoader(_Loader):
         [n_calls, seeds] tensor or None (input_ts None: no timestamps)."""
         raise NotImplementedError
 
+    def _post_run(self, slabs):
+        """Called directly behind slabs.run(...), before the read-back: may launch more work on the slabs and return
+        another object with their fields (samples, rows, cols, edge_index, counts) that is read back and flattened in
+        their place."""
+        return slabs
+
     def _read_back(self, slabs):
         """The launch's only read-back -> (host counts [n_calls, >= T + R], what _decorate and _check_panic want)."""
         return slabs.counts.cpu(), None
@@ -467,6 +473,7 @@ class _TypedLoader(_Loader):
         T = len(self.node_types)
         slabs = self._launch_for(seeds, seeds_ts)
         slabs.run(self.seed, self.call_id0 + first_batch)
+        slabs = self._post_run(slabs)
         counts, state = self._read_back(slabs)
         self._check_panic(counts, state, first_batch, None)
         flat_nodes, ts_parts, node_parts, edge_parts = [], [], [], []
@@ -529,26 +536,64 @@ class HeteroNeighborLoader(_TypedLoader):
     """The heterogeneous counterpart of NeighborLoader: seeds of ONE node type, `prefetch` mini-batches per
     tg_ns_hetero_batched launch (all hops and relations fused, default samplers), per-type / per-relation slabs flattened
     by tg_compact_rows, node attributes gathered per type, edge attributes per relation through the ingest permutation.
-    Mini-batch j of the epoch equals neighbor_sampling_heterogenous for (seed, call_id0 + j)."""
+    Mini-batch j of the epoch equals neighbor_sampling_heterogenous for (seed, call_id0 + j).
+
+    unique=True hands out PyG-style mini-batches: tg_ns_typed_unique runs directly behind the sampler, in place on the edge
+    slabs and before the read-back, so per node type `n_id` lists each node once (first occurrence first: distinct seeds
+    lead, in order), node attributes are gathered per unique node and every relation's `edge_index` is numbered against
+    the unique lists of its two types (edges are not merged).  `e_id`, the edge attributes and `layer_offsets` stay the
+    forest's; `g[input_type].batch_size` is the unique-seed count.  A launch is read back in two copies, as the forest's
+    is: `layer_offsets`, and the unique counts with the unique-seed counts in one tensor.  The flat form's workspace, where
+    the shape needs one, and the dedup's own outputs are kept by the loader and sized once for a full launch.
+    BudgetLoader, HGTLoader and NegativeLoader have no such switch yet: BudgetLoader._e_id reads `cols` as forest
+    positions, so wiring them up is a later step."""
 
     def __init__(self, data, num_neighbors: List[int], input_type: str, input_nodes: Optional[Tensor] = None,
                  batch_size: int = 1024, prefetch: int = 16, replace: bool = False, drop_last: bool = False, seed: int = 0,
-                 call_id0: int = 0, device="cuda"):
+                 call_id0: int = 0, device="cuda", unique: bool = False):
         super().__init__(data, input_type, input_nodes, batch_size, drop_last, seed, call_id0, device)
         self.fanout, self.prefetch = [int(k) for k in num_neighbors], max(1, int(prefetch))
         self.sampler = _cabi.SAMPLER_UNIFORM_REPL if replace else _cabi.SAMPLER_UNIFORM
         self._rels = self._csc_rels(lambda et: self.fanout)
+        self.unique = bool(unique)
+        self._id_bounds = [max(_num_nodes(data[t]), 1) for t in self.node_types]
+        self._unique_ws = None              # the dedup's tables (flat form), sized once for a full launch
+        self._unique_out = None             # its node slabs and counts for a full launch (the edge slabs are the sampler's)
+        self._unique_need = 0               # ... and the workspace bytes that launch asks for (0: the LDS form)
 
     def _new_launch(self, inputs, input_ts, n_calls):
         return _cabi.NsHeteroBatched(len(self.node_types), self._rels, inputs, len(self.fanout), n_calls, self.device,
                                      sampler=self.sampler)
 
+    def _post_run(self, slabs):
+        if not self.unique:
+            return slabs
+        shapes = [x.shape for x in slabs.samples]
+        out, need = self._unique_out, self._unique_need             # a full launch's outputs and plan are kept
+        if out is None or [x.shape for x in out.nodes] != shapes:
+            full = max(slabs.nb, min(self.prefetch, len(self)))
+            need = _cabi.ns_typed_unique_workspace_bytes([s[1] for s in shapes], self._id_bounds, full)[0]
+            if need and (self._unique_ws is None or self._unique_ws.numel() * 8 < need):    # 0: the LDS form takes none
+                self._unique_ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=self.device)
+            out = _cabi.NsTypedUniqueOut(slabs, in_place=True, with_inverse=False)
+            if slabs.nb == full and slabs.n_inputs[self._it] == self.batch_size:
+                self._unique_out, self._unique_need = out, need
+        return _cabi.ns_typed_unique(slabs, slabs.nb, self._id_bounds, ws=self._unique_ws if need else None,
+                                     form=0 if need else 1, result=out.rebind(slabs))
+
     def _read_back(self, slabs):
-        return slabs.counts.cpu(), slabs.layer_offsets.cpu().tolist()
+        lo = slabs.layer_offsets.cpu().tolist()
+        if not self.unique:
+            return slabs.counts.cpu(), (lo, None)
+        counts, seed_counts = slabs.read_state()                    # the unique counts and the unique seeds in one copy
+        return counts, (lo, seed_counts[:, self._it].tolist())
 
     def _decorate(self, g, b, n_seeds, state, ts_parts):
+        lo, seed_counts = state
         for r, et in enumerate(self.edge_types):
-            g[et].layer_offsets = [tuple(x) for x in state[b][r][:len(self.fanout)]]
+            g[et].layer_offsets = [tuple(x) for x in lo[b][r][:len(self.fanout)]]
+        if seed_counts is not None:
+            g[self.input_type].batch_size = seed_counts[b]
 
 
 class HGTLoader(_TemporalInputs, _TypedLoader):

@@ -12,7 +12,10 @@ to one launch per relation and hop).
 neighbor_sampling_homogenous returns the reference's forest (a vertex reached along two paths holds two slots of
 `samples`, rows[e] == n_seeds + e).  The PyG-style form -- each node once, edges numbered against that list -- is made
 behind it, not inside it: transforms.unique_nodes(samples, rows, cols) -> (nodes, rows_u, cols_u, inverse) for one call
-(tg_ns_homo_unique, csrc/ns_unique.hip), loader.NeighborLoader(..., unique=True) for mini-batches."""
+(tg_ns_homo_unique, csrc/ns_unique.hip), loader.NeighborLoader(..., unique=True) for mini-batches.  Likewise per node
+type for neighbor_sampling_heterogenous: transforms.unique_nodes_hetero(samples, rows, cols, edge_types, num_nodes=None)
+-> (nodes, rows_u, cols_u, inverse) dicts (tg_ns_typed_unique, csrc/ns_unique_typed.hip),
+loader.HeteroNeighborLoader(..., unique=True) for mini-batches."""
 from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor

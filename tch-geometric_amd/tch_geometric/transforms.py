@@ -195,6 +195,69 @@ def unique_nodes(samples: Tensor, rows: Tensor, cols: Tensor, id_bound: Optional
     return u.nodes[0, :n_unique], u.rows[0, :m], u.cols[0, :m], u.inverse[0, :samples.numel()]
 
 
+class _OneCallTypedSlabs:
+    """One call's per-type samples and per-relation rows / cols as the single-batch typed slabs tg_ns_typed_unique reads."""
+
+    def __init__(self, samples: List[Tensor], rows: List[Tensor], cols: List[Tensor], rel_src, rel_dst, dev):
+        pad = lambda x: (x if x.numel() else torch.zeros(1, dtype=torch.int64, device=dev)).contiguous().view(1, -1)
+        self.T, self.R, self.rel_src, self.rel_dst = len(samples), len(rows), rel_src, rel_dst
+        self.samples, self.rows, self.cols = [pad(x) for x in samples], [pad(x) for x in rows], [pad(x) for x in cols]
+        self.edge_index, self.n_inputs = self.rows, [0] * self.T
+        self.counts = torch.tensor([[x.numel() for x in samples] + [x.numel() for x in rows]], dtype=torch.int64).to(dev)
+
+
+def unique_nodes_hetero(samples: Dict[str, Tensor], rows: Dict[str, Tensor], cols: Dict[str, Tensor], edge_types,
+                        num_nodes: Optional[Dict[str, int]] = None):
+    """Per-type node dedup and relabel of ONE call's output of neighbor_sampling_heterogenous (a forest per node type) ->
+    (nodes, rows_u, cols_u, inverse), dicts keyed as the inputs: per node type `nodes[t]` lists each value of samples[t]
+    once, in order of first occurrence, nodes[t][inverse[t]] == samples[t]; per relation rows_u = inverse[src type][rows],
+    cols_u = inverse[dst type][cols] (an end that is no position of its list gives -1); edges are not merged.  Relation
+    keys are as the operator returns them ("src__rel__dst"); edge_types (the (src, rel, dst) triples) gives each key's two
+    node types.  Device tensors run
+    tg_ns_typed_unique as a single-batch launch (csrc/ns_unique_typed.hip; one read-back of the unique counts); CPU tensors
+    take a torch implementation of the same rule.  num_nodes: per node type, every id is in [0, num_nodes[t]) (at most 2^31
+    takes 32-bit hash keys); a type without an entry assumes nothing beyond non-negative int64 ids."""
+    ends = {rel_key(et): (et[0], et[2]) for et in edge_types}
+    for k in rows:
+        if k not in ends or k not in cols:
+            raise ValueError("relation %s has no edge type / no cols" % k)
+        if rows[k].numel() != cols[k].numel():
+            raise ValueError("rows and cols of %s differ in length" % k)
+    for t in list(samples.values()) + list(rows.values()) + [cols[k] for k in rows]:
+        if t.dtype != torch.int64:
+            raise ValueError("Tensor must be a is of invalid type. Expected Int64 but got %s" % t.dtype)
+    rels = list(rows)
+    flat = {t: x.reshape(-1) for t, x in samples.items()}
+    for k in rels:                                                  # a type only a relation names: an empty list
+        for t in ends[k]:
+            flat.setdefault(t, torch.zeros(0, dtype=torch.int64))
+    types = list(flat)
+    if not any(x.is_cuda for x in flat.values()):
+        empty = torch.zeros(0, dtype=torch.int64)
+        parts = {t: unique_nodes(flat[t], empty, empty) for t in types}
+        inverse = {t: parts[t][3] for t in types}
+
+        def relabel(inv, end):                                      # an end that is no position of its list gives -1
+            end = end.reshape(-1)
+            ok = (end >= 0) & (end < inv.numel())
+            return torch.where(ok, torch.cat([inv, inv.new_zeros(1)])[torch.where(ok, end, 0)], -1)
+
+        return ({t: parts[t][0] for t in types}, {k: relabel(inverse[ends[k][0]], rows[k]) for k in rels},
+                {k: relabel(inverse[ends[k][1]], cols[k]) for k in rels}, inverse)
+    dev = next(x.device for x in flat.values() if x.is_cuda)
+    tix = {t: i for i, t in enumerate(types)}
+    slabs = _OneCallTypedSlabs([flat[t].to(dev) for t in types], [rows[k].reshape(-1).to(dev) for k in rels],
+                               [cols[k].reshape(-1).to(dev) for k in rels], [tix[ends[k][0]] for k in rels],
+                               [tix[ends[k][1]] for k in rels], dev)
+    bounds = [max(int(num_nodes[t]), 1) if num_nodes is not None and t in num_nodes else 1 << 62 for t in types]
+    u = _cabi.ns_typed_unique(slabs, 1, bounds)
+    n_unique = u.counts[0].tolist()
+    return ({t: u.nodes[i][0, :n_unique[i]] for i, t in enumerate(types)},
+            {k: u.rows[r][0, :rows[k].numel()] for r, k in enumerate(rels)},
+            {k: u.cols[r][0, :rows[k].numel()] for r, k in enumerate(rels)},
+            {t: u.inverse[i][0, :flat[t].numel()] for i, t in enumerate(types)})
+
+
 def _is_hetero(data) -> bool:
     return hasattr(data, "node_types") and hasattr(data, "edge_types")
 
