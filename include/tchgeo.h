@@ -915,6 +915,52 @@ TG_API int tg_ns_typed_unique_workspace_bytes(int32_t n_types, const int64_t *pi
 TG_API int tg_ns_typed_unique(const tg_ns_typed_in *in, int64_t n_batches, const tg_ns_typed_unique_out *out,
                               void *workspace, int64_t workspace_bytes, int32_t form, void *stream);
 
+/* ---- per-batch induced subgraph of a list of distinct nodes (PyG directed=False / subgraph_type="induced") --------------
+ * The dedup above fixes the node contract; its edges are still the sampler's forest.  This pair makes, for every batch b
+ * independently (nodes = in.nodes[b][:n], n = counts[b * counts_stride] clamped to the pitch), EVERY edge of the graph
+ * between two nodes of the batch:
+ *   local(v) = the FIRST position of v in nodes                  (no position: v is not in the batch)
+ *   for i in 0 .. n-1, for e in ptrs[nodes[i]] .. ptrs[nodes[i]+1]-1 ascending:
+ *       j = local(indices[e]);  if j exists: emit (row = j, col = i, edge_index = e)
+ * Output order is (i, e) ascending; parallel edges (separate CSC offsets) are each emitted, self loops too; m_b = the
+ * number of triples.  This is the edge loop of PyG's neighbor_sample(..., directed=False).  The contract is a
+ * list of distinct ids (tg_ns_unique_out.nodes); a list with repeats is still deterministic -- every position scans its
+ * column, local is the first position -- and never faults.  An id outside [0, csc->n_major) is a column of length 0 and
+ * raises status bit 1.
+ * Two exact passes: tg_ns_induced_count gives m_b, the caller allocates and passes the exclusive prefix, tg_ns_induced_emit
+ * writes; no capacity guess, no retry.  Columns are scanned in chunks of 512 consecutive CSC offsets spread over the whole
+ * device (a hub column is scanned by many wavefronts at once), each entry probed in the batch's hash table in `workspace`.
+ * The workspace is bounded by the graph: distinct nodes have disjoint columns, so a batch has at most pitch_nodes +
+ * ceil(csc->n_edges / 512) chunks.  A list with repeats that exceeds the bound raises status bit 0 and gets m_b = 0 (pass
+ * 2 writes nothing for it); other batches are unaffected.  The workspace must hold all n_batches at once (bytes =
+ * n_batches * bytes_min; a caller with less memory splits the launch).  id_bound (>= csc->n_major) <= 2^31 takes 32-bit
+ * hash keys, else 64-bit ones; indices32 / ptrs32 are used when given, with equal results.  Limits: pitch_nodes in
+ * [0, 2^30], n_marks in [0, TG_MAX_HOPS], the chunk bound <= 2^31.  Bad arguments (null pointers, negative sizes, a short or
+ * misaligned workspace) are refused with TG_ERR_INVALID before anything is launched; the calls do not synchronise,
+ * allocate or read back. */
+typedef struct {
+    const int64_t *nodes;      /* device [n_batches * pitch_nodes]: distinct ids per batch (tg_ns_unique_out.nodes) */
+    int64_t pitch_nodes;
+    const int64_t *counts;     /* device: n of batch b = counts[b * counts_stride] (tg_ns_unique_out.counts: stride 2) */
+    int64_t counts_stride;
+    const int64_t *node_marks; /* device [n_batches * n_marks] or NULL: positions (e.g. tg_ns_unique_out.layer_nodes) */
+    int32_t n_marks;
+} tg_ns_induced_in;
+
+TG_API int tg_ns_induced_workspace_bytes(const tg_graph *csc, int64_t pitch_nodes, int64_t id_bound, int64_t n_batches,
+                                         int64_t *bytes, int64_t *bytes_min /* one batch */);
+/* pass 1: n_edges[b] = m_b (device [n_batches]); edge_marks[b*n_marks+k] = induced edges with col < clamp(node_marks[b][k], 0, n)
+ * (or NULL); leaves tables / prefixes in `workspace` for pass 2.  status: device int32, zeroed by the caller. */
+TG_API int tg_ns_induced_count(const tg_graph *csc, const tg_ns_induced_in *in, int64_t n_batches, int64_t id_bound,
+                               int64_t *n_edges, int64_t *edge_marks, int32_t *status, void *workspace,
+                               int64_t workspace_bytes, void *stream);
+/* pass 2, same arguments and the SAME untouched workspace: batch b's triples to rows / cols / edge_index[edge_off[b] ..
+ * edge_off[b] + m_b) of three FLAT arrays (edge_off: device [n_batches], the caller's exclusive prefix of n_edges).
+ * Nothing outside those ranges is written. */
+TG_API int tg_ns_induced_emit(const tg_graph *csc, const tg_ns_induced_in *in, int64_t n_batches, int64_t id_bound,
+                              const int64_t *edge_off, int64_t *rows, int64_t *cols, int64_t *edge_index,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Ragged rows of an int64 slab -> one flat array: dst[offsets[r] + i] = src[r * pitch + i] for
  * i < lens[r * lens_stride] (lens, offsets: device arrays).  The per-type / per-relation slabs of
  * tg_ns_hetero_batched are flattened with it (tch_geometric/loader.py). */

@@ -259,33 +259,7 @@ template <typename K> __global__ void __launch_bounds__(NSU_TILE_THREADS) nsu_re
     }
 }
 
-// ---- host side: what a shape needs, which form it takes -----------------------------------------------------------------
-struct NsuPlan {
-    int key_bytes;
-    int64_t table_cap, lds_bytes;   // of the LDS form
-    int lds_ok;                     // the LDS form's words fit their widths (the LDS limit is checked apart)
-    int threads;                    // of the LDS form
-    int64_t n_node_tiles, vals_off, slot_off, tile_off, batch_bytes; // flat form: a batch's part of the workspace
-};
-
-static int nsu_plan(int64_t cap_nodes, int64_t id_bound, const char *who, NsuPlan &pl) {
-    TG_REQUIRE(cap_nodes >= 0 && cap_nodes <= NSU_MAX_NODES, "%s: cap_nodes = %lld outside [0, 2^30]", who, (long long)cap_nodes);
-    TG_REQUIRE(id_bound >= 1, "%s: id_bound = %lld, at least 1 expected", who, (long long)id_bound);
-    pl.key_bytes = id_bound <= ((int64_t)1 << 31) ? 4 : 8;
-    pl.table_cap = pow2_at_least((4 * cap_nodes + 2) / 3); // > cap_nodes: a probe always meets an empty slot
-    pl.lds_bytes = pl.table_cap * (pl.key_bytes + 4) + ((2 * cap_nodes + 15) & ~(int64_t)15) + NSU_STATIC_LDS;
-    pl.lds_ok = cap_nodes <= NSU_LDS_MAX_NODES;
-    pl.threads = cap_nodes >= NSU_THREADS ? NSU_THREADS : (int)(cap_nodes < 64 ? 64 : (cap_nodes + 63) & ~(int64_t)63);
-    pl.n_node_tiles = cap_nodes > 0 ? (cap_nodes + NSU_TILE - 1) / NSU_TILE : 1;
-    pl.vals_off = nsu_r256(pl.table_cap * pl.key_bytes);
-    pl.slot_off = pl.vals_off + nsu_r256(pl.table_cap * 4);
-    pl.tile_off = pl.slot_off + nsu_r256(cap_nodes * 4);
-    pl.batch_bytes = pl.tile_off + nsu_r256(pl.n_node_tiles * 4);
-    return TG_OK;
-}
-
-static inline bool nsu_fits(const NsuPlan &pl, int64_t lds_limit) { return pl.lds_ok && pl.lds_bytes <= lds_limit; }
-
+// ---- host side (the plan, what a shape needs and which form it takes: ns_unique.h) --------------------------------------
 template <typename K> static int nsu_launch_lds(const NsuArgs &a, const NsuPlan &pl, hipStream_t stream) {
     const int64_t dyn = pl.lds_bytes - NSU_STATIC_LDS;
     if (dyn > 64 * 1024) { // above the default limit of a launch: raise it once per device (the plan keeps it below the device's)

@@ -36,7 +36,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_hgt_batched_workspace_bytes", "tg_hgt_sample_batched", "tg_budget_batched_workspace_bytes",
            "tg_budget_sample_batched", "tg_neg_batched_capacity", "tg_neg_batched_form", "tg_neg_batched_workspace_bytes",
            "tg_neg_sample_batched", "tg_ns_homo_unique_form", "tg_ns_homo_unique_workspace_bytes", "tg_ns_homo_unique",
-           "tg_ns_typed_unique_form", "tg_ns_typed_unique_workspace_bytes", "tg_ns_typed_unique"]
+           "tg_ns_typed_unique_form", "tg_ns_typed_unique_workspace_bytes", "tg_ns_typed_unique",
+           "tg_ns_induced_workspace_bytes", "tg_ns_induced_count", "tg_ns_induced_emit"]
 
 
 class TgGraph(C.Structure):
@@ -909,6 +910,95 @@ def ns_homo_unique(out, n_batches, id_bound, form=0, ws=None, in_place=False, re
                                 C.c_int32(form), stream_ptr(out.samples.device)))
     res._ws = ws                              # the launch borrows it: alive as long as the result
     return res
+
+
+class TgNsInducedIn(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("pitch_nodes", C.c_int64), ("counts", C.c_void_p), ("counts_stride", C.c_int64),
+                ("node_marks", C.c_void_p), ("n_marks", C.c_int32)]
+
+
+def ns_induced_workspace_bytes(graph, pitch_nodes, id_bound, n_batches):
+    """-> (bytes, bytes_min): the workspace of the induced pair for n_batches batches at once (n_batches * bytes_min) and
+    for one batch; graph: a tg_graph view (only n_major and n_edges are read)."""
+    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_ns_induced_workspace_bytes(C.byref(graph), C.c_int64(pitch_nodes), C.c_int64(id_bound),
+                                            C.c_int64(n_batches), C.byref(nbytes), C.byref(bmin)))
+    return nbytes.value, bmin.value
+
+
+class NsInduced:
+    """The induced pair over the node slab `nodes` [>= n_batches, pitch] with n of batch b at
+    counts.reshape(-1)[b * counts_stride]; node_marks: [n_batches, n_marks] positions or None.  Owns what the passes share:
+    n_edges [n_batches], edge_marks [n_batches, n_marks], status [1] and the workspace (`ws`: an int64 tensor of an earlier
+    launch of the same shape, reused when large enough).  count() then emit() run on the current stream; neither
+    synchronises."""
+
+    def __init__(self, graph, nodes, counts, counts_stride, n_batches, id_bound, node_marks=None, ws=None):
+        dev = nodes.device
+        self.graph, self.n_batches, self.id_bound = graph, int(n_batches), int(id_bound)
+        self.nodes, self.counts, self.node_marks = nodes, counts, node_marks
+        si = self.struct = TgNsInducedIn()
+        si.nodes, si.pitch_nodes = nodes.data_ptr(), nodes.shape[-1]
+        si.counts, si.counts_stride = counts.data_ptr(), int(counts_stride)
+        self.n_marks = 0 if node_marks is None else int(node_marks.shape[-1])
+        si.node_marks, si.n_marks = (node_marks.data_ptr() if self.n_marks else None), self.n_marks
+        need = ns_induced_workspace_bytes(graph, si.pitch_nodes, self.id_bound, self.n_batches)[0]
+        if ws is None or ws.numel() * 8 < need:
+            ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+        self.ws = ws
+        # n_edges, the marks and the status word in one tensor: a loader reads them back in one copy
+        self.state = torch.zeros(self.n_batches * (1 + self.n_marks) + 1, dtype=torch.int64, device=dev)
+        self.n_edges = self.state[:self.n_batches]
+        self.edge_marks = self.state[self.n_batches:self.n_batches * (1 + self.n_marks)].view(self.n_batches, self.n_marks)
+        self.status = self.state[-1:].view(torch.int32)[:1]
+
+    def count(self, n_batches=None):
+        """pass 1 over the first n_batches batches (all when None); emit() then runs the same ones"""
+        self.live = self.n_batches if n_batches is None else int(n_batches)
+        self.state[-1:].zero_()
+        check(lib.tg_ns_induced_count(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live),
+                                      C.c_int64(self.id_bound), ptr(self.n_edges), ptr(self.edge_marks) if self.n_marks else None,
+                                      ptr(self.status), ptr(self.ws), C.c_int64(self.ws.numel() * 8),
+                                      stream_ptr(self.nodes.device)))
+        return self
+
+    def emit(self, edge_off, rows, cols, edge_index):
+        """pass 2 into the caller's flat arrays; edge_off: device [n_batches], the exclusive prefix of n_edges"""
+        check(lib.tg_ns_induced_emit(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live),
+                                     C.c_int64(self.id_bound), ptr(edge_off), ptr(rows), ptr(cols), ptr(edge_index),
+                                     ptr(self.ws), C.c_int64(self.ws.numel() * 8), stream_ptr(self.nodes.device)))
+
+
+def induced_status_check(status, who):
+    """the status word of tg_ns_induced_count after its read-back: non-zero raises"""
+    if status:
+        raise RuntimeError("%s: status %d (%s)" % (who, status, " and ".join(
+            t for bit, t in ((1, "a list with repeats exceeds the chunk bound"), (2, "a node id outside the graph")) if status & bit)))
+
+
+def ns_induced_count(graph, nodes, counts, counts_stride, n_batches, id_bound, node_marks=None, ws=None):
+    """tg_ns_induced_count on the current stream -> the NsInduced launch (n_edges, edge_marks, status on the device)."""
+    return NsInduced(graph, nodes, counts, counts_stride, n_batches, id_bound, node_marks, ws).count()
+
+
+def ns_induced_emit(launch, n_edges_host=None):
+    """tg_ns_induced_emit of a counted launch into exact flat arrays -> ([2, M] rows over cols, edge_index [M], edge_off
+    [n_batches + 1] as a python list).  n_edges_host: the counts already read back; read here (one synchronisation) when
+    not given, together with the status word, which raises when non-zero."""
+    if n_edges_host is None:
+        state = launch.state.cpu()
+        induced_status_check(int(state[-1:].view(torch.int32)[0]), "ns_induced_emit")
+        n_edges_host = state[:launch.n_batches].tolist()
+    off = [0]
+    for m in n_edges_host:
+        off.append(off[-1] + int(m))
+    dev = launch.nodes.device
+    rc = torch.empty((2, off[-1]), dtype=torch.int64, device=dev)
+    eidx = torch.empty(off[-1], dtype=torch.int64, device=dev)
+    if off[-1]:
+        edge_off = torch.cumsum(launch.n_edges, 0) - launch.n_edges
+        launch.emit(edge_off, rc[0], rc[1], eidx)
+    return rc, eidx, off
 
 
 class TgNsTypedIn(C.Structure):

@@ -63,7 +63,8 @@ class SuperBatch:
     mini-batches as `MiniBatch` views; a consumer that can take the whole super-batch (a model over a batch of
     sub-graphs with `ptr` offsets) pays no per-mini-batch host work at all."""
     __slots__ = ("n_id", "edge_index", "_e_id", "_e_ptr", "_perm", "node_attrs", "edge_attrs", "node_ptr", "edge_ptr",
-                 "layer_offsets", "layer_nodes", "seed_counts", "batch_size", "call_id0", "n_hops", "_views", "_index")
+                 "layer_offsets", "layer_nodes", "layer_edges", "seed_counts", "batch_size", "call_id0", "n_hops", "_views",
+                 "_index")
 
     @property
     def e_id(self):
@@ -133,8 +134,19 @@ class MiniBatch:
         ln = self._sb.layer_nodes
         return None if ln is None else list(ln[self._j][:self._sb.n_hops])
 
+    @property
+    def layer_edges(self):
+        """induced=True: [hops] induced edges whose target is among the first layer_nodes[h] nodes (a prefix of edge_index)"""
+        le = self._sb.layer_edges
+        return None if le is None else list(le[self._j][:self._sb.n_hops])
+
     call_id = property(lambda self: self._sb.call_id0 + self._j)
-    layer_offsets = property(lambda self: [tuple(x) for x in self._sb.layer_offsets[self._j][:self._sb.n_hops]])
+
+    @property
+    def layer_offsets(self):
+        """the forest's (node begin, node end, edge end) per hop; None from an induced=True loader"""
+        lo = self._sb.layer_offsets
+        return None if lo is None else [tuple(x) for x in lo[self._j][:self._sb.n_hops]]
 
     def _all(self):  # the views of this mini-batch: one call into the host module on first use, then a tuple
         c = self._cache
@@ -174,11 +186,23 @@ class NeighborLoader(_Loader):
     lists each node once (first occurrence first, so the distinct seeds lead), `edge_index` is numbered against it (edges
     are not merged), node attributes are gathered per unique node; `e_id` and the edge attributes are the forest's.
     `batch_size` is the unique-seed count, `layer_nodes[h]` the unique nodes known when hop h starts; `layer_offsets`
-    stays the forest's."""
+    stays the forest's.
+
+    induced=True (needs unique=True) replaces the forest's edges by the induced subgraph of `n_id`, PyG's directed=False:
+    every edge of the graph between two nodes of the mini-batch, ordered by target position, then CSC offset.
+    tg_ns_induced_count runs on the side stream directly behind the dedup (its edge counts travel to pinned memory with the
+    other sizes: still one wait per launch), tg_ns_induced_emit on the caller's stream straight into the flat `edge_index`;
+    the workspace the two passes share belongs to the slab set.  `edge_index`, `num_edges`, `e_id` and the edge attributes
+    are the induced edges'; `layer_edges[h]` counts those whose target is among the first `layer_nodes[h]` nodes, a prefix
+    of `edge_index`; `layer_offsets` is None.  Induced edges are not filtered."""
 
     def __init__(self, data, num_neighbors: List[int], input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
                  prefetch: int = 16, replace: bool = False, shuffle: bool = False, drop_last: bool = False,
-                 seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0, unique: bool = False):
+                 seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0, unique: bool = False,
+                 induced: bool = False):
+        if induced and not unique:
+            raise ValueError("induced=True needs unique=True: the induced edges are numbered against the unique node list")
+        self.induced = bool(induced)
         self.data, self.fanout = data, [int(k) for k in num_neighbors]
         self.device = torch.device(device)
         self.batch_size, self.prefetch = int(batch_size), max(1, int(prefetch))
@@ -253,6 +277,14 @@ class NeighborLoader(_Loader):
                 _cabi.ns_homo_unique(out, G, self.n_nodes, ws=self._unique_ws if need else None, result=uniq)
                 if H:
                     slab["ln"][:G].copy_(uniq.layer_nodes[:G], non_blocking=True)
+                if self.induced:             # pass 1: the edge counts join the sizes the host waits for
+                    ind = slab.get("ind")
+                    if ind is None:
+                        ind = slab["ind"] = _cabi.NsInduced(self._graph, uniq.nodes, uniq.counts, 2, out.n_batches,
+                                                            self.n_nodes, node_marks=uniq.layer_nodes if H else None)
+                        slab["ist"] = torch.empty(ind.state.numel(), dtype=torch.int64).pin_memory()
+                    ind.count(G)
+                    slab["ist"].copy_(ind.state, non_blocking=True)
             slab["counts"][:G].copy_(sizes.counts[:G], non_blocking=True)
             slab["lo"][:G].copy_(out.layer_offsets[:G], non_blocking=True)
             done = torch.cuda.Event()
@@ -270,7 +302,14 @@ class NeighborLoader(_Loader):
         counts = slab["counts"][:G]
         n_nodes, n_edges = counts[:, 0].tolist(), counts[:, 1].tolist()
         src = slab["uniq"] if self.unique else out                 # unique: the deduplicated, relabelled view of the slabs
-        n_id, edge_index, e_ptr = _cabi.ns_homo_compact(src, G, counts, stacked=True)   # copies: the slabs go back to the sampler
+        if self.induced:                     # pass 2 writes the flat arrays itself: no edge slab, no edge compaction
+            ind, ist = slab["ind"], slab["ist"]
+            _cabi.induced_status_check(int(ist[-1]) & 0xFFFFFFFF, "NeighborLoader(induced=True)")
+            n_edges = ist[:G].tolist()
+            n_id = _flat_rows(src.nodes[:G], src.counts[:G, 0], sum(n_nodes))
+            edge_index, e_ptr, _ = _cabi.ns_induced_emit(ind, n_edges)
+        else:
+            n_id, edge_index, e_ptr = _cabi.ns_homo_compact(src, G, counts, stacked=True)   # copies: the slabs go back to the sampler
         free = torch.cuda.Event()
         free.record(cur)
         slab["free"] = free
@@ -288,7 +327,11 @@ class NeighborLoader(_Loader):
             ptr_e.append(e)
         sb.node_ptr, sb.edge_ptr = ptr_n, ptr_e
         sb.layer_offsets = slab["lo"][:G].tolist()
-        sb.layer_nodes = sb.seed_counts = None
+        sb.layer_nodes = sb.seed_counts = sb.layer_edges = None
+        if self.induced:
+            cap, H = slab["ind"].n_batches, len(self.fanout)
+            sb.layer_offsets = None
+            sb.layer_edges = slab["ist"][cap:cap * (1 + H)].view(cap, H)[:G].tolist()
         if self.unique:
             H = len(self.fanout)
             sb.layer_nodes = slab["ln"][:G, :H].tolist()

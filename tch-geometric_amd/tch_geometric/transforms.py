@@ -195,6 +195,45 @@ def unique_nodes(samples: Tensor, rows: Tensor, cols: Tensor, id_bound: Optional
     return u.nodes[0, :n_unique], u.rows[0, :m], u.cols[0, :m], u.inverse[0, :samples.numel()]
 
 
+def induced_subgraph(nodes: Tensor, col_ptrs: Tensor, row_indices: Tensor, id_bound: Optional[int] = None):
+    """Every edge of the CSC graph (col_ptrs, row_indices) between two nodes of ONE list (PyG's directed=False /
+    subgraph_type="induced") -> (rows, cols, edge_index): for every position i of `nodes` in order and every CSC offset e of
+    column nodes[i] in ascending order, (local(row_indices[e]), i, e) where local(v), the FIRST position of v in `nodes`,
+    exists.  Parallel edges and self loops are kept.  `nodes` is meant to be a list of distinct ids (unique_nodes'); with
+    repeats every position scans its column.  Device tensors run tg_ns_induced_count / tg_ns_induced_emit as a single-batch
+    launch (csrc/ns_induced.hip; one read-back of the edge count); CPU tensors take a torch implementation of the same
+    rule.  An id outside the graph raises IndexError.  id_bound: every id is in [0, id_bound) (at most 2^31 takes 32-bit
+    hash keys); None takes the graph's node count."""
+    for t in (nodes, col_ptrs, row_indices):
+        if t.dtype != torch.int64:
+            raise ValueError("Tensor must be a is of invalid type. Expected Int64 but got %s" % t.dtype)
+    nodes = nodes.reshape(-1)
+    n, n_major = nodes.numel(), col_ptrs.numel() - 1
+    if n and (int(nodes.min()) < 0 or int(nodes.max()) >= n_major):
+        raise IndexError("induced_subgraph: node id outside [0, %d)" % n_major)
+    if not nodes.is_cuda:
+        begin = col_ptrs[nodes]
+        deg = col_ptrs[nodes + 1] - begin
+        cols = torch.repeat_interleave(torch.arange(n), deg)
+        edge = torch.arange(cols.numel()) - torch.repeat_interleave(torch.cumsum(deg, 0) - deg, deg) + begin[cols]
+        values, inv = torch.unique(nodes, return_inverse=True)
+        first = torch.full((values.numel(),), n, dtype=torch.int64).scatter_reduce_(0, inv, torch.arange(n), "amin")
+        src = row_indices[edge]
+        at = torch.searchsorted(values, src).clamp_(max=max(values.numel() - 1, 0))
+        keep = values[at] == src if n else torch.zeros(0, dtype=torch.bool)
+        return first[at[keep]], cols[keep], edge[keep]
+    dev = nodes.device
+    if n == 0:
+        return tuple(torch.empty(0, dtype=torch.int64, device=dev) for _ in range(3))
+    col_ptrs, row_indices = col_ptrs.to(dev).contiguous(), row_indices.to(dev).contiguous()
+    graph = _cabi.graph_view(col_ptrs, row_indices)
+    counts = torch.tensor([n], dtype=torch.int64).to(dev)
+    launch = _cabi.ns_induced_count(graph, nodes.contiguous().view(1, -1), counts, 1, 1,
+                                    n_major if id_bound is None else int(id_bound))
+    rc, edge_index, _ = _cabi.ns_induced_emit(launch)
+    return rc[0], rc[1], edge_index
+
+
 class _OneCallTypedSlabs:
     """One call's per-type samples and per-relation rows / cols as the single-batch typed slabs tg_ns_typed_unique reads."""
 
