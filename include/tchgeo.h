@@ -520,6 +520,65 @@ TG_API int tg_edge_set_build(const tg_graph *csr, void *edge_set, int64_t bytes,
 TG_API int tg_random_walk_es(const tg_graph *csr, const void *edge_set, int64_t edge_set_bytes, const int64_t *start, int64_t n,
                              int64_t walk_length, float p, float q, const tg_rng *rng, int64_t *walks, void *stream);
 
+/* ---- Node2Vec skip-gram batches: walks, context windows and negatives of G mini-batches in one launch -------------------
+ * What the reference's examples/random_walk.py composes per mini-batch (random_walk, PyG's strided slices + cat,
+ * randint), fused: a walker's row never leaves LDS as a [n, L] tensor, only its windows are written.
+ * A launch samples n_batches = G mini-batches of batch_size = B seeds (seeds: device int64 [G, B], ids < csr->n_major).
+ * T = walk_length steps give rows of L = T + 1 columns (as tg_random_walk), C = context_size (1 <= C <= L) gives
+ * nw = L - C + 1 windows, R = walks_per_node >= 1, K = num_negative_samples >= 0; p, q and the optional edge set are
+ * tg_random_walk_es's.  Mini-batch g draws with call id rng->call_id + g.
+ *  positives  W = R * B walkers per mini-batch; walker w = r * B + i starts at seeds[g][i] (PyG's batch.repeat(R)).
+ *             walk_g[w][0..L) equals, value for value, tg_random_walk(start = seeds[g] repeated R times, n = W, T, p, q,
+ *             edge set, seed, call id + g): the draw of step l, attempt a is (call key of TAG_RW, id = w, d0 = l, d1 = a).
+ *             pos_rw[g] is [nw * W, C]: row j * W + w, column c holds walk_g[w][j + c] -- PyG's
+ *             cat([rw[:, j:j + C] for j in range(nw)], 0).  A walker that meets a dead end keeps the reference's -1
+ *             padding, and so do its windows: a consumer masks with (pos_rw >= 0).all(1).
+ *  negatives  U = R * K * B walkers per mini-batch; x_u[0] = seeds[g][u mod B], and for m >= 1
+ *             x_u[m] = floor(a * n_nodes / 2^64), a = the low 64 bits of the draw (call key of (seed, call id + g,
+ *             TAG_RW_NEG = 12), id = u, d0 = m, d1 = 0).  neg_rw[g] is [nw * U, C]: row j * U + u, column c holds
+ *             x_u[j + c].  K = 0: an empty [0, C] slab, neg_rw may be NULL.
+ * The slabs of a launch are batch-major and contiguous: pos_rw [G, nw * W, C], neg_rw [G, nw * U, C] (device int64),
+ * every word of them is written, nothing is counted and nothing is read back; the call does not synchronise.
+ * `form`: 0 auto; 1, 2 the LDS form -- one lane per walker (walkers of a launch flat, t = g * W + w), a wavefront stages
+ * its 64 walkers' whole rows in LDS (1: as uint32 with 0xffffffff for -1, needs id_bound = max(csr->n_major, n_nodes) <
+ * 2^32 - 1; 2: as int64) at an odd pitch and then streams every window out, 64 * C * 8 contiguous bytes per window inside
+ * a mini-batch; the negatives go through the same routine.  A workgroup is one wavefront with 64 * (L | 1) * word + 512
+ * bytes of LDS, taken while that is <= 40 KiB, so that a CU always keeps a wavefront per SIMD resident: L <= 157 for
+ * form 1, L <= 79 for form 2.  3 the flat form, any L: a walk kernel writes [G * W, L] int64 into `workspace`
+ * (tg_rw_skipgram_workspace_bytes), a second kernel streams the windows out of it, a third makes the negatives
+ * element-wise.  Auto takes 1, else 2, else 3, whichever fits first.  All forms write identical outputs.
+ * Bad arguments (a null buffer, C < 1, C > L, R < 1, K < 0, T < 1, n_nodes < 1 with K > 0, p or q <= 0, a forced form
+ * that does not fit, a short workspace) are refused with TG_ERR_INVALID before anything is launched; G = 0 or B = 0
+ * returns TG_OK and launches nothing. */
+typedef struct {
+    int64_t walk_length;          /* T */
+    int64_t context_size;         /* C */
+    int64_t walks_per_node;       /* R */
+    int64_t num_negative_samples; /* K */
+    int64_t n_nodes;              /* range of the negative draws */
+    float p, q;
+} tg_rw_skipgram_config;
+
+typedef struct {
+    int64_t *pos_rw; /* [G, nw * W, C] */
+    int64_t *neg_rw; /* [G, nw * U, C], or NULL when K = 0 */
+} tg_rw_skipgram_out;
+
+/* rows of pos_rw and neg_rw per mini-batch: nw * R * B and nw * R * K * B */
+TG_API int tg_rw_skipgram_capacity(const tg_rw_skipgram_config *cfg, int64_t batch_size, int64_t *pos_rows,
+                                   int64_t *neg_rows);
+/* Which form an auto call takes for ids in [0, id_bound): *form = 1, 2 or 3; *lds_bytes = the LDS a workgroup of the
+ * narrowest LDS form the ids allow asks for.  lds_limit_bytes > 0 replaces the 40 KiB limit.  No device is touched. */
+TG_API int tg_rw_skipgram_form(const tg_rw_skipgram_config *cfg, int64_t id_bound, int64_t lds_limit_bytes, int32_t *form,
+                               int64_t *lds_bytes);
+/* the workspace a call of this form needs (form 0: the form auto takes): 0 for the LDS forms, G * W * L * 8 for flat */
+TG_API int tg_rw_skipgram_workspace_bytes(const tg_rw_skipgram_config *cfg, int64_t n_batches, int64_t batch_size,
+                                          int64_t id_bound, int32_t form, int64_t *bytes);
+TG_API int tg_rw_skipgram(const tg_graph *csr, const void *edge_set, int64_t edge_set_bytes, const int64_t *seeds,
+                          int64_t n_batches, int64_t batch_size, const tg_rw_skipgram_config *cfg, const tg_rng *rng,
+                          const tg_rw_skipgram_out *out, void *workspace, int64_t workspace_bytes, int32_t form,
+                          void *stream);
+
 /* tempo_random_walk (random_walk.rs:80-158; binding python.rs:611-642).
  * walks, walks_ts: [n, walk_length] device int64. */
 TG_API int tg_tempo_random_walk(const tg_graph *csr, const int64_t *node_ts, const int64_t *edge_ts, const int64_t *start,

@@ -15,6 +15,7 @@
 //   probability 1/m, candidate 1 always does) from one addressed draw per
 //   candidate.  HBM-bound on 16 B per inspected edge.
 #include "row_stream.h"
+#include "rw_walk.h"
 #include "tg_device.h"
 #include "tg_host.h"
 #include "tg_map.h"
@@ -23,38 +24,8 @@ namespace tg {
 
 constexpr int RW_STAGE = 16; // steps staged per walker between flushes
 
-// CSR accessors: the optional u32 shadows (tg_graph.ptrs32 / indices32) hold the same values in half the bytes --
-// twice the entries per gathered line, and the whole offset table of RMAT-24 (67 MB) stays in the Infinity Cache
-struct CsrView {
-    const int64_t *ptrs, *indices;
-    const uint32_t *ptrs32, *indices32;
-    const uint64_t *edge_set; // optional hash set of the edges (tg_edge_set_build) and its slot mask
-    uint64_t edge_mask;
-    __device__ __forceinline__ int64_t ptr(int64_t i) const { return ptrs32 ? (int64_t)ptrs32[i] : ptrs[i]; }
-    __device__ __forceinline__ int64_t idx(int64_t e) const { return indices32 ? (int64_t)indices32[e] : indices[e]; }
-};
+// CsrView, the edge-set probe, has_edge and the walk step: rw_walk.h (shared with rw_skipgram.hip)
 
-// ---- the edge set: has_edge as a hash probe --------------------------------------------------------------------------
-// graph.rs:80-83 answers has_edge(x, y) by a binary search of row x: log2(deg) DEPENDENT random line requests, ~13 on
-// RMAT-24, and node2vec with p != q asks once per proposal -- the walk then sits on the chip's random-request ceiling.
-// The set holds every edge once as the key x << 32 | y in an open-addressing table (linear probing, load <= 1/2, 8-byte
-// slots: a probe sequence usually stays inside one 128-byte line), so the same question is ONE line request, with the
-// same answer (a multi-edge is one key; ids must be < 2^32 - 1).
-constexpr uint64_t EDGE_SET_EMPTY = ~0ull;
-__device__ __forceinline__ uint64_t edge_key_hash(uint64_t k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 29;
-    return k;
-}
-__device__ __forceinline__ bool edge_set_has(const uint64_t *__restrict__ slots, uint64_t mask, int64_t x, int64_t y) {
-    const uint64_t key = ((uint64_t)x << 32) | (uint64_t)y;
-    for (uint64_t s = edge_key_hash(key) & mask;; s = (s + 1) & mask) {
-        const uint64_t v = slots[s];
-        if (v == key) return true;
-        if (v == EDGE_SET_EMPTY) return false;
-    }
-}
 __global__ void edge_set_clear_kernel(uint64_t *slots, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         slots[i] = EDGE_SET_EMPTY;
@@ -92,21 +63,6 @@ __global__ void edge_set_insert_kernel(const int64_t *__restrict__ ptrs, const i
     }
 }
 
-__device__ __forceinline__ bool has_edge(const CsrView &g, int64_t x, int64_t y) { // graph.rs:80-83
-    if (g.edge_set) return edge_set_has(g.edge_set, g.edge_mask, x, y);
-    int64_t lo = g.ptr(x), hi = g.ptr(x + 1);
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const int64_t v = g.idx(mid);
-        if (v == y) return true;
-        if (v < y)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return false;
-}
-
 // StageT = uint32_t for the has_edge variants when the vertex ids fit (0xffffffff stands for -1): half the LDS per
 // workgroup, twice the resident wavefronts -- those variants are bound by the latency of their dependent loads (p != q:
 // 11.8 -> 9.1 ms; p = q = 1 is not: 1.16 ms with int64 staging, 1.27 with u32, so it keeps int64)
@@ -121,7 +77,8 @@ __global__ void rw_node2vec_kernel(const CsrView g, const int64_t *__restrict__ 
     const bool live = t < n;
     const CallKey ck = call_key(seed, call_id, TAG_RW);
     const int64_t L = walk_length + 1;
-    const bool always_accept = prob0 >= 1.0f && prob1 >= 1.0f && prob2 >= 1.0f; // r < 1 always holds
+    const WalkProbs pr{prob0, prob1, prob2};
+    const bool always_accept = pr.always_accept();
 
     int64_t prev = -1, cur = live ? start[t] : -1;
     bool dead = !live;
@@ -134,30 +91,10 @@ __global__ void rw_node2vec_kernel(const CsrView g, const int64_t *__restrict__ 
             if (col == 0) {
                 val = cur;
             } else if (!dead) {
-                const int64_t l = col - 1;
-                const int64_t b = g.ptr(cur), e = g.ptr(cur + 1);
-                if (e <= b) { // random_walk.rs:45-47
-                    dead = true;
-                } else {
-                    const uint64_t deg = (uint64_t)(e - b);
-                    int64_t next;
-                    for (uint32_t attempt = 0;; ++attempt) { // :52-66
-                        const Draw d = draw(ck, (uint64_t)t, (uint32_t)l, attempt);
-                        next = g.idx(b + (int64_t)bounded64(d.a(), deg));
-                        if (always_accept) break;
-                        const float r = u32_to_f32_01(d.w[2]);
-                        if (next == prev) {
-                            if (r < prob0) break;
-                        } else if (prev >= 0 && has_edge(g, next, prev)) {
-                            if (r < prob1) break;
-                        } else if (r < prob2) {
-                            break;
-                        }
-                    }
-                    prev = cur;
-                    cur = next;
+                if (walk_step(g, ck, (uint64_t)t, (uint32_t)(col - 1), pr, always_accept, prev, cur))
                     val = cur;
-                }
+                else
+                    dead = true;
             }
             stage[lane * (RW_STAGE + 1) + j] = (StageT)val; // -1 -> all ones
         }
@@ -284,11 +221,6 @@ __global__ void rw_tempo_kernel(const int64_t *__restrict__ ptrs, const int64_t 
 
 } // namespace tg
 
-static int64_t edge_set_slots(int64_t n_edges) {
-    int64_t cap = 64;
-    while (cap < 2 * n_edges) cap <<= 1;
-    return cap;
-}
 extern "C" int tg_edge_set_bytes(const tg_graph *csr, int64_t *bytes) {
     TG_REQUIRE(csr && bytes && csr->n_edges >= 0 && csr->n_major >= 0, "tg_edge_set_bytes: bad arguments");
     TG_REQUIRE(csr->n_major < (int64_t)0xffffffff, "tg_edge_set_bytes: ids of %lld vertices do not fit the 32-bit halves of a key",
@@ -328,17 +260,12 @@ extern "C" int tg_random_walk_es(const tg_graph *csr, const void *edge_set, int6
     }
     if (n == 0) return TG_OK;
     TG_REQUIRE(start && walks, "tg_random_walk: null buffers");
-    // random_walk.rs:29-36, all in f32
-    const float inv_p = 1.0f / p, inv_q = 1.0f / q;
-    float max_prob = inv_p;
-    if (1.0f >= max_prob) max_prob = 1.0f;
-    if (inv_q >= max_prob) max_prob = inv_q;
-    const float prob0 = 1.0f / p / max_prob, prob1 = 1.0f / max_prob, prob2 = 1.0f / q / max_prob;
+    const tg::WalkProbs pr = walk_probs(p, q);
+    const float prob0 = pr.prob0, prob1 = pr.prob1, prob2 = pr.prob2;
     const unsigned blocks = (unsigned)((n + 255) / 256);
     const tg::CsrView view{csr->ptrs, csr->indices, csr->ptrs32, csr->indices32, reinterpret_cast<const uint64_t *>(edge_set),
                            edge_mask};
-    const bool always_accept = prob0 >= 1.0f && prob1 >= 1.0f && prob2 >= 1.0f;
-    if (!always_accept && csr->n_major < (int64_t)0xffffffff)
+    if (!pr.always_accept() && csr->n_major < (int64_t)0xffffffff)
         hipLaunchKernelGGL(tg::rw_node2vec_kernel<uint32_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, view, start, n,
                            walk_length, prob0, prob1, prob2, rng->seed, rng->call_id, walks);
     else

@@ -1,0 +1,319 @@
+// Node2Vec skip-gram batches on gfx950: tg_rw_skipgram (contract: include/tchgeo.h; DESIGN.md "Skip-gram batches").
+//
+// What a Node2Vec trainer composes per mini-batch -- random_walk, PyG's `cat([rw[:, j:j + C] for j in range(nw)])`,
+// randint -- as ONE launch for G mini-batches.  The walk is tg_random_walk's (same step, same draws: rw_walk.h), so
+// the kernel is latency-bound on dependent look-ups with one LANE per walker; what changes is where the row goes.
+//
+// LDS form (rws_lds_kernel): a workgroup is one wavefront, its 64 walkers' whole rows sit in LDS ([walker][column] at an
+//   odd pitch: the 64 lanes of a column write hit 64 different banks), and after the walk the wave writes, window by window,
+//   its walkers' C-wide rows: inside one mini-batch rows j*W + w .. j*W + w + 63 are 64*C*8 contiguous bytes, so every
+//   store instruction covers 512 contiguous bytes.  A wave that straddles a mini-batch boundary (W no multiple of 64)
+//   needs nothing special: every element takes its walker's own base offset from a 64-entry table in LDS.  The [n, L]
+//   walks are never written or read back: bytes written = nw*C*8 per walker instead of L*8 + 2*nw*C*8 moved.
+//   The negative walkers are waves of the same grid: their rows are addressed draws instead of look-ups.
+// Flat form (any L): walks -> workspace [G*W, L] (rws_walk_kernel, 16 columns staged per flush as rw_node2vec_kernel),
+//   then rws_windows_kernel streams the windows out and rws_negatives_kernel makes the negatives element-wise.
+#include "rw_walk.h"
+#include "tg_device.h"
+#include "tg_host.h"
+#include "tg_map.h"
+
+namespace tg {
+
+constexpr uint32_t TAG_RW_NEG = 12u;
+constexpr int RWS_STAGE = 16;                   // flat form: columns staged per walker between flushes
+constexpr int64_t RWS_LDS_LIMIT = 40 * 1024;    // LDS form: 4 workgroups (one wavefront each) stay resident per CU
+constexpr int64_t RWS_TABLE_BYTES = 64 * 8;     // the wave's per-walker output offsets
+
+struct SkipgramParams {
+    CsrView g;
+    const int64_t *seeds;  // [G, B]
+    int64_t B, W, U;       // per mini-batch: seeds, positive walkers, negative walkers
+    int64_t n_pos, n_neg;  // G * W, G * U
+    int64_t pos_blocks;    // LDS form: the first pos_blocks wavefronts walk, the others draw negatives
+    int32_t L, C, nw, pitch;
+    WalkProbs pr;
+    uint64_t seed, call_id, n_nodes;
+    int64_t *pos, *neg;
+    int64_t *walks;        // flat form: [G * W, L]
+};
+
+__device__ __forceinline__ int64_t negative_value(CallKey ck, uint64_t u, uint32_t m, uint64_t n_nodes) {
+    return (int64_t)bounded64(draw(ck, u, m, 0u).a(), n_nodes);
+}
+
+template <typename StageT> __global__ __launch_bounds__(64) void rws_lds_kernel(const SkipgramParams p) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    int64_t *base = reinterpret_cast<int64_t *>(smem); // [64] element offset of walker's window-0 row in `out`
+    StageT *stage = reinterpret_cast<StageT *>(smem + RWS_TABLE_BYTES);
+    const int lane = threadIdx.x;
+    const bool neg = (int64_t)blockIdx.x >= p.pos_blocks; // uniform
+    const int64_t per = neg ? p.U : p.W, total = neg ? p.n_neg : p.n_pos;
+    int64_t *__restrict__ out = neg ? p.neg : p.pos;
+    const int64_t t0 = ((int64_t)blockIdx.x - (neg ? p.pos_blocks : 0)) * 64, t = t0 + lane;
+    const bool live = t < total;
+    const int64_t gi = live ? t / per : 0, w = live ? t - gi * per : 0;
+    const int L = p.L, C = p.C;
+    StageT *row = stage + lane * p.pitch;
+    base[lane] = (gi * p.nw * per + w) * C;
+
+    const int64_t first = live ? p.seeds[gi * p.B + w % p.B] : -1;
+    row[0] = (StageT)first;
+    if (!neg) {
+        const CallKey ck = call_key(p.seed, p.call_id + (uint64_t)gi, TAG_RW);
+        const bool always_accept = p.pr.always_accept();
+        int64_t prev = -1, cur = first;
+        bool dead = !live;
+        for (int col = 1; col < L; ++col) { // column col is step col - 1
+            int64_t val = -1;
+            if (!dead) {
+                if (walk_step(p.g, ck, (uint64_t)w, (uint32_t)(col - 1), p.pr, always_accept, prev, cur))
+                    val = cur;
+                else
+                    dead = true;
+            }
+            row[col] = (StageT)val; // -1 -> all ones
+        }
+    } else {
+        const CallKey ck = call_key(p.seed, p.call_id + (uint64_t)gi, TAG_RW_NEG);
+        for (int m = 1; m < L; ++m) row[m] = live ? (StageT)negative_value(ck, (uint64_t)w, (uint32_t)m, p.n_nodes) : (StageT)-1;
+    }
+    wave_lds_handoff();
+    // emit: element q of a window's run is column q % C of walker q / C; lanes step by 64 elements without dividing
+    const int n_el = 64 * C, dw = 64 / C, dc = 64 % C;
+    const int w_first = lane / C, c_first = lane - w_first * C;
+    const int64_t win_stride = per * C;
+    for (int j = 0; j < p.nw; ++j) {
+        int wl = w_first, c = c_first;
+        for (int q = lane; q < n_el; q += 64) {
+            if (t0 + wl < total) {
+                const StageT v = stage[wl * p.pitch + j + c];
+                out[base[wl] + j * win_stride + c] = v == (StageT)-1 ? (int64_t)-1 : (int64_t)v;
+            }
+            c += dc;
+            wl += dw;
+            if (c >= C) {
+                c -= C;
+                ++wl;
+            }
+        }
+    }
+}
+
+// flat form, kernel 1: rw_node2vec_kernel with the mini-batch dimension; one wavefront per workgroup
+__global__ __launch_bounds__(64) void rws_walk_kernel(const SkipgramParams p) {
+    __shared__ int64_t stage[64 * (RWS_STAGE + 1)]; // [walker * 17 + step]: odd pitch spreads LDS banks
+    const int lane = threadIdx.x;
+    const int64_t t0 = (int64_t)blockIdx.x * 64, t = t0 + lane;
+    const bool live = t < p.n_pos;
+    const int64_t gi = live ? t / p.W : 0, w = live ? t - gi * p.W : 0;
+    const CallKey ck = call_key(p.seed, p.call_id + (uint64_t)gi, TAG_RW);
+    const bool always_accept = p.pr.always_accept();
+    const int64_t L = p.L;
+    int64_t prev = -1, cur = live ? p.seeds[gi * p.B + w % p.B] : -1;
+    bool dead = !live;
+    for (int64_t c0 = 0; c0 < L; c0 += RWS_STAGE) {
+        const int ncols = (int)min((int64_t)RWS_STAGE, L - c0);
+        for (int j = 0; j < ncols; ++j) {
+            const int64_t col = c0 + j;
+            int64_t val = -1;
+            if (col == 0) {
+                val = cur;
+            } else if (!dead) {
+                if (walk_step(p.g, ck, (uint64_t)w, (uint32_t)(col - 1), p.pr, always_accept, prev, cur))
+                    val = cur;
+                else
+                    dead = true;
+            }
+            stage[lane * (RWS_STAGE + 1) + j] = val;
+        }
+        wave_lds_handoff();
+        const int n_el = 64 * ncols;
+        for (int q = lane; q < n_el; q += 64) {
+            const int wl = q / ncols, j = q - wl * ncols;
+            if (t0 + wl < p.n_pos) p.walks[(t0 + wl) * L + c0 + j] = stage[wl * (RWS_STAGE + 1) + j];
+        }
+        wave_lds_handoff();
+    }
+}
+
+// flat form, kernel 2: pos[g][j * W + w][c] = walks[g * W + w][j + c], one output word per thread and round
+__global__ void rws_windows_kernel(const SkipgramParams p, int64_t n_words) {
+    const int64_t per_batch = (int64_t)p.nw * p.W * p.C, per_window = p.W * p.C;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t gi = i / per_batch, r = i - gi * per_batch;
+        const int64_t j = r / per_window, r2 = r - j * per_window;
+        const int64_t w = r2 / p.C, c = r2 - w * p.C;
+        p.pos[i] = p.walks[(gi * p.W + w) * p.L + j + c];
+    }
+}
+
+// flat form, kernel 3: neg[g][j * U + u][c] = x_u[j + c]
+__global__ void rws_negatives_kernel(const SkipgramParams p, int64_t n_words) {
+    const int64_t per_batch = (int64_t)p.nw * p.U * p.C, per_window = p.U * p.C;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t gi = i / per_batch, r = i - gi * per_batch;
+        const int64_t j = r / per_window, r2 = r - j * per_window;
+        const int64_t u = r2 / p.C, c = r2 - u * p.C;
+        const int64_t m = j + c;
+        p.neg[i] = m == 0 ? p.seeds[gi * p.B + u % p.B]
+                          : negative_value(call_key(p.seed, p.call_id + (uint64_t)gi, TAG_RW_NEG), (uint64_t)u, (uint32_t)m, p.n_nodes);
+    }
+}
+
+// ---- host side: the plan ------------------------------------------------------------------------------------------------
+struct RwsPlan {
+    int64_t L, nw, pitch;
+    int64_t lds_u32, lds_i64;
+};
+constexpr int64_t RWS_MAX = (int64_t)1 << 40; // every product below stays far inside int64
+
+static int rws_plan(const tg_rw_skipgram_config *cfg, const char *who, RwsPlan &pl) {
+    TG_REQUIRE(cfg, "%s: null config", who);
+    TG_REQUIRE(cfg->walk_length >= 1 && cfg->walk_length < 0x7fffffff, "%s: walk_length = %lld outside [1, 2^31 - 1)", who,
+               (long long)cfg->walk_length);
+    pl.L = cfg->walk_length + 1;
+    TG_REQUIRE(cfg->context_size >= 1 && cfg->context_size <= pl.L, "%s: context_size = %lld outside [1, walk_length + 1 = %lld]",
+               who, (long long)cfg->context_size, (long long)pl.L);
+    TG_REQUIRE(cfg->walks_per_node >= 1 && cfg->walks_per_node < RWS_MAX, "%s: walks_per_node = %lld, must be >= 1", who,
+               (long long)cfg->walks_per_node);
+    TG_REQUIRE(cfg->num_negative_samples >= 0 && cfg->num_negative_samples < RWS_MAX,
+               "%s: num_negative_samples = %lld, must be >= 0", who, (long long)cfg->num_negative_samples);
+    TG_REQUIRE(cfg->num_negative_samples == 0 || cfg->n_nodes >= 1, "%s: n_nodes = %lld, negatives need n_nodes >= 1", who,
+               (long long)cfg->n_nodes);
+    TG_REQUIRE(cfg->p > 0.0f && cfg->q > 0.0f, "%s: p and q must be positive (random_walk.rs:29-30)", who);
+    pl.nw = pl.L - cfg->context_size + 1;
+    pl.pitch = pl.L | 1;
+    pl.lds_u32 = 64 * pl.pitch * 4 + RWS_TABLE_BYTES;
+    pl.lds_i64 = 64 * pl.pitch * 8 + RWS_TABLE_BYTES;
+    return TG_OK;
+}
+static int rws_auto_form(const RwsPlan &pl, int64_t id_bound, int64_t limit) {
+    if (id_bound < (int64_t)0xffffffff && pl.lds_u32 <= limit) return 1;
+    if (pl.lds_i64 <= limit) return 2;
+    return 3;
+}
+// per mini-batch walkers and the launch's totals; refuses sizes whose products would leave int64 or the grid
+static int rws_sizes(const tg_rw_skipgram_config *cfg, const RwsPlan &pl, int64_t G, int64_t B, const char *who, int64_t &W,
+                     int64_t &U) {
+    TG_REQUIRE(G >= 0 && B >= 0 && G < RWS_MAX && B < RWS_MAX, "%s: n_batches = %lld, batch_size = %lld: bad sizes", who,
+               (long long)G, (long long)B);
+    const __int128 w = (__int128)cfg->walks_per_node * B, u = w * cfg->num_negative_samples;
+    const __int128 widest = (__int128)pl.nw * cfg->context_size > pl.L ? (__int128)pl.nw * cfg->context_size : (__int128)pl.L;
+    const __int128 words = (w + u) * (G > 0 ? G : 1) * widest; // >= every slab's words
+    TG_REQUIRE(words < ((__int128)1 << 59), "%s: a launch of %lld x %lld seeds is too large", who, (long long)G, (long long)B);
+    W = (int64_t)w;
+    U = (int64_t)u;
+    return TG_OK;
+}
+
+} // namespace tg
+
+extern "C" int tg_rw_skipgram_capacity(const tg_rw_skipgram_config *cfg, int64_t batch_size, int64_t *pos_rows,
+                                       int64_t *neg_rows) {
+    using namespace tg;
+    const char *who = "tg_rw_skipgram_capacity";
+    TG_REQUIRE(pos_rows && neg_rows, "%s: null output", who);
+    RwsPlan pl;
+    if (const int rc = rws_plan(cfg, who, pl)) return rc;
+    int64_t W, U;
+    if (const int rc = rws_sizes(cfg, pl, 1, batch_size, who, W, U)) return rc;
+    *pos_rows = pl.nw * W;
+    *neg_rows = pl.nw * U;
+    return TG_OK;
+}
+
+extern "C" int tg_rw_skipgram_form(const tg_rw_skipgram_config *cfg, int64_t id_bound, int64_t lds_limit_bytes, int32_t *form,
+                                   int64_t *lds_bytes) {
+    using namespace tg;
+    const char *who = "tg_rw_skipgram_form";
+    TG_REQUIRE(form && lds_bytes, "%s: null output", who);
+    TG_REQUIRE(id_bound >= 0, "%s: id_bound = %lld", who, (long long)id_bound);
+    RwsPlan pl;
+    if (const int rc = rws_plan(cfg, who, pl)) return rc;
+    *form = rws_auto_form(pl, id_bound, lds_limit_bytes > 0 ? lds_limit_bytes : RWS_LDS_LIMIT);
+    *lds_bytes = id_bound < (int64_t)0xffffffff ? pl.lds_u32 : pl.lds_i64;
+    return TG_OK;
+}
+
+extern "C" int tg_rw_skipgram_workspace_bytes(const tg_rw_skipgram_config *cfg, int64_t n_batches, int64_t batch_size,
+                                              int64_t id_bound, int32_t form, int64_t *bytes) {
+    using namespace tg;
+    const char *who = "tg_rw_skipgram_workspace_bytes";
+    TG_REQUIRE(bytes, "%s: null output", who);
+    TG_REQUIRE(form >= 0 && form <= 3, "%s: form = %d outside [0, 3]", who, (int)form);
+    TG_REQUIRE(id_bound >= 0, "%s: id_bound = %lld", who, (long long)id_bound);
+    RwsPlan pl;
+    if (const int rc = rws_plan(cfg, who, pl)) return rc;
+    int64_t W, U;
+    if (const int rc = rws_sizes(cfg, pl, n_batches, batch_size, who, W, U)) return rc;
+    if (form == 0) form = rws_auto_form(pl, id_bound, RWS_LDS_LIMIT);
+    *bytes = form == 3 ? n_batches * W * pl.L * 8 : 0;
+    return TG_OK;
+}
+
+extern "C" int tg_rw_skipgram(const tg_graph *csr, const void *edge_set, int64_t edge_set_bytes, const int64_t *seeds,
+                              int64_t n_batches, int64_t batch_size, const tg_rw_skipgram_config *cfg, const tg_rng *rng,
+                              const tg_rw_skipgram_out *out, void *workspace, int64_t workspace_bytes, int32_t form,
+                              void *stream_) {
+    using namespace tg;
+    const char *who = "tg_rw_skipgram";
+    RwsPlan pl;
+    if (const int rc = rws_plan(cfg, who, pl)) return rc;
+    TG_REQUIRE(form >= 0 && form <= 3, "%s: form = %d outside [0, 3]", who, (int)form);
+    TG_REQUIRE(rng, "%s: null rng", who);
+    int64_t W, U;
+    const int64_t G = n_batches, B = batch_size;
+    if (const int rc = rws_sizes(cfg, pl, G, B, who, W, U)) return rc;
+    if (G == 0 || B == 0) return TG_OK;
+    TG_REQUIRE(csr && csr->ptrs && (csr->indices || csr->n_edges == 0), "%s: null graph", who);
+    TG_REQUIRE(seeds && out && out->pos_rw && (out->neg_rw || U == 0), "%s: null buffers", who);
+    uint64_t edge_mask = 0;
+    if (edge_set) {
+        const int64_t cap = edge_set_slots(csr->n_edges);
+        TG_REQUIRE(edge_set_bytes == 8 * cap && csr->n_major < (int64_t)0xffffffff,
+                   "%s: the edge set (%lld bytes) was not built for this graph (%lld bytes)", who, (long long)edge_set_bytes,
+                   (long long)(8 * cap));
+        edge_mask = (uint64_t)(cap - 1);
+    }
+    const int64_t id_bound = csr->n_major > cfg->n_nodes ? csr->n_major : cfg->n_nodes;
+    if (form == 0) form = rws_auto_form(pl, id_bound, RWS_LDS_LIMIT);
+    TG_REQUIRE(form != 1 || (id_bound < (int64_t)0xffffffff && pl.lds_u32 <= RWS_LDS_LIMIT),
+               "%s: form 1: ids below %lld and rows of %lld columns (%lld bytes of LDS) do not fit the 32-bit LDS form", who,
+               (long long)id_bound, (long long)pl.L, (long long)pl.lds_u32);
+    TG_REQUIRE(form != 2 || pl.lds_i64 <= RWS_LDS_LIMIT, "%s: form 2: rows of %lld columns (%lld bytes of LDS) do not fit", who,
+               (long long)pl.L, (long long)pl.lds_i64);
+    const int64_t n_pos = G * W, n_neg = G * U;
+    const int64_t pos_blocks = (n_pos + 63) / 64, neg_blocks = (n_neg + 63) / 64;
+    TG_REQUIRE(pos_blocks + neg_blocks <= 0x7fffffff, "%s: %lld walkers are more than one launch takes", who,
+               (long long)(n_pos + n_neg));
+    if (form == 3) {
+        const int64_t need = n_pos * pl.L * 8;
+        TG_REQUIRE(workspace && workspace_bytes >= need, "%s: the flat form needs a workspace of %lld bytes, %lld given", who,
+                   (long long)need, (long long)(workspace ? workspace_bytes : 0));
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    SkipgramParams p;
+    p.g = CsrView{csr->ptrs, csr->indices, csr->ptrs32, csr->indices32, reinterpret_cast<const uint64_t *>(edge_set), edge_mask};
+    p.seeds = seeds;
+    p.B = B, p.W = W, p.U = U, p.n_pos = n_pos, p.n_neg = n_neg, p.pos_blocks = pos_blocks;
+    p.L = (int32_t)pl.L, p.C = (int32_t)cfg->context_size, p.nw = (int32_t)pl.nw, p.pitch = (int32_t)pl.pitch;
+    p.pr = walk_probs(cfg->p, cfg->q);
+    p.seed = rng->seed, p.call_id = rng->call_id, p.n_nodes = (uint64_t)cfg->n_nodes;
+    p.pos = out->pos_rw, p.neg = out->neg_rw, p.walks = reinterpret_cast<int64_t *>(workspace);
+    if (form == 1)
+        hipLaunchKernelGGL(rws_lds_kernel<uint32_t>, dim3((unsigned)(pos_blocks + neg_blocks)), dim3(64), (size_t)pl.lds_u32,
+                           stream, p);
+    else if (form == 2)
+        hipLaunchKernelGGL(rws_lds_kernel<int64_t>, dim3((unsigned)(pos_blocks + neg_blocks)), dim3(64), (size_t)pl.lds_i64,
+                           stream, p);
+    else {
+        hipLaunchKernelGGL(rws_walk_kernel, dim3((unsigned)pos_blocks), dim3(64), 0, stream, p);
+        const int64_t pos_words = n_pos * pl.nw * p.C, neg_words = n_neg * pl.nw * p.C;
+        hipLaunchKernelGGL(rws_windows_kernel, dim3(grid_1d(pos_words)), dim3(256), 0, stream, p, pos_words);
+        if (neg_words > 0)
+            hipLaunchKernelGGL(rws_negatives_kernel, dim3(grid_1d(neg_words)), dim3(256), 0, stream, p, neg_words);
+    }
+    TG_LAUNCH_CHECK();
+    return TG_OK;
+}

@@ -37,7 +37,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_budget_sample_batched", "tg_neg_batched_capacity", "tg_neg_batched_form", "tg_neg_batched_workspace_bytes",
            "tg_neg_sample_batched", "tg_ns_homo_unique_form", "tg_ns_homo_unique_workspace_bytes", "tg_ns_homo_unique",
            "tg_ns_typed_unique_form", "tg_ns_typed_unique_workspace_bytes", "tg_ns_typed_unique",
-           "tg_ns_induced_workspace_bytes", "tg_ns_induced_count", "tg_ns_induced_emit"]
+           "tg_ns_induced_workspace_bytes", "tg_ns_induced_count", "tg_ns_induced_emit", "tg_rw_skipgram_capacity",
+           "tg_rw_skipgram_form", "tg_rw_skipgram_workspace_bytes", "tg_rw_skipgram"]
 
 
 class TgGraph(C.Structure):
@@ -350,6 +351,81 @@ def random_walk(graph, start, walk_length, p, q, seed, call_id, edge_set=None):
                                     C.c_int64(start.numel()), C.c_int64(walk_length), C.c_float(p), C.c_float(q),
                                     C.byref(rng), ptr(walks), stream_ptr(start.device)))
     return walks
+
+
+class TgRwSkipgramConfig(C.Structure):
+    _fields_ = [("walk_length", C.c_int64), ("context_size", C.c_int64), ("walks_per_node", C.c_int64),
+                ("num_negative_samples", C.c_int64), ("n_nodes", C.c_int64), ("p", C.c_float), ("q", C.c_float)]
+
+
+class TgRwSkipgramOut(C.Structure):
+    _fields_ = [("pos_rw", C.c_void_p), ("neg_rw", C.c_void_p)]
+
+
+RW_SKIPGRAM_AUTO, RW_SKIPGRAM_LDS32, RW_SKIPGRAM_LDS64, RW_SKIPGRAM_FLAT = 0, 1, 2, 3   # tg_rw_skipgram's `form`
+
+
+def rw_skipgram_config(walk_length, context_size, walks_per_node=1, num_negative_samples=1, n_nodes=0, p=1.0, q=1.0):
+    return TgRwSkipgramConfig(int(walk_length), int(context_size), int(walks_per_node), int(num_negative_samples),
+                              int(n_nodes), float(p), float(q))
+
+
+def rw_skipgram_capacity(cfg, batch_size):
+    """-> (rows of pos_rw, rows of neg_rw) per mini-batch of batch_size seeds: nw * R * B and nw * R * K * B."""
+    pos, neg = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_rw_skipgram_capacity(C.byref(cfg), C.c_int64(batch_size), C.byref(pos), C.byref(neg)))
+    return pos.value, neg.value
+
+
+def rw_skipgram_form(cfg, id_bound, lds_limit_bytes=0):
+    """-> (form, lds_bytes): the form an auto tg_rw_skipgram call takes for ids in [0, id_bound) (1 = rows staged in LDS as
+    uint32, 2 = as int64, 3 = flat through a workspace) and the LDS a workgroup of the LDS form asks for.  lds_limit_bytes
+    > 0 replaces the library's limit.  No device is touched."""
+    form, nbytes = C.c_int32(-1), C.c_int64(0)
+    check(lib.tg_rw_skipgram_form(C.byref(cfg), C.c_int64(id_bound), C.c_int64(lds_limit_bytes), C.byref(form),
+                                  C.byref(nbytes)))
+    return form.value, nbytes.value
+
+
+def rw_skipgram_workspace_bytes(cfg, n_batches, batch_size, id_bound, form=0):
+    """The workspace a launch of n_batches x batch_size seeds needs in this form (0: the one auto takes): 0 for the LDS
+    forms, the [G * W, L] int64 walks for the flat form."""
+    nbytes = C.c_int64(-1)
+    check(lib.tg_rw_skipgram_workspace_bytes(C.byref(cfg), C.c_int64(n_batches), C.c_int64(batch_size), C.c_int64(id_bound),
+                                             C.c_int32(form), C.byref(nbytes)))
+    return nbytes.value
+
+
+def rw_skipgram(graph, seeds, walk_length, context_size, walks_per_node, num_negative_samples, p, q, seed, call_id, n_nodes,
+                edge_set=None, form=0, ws=None, out=None):
+    """Node2Vec skip-gram batches (tg_rw_skipgram) of the G mini-batches seeds[G, B] in one launch on the current stream:
+    -> (pos_rw [G, nw * R * B, C], neg_rw [G, nw * R * K * B, C]); mini-batch g draws with call id call_id + g and is a
+    free view.  Dead ends keep their -1 padding: mask with (pos_rw >= 0).all(-1).  form: 0 auto, 1 / 2 LDS (uint32 /
+    int64 staging), 3 flat; ws: the flat form's workspace, allocated here when needed and not given; out: (pos_rw,
+    neg_rw) of an earlier call of the same shape, reused."""
+    if seeds.dim() != 2 or seeds.dtype != torch.int64 or not seeds.is_contiguous():
+        raise ValueError("rw_skipgram: seeds must be a contiguous int64 [n_batches, batch_size] tensor")
+    G, B = seeds.shape
+    cfg = rw_skipgram_config(walk_length, context_size, walks_per_node, num_negative_samples, n_nodes, p, q)
+    pos_rows, neg_rows = rw_skipgram_capacity(cfg, B)
+    dev = seeds.device
+    if out is None:
+        out = (torch.empty((G, pos_rows, cfg.context_size), dtype=torch.int64, device=dev),
+               torch.empty((G, neg_rows, cfg.context_size), dtype=torch.int64, device=dev))
+    pos, neg = out
+    if tuple(pos.shape) != (G, pos_rows, cfg.context_size) or tuple(neg.shape) != (G, neg_rows, cfg.context_size) \
+            or not (pos.is_contiguous() and neg.is_contiguous()):
+        raise ValueError("rw_skipgram: out does not have this launch's shapes")
+    need = rw_skipgram_workspace_bytes(cfg, G, B, max(graph.n_major, cfg.n_nodes), form)
+    if need and (ws is None or ws.numel() * ws.element_size() < need):
+        ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    o = TgRwSkipgramOut(pos.data_ptr() if pos.numel() else None, neg.data_ptr() if neg.numel() else None)
+    rng = TgRng(seed, call_id)
+    check(lib.tg_rw_skipgram(C.byref(graph), ptr(edge_set), C.c_int64(edge_set.numel() * 8 if edge_set is not None else 0),
+                             ptr(seeds), C.c_int64(G), C.c_int64(B), C.byref(cfg), C.byref(rng), C.byref(o),
+                             ptr(ws) if need else C.c_void_p(0), C.c_int64(ws.numel() * ws.element_size() if need else 0),
+                             C.c_int32(form), stream_ptr(dev)))
+    return pos, neg
 
 
 def tempo_random_walk(graph, node_ts, edge_ts, start, start_ts, walk_length, window, seed, call_id):

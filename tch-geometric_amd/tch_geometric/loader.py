@@ -814,3 +814,113 @@ class NegativeLoader(_TypedLoader):
         if self.hetero:                                             # as the transform: every node type says how many seeds
             for t, nt in enumerate(self.node_types):
                 g[nt].batch_size = n_seeds if t == self._it else 0
+
+
+class SkipGramBatch:
+    """One Node2Vec mini-batch: `pos_rw` [nw * R * B, C] context windows of the walks, `neg_rw` [nw * R * K * B, C] windows
+    of the negative rows (views of the launch's slabs), `batch_size` = B seeds, `call_id`.  A walk that met a dead end is
+    padded with -1, and so are its windows: mask with (pos_rw >= 0).all(1)."""
+    __slots__ = ("pos_rw", "neg_rw", "batch_size", "call_id")
+
+    def __init__(self, pos_rw, neg_rw, batch_size, call_id):
+        self.pos_rw, self.neg_rw, self.batch_size, self.call_id = pos_rw, neg_rw, batch_size, call_id
+
+
+class SkipGramSuperBatch:
+    """The mini-batches of ONE tg_rw_skipgram launch: `pos_rw` [G, nw * R * B, C], `neg_rw` [G, nw * R * K * B, C], batch-major,
+    `batch_size`, `call_id0` (mini-batch g drew with call_id0 + g).  Iterating or indexing yields SkipGramBatch views."""
+    __slots__ = ("pos_rw", "neg_rw", "batch_size", "call_id0")
+
+    def __init__(self, pos_rw, neg_rw, batch_size, call_id0):
+        self.pos_rw, self.neg_rw, self.batch_size, self.call_id0 = pos_rw, neg_rw, batch_size, call_id0
+
+    def __len__(self):
+        return self.pos_rw.shape[0]
+
+    def __getitem__(self, g):
+        if g < 0:
+            g += len(self)
+        if not 0 <= g < len(self):
+            raise IndexError(g)
+        return SkipGramBatch(self.pos_rw[g], self.neg_rw[g], self.batch_size, self.call_id0 + g)
+
+    def __iter__(self):
+        for g in range(len(self)):
+            yield self[g]
+
+
+class Node2VecLoader(_Loader):
+    """Node2Vec training batches (the reference's examples/random_walk.py: positive walks, negative rows, context windows)
+    as a loader: ONE tg_rw_skipgram launch walks `prefetch` mini-batches, cuts every walk into its context windows in LDS
+    and draws the negatives; nothing is read back, so a launch costs the host one call.  `walk_length` counts steps (rows
+    of walk_length + 1 nodes, as random_walk), `context_size` <= walk_length + 1, each seed starts `walks_per_node` walks
+    and `walks_per_node * num_negative_samples` negative rows.  Windows of a walk that met a dead end carry its -1 padding.
+
+    The CSR is built once, on first use; so is the edge set that answers has_edge in one probe, when p, q make the
+    acceptance probabilities differ and the ids fit its 32-bit halves.  Mini-batch j of epoch e equals _cabi.rw_skipgram
+    for (seed, call_id0 + e * len(loader) + j); the ragged last mini-batch is a launch of its own.  A launch's device
+    memory is prefetch x (the two slabs + the flat form's workspace of one mini-batch): prefetch is clamped to keep it
+    within `max_workspace_bytes` (at least one mini-batch per launch).  `form` is tg_rw_skipgram's (0 auto)."""
+
+    def __init__(self, data, walk_length: int, context_size: int, walks_per_node: int = 1, num_negative_samples: int = 1,
+                 p: float = 1.0, q: float = 1.0, input_nodes: Optional[Tensor] = None, batch_size: int = 128,
+                 prefetch: int = 256, drop_last: bool = False, seed: int = 0, call_id0: int = 0,
+                 max_workspace_bytes: int = 4 << 30, device="cuda", form: int = 0):
+        self.data, self.device = data, torch.device(device)
+        self.n_nodes = _num_nodes(data)
+        self.p, self.q = float(p), float(q)
+        # refuses a bad shape here, on the host (C > L, R < 1, K < 0, ...)
+        self.cfg = _cabi.rw_skipgram_config(walk_length, context_size, walks_per_node, num_negative_samples, self.n_nodes,
+                                            self.p, self.q)
+        self.batch_size, self.drop_last, self.seed, self.call_id0 = int(batch_size), drop_last, int(seed), int(call_id0)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.form = int(form)
+        nodes = torch.arange(self.n_nodes) if input_nodes is None else input_nodes
+        self.input_nodes = _checked_inputs(nodes, self.n_nodes)
+        pos_rows, neg_rows = _cabi.rw_skipgram_capacity(self.cfg, self.batch_size)
+        per_call = (pos_rows + neg_rows) * self.cfg.context_size * 8 + \
+            _cabi.rw_skipgram_workspace_bytes(self.cfg, 1, self.batch_size, self.n_nodes, self.form)
+        self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // max(per_call, 1)))
+        self._graph = self._edge_set = self._ws = None
+        self.epoch = 0
+
+    def plan(self, epoch: int):
+        """The launches of an epoch: [(start, n_batches, batch_width, first call id)] over input_nodes."""
+        batch0 = epoch * len(self)
+        return [(start, G, width, self.call_id0 + batch0 + start // self.batch_size)
+                for start, G, width in _epoch_plan(self.input_nodes.numel(), self.batch_size, self.prefetch, self.drop_last)]
+
+    def _prepare(self):
+        if self._graph is not None:
+            return
+        self.input_nodes = self.input_nodes.to(self.device)
+        self.row_ptrs, self.col_indices, _ = _host.to_csr(self.data.edge_index.to(self.device), self.n_nodes)
+        small = self.n_nodes < 2 ** 31 and self.col_indices.numel() < 2 ** 31
+        self._graph = _cabi.graph_view(self.row_ptrs, self.col_indices,
+                                       indices32=self.col_indices.to(torch.int32) if small else None,
+                                       ptrs32=self.row_ptrs.to(torch.int32) if small else None)
+        if not (self.p == 1.0 and self.q == 1.0) and self.n_nodes < 2 ** 32 - 1:
+            self._edge_set = _cabi.edge_set(self._graph, self.device)
+
+    def _launch(self, seeds: Tensor, call_id: int) -> SkipGramSuperBatch:
+        c = self.cfg
+        need = _cabi.rw_skipgram_workspace_bytes(c, seeds.shape[0], seeds.shape[1], self.n_nodes, self.form)
+        if need and (self._ws is None or self._ws.numel() * 8 < need):
+            self._ws = torch.empty(need // 8, dtype=torch.int64, device=self.device)
+        pos, neg = _cabi.rw_skipgram(self._graph, seeds, c.walk_length, c.context_size, c.walks_per_node,
+                                     c.num_negative_samples, self.p, self.q, self.seed, call_id, self.n_nodes,
+                                     edge_set=self._edge_set, form=self.form, ws=self._ws)
+        return SkipGramSuperBatch(pos, neg, seeds.shape[1], call_id)
+
+    def super_batches(self) -> Iterator[SkipGramSuperBatch]:
+        """The epoch launch by launch: the [G, rows, C] slabs of up to `prefetch` mini-batches."""
+        self._prepare()
+        launches = self.plan(self.epoch)                             # fresh draws every epoch (see NeighborLoader)
+        self.epoch += 1
+        for start, G, width, call_id in launches:
+            yield self._launch(self.input_nodes[start:start + G * width].reshape(G, width).contiguous(), call_id)
+
+    def __iter__(self) -> Iterator[SkipGramBatch]:
+        for sb in self.super_batches():
+            yield from sb

@@ -15,7 +15,11 @@ behind it, not inside it: transforms.unique_nodes(samples, rows, cols) -> (nodes
 (tg_ns_homo_unique, csrc/ns_unique.hip), loader.NeighborLoader(..., unique=True) for mini-batches.  Likewise per node
 type for neighbor_sampling_heterogenous: transforms.unique_nodes_hetero(samples, rows, cols, edge_types, num_nodes=None)
 -> (nodes, rows_u, cols_u, inverse) dicts (tg_ns_typed_unique, csrc/ns_unique_typed.hip),
-loader.HeteroNeighborLoader(..., unique=True) for mini-batches."""
+loader.HeteroNeighborLoader(..., unique=True) for mini-batches.
+
+random_walk returns the [n, walk_length + 1] walks of one call.  Node2Vec training batches -- the walks cut into context
+windows plus negative rows, many mini-batches per launch -- come from Node2VecLoader (exported by the package;
+tg_rw_skipgram, csrc/rw_skipgram.hip): it yields objects with pos_rw [rows, context_size], neg_rw, batch_size, call_id."""
 from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor
