@@ -109,7 +109,22 @@ typedef struct {
     int64_t *states;
     int64_t cap_nodes; /* >= tg_ns_homo_capacity() */
     int64_t cap_edges;
+    /* rows[e] = n_seeds + e whatever was sampled: for a given n_seeds the `rows` slab of every batch is the same arange in
+     * every launch.  0 = off.  1 + n_seeds = the caller states that rows[b*cap_edges + e] == n_seeds + e for EVERY
+     * e < cap_edges of every batch (tg_ns_rows_fill writes that); a launch whose own n_seeds matches MAY then leave `rows`
+     * unwritten.  The unfiltered, unweighted tg_ns_homo_batched / _ws launches do (the fused per-batch kernel and both
+     * pipelines of the window-ordered form: 8 of the 32 bytes written per sampled edge); the weighted / filtered samplers
+     * and the partitioned emit passes ignore the field and write `rows`, which is always correct.  A launch with another
+     * n_seeds writes `rows` as with 0 -- the slab then no longer holds what the field states, and the caller clears it.
+     * Readers of `rows` (tg_ns_homo_compact, tg_ns_homo_unique, tg_ns_induced_*, the partitioned protocol) never look at
+     * the field: the pointer is always valid and always holds the values.  Whoever overwrites `rows` (tg_ns_homo_unique
+     * with an in-place result) ends the statement: pass 0 from then on.  Zero-initialise the struct (tg_ns_out o = {0}). */
+    int64_t rows_prefilled;
 } tg_ns_out;
+
+/* rows[b*cap_edges + e] = n_seeds + e for e < cap_edges, b < n_batches: what tg_ns_out.rows_prefilled = 1 + n_seeds
+ * states.  One streaming pass, once per slab (not per launch).  `rows` 8-byte aligned.  Stream-ordered. */
+TG_API int tg_ns_rows_fill(int64_t *rows, int64_t n_batches, int64_t cap_edges, int64_t n_seeds, void *stream);
 
 /* *max_degree_dev (device int64) = the longest column of `g` (reads ptrs32 when given, else ptrs).  Stream-ordered. */
 TG_API int tg_graph_max_degree(const tg_graph *g, int64_t *max_degree_dev, void *stream);

@@ -22,7 +22,10 @@
 //           fully coalesced.
 // Algorithmic HBM bytes per hop (F frontier slots, S sampled edges):
 //   reads 8F (frontier id) + 16F (ptrs pair) + 8S (gather), writes 32S.
+#include <stdint.h>
 #include <stdlib.h>
+
+#include <algorithm>
 
 #include "ns_tickets.h"
 #include "tg_device.h"
@@ -73,8 +76,8 @@ constexpr int NS_EMIT = 4; // gathers per lane and batch of the emit loop (two b
 template <typename IDX, bool NT>
 __device__ __forceinline__ void emit_chunk(const IDX *__restrict__ idx, uint32_t total, int lane, const uint8_t *slane,
                                            const uint32_t *spos, const int64_t *ebase, int64_t e_chunk, int64_t i0,
-                                           int64_t n_seeds, int64_t *samples, int64_t *rows, int64_t *cols,
-                                           int64_t *eidx) {
+                                           int64_t n_seeds, int64_t *samples, int64_t *rows_base, int64_t rows_at,
+                                           int64_t *cols, int64_t *eidx) {
     if (total == 0) return;
     struct Batch {
         int l[NS_EMIT];
@@ -100,11 +103,11 @@ __device__ __forceinline__ void emit_chunk(const IDX *__restrict__ idx, uint32_t
                 const int64_t e = e_chunk + q;
                 samples[n_seeds + e] = (int64_t)t.v[u]; // :215 (re-read as the next hop's frontier: keep it cacheable)
                 if (NT) { // write-once outputs: stream them past L2 so gathers keep the cache
-                    __builtin_nontemporal_store(n_seeds + e, &rows[e]);          // :217 j
+                    if (rows_base) __builtin_nontemporal_store(n_seeds + e, &rows_base[rows_at + e]); // :217 j  (null: prefilled)
                     __builtin_nontemporal_store(i0 + (int64_t)t.l[u], &cols[e]); // :217 i
                     __builtin_nontemporal_store(t.ep[u], &eidx[e]);              // :217 edge_ptr
                 } else {
-                    rows[e] = n_seeds + e;
+                    if (rows_base) rows_base[rows_at + e] = n_seeds + e;
                     cols[e] = i0 + (int64_t)t.l[u];
                     eidx[e] = t.ep[u];
                 }
@@ -138,7 +141,7 @@ __global__ void ns_homo_uniform_kernel(const NsHomoParams p) {
     (void)strip;
 
     int64_t *samples = p.samples + b * p.cap_nodes;
-    int64_t *rows = p.rows + b * p.cap_edges;
+    // p.rows == nullptr (wave-uniform): tg_ns_out.rows_prefilled matched; no per-batch pointer is formed from it
     int64_t *cols = p.cols + b * p.cap_edges;
     int64_t *eidx = p.edge_index + b * p.cap_edges;
     const int64_t n_seeds = p.n_seeds;
@@ -232,10 +235,10 @@ __global__ void ns_homo_uniform_kernel(const NsHomoParams p) {
                 const int64_t e_chunk = ne + (int64_t)chunk_off[c];
                 if (p.indices32)
                     emit_chunk<uint32_t, NT>(p.indices32, total, lane, slane, spos, ebase, e_chunk, i0, n_seeds, samples,
-                                             rows, cols, eidx);
+                                             p.rows, b * p.cap_edges, cols, eidx);
                 else
-                    emit_chunk<int64_t, NT>(p.indices, total, lane, slane, spos, ebase, e_chunk, i0, n_seeds, samples, rows,
-                                            cols, eidx);
+                    emit_chunk<int64_t, NT>(p.indices, total, lane, slane, spos, ebase, e_chunk, i0, n_seeds, samples,
+                                            p.rows, b * p.cap_edges, cols, eidx);
                 wave_lds_handoff();
             }
             __syncthreads();
@@ -248,6 +251,30 @@ __global__ void ns_homo_uniform_kernel(const NsHomoParams p) {
     if (tid == 0) {
         p.counts[b * 2 + 0] = n_seeds + ne;
         p.counts[b * 2 + 1] = ne;
+    }
+}
+
+// ---------------------------------------------------------------- rows of a slab, once: rows[b][e] = n_seeds + e
+// Thread t owns the elements {2t, 2t + 1} of the flat slab counted from its first 16-byte boundary; the element before the
+// boundary and the one a pair would carry past the end are stored alone.
+__global__ void __launch_bounds__(256) ns_rows_fill_kernel(int64_t *__restrict__ rows, const int64_t total,
+                                                           const int64_t cap_edges, const int64_t n_seeds,
+                                                           const int64_t head) {
+    typedef long long i64x2 __attribute__((ext_vector_type(2)));
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x * 2;
+    int64_t i = head + ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (head && blockIdx.x == 0 && threadIdx.x == 0) rows[0] = n_seeds;
+    int64_t e = i % cap_edges; // one division per thread: the loop keeps e = i mod cap_edges by subtraction
+    const int64_t step = stride % cap_edges;
+    for (; i < total; i += stride) {
+        const int64_t e1 = e + 1 == cap_edges ? 0 : e + 1;
+        if (i + 1 < total) {
+            i64x2 v = {n_seeds + e, n_seeds + e1};
+            __builtin_nontemporal_store(v, reinterpret_cast<i64x2 *>(rows + i));
+        } else
+            __builtin_nontemporal_store(n_seeds + e, rows + i);
+        e += step;
+        if (e >= cap_edges) e -= cap_edges;
     }
 }
 
@@ -298,6 +325,22 @@ extern "C" int tg_ns_homo_capacity(int64_t n_seeds, const int64_t *fanout, int32
     }
     if (cap_nodes) *cap_nodes = n_seeds + edges;
     if (cap_edges) *cap_edges = edges;
+    return TG_OK;
+}
+
+extern "C" int tg_ns_rows_fill(int64_t *rows, int64_t n_batches, int64_t cap_edges, int64_t n_seeds, void *stream) {
+    TG_REQUIRE(rows, "tg_ns_rows_fill: null rows");
+    TG_REQUIRE(n_batches >= 0 && cap_edges >= 0 && n_seeds >= 0, "tg_ns_rows_fill: negative sizes");
+    TG_REQUIRE(((uintptr_t)rows & 7u) == 0, "tg_ns_rows_fill: rows must be 8-byte aligned");
+    TG_REQUIRE(cap_edges == 0 || n_batches <= INT64_MAX / 8 / cap_edges, "tg_ns_rows_fill: slab size overflows int64");
+    const int64_t total = n_batches * cap_edges;
+    if (total == 0) return TG_OK;
+    const int64_t head = (int64_t)(((uintptr_t)rows >> 3) & 1u); // elements before the first 16-byte boundary
+    const int64_t pairs = (total - head + 1) / 2;
+    const int64_t blocks = std::min<int64_t>((pairs + 255) / 256, 256 * 64); // grid-stride: >= 1 (the head), 64 per CU at most
+    hipLaunchKernelGGL(tg::ns_rows_fill_kernel, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0,
+                       (hipStream_t)stream, rows, total, cap_edges, n_seeds, head);
+    TG_LAUNCH_CHECK();
     return TG_OK;
 }
 
@@ -374,7 +417,7 @@ static int ns_homo_batched_impl(const tg_graph *csc, const int64_t *seeds, int64
     p.cap_nodes = out->cap_nodes;
     p.cap_edges = out->cap_edges;
     p.samples = out->samples;
-    p.rows = out->rows;
+    p.rows = tg::ns_rows_prefilled(out, n_seeds) ? nullptr : out->rows; // the slab already holds this launch's rows
     p.cols = out->cols;
     p.edge_index = out->edge_index;
     p.layer_offsets = out->layer_offsets;

@@ -562,7 +562,9 @@ __device__ __forceinline__ void win_stage_emit_batch(const WinParams &p, const S
     uint8_t *slane = reinterpret_cast<uint8_t *>(sptr + (size_t)64 * k);
 
     int64_t *samples = p.samples + b * p.cap_nodes;
-    int64_t *rows = p.rows + b * p.cap_edges;
+    // p.rows == nullptr (wave-uniform): the slab holds rows[e] = n_seeds + e already (tg_ns_out.rows_prefilled) -- no
+    // pointer is formed from it, no head is computed and the stream's stores are branched around
+    const bool put_rows = !SPLIT && p.rows != nullptr;
     int64_t *cols = p.cols + b * p.cap_edges;
     int64_t *eidx = p.edge_index + b * p.cap_edges;
     const int64_t n_seeds = p.n_seeds;
@@ -657,7 +659,9 @@ __device__ __forceinline__ void win_stage_emit_batch(const WinParams &p, const S
             // (tg_ns_win_tuning.store_align64, profiles/r04/ab_store_align64.jsonl)
             const uint32_t am = p.store_align;
             const uint32_t head_s = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(samples + n_seeds + ea) >> 3) & am)) & am);
-            const uint32_t head_r = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(rows + ea) >> 3) & am)) & am);
+            int64_t *rows = put_rows ? p.rows + b * p.cap_edges : nullptr;
+            const uint32_t head_r =
+                put_rows ? (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(rows + ea) >> 3) & am)) & am) : 0u;
             const uint32_t head_c = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(cols + ea) >> 3) & am)) & am);
             const uint32_t head_e = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(eidx + ea) >> 3) & am)) & am);
             if ((uint32_t)lane < total && !SPLIT) {
@@ -675,7 +679,7 @@ __device__ __forceinline__ void win_stage_emit_batch(const WinParams &p, const S
                 } else
                     __builtin_nontemporal_store((int64_t)sval[q], &samples[n_seeds + e]);
             }
-            if (!SPLIT)
+            if (put_rows)
             for (uint32_t q = head_r + 2u * lane; q < total; q += 128) { // :217
                 const int64_t e = ea + q;
                 if (q + 1 < total) {

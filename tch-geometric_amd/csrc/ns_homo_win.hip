@@ -200,7 +200,9 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
     Item *items = static_cast<Item *>(p.items_in);
 
     int64_t *samples = p.samples + b * p.cap_nodes;
-    int64_t *rows = p.rows + b * p.cap_edges;
+    // p.rows == nullptr (a kernel argument: wave-uniform): the slab holds rows[e] = n_seeds + e already
+    // (tg_ns_out.rows_prefilled) -- no pointer is formed from it and the stream's stores are branched around
+    const bool put_rows = p.rows != nullptr;
     int64_t *cols = p.cols + b * p.cap_edges;
     int64_t *eidx = p.edge_index + b * p.cap_edges;
     const int64_t n_seeds = p.n_seeds;
@@ -357,7 +359,7 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                         if (q < total) {
                             const int64_t e = e_chunk + q;
                             samples[n_seeds + e] = v[u]; // :215 (the next hop's frontier)
-                            __builtin_nontemporal_store(n_seeds + e, &rows[e]);
+                            if (put_rows) __builtin_nontemporal_store(n_seeds + e, &p.rows[b * p.cap_edges + e]);
                             __builtin_nontemporal_store(i0 + (int64_t)l4[u], &cols[e]);
                             __builtin_nontemporal_store(ep[u], &eidx[e]);
                             if (NEXT) win_next_item(p, b, (uint32_t)(n_seeds + e - end), (uint32_t)v[u], lhist);
@@ -378,7 +380,9 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                 // its own ADDRESS: with an odd cap_edges the slabs of odd batches start on an odd element, and tg_ns_out
                 // takes four independent 8-byte aligned pointers, so rows / cols / edge_index need not share an alignment
                 const uint32_t am = p.store_align;
-                const uint32_t head_r = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(rows + ea) >> 3) & am)) & am);
+                int64_t *rows = put_rows ? p.rows + b * p.cap_edges : nullptr;
+                const uint32_t head_r =
+                    put_rows ? (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(rows + ea) >> 3) & am)) & am) : 0u;
                 const uint32_t head_c = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(cols + ea) >> 3) & am)) & am);
                 const uint32_t head_e = (uint32_t)((am + 1u - (uint32_t)(((uintptr_t)(eidx + ea) >> 3) & am)) & am);
                 if ((uint32_t)lane < total) {
@@ -387,6 +391,7 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                     if ((uint32_t)lane < head_e)
                         __builtin_nontemporal_store(col0[c * 64 + slane[lane]] + (int64_t)spos[lane], &eidx[ea + lane]);
                 }
+                if (put_rows)
                 for (uint32_t q = head_r + 2u * lane; q < total; q += 128) {
                     const int64_t e = ea + q;
                     if (q + 1 < total) {
@@ -1389,7 +1394,7 @@ int tg_ns_homo_windowed_launch(const tg_graph *csc, const int64_t *seeds, int64_
     p.cap_nodes = out->cap_nodes;
     p.cap_edges = out->cap_edges;
     p.samples = out->samples;
-    p.rows = out->rows;
+    p.rows = ns_rows_prefilled(out, n_seeds) ? nullptr : out->rows; // null: no kernel of the launch stores that stream
     p.cols = out->cols;
     p.edge_index = out->edge_index;
     p.layer_offsets = out->layer_offsets;

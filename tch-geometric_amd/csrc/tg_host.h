@@ -18,6 +18,11 @@ inline int fail(int code, const char *fmt, ...) {
     return code;
 }
 
+// tg_ns_out.rows_prefilled: the slab holds rows[e] = n_seeds + e for THIS launch's n_seeds -> the launch leaves `rows` alone
+inline bool ns_rows_prefilled(const tg_ns_out *out, int64_t n_seeds) {
+    return out->rows_prefilled != 0 && out->rows_prefilled == n_seeds + 1;
+}
+
 } // namespace tg
 
 #define TG_REQUIRE(cond, ...)                                                                                          \

@@ -38,7 +38,7 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_neg_sample_batched", "tg_ns_homo_unique_form", "tg_ns_homo_unique_workspace_bytes", "tg_ns_homo_unique",
            "tg_ns_typed_unique_form", "tg_ns_typed_unique_workspace_bytes", "tg_ns_typed_unique",
            "tg_ns_induced_workspace_bytes", "tg_ns_induced_count", "tg_ns_induced_emit", "tg_rw_skipgram_capacity",
-           "tg_rw_skipgram_form", "tg_rw_skipgram_workspace_bytes", "tg_rw_skipgram"]
+           "tg_rw_skipgram_form", "tg_rw_skipgram_workspace_bytes", "tg_rw_skipgram", "tg_ns_rows_fill"]
 
 
 class TgGraph(C.Structure):
@@ -60,7 +60,7 @@ class TgNsConfig(C.Structure):
 class TgNsOut(C.Structure):
     _fields_ = [("samples", C.c_void_p), ("rows", C.c_void_p), ("cols", C.c_void_p), ("edge_index", C.c_void_p),
                 ("layer_offsets", C.c_void_p), ("counts", C.c_void_p), ("states", C.c_void_p),
-                ("cap_nodes", C.c_int64), ("cap_edges", C.c_int64)]
+                ("cap_nodes", C.c_int64), ("cap_edges", C.c_int64), ("rows_prefilled", C.c_int64)]
 
 
 if not os.path.exists(LIB_PATH):
@@ -170,8 +170,44 @@ def ns_homo_capacity(n_seeds, fanout):
     return cn.value, ce.value
 
 
+_ROWS_MARK = "_tg_rows_prefilled"   # on a `rows` TENSOR: (n_seeds it was filled for, its _version at that moment)
+
+
+def ns_rows_fill(rows, n_seeds):
+    """rows[b, e] = n_seeds + e over the whole slab (tg_ns_rows_fill, current stream), and the mark on the tensor object that
+    lets NsBatchedOut.struct() state tg_ns_out.rows_prefilled: launches with this n_seeds then leave the slab alone.  The
+    mark is on the tensor, not on who holds it: an output object assembled from another's slabs keeps it, a view has none."""
+    assert rows.dtype == torch.int64 and rows.dim() == 2 and rows.is_contiguous()
+    check(lib.tg_ns_rows_fill(ptr(rows), C.c_int64(rows.shape[0]), C.c_int64(rows.shape[1]), C.c_int64(n_seeds),
+                              stream_ptr(rows.device)))
+    try:
+        setattr(rows, _ROWS_MARK, (int(n_seeds), rows._version))
+    except RuntimeError:                      # an inference tensor keeps no version: filled, but nothing is stated about it
+        setattr(rows, _ROWS_MARK, None)
+
+
+def ns_rows_unmark(rows):
+    """Called by whoever writes a `rows` slab through its raw pointer with anything but n_seeds + e (in-place torch writes
+    need not: they bump the tensor's _version, which ends the mark by itself)."""
+    if getattr(rows, _ROWS_MARK, None) is not None:
+        setattr(rows, _ROWS_MARK, None)
+
+
+def _rows_prefilled(rows, n_seeds):
+    """The value of tg_ns_out.rows_prefilled for this tensor and n_seeds: n_seeds + 1 while the mark holds, else 0."""
+    mark = getattr(rows, _ROWS_MARK, None)
+    if mark is None or n_seeds is None:
+        return 0
+    try:
+        version = rows._version
+    except RuntimeError:                      # inference tensors keep no version: nothing can be stated about them
+        return 0
+    return n_seeds + 1 if mark == (n_seeds, version) else 0
+
+
 class NsBatchedOut:
-    """Per-batch output slabs (device) of tg_ns_homo_batched."""
+    """Per-batch output slabs (device) of tg_ns_homo_batched.  `rows` is filled once, here (rows[b, e] = n_seeds + e whatever
+    is sampled), and marked; struct() then sets tg_ns_out.rows_prefilled and the plain launches skip that stream."""
 
     def __init__(self, n_batches, n_seeds, fanout, device, with_states=False):
         self.n_batches, self.n_seeds, self.n_hops = n_batches, n_seeds, len(fanout)
@@ -184,6 +220,8 @@ class NsBatchedOut:
         self.layer_offsets = torch.zeros((n_batches, max(self.n_hops, 1), 3), **o)
         self.counts = torch.zeros((n_batches, 2), **o)
         self.states = torch.empty((n_batches, max(self.cap_nodes, 1)), **o) if with_states else None
+        if self.rows.is_cuda:
+            ns_rows_fill(self.rows, n_seeds)
 
     def struct(self):
         s = TgNsOut()
@@ -192,6 +230,7 @@ class NsBatchedOut:
         s.counts = self.counts.data_ptr()
         s.states = self.states.data_ptr() if self.states is not None else None
         s.cap_nodes, s.cap_edges = self.samples.shape[1], self.rows.shape[1]
+        s.rows_prefilled = _rows_prefilled(self.rows, getattr(self, "n_seeds", None))
         return s
 
     def batch(self, b, counts=None):
@@ -247,6 +286,9 @@ def ns_homo_batched(graph, seeds, fanout, seed, call_id, out, sampler=SAMPLER_UN
     rng = TgRng(seed, call_id)
     fan = (C.c_int64 * max(len(fanout), 1))(*fanout)
     so = out.struct()
+    mark = getattr(out.rows, _ROWS_MARK, None)
+    if mark is not None and mark[0] != seeds.shape[1]:
+        ns_rows_unmark(out.rows)              # a launch with another n_seeds writes ITS rows (n_seeds + e) into the slab
     if ws is not None:
         check(lib.tg_ns_homo_batched_ws(C.byref(graph), ptr(seeds), C.c_int64(seeds.shape[0]),
                                         C.c_int64(seeds.shape[1]), fan, C.c_int32(len(fanout)), C.byref(cfg),
@@ -955,6 +997,8 @@ class NsUniqueOut:
         self.inverse = torch.empty_like(src.samples) if with_inverse else None
         self.rows = src.rows if in_place else torch.empty_like(src.rows)
         self.cols = src.cols if in_place else torch.empty_like(src.cols)
+        if in_place:
+            ns_rows_unmark(src.rows)          # the relabelled rows replace the arange: launches write the slab again
         self.edge_index, self.layer_offsets, self.states = src.edge_index, src.layer_offsets, None
         self.counts = torch.zeros((self.n_batches, 2), **o)
         self.layer_nodes = torch.zeros((self.n_batches, max(self.n_hops, 1)), **o)[:, :self.n_hops]
@@ -981,6 +1025,7 @@ def ns_homo_unique(out, n_batches, id_bound, form=0, ws=None, in_place=False, re
     if ws is None:
         ws = ns_homo_unique_workspace(out.samples.shape[1], id_bound, n_batches, out.samples.device, form)
     si, su = out.struct(), res.unique_struct()
+    ns_rows_unmark(res.rows)                  # written through the raw pointer (under in_place: out's own slab)
     check(lib.tg_ns_homo_unique(C.byref(si), C.c_int64(n_batches), C.c_int64(out.n_seeds), C.c_int32(out.n_hops),
                                 C.c_int64(id_bound), C.byref(su), ptr(ws), C.c_int64(ws.numel() * 8 if ws is not None else 0),
                                 C.c_int32(form), stream_ptr(out.samples.device)))
@@ -1233,6 +1278,7 @@ def probe_ns_sol(src, dst, seeds, n_hops):
     """The algorithmic bytes of the finished launch `src` moved as pure streams into `dst` (tg_probe_ns_sol)."""
     sink = torch.zeros(seeds.shape[0], dtype=torch.int64, device=seeds.device)
     a, b = src.struct(), dst.struct()
+    ns_rows_unmark(dst.rows)                  # the probe copies src's streams over dst's
     check(lib.tg_probe_ns_sol(C.byref(a), C.byref(b), ptr(seeds), C.c_int64(seeds.shape[0]), C.c_int64(seeds.shape[1]),
                               C.c_int32(n_hops), ptr(sink), stream_ptr(seeds.device)))
     return sink
