@@ -594,6 +594,39 @@ TG_API int tg_rw_skipgram(const tg_graph *csr, const void *edge_set, int64_t edg
                           const tg_rw_skipgram_out *out, void *workspace, int64_t workspace_bytes, int32_t form,
                           void *stream);
 
+/* ---- Link-level seed rows: positive edges plus checked negatives of G mini-batches in one launch --------------------------
+ * What a link-prediction trainer composes per mini-batch (randint negatives, cat with the positives), with the negatives
+ * checked against the graph as the reference's negative sampler checks them (negative_sampling.rs: has_edge(v, w) and
+ * v == w are rejected) and addressed, so a row depends on (seed, call id) alone.  The rows feed tg_ns_homo_batched.
+ * csc: the graph the sampler walks (column = target), optionally with ptrs32 / indices32.  edge_set: NULL, or the set
+ * tg_edge_set_build made over THIS csc (key = column << 32 | row; ids < 2^32 - 1).  edge(s -> d) means: s is among
+ * indices[ptrs[d] .. ptrs[d + 1]) -- a binary search of column d, or one probe of the set.
+ * src, dst: device int64 [G, E], the positive edges of n_batches = G mini-batches of n_edges = E each.  K = n_neg >= 0
+ * negatives per positive, try_count >= 1, n_nodes = csc->n_major.  Mini-batch g draws with call id rng->call_id + g:
+ * attempt a of negative u is the draw (call key of (seed, call id + g, TAG_LINK_NEG = 13), id = u, d0 = a, d1 = 0); a
+ * candidate is floor(half * n_nodes / 2^64) of a 64-bit half of it (words 0,1 / words 2,3).
+ *  TG_LINK_BINARY   P = E + K * E pairs, S = 2 P.  seeds[g] = [src_pos(E) | src_neg(K E) | dst_pos(E) | dst_neg(K E)], so
+ *                   seeds[g] viewed as [2, P] is the global edge_label_index.  Attempt a proposes s_a (words 0,1) and d_a
+ *                   (words 2,3); accepted when s_a != d_a and not edge(s_a -> d_a).
+ *  TG_LINK_TRIPLET  S = E * (2 + K), P = E + K * E.  seeds[g] = [src(E) | dst_pos(E) | dst_neg(E K)], negative u = i * K + k
+ *                   belongs to positive i.  Attempt a proposes d_a (words 0,1); accepted when d_a != src[g][i] and not
+ *                   edge(src[g][i] -> d_a).
+ * The first accepted attempt a < try_count is kept.  When none is, the candidate of attempt try_count - 1 is kept and
+ * unverified[g] counts it (the row's shape is fixed: a slot cannot be dropped as the reference drops it).  try_count = 1
+ * makes no look-up: attempt 0 is kept as it is (PyG's unchecked negatives) and unverified[g] = 0.
+ * seeds: device int64 [G, S], contiguous; every word is written and nothing else.  unverified: device int64 [G] (written
+ * for every g) or NULL.  Nothing is read back; the call does not synchronise.  Bad arguments (a null pointer, a negative
+ * size, try_count < 1, an unknown mode, n_nodes < 1 or != csc->n_major, an edge set of another size or with ids >= 2^32 - 1)
+ * are refused with TG_ERR_INVALID before anything is launched; G = 0 or E = 0 returns TG_OK and launches nothing. */
+#define TG_LINK_BINARY 0
+#define TG_LINK_TRIPLET 1
+/* *seeds_per_batch = S and *pairs = P of a mini-batch of n_edges positives with n_neg negatives each */
+TG_API int tg_link_seeds_capacity(int64_t n_edges, int64_t n_neg, int32_t mode, int64_t *seeds_per_batch, int64_t *pairs);
+TG_API int tg_link_seeds(const tg_graph *csc, const void *edge_set, int64_t edge_set_bytes, const int64_t *src,
+                         const int64_t *dst, int64_t n_batches, int64_t n_edges, int64_t n_neg, int32_t mode,
+                         int32_t try_count, const tg_rng *rng, int64_t n_nodes, int64_t *seeds, int64_t *unverified,
+                         void *stream);
+
 /* tempo_random_walk (random_walk.rs:80-158; binding python.rs:611-642).
  * walks, walks_ts: [n, walk_length] device int64. */
 TG_API int tg_tempo_random_walk(const tg_graph *csr, const int64_t *node_ts, const int64_t *edge_ts, const int64_t *start,

@@ -38,7 +38,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_neg_sample_batched", "tg_ns_homo_unique_form", "tg_ns_homo_unique_workspace_bytes", "tg_ns_homo_unique",
            "tg_ns_typed_unique_form", "tg_ns_typed_unique_workspace_bytes", "tg_ns_typed_unique",
            "tg_ns_induced_workspace_bytes", "tg_ns_induced_count", "tg_ns_induced_emit", "tg_rw_skipgram_capacity",
-           "tg_rw_skipgram_form", "tg_rw_skipgram_workspace_bytes", "tg_rw_skipgram", "tg_ns_rows_fill"]
+           "tg_rw_skipgram_form", "tg_rw_skipgram_workspace_bytes", "tg_rw_skipgram", "tg_ns_rows_fill",
+           "tg_link_seeds_capacity", "tg_link_seeds"]
 
 
 class TgGraph(C.Structure):
@@ -468,6 +469,48 @@ def rw_skipgram(graph, seeds, walk_length, context_size, walks_per_node, num_neg
                              ptr(ws) if need else C.c_void_p(0), C.c_int64(ws.numel() * ws.element_size() if need else 0),
                              C.c_int32(form), stream_ptr(dev)))
     return pos, neg
+
+
+LINK_BINARY, LINK_TRIPLET = 0, 1   # tg_link_seeds' `mode`
+
+
+def link_seeds_capacity(n_edges, n_neg, mode=LINK_BINARY):
+    """-> (S, P) of a mini-batch of n_edges positives with n_neg negatives each: seeds per row and (src, dst) pairs."""
+    S, P = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_link_seeds_capacity(C.c_int64(n_edges), C.c_int64(n_neg), C.c_int32(mode), C.byref(S), C.byref(P)))
+    return S.value, P.value
+
+
+def link_seeds(graph, src, dst, K, mode, try_count, seed, call_id, n_nodes, edge_set=None, out=None, unverified=None):
+    """Seed rows of the G mini-batches of positive edges src[G, E] -> dst[G, E] with K checked negatives each
+    (tg_link_seeds), one launch on the current stream, nothing read back: -> (seeds [G, S], unverified [G]).  `graph` is the
+    CSC the sampler walks, `edge_set` the optional set built over it (_cabi.edge_set); mini-batch g draws with call id
+    call_id + g.  mode LINK_BINARY: seeds[g].view(2, P) is the global edge_label_index; LINK_TRIPLET: [src | dst_pos |
+    dst_neg [E, K]].  The endpoints are not range-checked here (a loader checks them once); out / unverified: tensors of an
+    earlier call of the same shape, reused."""
+    for name, t in (("src", src), ("dst", dst)):
+        if t.dim() != 2 or t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError("link_seeds: %s must be a contiguous int64 [n_batches, n_edges] tensor" % name)
+    if src.shape != dst.shape or src.device != dst.device:
+        raise ValueError("link_seeds: src and dst differ in shape or device")
+    G, E = src.shape
+    S, _ = link_seeds_capacity(E, K, mode)
+    dev = src.device
+    if out is None:
+        out = torch.empty((G, S), dtype=torch.int64, device=dev)
+    if unverified is None:
+        unverified = torch.zeros(G, dtype=torch.int64, device=dev)
+    if tuple(out.shape) != (G, S) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("link_seeds: out is not a contiguous int64 [%d, %d] tensor on %s" % (G, S, dev))
+    if tuple(unverified.shape) != (G,) or unverified.dtype != torch.int64 or not unverified.is_contiguous() \
+            or unverified.device != dev:
+        raise ValueError("link_seeds: unverified is not a contiguous int64 [%d] tensor on %s" % (G, dev))
+    rng = TgRng(seed, call_id)
+    check(lib.tg_link_seeds(C.byref(graph), ptr(edge_set), C.c_int64(edge_set.numel() * 8 if edge_set is not None else 0),
+                            ptr(src), ptr(dst), C.c_int64(G), C.c_int64(E), C.c_int64(K), C.c_int32(mode),
+                            C.c_int32(try_count), C.byref(rng), C.c_int64(n_nodes), ptr(out), ptr(unverified),
+                            stream_ptr(dev)))
+    return out, unverified
 
 
 def tempo_random_walk(graph, node_ts, edge_ts, start, start_ts, walk_length, window, seed, call_id):
@@ -932,12 +975,16 @@ def ns_homo_compact(out, n_batches, counts_host, stacked=False):
     off = torch.zeros((2, n_batches + 1), dtype=torch.int64, device=dev)
     off[:, 1:] = torch.cumsum(c.t(), dim=1)
     o = dict(dtype=torch.int64, device=dev)
-    fs, fe = torch.empty(total_n, **o), torch.empty(total_e, **o)
-    rc = torch.empty((2, total_e), **o)
+    pad = max(total_e, 1)                     # no hops, no edges: the library refuses null edge buffers, and an empty
+    fs, fe = torch.empty(total_n, **o), torch.empty(pad, **o)       # tensor's data_ptr() is null
+    rc = torch.empty((2, pad), **o)
     fr, fc = rc[0], rc[1]
     so = out.struct()
     check(lib.tg_ns_homo_compact(C.byref(so), C.c_int64(n_batches), ptr(off[0]), ptr(off[1]), ptr(fs), ptr(fr), ptr(fc),
                                  ptr(fe), stream_ptr(dev)))
+    if total_e == 0:
+        fe, rc = fe[:0], rc[:, :0]
+        fr, fc = rc[0], rc[1]
     return (fs, rc, fe) if stacked else (fs, fr, fc, fe)
 
 

@@ -236,11 +236,28 @@ class NeighborLoader(_Loader):
         self._side = None
         self.epoch = 0
 
+    # ---- what a loader whose work items are not the seeds themselves fills in (LinkNeighborLoader)
+    WITH_INVERSE = False            # unique=True: keep tg_ns_homo_unique's `inverse` slab (forest position -> n_id position)
+
+    def _seed_width(self, width: int) -> int:
+        """Seeds of a mini-batch of `width` work items."""
+        return width
+
+    def _seed_rows(self, slab, items: Tensor, first_batch: int) -> Tensor:
+        """The [G, seeds] rows the sampler starts from for the work items [G, width] of a launch whose first mini-batch is
+        first_batch; called on the side stream, directly ahead of the sampler."""
+        return items
+
+    def _new_super_batch(self, slab, G: int) -> SuperBatch:
+        """The launch's container; called on the caller's stream while the slab set is still the launch's (whatever a
+        subclass needs from it is copied here)."""
+        return SuperBatch()
+
     # ---- stage 1 (side stream): sample G mini-batches into slab set `which`, sizes -> pinned host memory
     def _sample(self, slabs, which, seeds: Tensor, first_batch: int):
         """`slabs` is the iterator's own set: slots 0 / 1 for full launches (one consumed, one sampled), "ragged" for the
         epoch's last, narrower mini-batch -- so that one neither replaces the big slabs nor is replaced by them"""
-        G, B = seeds.shape
+        G, B = seeds.shape[0], self._seed_width(seeds.shape[1])
         H = len(self.fanout)
         slab = slabs.get(which)
         if slab is None or slab["out"].n_batches < G or slab["out"].n_seeds != B:
@@ -250,7 +267,7 @@ class NeighborLoader(_Loader):
                     "lo": torch.empty((cap, max(H, 1), 3), dtype=torch.int64).pin_memory(),
                     "free": None}
             if self.unique:
-                slab["uniq"] = _cabi.NsUniqueOut(slab["out"], in_place=True, with_inverse=False)
+                slab["uniq"] = _cabi.NsUniqueOut(slab["out"], in_place=True, with_inverse=self.WITH_INVERSE)
                 slab["ln"] = torch.empty((cap, max(H, 1)), dtype=torch.int64).pin_memory()
             slabs[which] = slab
         if G >= 2048 and self._ws is None:   # many batches per launch: the window-ordered form pays
@@ -264,7 +281,8 @@ class NeighborLoader(_Loader):
         if slab["free"] is not None:
             side.wait_event(slab["free"])
         with torch.cuda.stream(side):
-            seeds = seeds.contiguous()
+            items = seeds.contiguous()
+            seeds = self._seed_rows(slab, items, first_batch)
             out = slab["out"]
             _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
                                   sampler=self.sampler, ws=self._ws if G >= 2048 else None, form=self.form)
@@ -289,7 +307,7 @@ class NeighborLoader(_Loader):
             slab["lo"][:G].copy_(out.layer_offsets[:G], non_blocking=True)
             done = torch.cuda.Event()
             done.record(side)
-        seeds.record_stream(side)
+        items.record_stream(side)
         return (slab, G, B, first_batch, done)
 
     # ---- stage 2 (caller's stream): flatten, gather the attribute rows
@@ -310,11 +328,11 @@ class NeighborLoader(_Loader):
             edge_index, e_ptr, _ = _cabi.ns_induced_emit(ind, n_edges)
         else:
             n_id, edge_index, e_ptr = _cabi.ns_homo_compact(src, G, counts, stacked=True)   # copies: the slabs go back to the sampler
+        sb = self._new_super_batch(slab, G)
         free = torch.cuda.Event()
         free.record(cur)
         slab["free"] = free
         rows_of = lambda table, index: _cabi.gather_rows(table, index)[0]   # ids come from the sampler: no range read-back
-        sb = SuperBatch()
         sb.n_id, sb.edge_index = n_id, edge_index
         sb._e_id, sb._e_ptr, sb._perm = None, e_ptr, self.perm
         sb.node_attrs = {k: rows_of(v, n_id) for k, v in self._node_attrs}
@@ -924,3 +942,150 @@ class Node2VecLoader(_Loader):
     def __iter__(self) -> Iterator[SkipGramBatch]:
         for sb in self.super_batches():
             yield from sb
+
+
+class LinkSuperBatch(SuperBatch):
+    """A SuperBatch of a LinkNeighborLoader: the G mini-batches of ONE tg_link_seeds + tg_ns_homo_batched launch, plus the
+    link fields as batch-major tensors (row g is mini-batch g's, numbered against ITS n_id): `input_id` [G, E],
+    `neg_unverified` [G], `batch_size` = E; binary: `edge_label_index` [G, 2, P], `edge_label` [G, P]; triplet:
+    `src_index`, `dst_pos_index` [G, E], `dst_neg_index` [G, E, K] (`edge_label` [G, E] only when the user gave labels)."""
+    __slots__ = ("neg_sampling", "edge_label_index", "edge_label", "src_index", "dst_pos_index", "dst_neg_index", "input_id",
+                 "neg_unverified")
+
+    def __getitem__(self, j):
+        if j < 0:
+            j += len(self)
+        if not 0 <= j < len(self):
+            raise IndexError(j)
+        return LinkMiniBatch(self, j)
+
+    def __iter__(self):
+        for j in range(len(self.node_ptr) - 1):
+            yield LinkMiniBatch(self, j)
+
+
+def _row_of(name):
+    def get(self):
+        t = getattr(self._sb, name)
+        return None if t is None else t[self._j]
+    return property(get)
+
+
+class LinkMiniBatch(MiniBatch):
+    """Mini-batch j of a LinkSuperBatch: a MiniBatch whose seeds are the endpoints of `batch_size` positive edges and their
+    negatives; n_id[edge_label_index] (binary) or n_id[src_index], n_id[dst_pos_index], n_id[dst_neg_index] (triplet) are
+    the global endpoints.  `neg_unverified` is a device scalar: negatives kept after try_count rejected attempts."""
+    __slots__ = ()
+    batch_size = property(lambda self: self._sb.batch_size)
+    edge_label_index = _row_of("edge_label_index")
+    edge_label = _row_of("edge_label")
+    src_index = _row_of("src_index")
+    dst_pos_index = _row_of("dst_pos_index")
+    dst_neg_index = _row_of("dst_neg_index")
+    input_id = _row_of("input_id")
+    neg_unverified = _row_of("neg_unverified")
+
+
+class LinkNeighborLoader(NeighborLoader):
+    """PyG's link-level loader: a NeighborLoader whose work items are edges.  A mini-batch is `batch_size` positive edges of
+    `edge_label_index` ([2, N], default data.edge_index); tg_link_seeds draws `neg_sampling_ratio` = K negatives per positive
+    ("binary": random pairs; "triplet": random destinations for the positive's source), each checked against the graph for
+    up to `try_count` attempts (try_count = 1: unchecked, as PyG), and lays positives and negatives out as the seed row the
+    sampler starts from -- `prefetch` mini-batches per launch, on the side stream, directly ahead of tg_ns_homo_batched.
+    Mini-batch j of epoch e uses call id call_id0 + e * len(loader) + j for the negatives and the sampler alike.
+
+    Numbering against n_id: under unique=False seed p sits at n_id[p], so the index tensors are constants shared by all
+    mini-batches of one width; under unique=True they are tg_ns_homo_unique's `inverse` of the seed positions, copied out of
+    the slab before the sampler gets it back.  `edge_label` (user labels [N]) is carried through only when K = 0.
+    `edge_set=True` builds the CSC's edge set once (one probe per check instead of a binary search) when the ids fit."""
+    WITH_INVERSE = True
+
+    def __init__(self, data, num_neighbors: List[int], edge_label_index: Optional[Tensor] = None,
+                 edge_label: Optional[Tensor] = None, neg_sampling_ratio: int = 1, neg_sampling: str = "binary",
+                 try_count: int = 8, batch_size: int = 1024, prefetch: int = 16, replace: bool = False, shuffle: bool = False,
+                 drop_last: bool = False, seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0,
+                 unique: bool = False, edge_set: bool = False):
+        if neg_sampling not in ("binary", "triplet"):
+            raise ValueError("neg_sampling must be 'binary' or 'triplet'")
+        K = int(neg_sampling_ratio)
+        if K != neg_sampling_ratio or K < 0:
+            raise ValueError("neg_sampling_ratio must be an integer >= 0")
+        if K > 0 and edge_label is not None:
+            raise ValueError("edge_label with neg_sampling_ratio > 0: shifting user labels past the negatives' 0 is not offered")
+        if int(try_count) < 1 or int(batch_size) < 1:
+            raise ValueError("try_count and batch_size must be >= 1")
+        dev = torch.device(device)
+        eli = data.edge_index if edge_label_index is None else edge_label_index
+        if eli.dim() != 2 or eli.shape[0] != 2:
+            raise ValueError("edge_label_index must be [2, N]")
+        eli = eli.to(dev).to(torch.int64).contiguous()
+        n_nodes = _num_nodes(data)
+        if eli.numel() and (int(eli.min()) < 0 or int(eli.max()) >= n_nodes):   # once, as _checked_inputs: no launch yet
+            raise IndexError("edge_label_index outside [0, %d)" % n_nodes)
+        if edge_label is not None and edge_label.shape[0] != eli.shape[1]:
+            raise ValueError("edge_label must have one entry per edge of edge_label_index")
+        super().__init__(data, num_neighbors, input_nodes=eli.new_empty(0), batch_size=batch_size, prefetch=prefetch,
+                         replace=replace, shuffle=shuffle, drop_last=drop_last, seed=seed, call_id0=call_id0, device=dev,
+                         form=form, unique=unique)
+        self.edge_label_index = eli
+        self.edge_label = None if edge_label is None else edge_label.to(dev)
+        self.input_nodes = torch.arange(eli.shape[1], device=dev)    # the work items: positions in edge_label_index
+        self.K, self.try_count = K, int(try_count)
+        self.neg_sampling = neg_sampling
+        self.mode = _cabi.LINK_BINARY if neg_sampling == "binary" else _cabi.LINK_TRIPLET
+        self._edge_set = _cabi.edge_set(self._graph, dev) if edge_set and self.n_nodes < 2 ** 32 - 1 else None
+        self._consts = {}
+
+    def _seed_width(self, width: int) -> int:
+        return _cabi.link_seeds_capacity(width, self.K, self.mode)[0]
+
+    def _seed_rows(self, slab, items: Tensor, first_batch: int) -> Tensor:
+        G, E = items.shape
+        S, cap = self._seed_width(E), slab["out"].n_batches
+        rows = slab.get("link")
+        if rows is None or rows.shape != (cap, S):
+            rows = slab["link"] = torch.empty((cap, S), dtype=torch.int64, device=self.device)
+            slab["unv"] = torch.zeros(cap, dtype=torch.int64, device=self.device)
+        slab["items"] = items
+        _cabi.link_seeds(self._graph, self.edge_label_index[0][items], self.edge_label_index[1][items], self.K, self.mode,
+                         self.try_count, self.seed, self.call_id0 + first_batch, self.n_nodes, edge_set=self._edge_set,
+                         out=rows[:G], unverified=slab["unv"][:G])
+        return rows[:G]
+
+    def _constants(self, E: int):
+        """What all mini-batches of E positives share: the forest's index tensors (seed p sits at n_id[p]) and the labels."""
+        c = self._consts.get(E)
+        if c is None:
+            S, P = _cabi.link_seeds_capacity(E, self.K, self.mode)
+            local = torch.arange(S, device=self.device)
+            label = torch.cat([torch.ones(E, device=self.device), torch.zeros(P - E, device=self.device)])
+            c = self._consts[E] = (local, label)
+        return c
+
+    def _new_super_batch(self, slab, G: int) -> LinkSuperBatch:
+        sb = LinkSuperBatch()
+        items = slab["items"]
+        E, K = items.shape[1], self.K
+        S, P = _cabi.link_seeds_capacity(E, K, self.mode)
+        const, label = self._constants(E)
+        if self.unique:                      # a copy (clone: a full slice is contiguous already): the slab goes back
+            local = slab["uniq"].inverse[:G, :S].clone(memory_format=torch.contiguous_format)
+        else:
+            local = const.expand(G, S)
+        sb.neg_sampling, sb.input_id = self.neg_sampling, items
+        sb.neg_unverified = slab["unv"][:G].clone()
+        sb.edge_label_index = sb.edge_label = sb.src_index = sb.dst_pos_index = sb.dst_neg_index = None
+        if self.mode == _cabi.LINK_BINARY:
+            sb.edge_label_index = local.view(G, 2, P)
+            sb.edge_label = label.expand(G, P)
+        else:
+            sb.src_index, sb.dst_pos_index = local[:, :E], local[:, E:2 * E]
+            sb.dst_neg_index = local[:, 2 * E:].reshape(G, E, K)
+        if self.edge_label is not None:      # K = 0: the user's labels of these positives
+            sb.edge_label = self.edge_label[items]
+        return sb
+
+    def _finish(self, ticket) -> LinkSuperBatch:
+        sb = super()._finish(ticket)
+        sb.batch_size = sb.input_id.shape[1]                         # positive edges, not seeds
+        return sb
