@@ -627,6 +627,43 @@ TG_API int tg_link_seeds(const tg_graph *csc, const void *edge_set, int64_t edge
                          int32_t try_count, const tg_rng *rng, int64_t n_nodes, int64_t *seeds, int64_t *unverified,
                          void *stream);
 
+/* ---- Typed link-level seed rows: tg_link_seeds for ONE relation (A, rel, B) of a typed graph --------------------------------
+ * The positives are edges of the relation: src[G, E] are ids of node type A in [0, n_src), dst[G, E] ids of node type B in
+ * [0, n_dst).  G, E, K = n_neg, mode, try_count, unverified and the draw law are tg_link_seeds' (same tag, mini-batch g
+ * draws with call id rng->call_id + g, attempt a of negative u is the block (id = u, d0 = a, d1 = 0)), with two ranges:
+ *  TG_LINK_BINARY   s_a = floor(words01 * n_src / 2^64), d_a = floor(words23 * n_dst / 2^64)
+ *  TG_LINK_TRIPLET  d_a = floor(words01 * n_dst / 2^64), s = the positive's source
+ * A candidate is accepted when edge(s -> d) is false (s among indices[ptrs[d] .. ptrs[d + 1]) of rel->csc, or one probe of
+ * rel->edge_set) and, ONLY if same_type, s != d.  A deliberate difference from the reference: its heterogeneous negative
+ * sampler rejects v == w even across node types (negative_sampling.rs:117); here equal ids of two different types are
+ * unrelated nodes and stay eligible.  same_type = 1 says both endpoints are one node type (needs n_src == n_dst).
+ * Mini-batch g writes TWO rows, the inputs of the two node types for tg_ns_hetero_batched (P, S of tg_link_seeds_capacity):
+ *  source row       src_seeds + g * src_pitch, Ws words: binary Ws = P [src_pos(E) | src_neg(K E)]; triplet Ws = E [src(E)]
+ *  destination row  dst_seeds + g * dst_pitch, Wd = P words: [dst_pos(E) | dst_neg(K E)] (triplet: negative i * K + k
+ *                   belongs to positive i)
+ * Pitches are in words and at least the widths.  Every word inside the widths is written and nothing else: not the words
+ * between width and pitch, nothing behind the last row.  The two regions must not overlap, except that their rows may
+ * interleave inside one common pitch: src_seeds = base, dst_seeds = base + Ws, both pitches = Ws + Wd = S is tg_link_seeds'
+ * row, and with same_type = 1 the output then equals tg_link_seeds' bit for bit (one input row when A == B).
+ * Refused with TG_ERR_INVALID before anything is launched: a null rel, rng or graph; n_src < 1 or n_dst < 1; n_dst !=
+ * csc->n_major; same_type with n_src != n_dst; a pitch below its width; try_count < 1; an unknown mode; negative sizes or
+ * products past tg_link_seeds' bounds; an edge set of another size or with n_src or n_dst >= 2^32 - 1; overlapping
+ * regions.  G = 0 or E = 0 returns TG_OK and launches nothing.  src < n_src, dst < n_dst and indices < n_src are the
+ * caller's contract.  Nothing is read back; the call does not synchronise. */
+typedef struct {
+    const tg_graph *csc;      /* the labelled relation's CSC: n_major == n_dst columns, every index < n_src;
+                                 ptrs32 / indices32 optional */
+    const void *edge_set;     /* NULL, or tg_edge_set_build over THIS csc (key = column << 32 | row) */
+    int64_t edge_set_bytes;
+    int64_t n_src, n_dst;     /* id ranges of the source and the destination node type */
+    int32_t same_type;        /* 1: both endpoints are ONE node type (needs n_src == n_dst); then s == d is rejected */
+} tg_link_rel;
+
+TG_API int tg_link_seeds_typed(const tg_link_rel *rel, const int64_t *src, const int64_t *dst, int64_t n_batches,
+                               int64_t n_edges, int64_t n_neg, int32_t mode, int32_t try_count, const tg_rng *rng,
+                               int64_t *src_seeds, int64_t src_pitch, int64_t *dst_seeds, int64_t dst_pitch,
+                               int64_t *unverified, void *stream);
+
 /* tempo_random_walk (random_walk.rs:80-158; binding python.rs:611-642).
  * walks, walks_ts: [n, walk_length] device int64. */
 TG_API int tg_tempo_random_walk(const tg_graph *csr, const int64_t *node_ts, const int64_t *edge_ts, const int64_t *start,

@@ -39,7 +39,7 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_ns_typed_unique_form", "tg_ns_typed_unique_workspace_bytes", "tg_ns_typed_unique",
            "tg_ns_induced_workspace_bytes", "tg_ns_induced_count", "tg_ns_induced_emit", "tg_rw_skipgram_capacity",
            "tg_rw_skipgram_form", "tg_rw_skipgram_workspace_bytes", "tg_rw_skipgram", "tg_ns_rows_fill",
-           "tg_link_seeds_capacity", "tg_link_seeds"]
+           "tg_link_seeds_capacity", "tg_link_seeds", "tg_link_seeds_typed"]
 
 
 class TgGraph(C.Structure):
@@ -511,6 +511,62 @@ def link_seeds(graph, src, dst, K, mode, try_count, seed, call_id, n_nodes, edge
                             C.c_int32(try_count), C.byref(rng), C.c_int64(n_nodes), ptr(out), ptr(unverified),
                             stream_ptr(dev)))
     return out, unverified
+
+
+class TgLinkRel(C.Structure):
+    _fields_ = [("csc", C.POINTER(TgGraph)), ("edge_set", C.c_void_p), ("edge_set_bytes", C.c_int64), ("n_src", C.c_int64),
+                ("n_dst", C.c_int64), ("same_type", C.c_int32)]
+
+
+def link_rel(graph, n_src, n_dst, same_type, edge_set=None):
+    """The tg_link_rel of a relation's CSC `graph` (n_dst columns, row ids below n_src) and its optional edge set."""
+    rel = TgLinkRel(C.pointer(graph), edge_set.data_ptr() if edge_set is not None else None,
+                    edge_set.numel() * 8 if edge_set is not None else 0, int(n_src), int(n_dst), int(bool(same_type)))
+    rel._keep = (graph, edge_set)                                     # the struct only borrows them
+    return rel
+
+
+def _link_rows(name, t, G, W, dev):
+    """A [G, W] int64 view whose rows are contiguous (row stride >= W: the pitch) -> its pitch in words."""
+    if t.dim() != 2 or tuple(t.shape) != (G, W) or t.dtype != torch.int64 or t.device != dev \
+            or (W > 1 and t.stride(1) != 1) or (G > 1 and t.stride(0) < W):
+        raise ValueError("link_seeds_typed: %s is not an int64 [%d, %d] view with contiguous rows on %s" % (name, G, W, dev))
+    return t.stride(0) if G > 1 else max(t.stride(0), W)
+
+
+def link_seeds_typed(graph, src, dst, K, mode, try_count, seed, call_id, n_src, n_dst, same_type, edge_set=None,
+                     src_out=None, dst_out=None, unverified=None):
+    """Typed seed rows (tg_link_seeds_typed) of the G mini-batches of positive edges src[G, E] -> dst[G, E] of ONE relation
+    with K checked negatives each, one launch on the current stream, nothing read back: -> (src rows [G, Ws], dst rows
+    [G, Wd], unverified [G]).  `graph` is the relation's CSC (n_dst columns, row ids < n_src), `edge_set` the optional set
+    built over it; same_type: both endpoints are one node type, s == d is then rejected.  LINK_BINARY: Ws = Wd = P, rows
+    [pos | neg]; LINK_TRIPLET: Ws = E [src], Wd = P [dst_pos | dst_neg [E, K]].  src_out / dst_out may be strided 2-D views
+    with contiguous rows (the pitch is the view's row stride), e.g. out[:, :Ws] and out[:, Ws:] of one [G, S] tensor, which
+    is tg_link_seeds' layout; they are allocated when not given.  The endpoints are not range-checked here."""
+    for name, t in (("src", src), ("dst", dst)):
+        if t.dim() != 2 or t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError("link_seeds_typed: %s must be a contiguous int64 [n_batches, n_edges] tensor" % name)
+    if src.shape != dst.shape or src.device != dst.device:
+        raise ValueError("link_seeds_typed: src and dst differ in shape or device")
+    G, E = src.shape
+    _, P = link_seeds_capacity(E, K, mode)
+    Ws, Wd = (P if mode == LINK_BINARY else E), P
+    dev = src.device
+    if src_out is None:
+        src_out = torch.empty((G, Ws), dtype=torch.int64, device=dev)
+    if dst_out is None:
+        dst_out = torch.empty((G, Wd), dtype=torch.int64, device=dev)
+    if unverified is None:
+        unverified = torch.zeros(G, dtype=torch.int64, device=dev)
+    sp, dp = _link_rows("src_out", src_out, G, Ws, dev), _link_rows("dst_out", dst_out, G, Wd, dev)
+    if tuple(unverified.shape) != (G,) or unverified.dtype != torch.int64 or not unverified.is_contiguous() \
+            or unverified.device != dev:
+        raise ValueError("link_seeds_typed: unverified is not a contiguous int64 [%d] tensor on %s" % (G, dev))
+    rel, rng = link_rel(graph, n_src, n_dst, same_type, edge_set), TgRng(seed, call_id)
+    check(lib.tg_link_seeds_typed(C.byref(rel), ptr(src), ptr(dst), C.c_int64(G), C.c_int64(E), C.c_int64(K), C.c_int32(mode),
+                                  C.c_int32(try_count), C.byref(rng), ptr(src_out), C.c_int64(sp), ptr(dst_out),
+                                  C.c_int64(dp), ptr(unverified), stream_ptr(dev)))
+    return src_out, dst_out, unverified
 
 
 def tempo_random_walk(graph, node_ts, edge_ts, start, start_ts, walk_length, window, seed, call_id):

@@ -13,6 +13,8 @@ The typed-graph loaders (HeteroNeighborLoader, HGTLoader, BudgetLoader, Negative
 `prefetch` mini-batches of one node type's seeds per launch of a batched operator, one read-back of the counts, every
 slab flattened and split per mini-batch, attributes gathered once per launch.  Each loader adds only its operator's
 launch object and a few hooks (e_id, extras, panics).  They run on the caller's stream, launch by launch.
+HeteroLinkNeighborLoader is HeteroNeighborLoader seeded by the edges of one relation: tg_link_seeds_typed fills the input
+tensors of the relation's two node types directly ahead of the sampler.
 """
 from typing import Iterator, List, Optional
 
@@ -608,6 +610,7 @@ class HeteroNeighborLoader(_TypedLoader):
     the shape needs one, and the dedup's own outputs are kept by the loader and sized once for a full launch.
     BudgetLoader, HGTLoader and NegativeLoader have no such switch yet: BudgetLoader._e_id reads `cols` as forest
     positions, so wiring them up is a later step."""
+    WITH_INVERSE = False            # unique=True: keep tg_ns_typed_unique's `inverse` slabs (forest position -> n_id position)
 
     def __init__(self, data, num_neighbors: List[int], input_type: str, input_nodes: Optional[Tensor] = None,
                  batch_size: int = 1024, prefetch: int = 16, replace: bool = False, drop_last: bool = False, seed: int = 0,
@@ -636,11 +639,15 @@ class HeteroNeighborLoader(_TypedLoader):
             need = _cabi.ns_typed_unique_workspace_bytes([s[1] for s in shapes], self._id_bounds, full)[0]
             if need and (self._unique_ws is None or self._unique_ws.numel() * 8 < need):    # 0: the LDS form takes none
                 self._unique_ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=self.device)
-            out = _cabi.NsTypedUniqueOut(slabs, in_place=True, with_inverse=False)
-            if slabs.nb == full and slabs.n_inputs[self._it] == self.batch_size:
+            out = _cabi.NsTypedUniqueOut(slabs, in_place=True, with_inverse=self.WITH_INVERSE)
+            if slabs.nb == full and slabs.n_inputs[self._it] == self._seed_width(self.batch_size):
                 self._unique_out, self._unique_need = out, need
         return _cabi.ns_typed_unique(slabs, slabs.nb, self._id_bounds, ws=self._unique_ws if need else None,
                                      form=0 if need else 1, result=out.rebind(slabs))
+
+    def _seed_width(self, width: int) -> int:
+        """Inputs of the input type in a mini-batch of `width` work items (here the work items are the seeds)."""
+        return width
 
     def _read_back(self, slabs):
         lo = slabs.layer_offsets.cpu().tolist()
@@ -1089,3 +1096,165 @@ class LinkNeighborLoader(NeighborLoader):
         sb = super()._finish(ticket)
         sb.batch_size = sb.input_id.shape[1]                         # positive edges, not seeds
         return sb
+
+
+class HeteroLinkNeighborLoader(HeteroNeighborLoader):
+    """LinkNeighborLoader for ONE relation et = (A, rel, B) of a typed graph: a HeteroNeighborLoader whose work items are
+    positions in the relation's `edge_label_index` -- PyG's form (edge_type, Tensor[2, N]), or a bare edge_type or
+    (edge_type, None) for the relation's own edge_index.  A mini-batch is `batch_size` positive edges;
+    tg_link_seeds_typed draws `neg_sampling_ratio` = K negatives per positive ("binary": a random A and a random B;
+    "triplet": random B for the positive's source), each checked against the relation for up to `try_count` attempts
+    (try_count = 1: unchecked), and writes them straight into the launch's per-type input tensors -- inputs[A] [G, Ws] and
+    inputs[B] [G, Wd], or ONE [G, S] tensor when A == B -- directly ahead of tg_ns_hetero_batched on the same stream.
+    Equal ids of A and B are unrelated nodes unless A == B: only then is s == d rejected.  Mini-batch j of epoch e uses
+    call id call_id0 + e * len(loader) + j for the negatives and the sampler alike.
+
+    A mini-batch is HeteroNeighborLoader's HeteroGraph plus: binary `g[et].edge_label_index` [2, P] (row 0 indexes
+    g[A].n_id, row 1 g[B].n_id) and `g[et].edge_label` [P]; triplet `g[A].src_index` [E], `g[B].dst_pos_index` [E],
+    `g[B].dst_neg_index` [E, K]; `g[et].input_id` [E], `g.neg_unverified` (a device scalar) and `batch_size` of A and of B:
+    the seeds of that type leading its n_id (the row width under the forest, the unique-seed count under unique=True).
+    Under unique=False a type's n_id starts with its inputs, so the positions are constants per width; under unique=True
+    they are tg_ns_typed_unique's `inverse` at those positions, copied out of the slab.  `edge_label` (user labels [N]) is
+    carried through only when K = 0; `edge_set=True` builds the relation's edge set once when both id ranges fit;
+    `shuffle=True` permutes the work items per epoch with a generator seeded by (seed, epoch), as NeighborLoader does."""
+    WITH_INVERSE = True
+
+    def __init__(self, data, num_neighbors: List[int], edge_label_index, edge_label: Optional[Tensor] = None,
+                 neg_sampling_ratio: int = 1, neg_sampling: str = "binary", try_count: int = 8, batch_size: int = 1024,
+                 prefetch: int = 16, replace: bool = False, shuffle: bool = False, drop_last: bool = False, seed: int = 0,
+                 call_id0: int = 0, device="cuda", unique: bool = False, edge_set: bool = False):
+        if not _is_hetero(data):
+            raise ValueError("HeteroLinkNeighborLoader takes a typed graph; LinkNeighborLoader is the loader of a homogeneous one")
+        if neg_sampling not in ("binary", "triplet"):
+            raise ValueError("neg_sampling must be 'binary' or 'triplet'")
+        K = int(neg_sampling_ratio)
+        if K != neg_sampling_ratio or K < 0:
+            raise ValueError("neg_sampling_ratio must be an integer >= 0")
+        if K > 0 and edge_label is not None:
+            raise ValueError("edge_label with neg_sampling_ratio > 0: shifting user labels past the negatives' 0 is not offered")
+        if int(try_count) < 1 or int(batch_size) < 1:
+            raise ValueError("try_count and batch_size must be >= 1")
+        et, eli = edge_label_index, None
+        if isinstance(et, (tuple, list)) and len(et) == 2 and isinstance(et[0], (tuple, list)):
+            et, eli = et
+        et = tuple(et)
+        if et not in [tuple(x) for x in data.edge_types]:
+            raise ValueError("edge_label_index must name one of the edge types %s" % list(data.edge_types))
+        dev = torch.device(device)
+        eli = data[et].edge_index if eli is None else eli
+        if eli.dim() != 2 or eli.shape[0] != 2:
+            raise ValueError("edge_label_index must be [2, N]")
+        eli = eli.to(dev).to(torch.int64).contiguous()
+        n_src, n_dst = _num_nodes(data[et[0]]), _num_nodes(data[et[2]])
+        for row, n, nt in ((eli[0], n_src, et[0]), (eli[1], n_dst, et[2])):   # once: nothing was launched with them yet
+            if row.numel() and (int(row.min()) < 0 or int(row.max()) >= n):
+                raise IndexError("edge_label_index: ids of %s outside [0, %d)" % (nt, n))
+        if edge_label is not None and edge_label.shape[0] != eli.shape[1]:
+            raise ValueError("edge_label must have one entry per edge of edge_label_index")
+        super().__init__(data, num_neighbors, et[0], input_nodes=eli.new_empty(0), batch_size=batch_size, prefetch=prefetch,
+                         replace=replace, drop_last=drop_last, seed=seed, call_id0=call_id0, device=dev, unique=unique)
+        self.edge_type, self.edge_label_index = et, eli
+        self.edge_label = None if edge_label is None else edge_label.to(dev)
+        self.input_nodes = torch.arange(eli.shape[1], device=dev)    # the work items: positions in edge_label_index
+        self.shuffle, self.K, self.try_count, self.neg_sampling = bool(shuffle), K, int(try_count), neg_sampling
+        self.mode = _cabi.LINK_BINARY if neg_sampling == "binary" else _cabi.LINK_TRIPLET
+        self._ta, self._tb, self.n_src, self.n_dst = self._tix[et[0]], self._tix[et[2]], n_src, n_dst
+        self.same_type = self._ta == self._tb
+        ptrs, idx = self.col_ptrs[rel_key(et)], self.row_indices[rel_key(et)]
+        small = max(n_src, n_dst) < 2 ** 31 and idx.numel() < 2 ** 31   # u32 shadows: half the bytes per look-up line
+        self._rel_graph = _cabi.graph_view(ptrs, idx, indices32=idx.to(torch.int32) if small else None,
+                                           ptrs32=ptrs.to(torch.int32) if small else None)
+        fits = max(n_src, n_dst) < 2 ** 32 - 1
+        self._edge_set = _cabi.edge_set(self._rel_graph, dev) if edge_set and fits else None
+        self._consts = {}
+
+    def _widths(self, E: int):
+        """-> (Ws, Wd): the source and the destination row of a mini-batch of E positives."""
+        P = _cabi.link_seeds_capacity(E, self.K, self.mode)[1]
+        return (P if self.mode == _cabi.LINK_BINARY else E), P
+
+    def _seed_width(self, width: int) -> int:
+        Ws, Wd = self._widths(width)
+        return Ws + Wd if self.same_type else Ws
+
+    def _launch_for(self, items: Tensor, seeds_ts):
+        G, E = items.shape
+        Ws, Wd = self._widths(E)
+        new = lambda w: torch.empty((G, w), dtype=torch.int64, device=self.device)
+        inputs = [None] * len(self.node_types)
+        if self.same_type:                                           # one input row per mini-batch: tg_link_seeds' layout
+            inputs[self._ta] = row = new(Ws + Wd)
+            src_out, dst_out = row[:, :Ws], row[:, Ws:]
+        else:
+            inputs[self._ta], inputs[self._tb] = src_out, dst_out = new(Ws), new(Wd)
+        unv = torch.zeros(G, dtype=torch.int64, device=self.device)
+        _cabi.link_seeds_typed(self._rel_graph, self.edge_label_index[0][items], self.edge_label_index[1][items], self.K,
+                               self.mode, self.try_count, self.seed, self._first_call, self.n_src, self.n_dst, self.same_type,
+                               edge_set=self._edge_set, src_out=src_out, dst_out=dst_out, unverified=unv)
+        slabs = self._new_launch(inputs, None, G)
+        slabs.link = (items, unv)
+        return slabs
+
+    def _emit(self, seeds: Tensor, seeds_ts, first_batch: int):
+        self._first_call = self.call_id0 + first_batch               # for _launch_for, the first thing the skeleton calls:
+        yield from super()._emit(seeds, seeds_ts, first_batch)       # set and read before this generator yields anything
+
+    def _constants(self, E: int):
+        """What all forest mini-batches of E positives share: positions (an input sits at its own place in its type's
+        n_id; the destinations follow the sources when A == B) and the labels."""
+        c = self._consts.get(E)
+        if c is None:
+            Ws, Wd = self._widths(E)
+            dev = self.device
+            c = self._consts[E] = (torch.arange(Ws, device=dev), torch.arange(Wd, device=dev) + (Ws if self.same_type else 0),
+                                   torch.cat([torch.ones(E, device=dev), torch.zeros(Wd - E, device=dev)]))
+        return c
+
+    def _read_back(self, slabs):
+        lo = slabs.layer_offsets.cpu().tolist()
+        counts, seed_counts = slabs.read_state() if self.unique else (slabs.counts.cpu(), None)
+        items, unv = (slabs.src if self.unique else slabs).link
+        G, E = items.shape
+        Ws, Wd = self._widths(E)
+        ca, cb, label = self._constants(E)
+        if self.unique:                      # copies: a kept NsTypedUniqueOut is written again by the next full launch
+            off = Ws if self.same_type else 0
+            la = slabs.inverse[self._ta][:, :Ws].clone()
+            lb = slabs.inverse[self._tb][:, off:off + Wd].clone()
+            seed_counts = seed_counts.tolist()
+            sizes = [(seed_counts[b][self._ta], seed_counts[b][self._tb]) for b in range(G)]
+        else:
+            la, lb = ca.expand(G, Ws), cb.expand(G, Wd)
+            sizes = [(Ws + Wd, Ws + Wd) if self.same_type else (Ws, Wd)] * G
+        link = dict(items=items, unv=unv, E=E, sizes=sizes, la=la, lb=lb,
+                    label=self.edge_label[items] if self.edge_label is not None else label.expand(G, Wd))
+        if self.mode == _cabi.LINK_BINARY:
+            link["eli"] = torch.stack([la, lb], dim=1)               # [G, 2, P], once per launch
+        return counts, (lo, link)
+
+    def _decorate(self, g, b, n_seeds, state, ts_parts):
+        lo, link = state
+        super()._decorate(g, b, n_seeds, (lo, None), ts_parts)
+        A, B, et, E = self.edge_type[0], self.edge_type[2], self.edge_type, link["E"]
+        g[A].batch_size, g[B].batch_size = link["sizes"][b]
+        st = g[et]
+        st.input_id = link["items"][b]
+        g.neg_unverified = link["unv"][b]
+        if self.mode == _cabi.LINK_BINARY:
+            st.edge_label_index, st.edge_label = link["eli"][b], link["label"][b]
+        else:
+            g[A].src_index = link["la"][b]
+            g[B].dst_pos_index, g[B].dst_neg_index = link["lb"][b, :E], link["lb"][b, E:].reshape(E, self.K)
+            if self.edge_label is not None:
+                st.edge_label = link["label"][b]
+
+    def __iter__(self):
+        items, B = self.input_nodes, self.batch_size
+        epoch, batch0 = self.epoch, self.epoch * len(self)           # fresh draws every epoch
+        self.epoch += 1
+        if self.shuffle:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(self.seed * 1000003 + epoch)
+            items = items[torch.randperm(items.numel(), device=self.device, generator=gen)]
+        for start, G, width in _epoch_plan(items.numel(), B, self.prefetch, self.drop_last):
+            yield from self._emit(items[start:start + G * width].reshape(G, width), None, batch0 + start // B)

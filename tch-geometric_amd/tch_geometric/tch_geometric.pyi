@@ -23,7 +23,8 @@ tg_rw_skipgram, csrc/rw_skipgram.hip): it yields objects with pos_rw [rows, cont
 
 Link-level mini-batches -- positive edges, checked negatives, the neighbourhood of all their endpoints, and
 edge_label_index numbered against n_id -- come from LinkNeighborLoader (exported by the package; tg_link_seeds,
-csrc/link_seeds.hip)."""
+csrc/link_seeds.hip), and for one relation (A, rel, B) of a typed graph from HeteroLinkNeighborLoader
+(tg_link_seeds_typed): edge_label_index's two rows are numbered against the n_id of A and of B."""
 from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor
