@@ -594,6 +594,67 @@ TG_API int tg_rw_skipgram(const tg_graph *csr, const void *edge_set, int64_t edg
                           const tg_rw_skipgram_out *out, void *workspace, int64_t workspace_bytes, int32_t form,
                           void *stream);
 
+/* ---- MetaPath2Vec skip-gram batches: tg_rw_skipgram along a metapath of a typed graph ---------------------------------------
+ * What PyG's MetaPath2Vec composes per mini-batch (a sample per step over the step's relation, the offset of the column's
+ * node type into ONE embedding table, dummy_idx for ended walks, strided slices + cat, randint per column type), as one
+ * launch for G mini-batches.  The metapath has M = n_steps relations; step l of a walk goes over metapath[l mod M], so a
+ * walk longer than M repeats the path, which must then close (step_dst[M - 1] == step_src[0]).  G, B, T, C, R, K, L, nw, W,
+ * U, the slabs (tg_rw_skipgram_out: pos_rw [G, nw * W, C], neg_rw [G, nw * U, C], batch-major, every word written, nothing
+ * read back, no synchronisation), the window rule (pos_rw[g] row j * W + w, column c = walk_g[w][j + c]; neg_rw[g] row
+ * j * U + u, column c = x_u[j + c]) and walker w = r * B + i starting at seeds[g][i] are tg_rw_skipgram's.  seeds: device
+ * int64 [G, B], LOCAL ids of type step_src[0].  context_size = L yields the raw walks.
+ *  column types  column 0 has type step_src[0], column l + 1 has type step_dst[l mod M].
+ *  positives     step l stands at local id cur of type step_src[l mod M] and reads row [b, e) = ptrs[cur], ptrs[cur + 1] of
+ *                graphs[l mod M].  e <= b: the walk is over, this column and all later ones are pad_value.  Otherwise the
+ *                draw is (call key of (seed, call id + g, TAG_RW), id = w, d0 = l, d1 = 0) and, a = its low 64 bits, the
+ *                next local id is indices[b + floor(a * (e - b) / 2^64)]: tg_random_walk's step with p = q = 1 on the
+ *                step's own CSR.
+ *  negatives     x_u[0] = seeds[g][u mod B]; for m >= 1 x_u[m] = floor(a * type_count[type of column m] / 2^64), a = the
+ *                low 64 bits of the draw (call key of (seed, call id + g, TAG_RW_NEG = 12), id = u, d0 = m, d1 = 0).
+ *  output word   local id + type_start[type of its column], added in 64 bits: global ids may pass 2^32 while local ids do
+ *                not.  type_start = NULL: local ids.
+ * The two tags are tg_rw_skipgram's on purpose: with M = 1, one node type, type_start = NULL and pad_value = -1 both slabs
+ * equal tg_rw_skipgram(p = q = 1, n_nodes = type_count[0]) bit for bit.
+ * `form` as tg_rw_skipgram: 1, 2 stage a wavefront's 64 rows in LDS as LOCAL ids (1: uint32 with 0xffffffff for an ended
+ * walk, needs max(type_count) < 2^32 - 1; 2: int64) and add the start / put in pad_value when a word is emitted, from a
+ * per-column table of L int64 in LDS; a workgroup is one wavefront with TG_MP_SKIPGRAM_LDS_BYTES(L, word) bytes of LDS,
+ * taken while that is <= 40 KiB: L <= 153 for form 1, L <= 77 for form 2.  3 the flat form, any L: finished words go
+ * through `workspace` [G * W, L] int64.  Auto takes 1, else 2, else 3, whichever fits first.  All forms write identical words.
+ * Refused with TG_ERR_INVALID before anything is launched, with the step named: a null config, graphs, step arrays,
+ * type_count or rng; M outside [1, TG_MP_MAX_STEPS]; a type index outside [0, n_types); step_dst[m] != step_src[m + 1] (a
+ * broken chain); walk_length > M on an open path; graphs[m].n_major != type_count[step_src[m]]; a type_count < 1;
+ * tg_rw_skipgram's own checks (C, R, K, T, a forced form that does not fit, a short workspace, null buffers, sizes whose
+ * products overflow).  G = 0 or B = 0 returns TG_OK and launches nothing.  seeds < type_count[step_src[0]] and
+ * indices < type_count[step_dst[m]] are the caller's contract. */
+#define TG_MP_MAX_STEPS 16
+/* LDS of one workgroup of the LDS forms: 64 rows at the odd pitch L | 1, the 64 per-walker offsets, the L column starts */
+#define TG_MP_SKIPGRAM_LDS_BYTES(L, word_bytes) (64 * ((L) | 1) * (int64_t)(word_bytes) + 512 + 8 * (int64_t)(L))
+typedef struct {
+    int32_t n_types, n_steps;      /* n_steps = M = len(metapath), 1 <= M <= TG_MP_MAX_STEPS */
+    const tg_graph *graphs;        /* host [M]: CSR of metapath[m] (rows = source type, indices = ids of the dest type);
+                                      the same relation may appear at several steps; ptrs32 / indices32 optional */
+    const int32_t *step_src;       /* host [M] node-type index */
+    const int32_t *step_dst;       /* host [M] */
+    const int64_t *type_count;     /* host [n_types] nodes per type */
+    const int64_t *type_start;     /* host [n_types] added to every id of that type on output (PyG: start of the type in
+                                      the one embedding table); NULL = all zero = local ids */
+    int64_t walk_length, context_size, walks_per_node, num_negative_samples;   /* T, C, R, K as tg_rw_skipgram */
+    int64_t pad_value;             /* written for every column after a walk ended: -1, or PyG's dummy_idx */
+} tg_mp_skipgram_config;
+
+/* rows of pos_rw and neg_rw per mini-batch: nw * R * B and nw * R * K * B */
+TG_API int tg_mp_skipgram_capacity(const tg_mp_skipgram_config *cfg, int64_t batch_size, int64_t *pos_rows,
+                                   int64_t *neg_rows);
+/* Which form an auto call takes: *form = 1, 2 or 3; *lds_bytes = TG_MP_SKIPGRAM_LDS_BYTES of the narrowest LDS form that
+ * max(type_count) allows.  lds_limit_bytes > 0 replaces the 40 KiB limit.  No device is touched. */
+TG_API int tg_mp_skipgram_form(const tg_mp_skipgram_config *cfg, int64_t lds_limit_bytes, int32_t *form, int64_t *lds_bytes);
+/* the workspace a call of this form needs (form 0: the form auto takes): 0 for the LDS forms, G * W * L * 8 for flat */
+TG_API int tg_mp_skipgram_workspace_bytes(const tg_mp_skipgram_config *cfg, int64_t n_batches, int64_t batch_size,
+                                          int32_t form, int64_t *bytes);
+TG_API int tg_mp_skipgram(const tg_mp_skipgram_config *cfg, const int64_t *seeds, int64_t n_batches, int64_t batch_size,
+                          const tg_rng *rng, const tg_rw_skipgram_out *out, void *workspace, int64_t workspace_bytes,
+                          int32_t form, void *stream);
+
 /* ---- Link-level seed rows: positive edges plus checked negatives of G mini-batches in one launch --------------------------
  * What a link-prediction trainer composes per mini-batch (randint negatives, cat with the positives), with the negatives
  * checked against the graph as the reference's negative sampler checks them (negative_sampling.rs: has_edge(v, w) and

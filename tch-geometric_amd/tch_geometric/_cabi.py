@@ -39,7 +39,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_ns_typed_unique_form", "tg_ns_typed_unique_workspace_bytes", "tg_ns_typed_unique",
            "tg_ns_induced_workspace_bytes", "tg_ns_induced_count", "tg_ns_induced_emit", "tg_rw_skipgram_capacity",
            "tg_rw_skipgram_form", "tg_rw_skipgram_workspace_bytes", "tg_rw_skipgram", "tg_ns_rows_fill",
-           "tg_link_seeds_capacity", "tg_link_seeds", "tg_link_seeds_typed"]
+           "tg_link_seeds_capacity", "tg_link_seeds", "tg_link_seeds_typed", "tg_mp_skipgram_capacity",
+           "tg_mp_skipgram_form", "tg_mp_skipgram_workspace_bytes", "tg_mp_skipgram"]
 
 
 class TgGraph(C.Structure):
@@ -466,6 +467,96 @@ def rw_skipgram(graph, seeds, walk_length, context_size, walks_per_node, num_neg
     rng = TgRng(seed, call_id)
     check(lib.tg_rw_skipgram(C.byref(graph), ptr(edge_set), C.c_int64(edge_set.numel() * 8 if edge_set is not None else 0),
                              ptr(seeds), C.c_int64(G), C.c_int64(B), C.byref(cfg), C.byref(rng), C.byref(o),
+                             ptr(ws) if need else C.c_void_p(0), C.c_int64(ws.numel() * ws.element_size() if need else 0),
+                             C.c_int32(form), stream_ptr(dev)))
+    return pos, neg
+
+
+TG_MP_MAX_STEPS = 16
+
+
+class TgMpSkipgramConfig(C.Structure):
+    _fields_ = [("n_types", C.c_int32), ("n_steps", C.c_int32), ("graphs", C.POINTER(TgGraph)),
+                ("step_src", C.POINTER(C.c_int32)), ("step_dst", C.POINTER(C.c_int32)),
+                ("type_count", C.POINTER(C.c_int64)), ("type_start", C.POINTER(C.c_int64)), ("walk_length", C.c_int64),
+                ("context_size", C.c_int64), ("walks_per_node", C.c_int64), ("num_negative_samples", C.c_int64),
+                ("pad_value", C.c_int64)]
+
+
+def mp_skipgram_lds_bytes(L, word_bytes):
+    """tchgeo.h TG_MP_SKIPGRAM_LDS_BYTES: 64 rows at the odd pitch, the 64 per-walker offsets, the L column starts."""
+    return 64 * (L | 1) * word_bytes + 512 + 8 * L
+
+
+def mp_skipgram_config(graphs, step_src, step_dst, type_count, walk_length, context_size, walks_per_node=1,
+                       num_negative_samples=1, type_start=None, pad_value=-1):
+    """The tg_mp_skipgram_config of a metapath: graphs[m] is the tg_graph (graph_view / graph_sizing) of the CSR of step m,
+    step_src / step_dst its node-type indices, type_count the nodes per type, type_start the offset added to every id of a
+    type on output (None: local ids), pad_value what an ended walk is padded with.  The struct borrows the views."""
+    M, n_types = len(graphs), len(type_count)
+    if not (len(step_src) == len(step_dst) == M) or (type_start is not None and len(type_start) != n_types):
+        raise ValueError("mp_skipgram_config: graphs, step_src and step_dst are per step, type_count and type_start per type")
+    arrays = ((TgGraph * max(M, 1))(), (C.c_int32 * max(M, 1))(*[int(x) for x in step_src]),
+              (C.c_int32 * max(M, 1))(*[int(x) for x in step_dst]), (C.c_int64 * max(n_types, 1))(*[int(x) for x in type_count]),
+              (C.c_int64 * n_types)(*[int(x) for x in type_start]) if type_start is not None else None)
+    for m, g in enumerate(graphs):
+        C.memmove(C.byref(arrays[0], m * C.sizeof(TgGraph)), C.byref(g), C.sizeof(TgGraph))
+    cfg = TgMpSkipgramConfig(n_types, M, arrays[0], arrays[1], arrays[2], arrays[3], arrays[4], int(walk_length),
+                             int(context_size), int(walks_per_node), int(num_negative_samples), int(pad_value))
+    cfg._keep = (arrays, list(graphs))                                # the struct only borrows them
+    return cfg
+
+
+def mp_skipgram_capacity(cfg, batch_size):
+    """-> (rows of pos_rw, rows of neg_rw) per mini-batch of batch_size seeds: nw * R * B and nw * R * K * B."""
+    pos, neg = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_mp_skipgram_capacity(C.byref(cfg), C.c_int64(batch_size), C.byref(pos), C.byref(neg)))
+    return pos.value, neg.value
+
+
+def mp_skipgram_form(cfg, lds_limit_bytes=0):
+    """-> (form, lds_bytes): the form an auto tg_mp_skipgram call takes (1 = rows staged in LDS as uint32 local ids, needs
+    max(type_count) < 2^32 - 1; 2 = as int64; 3 = flat through a workspace) and the LDS a workgroup of the LDS form asks
+    for.  lds_limit_bytes > 0 replaces the library's limit.  No device is touched."""
+    form, nbytes = C.c_int32(-1), C.c_int64(0)
+    check(lib.tg_mp_skipgram_form(C.byref(cfg), C.c_int64(lds_limit_bytes), C.byref(form), C.byref(nbytes)))
+    return form.value, nbytes.value
+
+
+def mp_skipgram_workspace_bytes(cfg, n_batches, batch_size, form=0):
+    """The workspace a launch of n_batches x batch_size seeds needs in this form (0: the one auto takes): 0 for the LDS
+    forms, the [G * W, L] int64 walks for the flat form."""
+    nbytes = C.c_int64(-1)
+    check(lib.tg_mp_skipgram_workspace_bytes(C.byref(cfg), C.c_int64(n_batches), C.c_int64(batch_size), C.c_int32(form),
+                                             C.byref(nbytes)))
+    return nbytes.value
+
+
+def mp_skipgram(cfg, seeds, seed, call_id, form=0, ws=None, out=None):
+    """MetaPath2Vec skip-gram batches (tg_mp_skipgram) of the G mini-batches seeds[G, B] (local ids of the metapath's first
+    node type) in one launch on the current stream: -> (pos_rw [G, nw * R * B, C], neg_rw [G, nw * R * K * B, C]);
+    mini-batch g draws with call id call_id + g and is a free view.  Every word is a local id plus its column type's
+    start; the columns behind an ended walk hold cfg.pad_value.  form, ws, out as rw_skipgram."""
+    if seeds.dim() != 2 or seeds.dtype != torch.int64 or not seeds.is_contiguous():
+        raise ValueError("mp_skipgram: seeds must be a contiguous int64 [n_batches, batch_size] tensor")
+    G, B = seeds.shape
+    pos_rows, neg_rows = mp_skipgram_capacity(cfg, B)
+    dev = seeds.device
+    if out is None:
+        out = (torch.empty((G, pos_rows, cfg.context_size), dtype=torch.int64, device=dev),
+               torch.empty((G, neg_rows, cfg.context_size), dtype=torch.int64, device=dev))
+    pos, neg = out
+    if neg is None:
+        neg = torch.empty((G, 0, cfg.context_size), dtype=torch.int64, device=dev)
+    if tuple(pos.shape) != (G, pos_rows, cfg.context_size) or tuple(neg.shape) != (G, neg_rows, cfg.context_size) \
+            or not (pos.is_contiguous() and neg.is_contiguous()):
+        raise ValueError("mp_skipgram: out does not have this launch's shapes")
+    need = mp_skipgram_workspace_bytes(cfg, G, B, form)
+    if need and (ws is None or ws.numel() * ws.element_size() < need):
+        ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    o = TgRwSkipgramOut(pos.data_ptr() if pos.numel() else None, neg.data_ptr() if neg.numel() else None)
+    rng = TgRng(seed, call_id)
+    check(lib.tg_mp_skipgram(C.byref(cfg), ptr(seeds), C.c_int64(G), C.c_int64(B), C.byref(rng), C.byref(o),
                              ptr(ws) if need else C.c_void_p(0), C.c_int64(ws.numel() * ws.element_size() if need else 0),
                              C.c_int32(form), stream_ptr(dev)))
     return pos, neg

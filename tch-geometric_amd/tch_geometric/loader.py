@@ -15,6 +15,8 @@ slab flattened and split per mini-batch, attributes gathered once per launch.  E
 launch object and a few hooks (e_id, extras, panics).  They run on the caller's stream, launch by launch.
 HeteroLinkNeighborLoader is HeteroNeighborLoader seeded by the edges of one relation: tg_link_seeds_typed fills the input
 tensors of the relation's two node types directly ahead of the sampler.
+Node2VecLoader and MetaPath2VecLoader hand out skip-gram batches (context windows of walks plus negative rows) of one
+tg_rw_skipgram / tg_mp_skipgram launch per `prefetch` mini-batches; nothing is read back.
 """
 from typing import Iterator, List, Optional
 
@@ -949,6 +951,93 @@ class Node2VecLoader(_Loader):
     def __iter__(self) -> Iterator[SkipGramBatch]:
         for sb in self.super_batches():
             yield from sb
+
+
+class MetaPath2VecLoader(Node2VecLoader):
+    """MetaPath2Vec training batches (PyG's MetaPath2Vec: walks along a metapath of a typed graph, negative rows drawn per
+    column type, context windows) as a loader: ONE tg_mp_skipgram launch per `prefetch` mini-batches.  `metapath` is a
+    list of edge types (src, rel, dst) of `data`, each ending where the next starts; step l of a walk goes over
+    metapath[l mod len(metapath)], so walk_length > len(metapath) needs a path that closes.  PyG's conventions: `start` /
+    `end` of every node type in ONE embedding table of `num_embeddings` = `dummy_idx` + 1 rows (types in data.node_types
+    order, dummy_idx = the total node count).  global_ids=True emits table rows (local id + start of the column's type)
+    and pads an ended walk with dummy_idx, whose row a trainer leaves alone or masks; global_ids=False emits local ids
+    and -1.  input_nodes are local ids of metapath[0][0] (default: all of them).
+
+    The CSR of every distinct relation of the metapath is built once, on first use, and shared where a relation repeats.
+    The epoch plan, the call ids, the prefetch clamp, plan(), super_batches() and iteration are Node2VecLoader's:
+    mini-batch j of epoch e equals _cabi.mp_skipgram for (seed, call_id0 + e * len(loader) + j)."""
+
+    def __init__(self, data, metapath, walk_length: int, context_size: int, walks_per_node: int = 1,
+                 num_negative_samples: int = 1, input_nodes: Optional[Tensor] = None, batch_size: int = 128,
+                 prefetch: int = 256, drop_last: bool = False, seed: int = 0, call_id0: int = 0, global_ids: bool = True,
+                 max_workspace_bytes: int = 4 << 30, device="cuda", form: int = 0):
+        self.data, self.device = data, torch.device(device)
+        self.node_types, self.metapath = list(data.node_types), [tuple(et) for et in metapath]
+        tix = {t: i for i, t in enumerate(self.node_types)}
+        M = len(self.metapath)
+        if not 1 <= M <= _cabi.TG_MP_MAX_STEPS:
+            raise ValueError("metapath must have 1 to %d steps, got %d" % (_cabi.TG_MP_MAX_STEPS, M))
+        known = [tuple(et) for et in data.edge_types]
+        for m, et in enumerate(self.metapath):
+            if et not in known:
+                raise ValueError("metapath step %d: %s is not an edge type of the graph" % (m, et))
+            nxt = self.metapath[m + 1] if m + 1 < M else None
+            if nxt is not None and et[2] != nxt[0]:
+                raise ValueError("metapath step %d: broken chain, it ends at %r and step %d starts at %r" % (m, et[2], m + 1, nxt[0]))
+        if int(walk_length) > M and self.metapath[-1][2] != self.metapath[0][0]:
+            raise ValueError("metapath step %d: open path, it ends at %r, not at %r where step 0 starts, and walk_length = %d > %d "
+                             "steps" % (M - 1, self.metapath[-1][2], self.metapath[0][0], int(walk_length), M))
+        self.type_count = [_num_nodes(data[t]) for t in self.node_types]
+        self.start, self.end, total = {}, {}, 0
+        for t, n in zip(self.node_types, self.type_count):
+            self.start[t], self.end[t] = total, total + n
+            total += n
+        self.dummy_idx, self.num_embeddings, self.global_ids = total, total + 1, bool(global_ids)
+        self._step_src, self._step_dst = [tix[et[0]] for et in self.metapath], [tix[et[2]] for et in self.metapath]
+        self._n_edges = [int(data[et].edge_index.shape[1]) for et in self.metapath]
+        self.batch_size, self.drop_last, self.seed, self.call_id0 = int(batch_size), drop_last, int(seed), int(call_id0)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.form = int(form)
+        self._shape = (int(walk_length), int(context_size), int(walks_per_node), int(num_negative_samples))
+        # sizes only: refuses a bad shape here, on the host (C > L, R < 1, K < 0, ...); _prepare puts the CSRs behind it
+        self.cfg = self._config([_cabi.graph_sizing(self.type_count[s], e) for s, e in zip(self._step_src, self._n_edges)])
+        n_in = self.type_count[self._step_src[0]]
+        nodes = torch.arange(n_in) if input_nodes is None else input_nodes
+        self.input_nodes = _checked_inputs(nodes, n_in)
+        pos_rows, neg_rows = _cabi.mp_skipgram_capacity(self.cfg, self.batch_size)
+        per_call = (pos_rows + neg_rows) * self.cfg.context_size * 8 + \
+            _cabi.mp_skipgram_workspace_bytes(self.cfg, 1, self.batch_size, self.form)
+        self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // max(per_call, 1)))
+        self._graph = self._ws = None
+        self.epoch = 0
+
+    def _config(self, graphs):
+        starts = [self.start[t] for t in self.node_types] if self.global_ids else None
+        return _cabi.mp_skipgram_config(graphs, self._step_src, self._step_dst, self.type_count, *self._shape,
+                                        type_start=starts, pad_value=self.dummy_idx if self.global_ids else -1)
+
+    def _prepare(self):
+        if self._graph is not None:
+            return
+        self.input_nodes = self.input_nodes.to(self.device)
+        self._graph = {}                                             # edge type -> its CSR view, built once
+        for et, s, d in zip(self.metapath, self._step_src, self._step_dst):
+            if et in self._graph:
+                continue
+            n_src, n_dst = self.type_count[s], self.type_count[d]
+            ptrs, idx, _ = _host.to_csr(self.data[et].edge_index.to(self.device), (n_src, n_dst))
+            small = max(n_src, n_dst) < 2 ** 31 and idx.numel() < 2 ** 31
+            self._graph[et] = _cabi.graph_view(ptrs, idx, indices32=idx.to(torch.int32) if small else None,
+                                               ptrs32=ptrs.to(torch.int32) if small else None)
+        self.cfg = self._config([self._graph[et] for et in self.metapath])
+
+    def _launch(self, seeds: Tensor, call_id: int) -> SkipGramSuperBatch:
+        need = _cabi.mp_skipgram_workspace_bytes(self.cfg, seeds.shape[0], seeds.shape[1], self.form)
+        if need and (self._ws is None or self._ws.numel() * 8 < need):
+            self._ws = torch.empty(need // 8, dtype=torch.int64, device=self.device)
+        pos, neg = _cabi.mp_skipgram(self.cfg, seeds, self.seed, call_id, form=self.form, ws=self._ws)
+        return SkipGramSuperBatch(pos, neg, seeds.shape[1], call_id)
 
 
 class LinkSuperBatch(SuperBatch):

@@ -20,6 +20,8 @@ loader.HeteroNeighborLoader(..., unique=True) for mini-batches.
 random_walk returns the [n, walk_length + 1] walks of one call.  Node2Vec training batches -- the walks cut into context
 windows plus negative rows, many mini-batches per launch -- come from Node2VecLoader (exported by the package;
 tg_rw_skipgram, csrc/rw_skipgram.hip): it yields objects with pos_rw [rows, context_size], neg_rw, batch_size, call_id.
+MetaPath2VecLoader (tg_mp_skipgram, csrc/mp_skipgram.hip) yields the same objects for walks along a metapath of a typed
+graph, with ids offset into one embedding table (PyG's MetaPath2Vec: start / end per type, dummy_idx, num_embeddings).
 
 Link-level mini-batches -- positive edges, checked negatives, the neighbourhood of all their endpoints, and
 edge_label_index numbered against n_id -- come from LinkNeighborLoader (exported by the package; tg_link_seeds,
