@@ -220,7 +220,10 @@ typedef struct {
                                      buys nothing -- both kernels are bound by vector-ALU work -- and every part costs 0.2 ms) */
     int32_t stage_part_min_batches; /* ... as long as every part keeps at least this many batches (default 1024) */
     int32_t stage_sort_blocks;      /* staged form: workgroups of the item sort = rows of its histogram = persistent workgroups
-                                       of the first kernel (default 768, at most 1024) */
+                                       of the first kernel (at most 1024).  Default -1 = auto: as many as stay resident on the
+                                       device -- per CU what the first kernel's LDS request and its 128 VGPRs allow, as
+                                       hipOccupancyMaxActiveBlocksPerMultiprocessor confirms (MI355X, u32 `ptrs32` shadow: 4 x 256);
+                                       _set: 0 keeps, < 0 = auto; _get reports -1 for auto */
     int32_t stage_fine;             /* staged form: second sort level (tiles of the coarse-sorted items ordered by vertex in LDS,
                                        so that a gather workgroup's slice lies in a few columns; default 1; < 0 in _set keeps) */
     int32_t stage_concurrent;       /* staged form, two hops, several parts: the parts' whole chains alternate between the caller's
@@ -240,6 +243,15 @@ typedef struct {
 } tg_ns_win_tuning;
 TG_API int tg_ns_win_tuning_get(tg_ns_win_tuning *t);
 TG_API int tg_ns_win_tuning_set(const tg_ns_win_tuning *t);
+
+/* The staged pipeline's first kernel (seeds, hop 0, the items of hop 1).  _first_lds_bytes: the workgroup size (*threads,
+ * optional) and dynamic LDS request it takes for `emit_threads`, the launch's largest fan-out, the coarse buckets and
+ * windows of the graph, and the form of its column starts (narrow = 1: u32, graphs with the `ptrs32` shadow) -- pure
+ * arithmetic, no device needed.  _first_launch: what the last staged launch of this process gave it (rows = persistent
+ * workgroups, workgroups_per_cu = what auto derived, 0 under a forced stage_sort_blocks).  Measurement and tests only. */
+TG_API int tg_ns_win_first_lds_bytes(int32_t emit_threads, int32_t kmax, int32_t n_coarse_buckets, int32_t n_windows,
+                              int32_t narrow, int32_t *threads, int64_t *lds_bytes);
+TG_API int tg_ns_win_first_launch(int32_t *rows, int32_t *workgroups_per_cu, int32_t *threads, int32_t *narrow, int64_t *lds_bytes);
 
 /* Per-stage times of the window-ordered launch: tg_ns_win_stage_timing(1) makes every later launch record HIP events
  * between its kernels (on its stream); tg_ns_win_stage_times waits for the last launch and returns up to `cap` stage

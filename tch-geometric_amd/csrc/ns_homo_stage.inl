@@ -87,20 +87,26 @@ __host__ __device__ inline size_t win_stage_tables_bytes(int n_buckets, int n_wi
 // Persistent: workgroup r walks batches b0 + r, b0 + r + gridDim.x, ... and keeps the COARSE histogram of the items it hands
 // over in LDS (row r of `hist`): the counting sort needs no pass of its own over the items to count them (hop 0 is bound
 // by its random line requests; the binary search per new item hides beneath them).
-template <int KMAX, bool REPLACE>
-__global__ void __launch_bounds__(WIN_EMIT_MAX_THREADS) win_stage_first_kernel(const WinParams p, const int k0) {
+// NARROW (the graph has the u32 `ptrs32` shadow): u32 column starts in LDS -- with the default shapes the request drops
+// from 42 376 to 38 280 bytes, under the 40 960 at which four workgroups share a CU's 160 KB instead of three.
+// Registers: fan-outs up to 16 are held to four wavefronts per SIMD (128 VGPRs; the lean ticket chain of ns_tickets.h
+// fits them without scratch), so that registers allow the same four workgroups of 256 per CU as the LDS; KMAX = 32
+// (without replacement: 183 VGPRs) stays at two.
+template <int KMAX, bool REPLACE, bool NARROW>
+__global__ void __launch_bounds__(WIN_EMIT_MAX_THREADS, (KMAX <= 16 ? 4 : 2)) win_stage_first_kernel(const WinParams p, const int k0) {
     extern __shared__ __align__(16) unsigned char smem[];
-    uint32_t *lhist = reinterpret_cast<uint32_t *>(smem + win_emit_lds_bytes(p.kmax, blockDim.x >> 6, WIN_STAGE_FIRST_RC));
+    uint32_t *lhist = reinterpret_cast<uint32_t *>(smem + win_emit_lds_bytes(p.kmax, blockDim.x >> 6, WIN_STAGE_FIRST_RC, NARROW));
     uint32_t *lvtab = lhist + p.n_buckets;
     for (int i = threadIdx.x; i < p.n_buckets; i += blockDim.x) lhist[i] = 0;
     for (int i = threadIdx.x; i <= p.n_windows; i += blockDim.x) lvtab[i] = p.vtab[i];
+    __syncthreads(); // the tables, before the first item is counted (the hop itself starts without a barrier)
     for (int64_t b = p.b0 + blockIdx.x; b < p.b0 + p.n_batches; b += gridDim.x) {
         int64_t *samples = p.samples + b * p.cap_nodes;
-        for (int64_t i = threadIdx.x; i < p.n_seeds; i += blockDim.x) samples[i] = p.seeds[b * p.n_seeds + i]; // :184
+        // :184 -- output only: the hop reads the seeds themselves, so no barrier orders this copy
+        for (int64_t i = threadIdx.x; i < p.n_seeds; i += blockDim.x) samples[i] = p.seeds[b * p.n_seeds + i];
         const CallKey ck = call_key(p.seed, p.call_id + (uint64_t)b, p.tag);
         if (threadIdx.x == 0) p.call_keys[b] = ck;
-        __syncthreads();
-        const WinState st = win_emit_hop<WinItemN, KMAX, REPLACE, true, false, true, true, WIN_STAGE_FIRST_RC>(
+        const WinState st = win_emit_hop<WinItemN, KMAX, REPLACE, true, false, true, true, WIN_STAGE_FIRST_RC, NARROW>(
             p, smem, b, 0, k0, WinState{0, p.n_seeds, 0, 0}, ck, lhist);
         win_store_state(p, b, 0, st);
         __syncthreads(); // the LDS staging of this batch is done before the next batch reuses it

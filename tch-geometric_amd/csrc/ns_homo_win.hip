@@ -28,6 +28,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 
 #include "ns_tickets.h"
 #include "stage_bits.h"
@@ -155,20 +156,21 @@ constexpr int WIN_EMIT_MAX_THREADS = 512; // launch bound of the STAGED form's f
 constexpr int WIN_STAGE_FIRST_RC = 16; // staged form: rounds of the first kernel (hop 0: usually <= 1 024 seeds) ...
 constexpr int WIN_STAGE_SIDE_RC = 8;   // ... and of the side pass, which shares the CUs with the gather kernel
 
-// K1's LDS: chunk offsets | fbase | column starts [slots] i64 | degrees [slots] u32 | per wave: staged positions
-// [64*k] u32, staged lanes [64*k] u8
+// K1's LDS: chunk offsets | fbase | column starts [slots] i64 (u32 in the narrow form) | degrees [slots] u32 | per wave:
+// staged positions [64*k] u32, staged lanes [64*k] u8
 __host__ __device__ inline size_t win_emit_wave_lds_bytes(int kmax) { // ... + the chunk's drawing lanes [64] u8
     return (size_t)64 * kmax * sizeof(uint32_t) + (((size_t)64 * kmax + 15) & ~(size_t)15) + 64;
 }
 
 // rc = chunks per round (WIN_ROUND_CHUNKS by default; the staged form's first and side kernels take fewer: less LDS, more
-// resident workgroups)
-__host__ __device__ inline size_t win_emit_head_bytes(int rc = WIN_ROUND_CHUNKS) {
+// resident workgroups).  narrow: the column starts are kept as u32 (the graph brings the `ptrs32` shadow, so every one of
+// them fits): 4 bytes less per slot -- what lets a fourth workgroup of the staged first kernel share a CU
+__host__ __device__ inline size_t win_emit_head_bytes(int rc = WIN_ROUND_CHUNKS, bool narrow = false) {
     return (((size_t)(rc + 1) * sizeof(uint32_t) + 15) & ~(size_t)15) + 16 +
-           (size_t)rc * 64 * (sizeof(int64_t) + sizeof(uint32_t));
+           (size_t)rc * 64 * ((narrow ? sizeof(uint32_t) : sizeof(int64_t)) + sizeof(uint32_t));
 }
-__host__ __device__ inline size_t win_emit_lds_bytes(int kmax, int n_waves, int rc = WIN_ROUND_CHUNKS) {
-    return win_emit_head_bytes(rc) + (size_t)n_waves * win_emit_wave_lds_bytes(kmax);
+__host__ __device__ inline size_t win_emit_lds_bytes(int kmax, int n_waves, int rc = WIN_ROUND_CHUNKS, bool narrow = false) {
+    return win_emit_head_bytes(rc, narrow) + (size_t)n_waves * win_emit_wave_lds_bytes(kmax);
 }
 
 // ---------------------------------------------------------------- K1: counts, offsets, draws, the three streams, items
@@ -180,10 +182,14 @@ __host__ __device__ inline size_t win_emit_lds_bytes(int kmax, int n_waves, int 
 // p.hop / p.k) so that one kernel can run consecutive hops of its batch back to back.
 __device__ __forceinline__ void win_next_item(const WinParams &p, int64_t b, uint32_t rel, uint32_t v, uint32_t *lhist); // staged form
 
-// NEXT (DIRECT only; staged form): every new sample is also handed to the next hop as an 8-byte item.
+// NEXT (DIRECT only; the staged form's first kernel, so: hop 0, the frontier IS the batch's seeds): every new sample is
+// also handed to the next hop as an 8-byte item.  The frontier is then read from `p.seeds` (not back from the copy the
+// workgroup has just stored into `samples`: one dependent round trip and the barrier that ordered it less), and the new
+// samples leave as streaming stores -- the items carry the vertex, no kernel of that pipeline reads them again.
 // ITEMS = false (staged form's side pass): only the three streams -- no items, no item-range atomics.
+// NARROW (needs p.ptrs32): the column starts are held in LDS as u32 (win_emit_head_bytes); chosen by the host, per launch.
 template <typename Item, int KMAX, bool REPLACE, bool DIRECT, bool FOLD = false, bool NEXT = false, bool ITEMS = true,
-          int RC = WIN_ROUND_CHUNKS>
+          int RC = WIN_ROUND_CHUNKS, bool NARROW = false>
 __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned char *smem, const int64_t b, const int hop,
                                                  const int k, const WinState st, const CallKey ck,
                                                  uint32_t *lhist = nullptr) {
@@ -192,9 +198,10 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
     constexpr int64_t ROUND_SLOTS = (int64_t)RC * 64;
     const size_t off_bytes = (((size_t)(RC + 1) * sizeof(uint32_t)) + 15) & ~(size_t)15;
     int64_t *shared_fbase = reinterpret_cast<int64_t *>(smem + off_bytes);
-    int64_t *col0 = reinterpret_cast<int64_t *>(smem + off_bytes + 16);
-    uint32_t *cdeg = reinterpret_cast<uint32_t *>(smem + off_bytes + 16 + (size_t)ROUND_SLOTS * sizeof(int64_t));
-    unsigned char *wbase = smem + win_emit_head_bytes(RC) + (size_t)wave * win_emit_wave_lds_bytes(p.kmax);
+    using Col = typename std::conditional<NARROW, uint32_t, int64_t>::type;
+    Col *col0 = reinterpret_cast<Col *>(smem + off_bytes + 16);
+    uint32_t *cdeg = reinterpret_cast<uint32_t *>(smem + off_bytes + 16 + (size_t)ROUND_SLOTS * sizeof(Col));
+    unsigned char *wbase = smem + win_emit_head_bytes(RC, NARROW) + (size_t)wave * win_emit_wave_lds_bytes(p.kmax);
     uint32_t *spos = reinterpret_cast<uint32_t *>(wbase);
     uint8_t *slane = wbase + (size_t)64 * p.kmax * sizeof(uint32_t);
     Item *items = static_cast<Item *>(p.items_in);
@@ -215,10 +222,10 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
         lo[1] = ne;
         lo[2] = n_seeds + ne;
         // this batch's range of the hop's flat item array (order between batches does not matter)
-        if (!FOLD) *shared_fbase = (DIRECT || !ITEMS) ? 0 : (int64_t)atomicAdd(&p.n_items[hop], (unsigned long long)(end - begin));
+        if (!FOLD && !NEXT) *shared_fbase = (DIRECT || !ITEMS) ? 0 : (int64_t)atomicAdd(&p.n_items[hop], (unsigned long long)(end - begin));
     }
-    if (!FOLD) __syncthreads();
-    const int64_t fbase = FOLD ? b * p.item_pitch : *shared_fbase;
+    if (!FOLD && !NEXT) __syncthreads();
+    const int64_t fbase = FOLD ? b * p.item_pitch : (NEXT ? 0 : *shared_fbase); // NEXT: direct, no item range to hand out
 
     for (int64_t round_begin = begin; round_begin < end; round_begin += ROUND_SLOTS) {
         const int64_t round_end = min(end, round_begin + ROUND_SLOTS);
@@ -227,9 +234,9 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
             const int64_t i = round_begin + (int64_t)c * 64 + lane;
             int64_t e0 = 0, deg = 0;
             if (i < round_end) {
-                int64_t w = samples[i];
+                int64_t w = NEXT ? p.seeds[b * n_seeds + i] : samples[i]; // NEXT: begin == 0, end == n_seeds
                 TG_CHECK_VERTEX(p, w);
-                if (p.ptrs32) {
+                if (NARROW || p.ptrs32) {
                     e0 = (int64_t)p.ptrs32[w];
                     deg = (int64_t)p.ptrs32[w + 1] - e0;
                 } else {
@@ -237,7 +244,7 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                     deg = p.ptrs[w + 1] - e0;
                 }
             }
-            col0[c * 64 + lane] = e0;
+            col0[c * 64 + lane] = (Col)e0;
             cdeg[c * 64 + lane] = deg > 0 ? (uint32_t)deg : 0u;
             const uint32_t cnt = (deg <= 0) ? 0u : (REPLACE ? (uint32_t)k : (uint32_t)min(deg, (int64_t)k));
             const uint32_t tot = wave_sum(cnt);
@@ -254,7 +261,7 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
         for (int c = wave; c < nc; c += n_waves) { // pass B: draws, items, the three streams
             const int64_t i0 = round_begin + (int64_t)c * 64;
             const int64_t i = i0 + lane;
-            const int64_t e0 = col0[c * 64 + lane];
+            const int64_t e0 = (int64_t)col0[c * 64 + lane];
             const uint32_t n = cdeg[c * 64 + lane];
             const uint32_t cnt = (n == 0) ? 0u : (REPLACE ? (uint32_t)k : min(n, (uint32_t)k));
             const uint64_t did = (uint64_t)(p.id_base + i);
@@ -319,7 +326,7 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                             slane[excl + sl] = (uint8_t)lane;
                         }
                     } else {
-                        sample_tickets_given<KMAX>(r, n, k, spos, slane, excl, lane);
+                        sample_tickets_given<KMAX, NEXT>(r, n, k, spos, slane, excl, lane); // NEXT: the lean chain (ns_tickets.h)
                     }
                 }
             } else if (cnt > 0) {
@@ -331,7 +338,7 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                         slane[excl + s] = (uint8_t)lane;
                     }
                 } else {
-                    sample_tickets<KMAX>(ck, did, n, k, spos, slane, excl, lane);
+                    sample_tickets<KMAX, NEXT>(ck, did, n, k, spos, slane, excl, lane);
                 }
             }
             wave_lds_handoff();
@@ -344,7 +351,7 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                         const uint32_t q = q0 + (uint32_t)(u * 64 + lane);
                         const uint32_t qq = q < total ? q : 0u;
                         l4[u] = slane[qq];
-                        ep[u] = col0[c * 64 + l4[u]] + (int64_t)spos[qq];
+                        ep[u] = (int64_t)col0[c * 64 + l4[u]] + (int64_t)spos[qq];
                     }
                     if (p.indices32) {
 #pragma unroll
@@ -358,7 +365,10 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                         const uint32_t q = q0 + (uint32_t)(u * 64 + lane);
                         if (q < total) {
                             const int64_t e = e_chunk + q;
-                            samples[n_seeds + e] = v[u]; // :215 (the next hop's frontier)
+                            if (NEXT)
+                                __builtin_nontemporal_store(v[u], &samples[n_seeds + e]); // :215 (output only: the item carries it on)
+                            else
+                                samples[n_seeds + e] = v[u]; // :215 (the next hop's frontier)
                             if (put_rows) __builtin_nontemporal_store(n_seeds + e, &p.rows[b * p.cap_edges + e]);
                             __builtin_nontemporal_store(i0 + (int64_t)l4[u], &cols[e]);
                             __builtin_nontemporal_store(ep[u], &eidx[e]);
@@ -389,7 +399,7 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                     if ((uint32_t)lane < head_r) __builtin_nontemporal_store(n_seeds + ea + (int64_t)lane, &rows[ea + lane]);
                     if ((uint32_t)lane < head_c) __builtin_nontemporal_store(i0 + (int64_t)slane[lane], &cols[ea + lane]);
                     if ((uint32_t)lane < head_e)
-                        __builtin_nontemporal_store(col0[c * 64 + slane[lane]] + (int64_t)spos[lane], &eidx[ea + lane]);
+                        __builtin_nontemporal_store((int64_t)col0[c * 64 + slane[lane]] + (int64_t)spos[lane], &eidx[ea + lane]);
                 }
                 if (put_rows)
                 for (uint32_t q = head_r + 2u * lane; q < total; q += 128) {
@@ -413,10 +423,10 @@ __device__ __forceinline__ WinState win_emit_hop(const WinParams &p, unsigned ch
                     const int l0 = slane[q];
                     if (q + 1 < total) {
                         const int l1 = slane[q + 1];
-                        i64x2 x = {col0[c * 64 + l0] + (int64_t)spos[q], col0[c * 64 + l1] + (int64_t)spos[q + 1]};
+                        i64x2 x = {(int64_t)col0[c * 64 + l0] + (int64_t)spos[q], (int64_t)col0[c * 64 + l1] + (int64_t)spos[q + 1]};
                         __builtin_nontemporal_store(x, reinterpret_cast<i64x2 *>(&eidx[e]));
                     } else
-                        __builtin_nontemporal_store(col0[c * 64 + l0] + (int64_t)spos[q], &eidx[e]);
+                        __builtin_nontemporal_store((int64_t)col0[c * 64 + l0] + (int64_t)spos[q], &eidx[e]);
                 }
             }
             wave_lds_handoff();
@@ -811,7 +821,7 @@ static WinTuning &win_tuning() {
         win_env_int("TG_WIN_STAGE_EMIT_THREADS", 256),
         win_env_int("TG_WIN_STAGE_PARTS", 1),
         win_env_int("TG_WIN_STAGE_PART_MIN_BATCHES", 1024),
-        win_env_int("TG_WIN_STAGE_SORT_BLOCKS", 768),
+        win_env_int("TG_WIN_STAGE_SORT_BLOCKS", 0), // <= 0: as many as stay resident (win_run_staged)
         win_env_int("TG_WIN_STAGE_FINE", 1),
         win_env_int("TG_WIN_STAGE_CONCURRENT", 0),
         win_env_int("TG_WIN_STAGE_SPLIT", 0),
@@ -1059,6 +1069,58 @@ static WinSide &win_side() {
     return s;
 }
 
+// LDS of the device a launch runs on, asked once per device: what a CU holds (how many workgroups share it) and what one
+// workgroup may be given (a request beyond 64 KB has to be allowed per kernel: hipFuncSetAttribute)
+struct WinDeviceLds {
+    int cus, per_cu, per_block;
+};
+static int win_device_lds(WinDeviceLds *out) {
+    constexpr int MAX_DEV = 64;
+    static std::mutex mu;
+    static WinDeviceLds known[MAX_DEV];
+    static bool have[MAX_DEV] = {};
+    int dev = 0;
+    TG_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    if (dev < 0 || dev >= MAX_DEV || !have[dev]) {
+        WinDeviceLds d;
+        TG_HIP(hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev));
+        TG_HIP(hipDeviceGetAttribute(&d.per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
+        TG_HIP(hipDeviceGetAttribute(&d.per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        if (dev < 0 || dev >= MAX_DEV) {
+            *out = d;
+            return TG_OK;
+        }
+        known[dev] = d;
+        have[dev] = true;
+    }
+    *out = known[dev];
+    return TG_OK;
+}
+
+// The staged first kernel's LDS request: the hop's head and per-wave staging (narrow: u32 column starts), the coarse
+// counters and the vertex table
+static size_t win_stage_first_lds(int kmax, int threads, int n_coarse, int n_windows, bool narrow) {
+    return win_emit_lds_bytes(kmax, threads / 64, WIN_STAGE_FIRST_RC, narrow) + win_stage_tables_bytes(n_coarse, n_windows);
+}
+// the workgroup size it takes: halved until the request fits what a workgroup gets without asking
+static int win_stage_first_threads(int emit_threads, int kmax, int n_coarse, int n_windows, bool narrow) {
+    int threads = std::min(emit_threads, WIN_EMIT_MAX_THREADS);
+    while (threads > 64 && win_stage_first_lds(kmax, threads, n_coarse, n_windows, narrow) > 64 * 1024)
+        threads = ((threads >> 1) + 63) & ~63;
+    return threads;
+}
+
+// what the last staged launch gave its first kernel (tg_ns_win_first_launch): measurement and tests only
+struct WinFirstLaunch {
+    int32_t rows = 0, per_cu = 0, threads = 0, narrow = 0;
+    int64_t lds_bytes = 0;
+};
+static WinFirstLaunch &win_first_launch() {
+    static WinFirstLaunch f;
+    return f;
+}
+
 // KFIRST: unroll bound of hop 0's direct kernel (any fan-out up to TG_MAX_FANOUT); KMAX: that of the ordered hops' gather /
 // emit / side kernels (<= 16 with one-chunk slots; 12 where the fan-outs allow: ~20 VGPRs less in the gather kernel)
 template <int W, int KFIRST, int KMAX, bool REPLACE>
@@ -1105,11 +1167,49 @@ static int win_run_staged(WinParams p, const tg_graph *csc, int64_t n_batches, c
     // launches run their earlier hops whole and only the LAST hop in parts
     const bool first_in_parts = parts > 1 && n_hops == 2;
 
-    int fthreads = std::min(t.emit_threads, WIN_EMIT_MAX_THREADS);
-    while (fthreads > 64 && win_emit_lds_bytes(p.kmax, fthreads / 64, WIN_STAGE_FIRST_RC) + tables > 64 * 1024)
-        fthreads = ((fthreads >> 1) + 63) & ~63;
+    WinDeviceLds dl;
+    {
+        const int rc = win_device_lds(&dl);
+        if (rc != TG_OK) return rc;
+    }
+    const bool narrow_cols = p.ptrs32 != nullptr; // every column start fits 32 bits: the first kernel keeps them as u32 in LDS
+    const int fthreads = win_stage_first_threads(t.emit_threads, p.kmax, p.n_buckets, p.n_windows, narrow_cols);
+    const size_t flds = win_stage_first_lds(p.kmax, fthreads, p.n_buckets, p.n_windows, narrow_cols);
+    // The first kernel is persistent and hangs on latency (a dependent chain of random lines per batch), so it gets as many
+    // workgroups as stay RESIDENT: per CU, what its LDS request leaves of the CU's LDS and what the 128 VGPRs it is held
+    // to for fan-outs <= 16 leave of the register file (512 per SIMD lane: 4 wavefronts on each of 4 SIMDs), with the
+    // runtime's occupancy query as the arbiter (allocation granules, and the KFIRST = 32 instances, which take more
+    // registers: two wavefronts per SIMD).  One query per shape.  The level-1 sort kernels share the row count (row r of
+    // the histogram = what workgroup r counted): at 1 024 rows against 768 their stage times stay within 0.01 ms.
+    int first_per_cu = 0;
+    if (t.stage_sort_blocks <= 0) {
+        struct Seen {
+            int dev = -1, threads = 0, narrow = 0, per_cu = 0;
+            size_t lds = 0;
+        };
+        static Seen seen; // per instantiation of this function template = per pair of first kernels
+        static std::mutex seen_mu;
+        int dev = 0;
+        TG_HIP(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lock(seen_mu);
+        if (seen.dev != dev || seen.threads != fthreads || seen.narrow != (int)narrow_cols || seen.lds != flds) {
+            const int by_lds = (int)((size_t)dl.per_cu / flds), by_regs = (4 * (512 / 128)) / (fthreads / 64);
+            int by_runtime = 0;
+            if (narrow_cols)
+                TG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_runtime, win_stage_first_kernel<KFIRST, REPLACE, true>, fthreads, flds));
+            else
+                TG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_runtime, win_stage_first_kernel<KFIRST, REPLACE, false>, fthreads, flds));
+            seen.dev = dev;
+            seen.threads = fthreads;
+            seen.narrow = (int)narrow_cols;
+            seen.lds = flds;
+            seen.per_cu = std::max(1, std::min(std::min(by_lds, by_regs), by_runtime > 0 ? by_runtime : 1));
+        }
+        first_per_cu = seen.per_cu;
+    }
+    const int64_t rows_wanted = t.stage_sort_blocks > 0 ? (int64_t)t.stage_sort_blocks : (int64_t)first_per_cu * std::max(dl.cus, 1);
     auto rows_of = [&](int64_t nb) { // sort workgroups = rows of the histogram = persistent workgroups of the first kernel
-        return (int32_t)std::min<int64_t>(std::min(std::max(t.stage_sort_blocks, 1), WIN_MAX_ROWS), nb);
+        return (int32_t)std::min<int64_t>(std::min<int64_t>(std::max<int64_t>(rows_wanted, 1), WIN_MAX_ROWS), nb);
     };
     auto part_tables = [&](int part) {
         p.hist = hist0 + (size_t)part * WIN_MAX_ROWS * (WIN_MAX_BUCKETS / 8);
@@ -1123,8 +1223,18 @@ static int win_run_staged(WinParams p, const tg_graph *csc, int64_t n_batches, c
         p.n_rows = rows_of(nb);
         p.next_pitch = pitch_of(1);
         p.next_idx_bits = bits_of(p.next_pitch);
-        hipLaunchKernelGGL((win_stage_first_kernel<KFIRST, REPLACE>), dim3((unsigned)p.n_rows), dim3(fthreads),
-                           win_emit_lds_bytes(p.kmax, fthreads / 64, WIN_STAGE_FIRST_RC) + tables, ps, p, (int)fanout[0]);
+        if (narrow_cols)
+            hipLaunchKernelGGL((win_stage_first_kernel<KFIRST, REPLACE, true>), dim3((unsigned)p.n_rows), dim3(fthreads), flds, ps,
+                               p, (int)fanout[0]);
+        else
+            hipLaunchKernelGGL((win_stage_first_kernel<KFIRST, REPLACE, false>), dim3((unsigned)p.n_rows), dim3(fthreads), flds, ps,
+                               p, (int)fanout[0]);
+        WinFirstLaunch &fl = win_first_launch();
+        fl.rows = p.n_rows;
+        fl.per_cu = first_per_cu;
+        fl.threads = fthreads;
+        fl.narrow = (int32_t)narrow_cols;
+        fl.lds_bytes = (int64_t)flds;
     };
     // stage_concurrent (two hops, several parts): the parts' WHOLE chains alternate between the caller's stream and the side
     // stream and run beside each other -- what two launches in flight give a caller, inside one launch
@@ -1172,13 +1282,18 @@ static int win_run_staged(WinParams p, const tg_graph *csc, int64_t n_batches, c
             const size_t elds = win_stage_emit_lds_bytes(W, p.k, ethreads / 64, rc, split);
             int gthreads = t.stage_gather_threads;
             const size_t per_wave = (size_t)(64 * (W + 1) + 64) * sizeof(uint32_t);
-            while (gthreads > 64 && (size_t)(gthreads / 64) * per_wave > 128 * 1024) gthreads = ((gthreads >> 1) + 63) & ~63;
-            if ((size_t)(gthreads / 64) * per_wave > 64 * 1024) { // gfx950: 160 KB of LDS per CU, a workgroup may take it all when asked
-                static bool raised = false; // per instantiation of this function template = per gather kernel
-                if (!raised) {
+            // gfx950: 160 KB of LDS per CU, a workgroup may take it all when asked.  Where the device gives a workgroup less
+            // (64 KB parts), the workgroup shrinks instead and nothing is asked for
+            const size_t gcap = std::max<size_t>(64 * 1024, std::min<size_t>((size_t)std::max(dl.per_block, 0), 128 * 1024));
+            while (gthreads > 64 && (size_t)(gthreads / 64) * per_wave > gcap) gthreads = ((gthreads >> 1) + 63) & ~63;
+            if ((size_t)(gthreads / 64) * per_wave > 64 * 1024) {
+                static int raised_on = -1; // per instantiation of this function template = per gather kernel; per device
+                int dev = 0;
+                TG_HIP(hipGetDevice(&dev));
+                if (raised_on != dev) {
                     TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&win_stage_gather_kernel<W, KMAX, REPLACE>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                    raised = true;
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)gcap));
+                    raised_on = dev;
                 }
             }
             const int gblocks = (std::max(t.stage_gather_blocks, 8) + 7) & ~7;
@@ -1454,7 +1569,7 @@ extern "C" int tg_ns_win_tuning_get(tg_ns_win_tuning *t) {
     t->stage_emit_threads = w.stage_emit_threads;
     t->stage_parts = w.stage_parts;
     t->stage_part_min_batches = w.stage_part_min_batches;
-    t->stage_sort_blocks = w.stage_sort_blocks;
+    t->stage_sort_blocks = w.stage_sort_blocks > 0 ? w.stage_sort_blocks : -1; // -1: auto
     t->stage_fine = w.stage_fine;
     t->stage_concurrent = w.stage_concurrent;
     t->stage_split = w.stage_split;
@@ -1490,7 +1605,7 @@ extern "C" int tg_ns_win_tuning_set(const tg_ns_win_tuning *t) {
     if (t->stage_emit_threads >= 64 && t->stage_emit_threads <= 1024) w.stage_emit_threads = t->stage_emit_threads & ~63;
     if (t->stage_parts > 0) w.stage_parts = t->stage_parts;
     if (t->stage_part_min_batches > 0) w.stage_part_min_batches = t->stage_part_min_batches;
-    if (t->stage_sort_blocks > 0) w.stage_sort_blocks = t->stage_sort_blocks;
+    if (t->stage_sort_blocks != 0) w.stage_sort_blocks = t->stage_sort_blocks > 0 ? t->stage_sort_blocks : 0; // < 0: auto
     if (t->stage_fine >= 0) w.stage_fine = t->stage_fine != 0;
     if (t->stage_concurrent >= 0) w.stage_concurrent = t->stage_concurrent != 0;
     if (t->stage_split >= 0) w.stage_split = t->stage_split != 0;
@@ -1498,6 +1613,27 @@ extern "C" int tg_ns_win_tuning_set(const tg_ns_win_tuning *t) {
     if (t->store_align64 >= 0) w.store_align64 = t->store_align64 != 0;
     if (t->stage_fine_sub_bits > 0) w.stage_fine_sub_bits = std::min(std::max(t->stage_fine_sub_bits, 4), tg::WIN_FINE_SUB_BITS_MAX);
     if (t->stage_fine_blocks > 0) w.stage_fine_blocks = std::min((t->stage_fine_blocks + 7) & ~7, 8192);
+    return TG_OK;
+}
+
+extern "C" int tg_ns_win_first_lds_bytes(int32_t emit_threads, int32_t kmax, int32_t n_coarse_buckets, int32_t n_windows,
+                                         int32_t narrow, int32_t *threads, int64_t *lds_bytes) {
+    TG_REQUIRE(lds_bytes && emit_threads >= 64 && emit_threads <= 1024 && emit_threads % 64 == 0 && kmax >= 1 && kmax <= TG_MAX_FANOUT &&
+                   n_coarse_buckets >= 0 && n_windows >= 0,
+               "tg_ns_win_first_lds_bytes: bad arguments");
+    const int th = tg::win_stage_first_threads(emit_threads, kmax, n_coarse_buckets, n_windows, narrow != 0);
+    if (threads) *threads = th;
+    *lds_bytes = (int64_t)tg::win_stage_first_lds(kmax, th, n_coarse_buckets, n_windows, narrow != 0);
+    return TG_OK;
+}
+
+extern "C" int tg_ns_win_first_launch(int32_t *rows, int32_t *workgroups_per_cu, int32_t *threads, int32_t *narrow, int64_t *lds_bytes) {
+    const tg::WinFirstLaunch &f = tg::win_first_launch();
+    if (rows) *rows = f.rows;
+    if (workgroups_per_cu) *workgroups_per_cu = f.per_cu;
+    if (threads) *threads = f.threads;
+    if (narrow) *narrow = f.narrow;
+    if (lds_bytes) *lds_bytes = f.lds_bytes;
     return TG_OK;
 }
 

@@ -66,26 +66,50 @@ __device__ __forceinline__ void sample_tickets_reg(CallKey ck, uint64_t id, uint
     ticket_chain<KMAX>(r, n, k, pos);
 }
 
-// ... staged in LDS in output order: positions at spos[out_base + s], the drawing lane beside them
-template <int KMAX>
+// ... staged in LDS in output order: positions at spos[out_base + s], the drawing lane beside them.
+// LEAN: the same chain with every position stored the moment it is known -- no pos[] beside the draws and the displaced
+// entries (the draws ARE the chain's keys).  The staged first kernel takes this form: at KMAX = 16 it then fits the 128
+// VGPRs of four wavefronts per SIMD (147 before); same positions, word for word.
+template <int KMAX, bool LEAN = false>
 __device__ __forceinline__ void sample_tickets_given(const uint32_t (&r)[KMAX], uint32_t n, int k, uint32_t *spos,
                                                      uint8_t *slane, uint32_t out_base, int lane) {
-    uint32_t pos[KMAX];
-    ticket_chain<KMAX>(r, n, k, pos);
+    if constexpr (LEAN) {
+        uint32_t vals[KMAX];
 #pragma unroll
-    for (int s = 0; s < KMAX; ++s) {
-        if (s < k) {
-            spos[out_base + s] = pos[s];
-            slane[out_base + s] = (uint8_t)lane;
+        for (int s = 0; s < KMAX; ++s) {
+            if (s < k) {
+                const uint32_t m = (n - 1u) - (uint32_t)s;
+                const uint32_t rs = r[s];
+                const uint32_t last = m - 1u;
+                uint32_t tr = rs, tl = last;
+#pragma unroll
+                for (int j = 0; j < s; ++j) {
+                    tr = (r[j] == rs) ? vals[j] : tr;
+                    tl = (r[j] == last) ? vals[j] : tl;
+                }
+                vals[s] = tl;
+                spos[out_base + s] = (tr < n - (uint32_t)k) ? (uint32_t)k + tr : (uint32_t)s;
+                slane[out_base + s] = (uint8_t)lane;
+            }
+        }
+    } else {
+        uint32_t pos[KMAX];
+        ticket_chain<KMAX>(r, n, k, pos);
+#pragma unroll
+        for (int s = 0; s < KMAX; ++s) {
+            if (s < k) {
+                spos[out_base + s] = pos[s];
+                slane[out_base + s] = (uint8_t)lane;
+            }
         }
     }
 }
-template <int KMAX>
+template <int KMAX, bool LEAN = false>
 __device__ __forceinline__ void sample_tickets(CallKey ck, uint64_t id, uint32_t n, int k, uint32_t *spos,
                                                uint8_t *slane, uint32_t out_base, int lane) {
     uint32_t r[KMAX];
     slot_draws<KMAX, false>(ck, id, n, k, r);
-    sample_tickets_given<KMAX>(r, n, k, spos, slane, out_base, lane);
+    sample_tickets_given<KMAX, LEAN>(r, n, k, spos, slane, out_base, lane);
 }
 
 // k draws of U[0, n) (sampling.rs:57-69), staged like the tickets

@@ -29,7 +29,7 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_sanitize_range", "tg_ns_hop_segments", "tg_het_hop_begin_all", "tg_het_hop_end_all", "tg_part_requests", "tg_part_count", "tg_part_scan_workspace_bytes", "tg_part_sample", "tg_part_emit", "tg_part_slot_words", "tg_part_sample_slots", "tg_part_emit_slots", "tg_part_unpack", "tg_part_pack", "tg_compact_rows", "tg_budget_capacity",
            "tg_budget_workspace_bytes", "tg_budget_sample", "tg_ns_homo_workspace_bytes", "tg_ns_homo_batched_ws", "tg_het_meta_words", "tg_het_step_begin",
            "tg_het_step_end", "tg_het_hop_end", "tg_ns_homo_batched_form", "tg_ns_win_tuning_get", "tg_ns_win_tuning_set",
-           "tg_ns_win_stage_timing", "tg_ns_win_stage_times", "tg_probe_ns_sol",
+           "tg_ns_win_stage_timing", "tg_ns_win_stage_times", "tg_ns_win_first_lds_bytes", "tg_ns_win_first_launch", "tg_probe_ns_sol",
            "tg_debug_bounds_set_flag", "tg_part_sample_workspace_bytes", "tg_part_sample_ws",
            "tg_part_sample_order_thresholds", "tg_ns_homo_batched_pipeline", "tg_graph_max_degree",
            "tg_ns_homo_workspace_bytes_for", "tg_ns_homo_batched_workspace_bytes", "tg_hgt_batched_capacity",
@@ -361,6 +361,25 @@ def ns_win_tuning_set(**kw):
         setattr(t, k, int(v))
     check(lib.tg_ns_win_tuning_set(C.byref(t)))
     return before
+
+
+STAGE_SORT_BLOCKS_AUTO = -1   # ns_win_tuning_set(stage_sort_blocks=...): as many persistent workgroups as stay resident (the default)
+
+
+def ns_win_first_lds_bytes(emit_threads, kmax, n_coarse_buckets, n_windows, narrow):
+    """-> (workgroup size, dynamic LDS bytes) of the staged pipeline's first kernel for these shapes; pure arithmetic."""
+    th, nbytes = C.c_int32(0), C.c_int64(0)
+    check(lib.tg_ns_win_first_lds_bytes(C.c_int32(emit_threads), C.c_int32(kmax), C.c_int32(n_coarse_buckets),
+                                        C.c_int32(n_windows), C.c_int32(int(bool(narrow))), C.byref(th), C.byref(nbytes)))
+    return th.value, nbytes.value
+
+
+def ns_win_first_launch():
+    """What the last staged launch gave its first kernel: dict(rows, workgroups_per_cu (0 when stage_sort_blocks was forced),
+    threads, narrow, lds_bytes)."""
+    r, w, th, nw, nbytes = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(lib.tg_ns_win_first_launch(C.byref(r), C.byref(w), C.byref(th), C.byref(nw), C.byref(nbytes)))
+    return dict(rows=r.value, workgroups_per_cu=w.value, threads=th.value, narrow=bool(nw.value), lds_bytes=nbytes.value)
 
 
 def ns_win_stage_timing(enable):
