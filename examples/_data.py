@@ -18,6 +18,15 @@ def fake_dataset(num_nodes=1000, avg_degree=10, channels=64, seed=0, device="cud
                  y=torch.randint(0, 10, (num_nodes,), generator=g).to(device))
 
 
+def fake_temporal_dataset(num_nodes=1000, avg_degree=10, t_max=100, seed=0, device="cuda"):
+    """fake_dataset with an int64 timestamp per edge (`timestamps`, in edge_index order) and a first-seen time per node"""
+    data = fake_dataset(num_nodes, avg_degree, seed=seed, device=device)
+    g = torch.Generator().manual_seed(seed + 1)
+    data.timestamps = torch.randint(0, t_max, (data.edge_index.shape[1],), generator=g).to(device)
+    data.node_time = torch.randint(0, t_max // 2, (num_nodes,), generator=g).to(device)
+    return data
+
+
 def fake_hetero_dataset(num_node_types=3, num_edge_types=6, avg_num_nodes=1000, avg_degree=10, channels=64, seed=0,
                         device="cuda"):
     g = torch.Generator().manual_seed(seed)

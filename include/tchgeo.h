@@ -667,6 +667,66 @@ TG_API int tg_mp_skipgram(const tg_mp_skipgram_config *cfg, const int64_t *seeds
                           const tg_rng *rng, const tg_rw_skipgram_out *out, void *workspace, int64_t workspace_bytes,
                           int32_t form, void *stream);
 
+/* ---- Temporal (CTDNE) skip-gram batches: tg_tempo_random_walk's walks as context windows, with their timestamps -----------
+ * What a temporal skip-gram trainer composes per mini-batch (tempo_random_walk, strided slices + cat for the nodes and for
+ * the timestamps, randint, slices + cat), fused as tg_rw_skipgram fuses Node2Vec's: a walker's [node | ts] row never leaves
+ * LDS as [n, L] tensors, only its windows are written.  A launch samples n_batches = G mini-batches of batch_size = B seeds
+ * (seeds, seeds_ts: device int64 [G, B]; ids < csr->n_major; a start time of -1 admits every edge).  csr, node_ts [n_major],
+ * edge_ts [n_edges, CSR order], win0, win1 are tg_tempo_random_walk's.  L = walk_length counts COLUMNS of a row, as
+ * tg_tempo_random_walk (column 0 is the start; tg_rw_skipgram's T counts steps, L = T + 1); C = context_size (1 <= C <= L)
+ * gives nw = L - C + 1 windows, R = walks_per_node >= 1, K = num_negative_samples >= 0.  W = R * B, U = R * K * B.
+ * Mini-batch g draws with call id rng->call_id + g.
+ *  positives  walker w = r * B + i starts at seeds[g][i] with start time seeds_ts[g][i].  walk_g[w][0..L) and
+ *             walk_ts_g[w][0..L) equal, value for value, tg_tempo_random_walk(start = seeds[g] repeated R times, start_ts
+ *             likewise, n = W, L, window, seed, call id + g): the draws of step l are addressed (call key of TAG_RW_TEMPO,
+ *             id = w * L + l), the chunked one-slot reservoir and the restart draw are that operator's.
+ *             pos_rw[g] is [nw * W, C]: row j * W + w, column c holds walk_g[w][j + c]; pos_ts[g] holds walk_ts_g[w][j + c]
+ *             at the same place.  A temporal walk never ends (it restarts), so there is no padding; a timestamp may be -1.
+ *  negatives  tg_rw_skipgram's rule exactly (TAG_RW_NEG = 12, id = u, d0 = m, floor(a * n_nodes / 2^64); x_u[0] =
+ *             seeds[g][u mod B]): neg_rw equals, bit for bit, the neg_rw of tg_rw_skipgram with T = L - 1 for the same
+ *             seeds, R, K, n_nodes, seed and call id.  K = 0: an empty slab, neg_rw may be NULL.
+ * The slabs are batch-major and contiguous: pos_rw, pos_ts [G, nw * W, C], neg_rw [G, nw * U, C] (device int64); every word
+ * of them is written and nothing else, nothing is read back, the call does not synchronise.  pos_ts = NULL: the timestamps
+ * are not wanted and not written.
+ * One wavefront walks one walker at a time (every step inspects a whole row).  A workgroup is one wavefront that owns
+ * walkers_per_workgroup consecutive walkers of the launch (flat t = g * W + w) and takes them in turn; their rows stay in
+ * LDS: per walker one 8-byte slab offset and a row of (2 L | 1) int64 (L nodes, L timestamps, odd pitch),
+ * TG_TEMPO_SKIPGRAM_LDS_BYTES(L, walkers) in all.  Then it streams the windows out; inside a mini-batch window j of the
+ * workgroup's walkers is one run of walkers * C * 8 contiguous bytes per slab, and a run that crosses a mini-batch boundary
+ * splits there.  walkers_per_workgroup is 4 while that fits 16 KiB (L <= 255), then 2 (L <= 511), then 1; a single walker
+ * may take up to 64 KiB (L <= 4095), beyond that the call returns TG_ERR_UNSUPPORTED, as tg_tempo_random_walk does for a
+ * row that does not fit.  The walk bounds the launch, not the stores (tools/bench_temporal_walk_loader.py).  The negatives
+ * are a second launch on the same stream.
+ * Bad arguments (a null buffer, config or rng, C < 1, C > L, R < 1, K < 0, L < 1, n_nodes < 1 with K > 0, negative sizes or
+ * sizes whose products leave tg_rw_skipgram's bounds) are refused with TG_ERR_INVALID before anything is launched; G = 0 or
+ * B = 0 returns TG_OK and launches nothing. */
+#define TG_TEMPO_SKIPGRAM_LDS_BYTES(L, walkers) ((int64_t)(walkers) * (((2 * (int64_t)(L)) | 1) + 1) * 8)
+typedef struct {
+    int64_t walk_length;          /* L: COLUMNS of a row, as tg_tempo_random_walk (column 0 is the start; not L + 1) */
+    int64_t context_size;         /* C, 1 <= C <= L; nw = L - C + 1 windows */
+    int64_t walks_per_node;       /* R >= 1 */
+    int64_t num_negative_samples; /* K >= 0 */
+    int64_t n_nodes;              /* range of the negative draws */
+    int64_t win0, win1;           /* the walk's half-open window relative to the start time, as tg_tempo_random_walk */
+} tg_tempo_skipgram_config;
+
+typedef struct {
+    int64_t *pos_rw; /* [G, nw * W, C] nodes */
+    int64_t *pos_ts; /* [G, nw * W, C] timestamps of the same words, or NULL: not wanted, not written */
+    int64_t *neg_rw; /* [G, nw * U, C], or NULL when K = 0 */
+} tg_tempo_skipgram_out;
+
+/* rows of pos_rw (and pos_ts) and of neg_rw per mini-batch: nw * R * B and nw * R * K * B */
+TG_API int tg_tempo_skipgram_capacity(const tg_tempo_skipgram_config *cfg, int64_t batch_size, int64_t *pos_rows,
+                                      int64_t *neg_rows);
+/* What a launch will use: *walkers_per_workgroup and *lds_bytes = TG_TEMPO_SKIPGRAM_LDS_BYTES(L, *walkers_per_workgroup);
+ * TG_ERR_UNSUPPORTED when one walker's rows do not fit.  No device is touched. */
+TG_API int tg_tempo_skipgram_lds_bytes(const tg_tempo_skipgram_config *cfg, int32_t *walkers_per_workgroup, int64_t *lds_bytes);
+TG_API int tg_tempo_skipgram(const tg_graph *csr, const int64_t *node_ts, const int64_t *edge_ts, const int64_t *seeds,
+                             const int64_t *seeds_ts, int64_t n_batches, int64_t batch_size,
+                             const tg_tempo_skipgram_config *cfg, const tg_rng *rng, const tg_tempo_skipgram_out *out,
+                             void *stream);
+
 /* ---- Link-level seed rows: positive edges plus checked negatives of G mini-batches in one launch --------------------------
  * What a link-prediction trainer composes per mini-batch (randint negatives, cat with the positives), with the negatives
  * checked against the graph as the reference's negative sampler checks them (negative_sampling.rs: has_edge(v, w) and

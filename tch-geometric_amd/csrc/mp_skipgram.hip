@@ -77,7 +77,7 @@ template <typename StageT> __global__ __launch_bounds__(64) void mps_lds_kernel(
     }
     wave_lds_handoff();
     const int64_t pad = p.pad;
-    rws_emit_windows(stage, base, out, lane, t0, total, per, C, p.nw, p.pitch,
+    rws_emit_windows(stage, base, out, lane, 64, t0, total, per, C, p.nw, p.pitch, 0, 1,
                      [=](StageT v, int col) { return v == (StageT)-1 ? pad : (int64_t)v + col_off[col]; });
 }
 

@@ -1,6 +1,7 @@
-// What the skip-gram batch kernels share (rw_skipgram.hip: tg_rw_skipgram; mp_skipgram.hip: tg_mp_skipgram): the window
-// emit of a wavefront whose 64 rows sit in LDS, the flat form's window kernel, the negatives' draw, and the host-side plan
-// (shape checks, LDS bytes of the staged rows, walkers per mini-batch).
+// What the skip-gram batch kernels share (rw_skipgram.hip: tg_rw_skipgram; mp_skipgram.hip: tg_mp_skipgram;
+// tempo_skipgram.hip: tg_tempo_skipgram): the window emit of a wavefront over rows that sit in LDS, the flat form's window
+// kernel, the negatives' draw and their element-wise kernel, and the host-side plan (shape checks, LDS bytes of the staged
+// rows, walkers per mini-batch).
 #pragma once
 #include "rw_walk.h"
 #include "tg_device.h"
@@ -18,16 +19,20 @@ __device__ __forceinline__ int64_t negative_value(CallKey ck, uint64_t u, uint32
     return (int64_t)bounded64(draw(ck, u, m, 0u).a(), n_nodes);
 }
 
-// The LDS forms' emit.  stage: the wave's rows [walker][column] at `pitch`; base[wl]: element offset of walker wl's
-// window-0 row in `out`; walkers t0 + wl < total are live.  Element q of a window's run is column q % C of walker q / C;
-// lanes step by 64 elements without dividing.  word(v, col) turns the staged value of column col into the output word.
+// The LDS forms' emit, by one wavefront.  stage: n_rows staged rows [walker][column] at `pitch`; base[wl]: element offset of
+// walker wl's window-0 row in `out`; walkers t0 + wl < total are live.  Element q of a window's run is column q % C of
+// walker q / C; lanes step by 64 elements without dividing.  The wave writes windows j0, j0 + j_step, ... (0, 1: all of
+// them; a workgroup of several wavefronts that share the rows gives each its own j0).  Every element takes its walker's own
+// base, so a run that crosses a mini-batch boundary splits there by itself.  word(v, col) turns the staged value of column
+// col into the output word.
 template <typename StageT, typename Word>
 __device__ __forceinline__ void rws_emit_windows(const StageT *stage, const int64_t *base, int64_t *__restrict__ out, int lane,
-                                                 int64_t t0, int64_t total, int64_t per, int C, int nw, int pitch, Word word) {
-    const int n_el = 64 * C, dw = 64 / C, dc = 64 % C;
+                                                 int n_rows, int64_t t0, int64_t total, int64_t per, int C, int nw, int pitch,
+                                                 int j0, int j_step, Word word) {
+    const int n_el = n_rows * C, dw = 64 / C, dc = 64 % C;
     const int w_first = lane / C, c_first = lane - w_first * C;
     const int64_t win_stride = per * C;
-    for (int j = 0; j < nw; ++j) {
+    for (int j = j0; j < nw; j += j_step) {
         int wl = w_first, c = c_first;
         for (int q = lane; q < n_el; q += 64) {
             if (t0 + wl < total) out[base[wl] + j * win_stride + c] = word(stage[wl * pitch + j + c], j + c);
@@ -55,6 +60,26 @@ static __global__ void rws_windows_kernel(const WindowParams p, int64_t n_words)
         const int64_t j = r / per_window, r2 = r - j * per_window;
         const int64_t w = r2 / p.C, c = r2 - w * p.C;
         p.pos[i] = p.walks[(gi * p.W + w) * p.L + j + c];
+    }
+}
+
+// element-wise negatives: neg[g][j * U + u][c] = x_u[j + c], x_u[0] = the walker's seed, x_u[m] = negative_value(.., u, m, ..)
+struct NegativeParams {
+    const int64_t *seeds; // [G, B]
+    int64_t *neg;
+    int64_t B, U;
+    int32_t C, nw;
+    uint64_t seed, call_id, n_nodes;
+};
+static __global__ void rws_negatives_kernel(const NegativeParams p, int64_t n_words) {
+    const int64_t per_batch = (int64_t)p.nw * p.U * p.C, per_window = p.U * p.C;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t gi = i / per_batch, r = i - gi * per_batch;
+        const int64_t j = r / per_window, r2 = r - j * per_window;
+        const int64_t u = r2 / p.C, c = r2 - u * p.C;
+        const int64_t m = j + c;
+        p.neg[i] = m == 0 ? p.seeds[gi * p.B + u % p.B]
+                          : negative_value(call_key(p.seed, p.call_id + (uint64_t)gi, TAG_RW_NEG), (uint64_t)u, (uint32_t)m, p.n_nodes);
     }
 }
 

@@ -67,7 +67,7 @@ template <typename StageT> __global__ __launch_bounds__(64) void rws_lds_kernel(
         for (int m = 1; m < L; ++m) row[m] = live ? (StageT)negative_value(ck, (uint64_t)w, (uint32_t)m, p.n_nodes) : (StageT)-1;
     }
     wave_lds_handoff();
-    rws_emit_windows(stage, base, out, lane, t0, total, per, C, p.nw, p.pitch,
+    rws_emit_windows(stage, base, out, lane, 64, t0, total, per, C, p.nw, p.pitch, 0, 1,
                      [](StageT v, int) { return v == (StageT)-1 ? (int64_t)-1 : (int64_t)v; });
 }
 
@@ -110,18 +110,7 @@ __global__ __launch_bounds__(64) void rws_walk_kernel(const SkipgramParams p) {
 
 // flat form, kernel 2: rws_windows_kernel (rw_skipgram.h)
 
-// flat form, kernel 3: neg[g][j * U + u][c] = x_u[j + c]
-__global__ void rws_negatives_kernel(const SkipgramParams p, int64_t n_words) {
-    const int64_t per_batch = (int64_t)p.nw * p.U * p.C, per_window = p.U * p.C;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t gi = i / per_batch, r = i - gi * per_batch;
-        const int64_t j = r / per_window, r2 = r - j * per_window;
-        const int64_t u = r2 / p.C, c = r2 - u * p.C;
-        const int64_t m = j + c;
-        p.neg[i] = m == 0 ? p.seeds[gi * p.B + u % p.B]
-                          : negative_value(call_key(p.seed, p.call_id + (uint64_t)gi, TAG_RW_NEG), (uint64_t)u, (uint32_t)m, p.n_nodes);
-    }
-}
+// flat form, kernel 3: rws_negatives_kernel (rw_skipgram.h)
 
 } // namespace tg
 
@@ -229,7 +218,8 @@ extern "C" int tg_rw_skipgram(const tg_graph *csr, const void *edge_set, int64_t
         hipLaunchKernelGGL(rws_windows_kernel, dim3(grid_1d(pos_words)), dim3(256), 0, stream,
                            WindowParams{p.walks, p.pos, W, p.L, p.C, p.nw}, pos_words);
         if (neg_words > 0)
-            hipLaunchKernelGGL(rws_negatives_kernel, dim3(grid_1d(neg_words)), dim3(256), 0, stream, p, neg_words);
+            hipLaunchKernelGGL(rws_negatives_kernel, dim3(grid_1d(neg_words)), dim3(256), 0, stream,
+                               NegativeParams{seeds, p.neg, B, U, p.C, p.nw, p.seed, p.call_id, p.n_nodes}, neg_words);
     }
     TG_LAUNCH_CHECK();
     return TG_OK;

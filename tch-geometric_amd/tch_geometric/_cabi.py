@@ -40,7 +40,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_ns_induced_workspace_bytes", "tg_ns_induced_count", "tg_ns_induced_emit", "tg_rw_skipgram_capacity",
            "tg_rw_skipgram_form", "tg_rw_skipgram_workspace_bytes", "tg_rw_skipgram", "tg_ns_rows_fill",
            "tg_link_seeds_capacity", "tg_link_seeds", "tg_link_seeds_typed", "tg_mp_skipgram_capacity",
-           "tg_mp_skipgram_form", "tg_mp_skipgram_workspace_bytes", "tg_mp_skipgram"]
+           "tg_mp_skipgram_form", "tg_mp_skipgram_workspace_bytes", "tg_mp_skipgram", "tg_tempo_skipgram_capacity",
+           "tg_tempo_skipgram_lds_bytes", "tg_tempo_skipgram"]
 
 
 class TgGraph(C.Structure):
@@ -688,6 +689,69 @@ def tempo_random_walk(graph, node_ts, edge_ts, start, start_ts, walk_length, win
                                    C.c_int64(window[1]), C.byref(rng), ptr(walks), ptr(wts),
                                    stream_ptr(start.device)))
     return walks, wts
+
+
+class TgTempoSkipgramConfig(C.Structure):
+    _fields_ = [("walk_length", C.c_int64), ("context_size", C.c_int64), ("walks_per_node", C.c_int64),
+                ("num_negative_samples", C.c_int64), ("n_nodes", C.c_int64), ("win0", C.c_int64), ("win1", C.c_int64)]
+
+
+class TgTempoSkipgramOut(C.Structure):
+    _fields_ = [("pos_rw", C.c_void_p), ("pos_ts", C.c_void_p), ("neg_rw", C.c_void_p)]
+
+
+def tempo_skipgram_config(walk_length, context_size, window, walks_per_node=1, num_negative_samples=1, n_nodes=0):
+    """walk_length counts COLUMNS of a row, as tempo_random_walk (rw_skipgram_config's counts steps)."""
+    return TgTempoSkipgramConfig(int(walk_length), int(context_size), int(walks_per_node), int(num_negative_samples),
+                                 int(n_nodes), int(window[0]), int(window[1]))
+
+
+def tempo_skipgram_capacity(cfg, batch_size):
+    """-> (rows of pos_rw / pos_ts, rows of neg_rw) per mini-batch of batch_size seeds: nw * R * B and nw * R * K * B."""
+    pos, neg = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_tempo_skipgram_capacity(C.byref(cfg), C.c_int64(batch_size), C.byref(pos), C.byref(neg)))
+    return pos.value, neg.value
+
+
+def tempo_skipgram_lds_bytes(cfg):
+    """-> (walkers_per_workgroup, lds_bytes) of a tg_tempo_skipgram launch: walkers * ((2 L | 1) + 1) * 8 bytes.  Raises
+    (TG_ERR_UNSUPPORTED) when one walker's rows do not fit.  No device is touched."""
+    walkers, nbytes = C.c_int32(-1), C.c_int64(-1)
+    check(lib.tg_tempo_skipgram_lds_bytes(C.byref(cfg), C.byref(walkers), C.byref(nbytes)))
+    return walkers.value, nbytes.value
+
+
+def tempo_skipgram(graph, node_ts, edge_ts, seeds, seeds_ts, cfg, seed, call_id, with_ts=True, out=None):
+    """Temporal skip-gram batches (tg_tempo_skipgram) of the G mini-batches seeds[G, B] with start times seeds_ts[G, B] in
+    one launch on the current stream: -> (pos_rw [G, nw * R * B, C], pos_ts of the same shape or None, neg_rw [G, nw * R *
+    K * B, C]); mini-batch g draws with call id call_id + g and is a free view.  pos_ts holds the timestamp of every word
+    of pos_rw (-1: none).  graph: the CSR, edge_ts in its edge order, node_ts per node.  out: the triple of an earlier call
+    of the same shape (and with_ts), reused."""
+    for name, t in (("seeds", seeds), ("seeds_ts", seeds_ts)):
+        if t.dim() != 2 or t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError("tempo_skipgram: %s must be a contiguous int64 [n_batches, batch_size] tensor" % name)
+    if seeds.shape != seeds_ts.shape or seeds.device != seeds_ts.device:
+        raise ValueError("tempo_skipgram: seeds and seeds_ts differ in shape or device")
+    G, B = seeds.shape
+    pos_rows, neg_rows = tempo_skipgram_capacity(cfg, B)
+    dev, Cs = seeds.device, cfg.context_size
+    if out is None:
+        out = (torch.empty((G, pos_rows, Cs), dtype=torch.int64, device=dev),
+               torch.empty((G, pos_rows, Cs), dtype=torch.int64, device=dev) if with_ts else None,
+               torch.empty((G, neg_rows, Cs), dtype=torch.int64, device=dev))
+    pos, pts, neg = out
+    if neg is None:
+        neg = torch.empty((G, 0, Cs), dtype=torch.int64, device=dev)
+    shapes = [(pos, pos_rows), (neg, neg_rows)] + ([(pts, pos_rows)] if with_ts else [])
+    if (pts is None) == bool(with_ts) or any(t is None or tuple(t.shape) != (G, rows, Cs) or t.dtype != torch.int64
+                                             or not t.is_contiguous() for t, rows in shapes):
+        raise ValueError("tempo_skipgram: out does not have this launch's shapes")
+    o = TgTempoSkipgramOut(pos.data_ptr() if pos.numel() else None, pts.data_ptr() if with_ts and pts.numel() else None,
+                           neg.data_ptr() if neg.numel() else None)
+    rng = TgRng(seed, call_id)
+    check(lib.tg_tempo_skipgram(C.byref(graph), ptr(node_ts), ptr(edge_ts), ptr(seeds), ptr(seeds_ts), C.c_int64(G),
+                                C.c_int64(B), C.byref(cfg), C.byref(rng), C.byref(o), stream_ptr(dev)))
+    return pos, pts, neg
 
 
 class TgHetProblem(C.Structure):

@@ -15,8 +15,9 @@ slab flattened and split per mini-batch, attributes gathered once per launch.  E
 launch object and a few hooks (e_id, extras, panics).  They run on the caller's stream, launch by launch.
 HeteroLinkNeighborLoader is HeteroNeighborLoader seeded by the edges of one relation: tg_link_seeds_typed fills the input
 tensors of the relation's two node types directly ahead of the sampler.
-Node2VecLoader and MetaPath2VecLoader hand out skip-gram batches (context windows of walks plus negative rows) of one
-tg_rw_skipgram / tg_mp_skipgram launch per `prefetch` mini-batches; nothing is read back.
+Node2VecLoader, MetaPath2VecLoader and TemporalWalkLoader hand out skip-gram batches (context windows of walks plus negative
+rows; the temporal one also the windows' timestamps) of one tg_rw_skipgram / tg_mp_skipgram / tg_tempo_skipgram launch per
+`prefetch` mini-batches; nothing is read back.
 """
 from typing import Iterator, List, Optional
 
@@ -946,7 +947,11 @@ class Node2VecLoader(_Loader):
         launches = self.plan(self.epoch)                             # fresh draws every epoch (see NeighborLoader)
         self.epoch += 1
         for start, G, width, call_id in launches:
-            yield self._launch(self.input_nodes[start:start + G * width].reshape(G, width).contiguous(), call_id)
+            yield self._launch(*self._launch_inputs(start, G, width), call_id)
+
+    def _launch_inputs(self, start: int, G: int, width: int):
+        """what _launch takes ahead of the call id: the [G, width] rows of every per-input tensor"""
+        return (self.input_nodes[start:start + G * width].reshape(G, width).contiguous(),)
 
     def __iter__(self) -> Iterator[SkipGramBatch]:
         for sb in self.super_batches():
@@ -1038,6 +1043,120 @@ class MetaPath2VecLoader(Node2VecLoader):
             self._ws = torch.empty(need // 8, dtype=torch.int64, device=self.device)
         pos, neg = _cabi.mp_skipgram(self.cfg, seeds, self.seed, call_id, form=self.form, ws=self._ws)
         return SkipGramSuperBatch(pos, neg, seeds.shape[1], call_id)
+
+
+class TemporalSkipGramBatch:
+    """One temporal skip-gram mini-batch: `pos_rw` [nw * R * B, C] context windows of the temporal walks, `pos_ts` the
+    timestamp of every word of pos_rw (-1: none; None when the loader was built with with_timestamps=False), `neg_rw`
+    [nw * R * K * B, C] windows of the negative rows (views of the launch's slabs), `batch_size` = B seeds, `call_id`.  A
+    temporal walk restarts instead of ending: there is no padding."""
+    __slots__ = ("pos_rw", "pos_ts", "neg_rw", "batch_size", "call_id")
+
+    def __init__(self, pos_rw, pos_ts, neg_rw, batch_size, call_id):
+        self.pos_rw, self.pos_ts, self.neg_rw, self.batch_size, self.call_id = pos_rw, pos_ts, neg_rw, batch_size, call_id
+
+
+class TemporalSkipGramSuperBatch:
+    """The mini-batches of ONE tg_tempo_skipgram launch: `pos_rw`, `pos_ts` (or None) [G, nw * R * B, C], `neg_rw` [G, nw * R *
+    K * B, C], batch-major, `batch_size`, `call_id0` (mini-batch g drew with call_id0 + g).  Iterating or indexing yields
+    TemporalSkipGramBatch views."""
+    __slots__ = ("pos_rw", "pos_ts", "neg_rw", "batch_size", "call_id0")
+
+    def __init__(self, pos_rw, pos_ts, neg_rw, batch_size, call_id0):
+        self.pos_rw, self.pos_ts, self.neg_rw, self.batch_size, self.call_id0 = pos_rw, pos_ts, neg_rw, batch_size, call_id0
+
+    def __len__(self):
+        return self.pos_rw.shape[0]
+
+    def __getitem__(self, g):
+        if g < 0:
+            g += len(self)
+        if not 0 <= g < len(self):
+            raise IndexError(g)
+        return TemporalSkipGramBatch(self.pos_rw[g], None if self.pos_ts is None else self.pos_ts[g], self.neg_rw[g],
+                                     self.batch_size, self.call_id0 + g)
+
+    def __iter__(self):
+        for g in range(len(self)):
+            yield self[g]
+
+
+class TemporalWalkLoader(Node2VecLoader):
+    """CTDNE-style training batches (temporal walks, their context windows and timestamps, negative rows) as a loader: ONE
+    tg_tempo_skipgram launch per `prefetch` mini-batches; nothing is read back.  `walk_length` counts COLUMNS of a walk, as
+    tempo_random_walk does (the start node is column 0) -- Node2VecLoader's counts steps, one less.  `context_size` <=
+    walk_length; `window` = (lo, hi) is the walk's half-open time window relative to a walker's start time.  Each seed
+    starts `walks_per_node` walks and `walks_per_node * num_negative_samples` negative rows.
+
+    `edge_timestamps`: int64 [E] in data.edge_index order (default: data.timestamps); `node_timestamps`: [N], used for an
+    edge without a timestamp (default: all -1); `input_timestamps`: one start time per input node (default: all -1 = no
+    start time, every edge admissible), sliced exactly as input_nodes.  with_timestamps=False leaves pos_ts out (None).
+
+    The CSR and the timestamps in its edge order are built once, on first use.  The epoch plan, the call ids, the prefetch
+    clamp, plan(), super_batches() and iteration are Node2VecLoader's: mini-batch j of epoch e equals
+    _cabi.tempo_skipgram for (seed, call_id0 + e * len(loader) + j); the ragged last mini-batch is a launch of its own."""
+
+    def __init__(self, data, walk_length: int, context_size: int, window, walks_per_node: int = 1,
+                 num_negative_samples: int = 1, edge_timestamps: Optional[Tensor] = None,
+                 node_timestamps: Optional[Tensor] = None, input_nodes: Optional[Tensor] = None,
+                 input_timestamps: Optional[Tensor] = None, with_timestamps: bool = True, batch_size: int = 128,
+                 prefetch: int = 256, drop_last: bool = False, seed: int = 0, call_id0: int = 0,
+                 max_workspace_bytes: int = 4 << 30, device="cuda"):
+        self.data, self.device = data, torch.device(device)
+        self.n_nodes = _num_nodes(data)
+        self.window = (int(window[0]), int(window[1]))
+        if self.window[0] >= self.window[1]:
+            raise ValueError("window = %r is empty: it is half open, window[0] < window[1]" % (window,))
+        self.cfg = _cabi.tempo_skipgram_config(walk_length, context_size, self.window, walks_per_node, num_negative_samples,
+                                               self.n_nodes)
+        self.batch_size, self.drop_last, self.seed, self.call_id0 = int(batch_size), drop_last, int(seed), int(call_id0)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        try:                                                         # the library's own refusals (C > L, R < 1, K < 0, too long ...)
+            pos_rows, neg_rows = _cabi.tempo_skipgram_capacity(self.cfg, self.batch_size)
+            _cabi.tempo_skipgram_lds_bytes(self.cfg)
+        except _cabi.TchGeoError as e:
+            raise ValueError(str(e)) from None
+        n_edges = int(data.edge_index.shape[1])
+        ets = getattr(data, "timestamps", None) if edge_timestamps is None else edge_timestamps
+        if ets is None:
+            raise ValueError("the graph has no `timestamps`: pass edge_timestamps (int64, one per edge in edge_index order)")
+        if ets.numel() != n_edges:
+            raise ValueError("edge_timestamps must have one entry per edge (%d), got %d" % (n_edges, ets.numel()))
+        if node_timestamps is not None and node_timestamps.numel() != self.n_nodes:
+            raise ValueError("node_timestamps must have one entry per node (%d), got %d" % (self.n_nodes, node_timestamps.numel()))
+        self._edge_ts_in, self._node_ts_in = ets, node_timestamps
+        nodes = torch.arange(self.n_nodes) if input_nodes is None else input_nodes
+        self.input_nodes = _checked_inputs(nodes, self.n_nodes)
+        if input_timestamps is None:
+            input_timestamps = torch.full((self.input_nodes.numel(),), -1, dtype=torch.int64)
+        self.input_ts = input_timestamps.reshape(-1).to(torch.int64)
+        if self.input_ts.numel() != self.input_nodes.numel():
+            raise ValueError("input_timestamps must have one entry per input node")
+        self.with_timestamps = bool(with_timestamps)
+        per_call = ((2 if self.with_timestamps else 1) * pos_rows + neg_rows) * self.cfg.context_size * 8
+        self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // max(per_call, 1)))
+        self._graph = None
+        self.epoch = 0
+
+    def _prepare(self):
+        if self._graph is not None:
+            return
+        self.input_nodes, self.input_ts = self.input_nodes.to(self.device), self.input_ts.to(self.device)
+        self.row_ptrs, self.col_indices, perm = _host.to_csr(self.data.edge_index.to(self.device), self.n_nodes)
+        ets = self._edge_ts_in.to(self.device).reshape(-1).to(torch.int64)
+        self.edge_ts = ets[perm] if ets.numel() else ets             # into CSR edge order
+        self.node_ts = torch.full((self.n_nodes,), -1, dtype=torch.int64, device=self.device) if self._node_ts_in is None \
+            else self._node_ts_in.to(self.device).reshape(-1).to(torch.int64).contiguous()
+        self._graph = _cabi.graph_view(self.row_ptrs, self.col_indices)
+
+    def _launch_inputs(self, start: int, G: int, width: int):
+        return super()._launch_inputs(start, G, width) + (self.input_ts[start:start + G * width].reshape(G, width).contiguous(),)
+
+    def _launch(self, seeds: Tensor, seeds_ts: Tensor, call_id: int) -> TemporalSkipGramSuperBatch:
+        pos, pts, neg = _cabi.tempo_skipgram(self._graph, self.node_ts, self.edge_ts, seeds, seeds_ts, self.cfg, self.seed,
+                                             call_id, with_ts=self.with_timestamps)
+        return TemporalSkipGramSuperBatch(pos, pts, neg, seeds.shape[1], call_id)
 
 
 class LinkSuperBatch(SuperBatch):
