@@ -24,6 +24,11 @@ and every other position (p < k, p != s; a zero-weight candidate p >= k) has pro
 loop these give the textbook values: (k-1)/(n-1) for the own position, 1/(n-1) for each later one, 1/((n-1)(n-2)) for
 two later positions.
 
+Batch kernels (link seed rows, skip-gram negatives, consecutive walk steps): their laws are stated where they are defined
+below -- the rejection loop of negative_sampling.rs with the last attempt kept (link_binary_law, link_triplet_law,
+link_unverified_law), PyG's randint per column (product_uniform_law) and the product of random_walk.rs' per-step laws with
+an absorbing `ended` category (chain_law).
+
 The test: chi-square goodness of fit of observed counts against such a law, categories pooled in order into bins of
 expected count >= 20, every structural zero asserted exactly (count == 0), rejection at p < 1e-6."""
 import numpy as np
@@ -249,16 +254,18 @@ def node2vec_probs(p, q):
     return float(inv_p / mx), float(one / mx), float(inv_q / mx)
 
 
-def node2vec_step_law(row_ptrs, col, cur, prev, p, q):
+def node2vec_step_law(row_ptrs, col, cur, prev, p, q, look=None):
     """P(next = position j of cur's row) of the rejection loop random_walk.rs:52-66: a uniform position, accepted with
-    prob0 if it is prev, prob1 if it has an edge to prev, prob2 otherwise; prev = -1 before the first step."""
+    prob0 if it is prev, prob1 if it has an edge to prev, prob2 otherwise; prev = -1 before the first step.  look: (ptrs,
+    col) of the graph whose rows answer has_edge, the walked graph unless a named wrong law says otherwise."""
     nb = col[row_ptrs[cur]:row_ptrs[cur + 1]]
     p0, p1, p2 = node2vec_probs(p, q)
     acc = np.empty(nb.size)
+    look_ptrs, look_col = (row_ptrs, col) if look is None else look
     for j, v in enumerate(nb):
         if v == prev:
             acc[j] = p0
-        elif prev >= 0 and prev in col[row_ptrs[v]:row_ptrs[v + 1]]:
+        elif prev >= 0 and prev in look_col[look_ptrs[v]:look_ptrs[v + 1]]:
             acc[j] = p1
         else:
             acc[j] = p2
@@ -665,6 +672,169 @@ def hgt_positions(k, n):
     return sorted({h for h in hgt_heavy_ranks(n) if h >= k} | {n - 1})
 
 
+# ---------------------------------------------------------------- link seed rows: checked negatives in rows of fixed shape
+# The rejection loop of negative_sampling.rs:33-43 (draw, reject on has_edge(v, w) or v == w, at most try_count times) with
+# the one rule tg_link_seeds adds because a row's shape is fixed (tchgeo.h, "The first accepted attempt..."): when no attempt
+# was accepted the LAST one is kept, and counted as unverified.  try_count = 1 makes no look-up: attempt 0 is kept.
+def link_admissible(ptrs, indices, n_src, same_type):
+    """bool [n_src, n_dst] of a relation's CSC (column d lists the sources s of its edges s -> d): True where a candidate
+    (s, d) is accepted -- not edge(s -> d) and, when both endpoints are one node type, s != d"""
+    ptrs, indices = np.asarray(ptrs, dtype=np.int64), np.asarray(indices, dtype=np.int64)
+    n_dst = ptrs.size - 1
+    adm = np.ones((n_src, n_dst), dtype=bool)
+    adm[indices, np.repeat(np.arange(n_dst), np.diff(ptrs))] = False
+    if same_type:
+        assert n_src == n_dst
+        adm[np.arange(n_src), np.arange(n_src)] = False
+    return adm
+
+
+def _kept_attempt_law(adm, tries, drop_last=False):
+    """Candidates uniform over adm's cells, up to `tries` attempts, the first admissible one kept, else the last attempt:
+    with q = 1 - |A| / n an admissible cell has (1 - q^tries) / |A| (the geometric sum of q^a / n), an inadmissible one
+    q^(tries-1) / n (tries - 1 rejections, then this very cell).  tries = 1: uniform.  drop_last=True is the named wrong law
+    that emits accepted attempts only (the reference's rule, which a row of fixed shape cannot follow): uniform over A."""
+    adm = np.asarray(adm, dtype=bool).ravel()
+    assert tries >= 1 and adm.size > 0
+    n, a = adm.size, int(adm.sum())
+    q = 1.0 - a / n
+    if drop_last:
+        assert a > 0
+        return adm / float(a)
+    P = np.full(n, q ** (tries - 1) / n)
+    if a:
+        P[adm] = (1.0 - q ** tries) / a
+    return P
+
+
+def link_binary_law(n_src, n_dst, admissible, tries, drop_last=False):
+    """TG_LINK_BINARY: one negative's (s, d), both ends drawn; category s * n_dst + d.  admissible: link_admissible's matrix"""
+    adm = np.asarray(admissible, dtype=bool)
+    assert adm.shape == (n_src, n_dst)
+    return _kept_attempt_law(adm, tries, drop_last)
+
+
+def link_triplet_law(n_dst, admissible_row, tries, drop_last=False):
+    """TG_LINK_TRIPLET: one negative's d given its anchor s; admissible_row = link_admissible(...)[s]"""
+    adm = np.asarray(admissible_row, dtype=bool)
+    assert adm.shape == (n_dst,)
+    return _kept_attempt_law(adm, tries, drop_last)
+
+
+def link_unverified_law(admissible, tries):
+    """[verified, unverified] of one negative: every attempt rejected has q^tries, so a launch's count is Binomial(N,
+    q^tries); tries = 1 makes no look-up and counts nothing (a structural zero)."""
+    adm = np.asarray(admissible, dtype=bool)
+    u = 0.0 if tries == 1 else (1.0 - adm.sum() / adm.size) ** tries
+    return np.array([1.0 - u, u])
+
+
+# ---------------------------------------------------------------- skip-gram negatives (PyG's randint per column)
+def product_uniform_law(n_a, n_b):
+    """two independent words, uniform on [0, n_a) and [0, n_b); category a * n_b + b"""
+    return np.full(n_a * n_b, 1.0 / (n_a * n_b))
+
+
+def shared_draw_pair_law(n_a, n_b):
+    """the named wrong law of two words made from ONE draw u in [0, 1): (floor(u n_a), floor(u n_b)); a cell's
+    probability is the length of the intersection of its two intervals"""
+    a, b = np.arange(n_a)[:, None], np.arange(n_b)[None, :]
+    overlap = np.minimum((a + 1) * n_b, (b + 1) * n_a) - np.maximum(a * n_b, b * n_a)      # in units of 1 / (n_a n_b)
+    return (np.maximum(overlap, 0) / float(n_a * n_b)).ravel()
+
+
+# ---------------------------------------------------------------- consecutive walk steps
+def chain_law(step_laws, start, sizes=None):
+    """Joint law of (x_1, ..., x_m) of a walk from `start`: the product of the per-step conditional laws.  step_laws[l]
+    (prev, cur) -> the law of x_{l+1} over the step's target ids given the walker stands at cur and came from prev (-1
+    before the first step), all zero (or empty) at a dead end: the walk has ended, random_walk.rs:45-47, and `ended` absorbs
+    every later column.  -> f64 array of shape (n_1 + 1, ..., n_m + 1), index n_l = ended; sizes: the n_l (else the sizes
+    of the laws returned, 0 for a step no walk reaches)."""
+    m = len(step_laws)
+    paths, seen = {}, [0] * m
+
+    def go(l, prev, cur, path, pr):
+        if l == m:
+            paths[path] = paths.get(path, 0.0) + pr
+            return
+        law = np.zeros(0) if cur < 0 else np.asarray(step_laws[l](prev, cur), dtype=np.float64)
+        seen[l] = max(seen[l], law.size)
+        nz = np.flatnonzero(law)
+        if nz.size == 0:
+            go(l + 1, cur, -1, path + (-1,), pr)
+            return
+        assert abs(law.sum() - 1.0) < 1e-12
+        for v in nz.tolist():
+            go(l + 1, cur, v, path + (v,), pr * float(law[v]))
+
+    go(0, -1, int(start), (), 1.0)
+    sizes = seen if sizes is None else list(sizes)
+    assert all(s >= t for s, t in zip(sizes, seen))
+    P = np.zeros([s + 1 for s in sizes])
+    for path, pr in paths.items():
+        P[tuple(s if v < 0 else v for v, s in zip(path, sizes))] += pr
+    return P
+
+
+def csr_step(ptrs, col, n_dst, rank_law=None):
+    """step law over a CSR row: rank_law(deg) over the row's positions (default uniform: random_walk.rs:53 with p = q = 1,
+    where every proposal is accepted, and the metapath step), folded onto the target ids"""
+    ptrs, col = np.asarray(ptrs, dtype=np.int64), np.asarray(col, dtype=np.int64)
+
+    def law(prev, cur):
+        lo, hi = int(ptrs[cur]), int(ptrs[cur + 1])
+        if hi == lo:
+            return np.zeros(n_dst)
+        w = np.full(hi - lo, 1.0 / (hi - lo)) if rank_law is None else rank_law(hi - lo)
+        return np.bincount(col[lo:hi], weights=w, minlength=n_dst)
+    return law
+
+
+def node2vec_step(ptrs, col, n, p, q, swap_lookup=False):
+    """node2vec_step_law folded onto vertex ids.  Step 1 has prev = -1: `next == prev` is false and has_edge(next, -1) is
+    false, so every proposal is accepted with prob2 and the step is uniform (random_walk.rs:39, 56-63).  swap_lookup=True
+    is the named wrong law that asks has_edge(prev, next) in place of has_edge(next, prev)."""
+    ptrs, col = np.asarray(ptrs, dtype=np.int64), np.asarray(col, dtype=np.int64)
+    look = None
+    if swap_lookup:                                                      # has_edge answered by the transposed graph
+        order = np.argsort(col, kind="stable")
+        look = np.concatenate([[0], np.cumsum(np.bincount(col, minlength=n))]), np.repeat(np.arange(n), np.diff(ptrs))[order]
+
+    def law(prev, cur):
+        lo, hi = int(ptrs[cur]), int(ptrs[cur + 1])
+        if hi == lo:
+            return np.zeros(n)
+        return np.bincount(col[lo:hi], weights=node2vec_step_law(ptrs, col, cur, prev, p, q, look), minlength=n)
+    return law
+
+
+def shared_draw_chain_law(csrs, start, m, sizes):
+    """the named wrong law of m uniform steps that all use ONE draw u in [0, 1): x_{l+1} = row[floor(u deg)] at every step
+    (step l over csrs[l mod M] = (ptrs, col)).  Exact: u runs over the cells of width 1 / lcm(degrees)."""
+    degs = [int(d) for ptrs, _ in csrs for d in np.diff(ptrs) if d > 0]
+    D = int(np.lcm.reduce(degs))
+    P = np.zeros([s + 1 for s in sizes])
+    for j in range(D):
+        cur, path = int(start), []
+        for l in range(m):
+            ptrs, col = csrs[l % len(csrs)]
+            if cur >= 0 and ptrs[cur + 1] > ptrs[cur]:
+                deg = int(ptrs[cur + 1] - ptrs[cur])
+                cur = int(col[ptrs[cur] + (j * deg) // D])
+                path.append(cur)
+            else:
+                cur = -1
+                path.append(sizes[l])
+        P[tuple(path)] += 1.0 / D
+    return P
+
+
+def complete_csr(n):
+    """the complete directed graph on n vertices without loops -> (ptrs, col), rows ascending"""
+    col = np.array([v for u in range(n) for v in range(n) if v != u], dtype=np.int64)
+    return np.arange(n + 1, dtype=np.int64) * (n - 1), col
+
+
 # ---------------------------------------------------------------- sample sizes of tests/test_gpu_exact_laws.py
 N_WALK = 1 << 20          # walkers per walk launch
 N_NEG = 1 << 20           # negative items per launch
@@ -677,3 +847,88 @@ def n_outcomes(k):
     while p < k:
         p <<= 1
     return min(1 << 20, (1 << 26) // p)
+
+
+# ---------------------------------------------------------------- configurations of tests/test_gpu_exact_laws_batches.py
+# tests/test_exact_laws_cpu.py asserts their power against the named wrong laws at these sample sizes
+LINK_N = 97                                  # the homogeneous graph: not a power of two
+LINK_TYPED = (61, 89)                        # n_src, n_dst of the typed relation
+LINK_DENSITIES = (0.5, 0.97)
+LINK_TRIES = (1, 2, 8)
+LINK_SHAPE = (256, 64, 64)                   # E, K, G: G * K * E = N_NEG negatives per launch
+LINK_ANCHORS = 4                             # triplet mode: mini-batch g has anchor g mod 4 at every positive
+LINK_TRIPLET_LAUNCHES = 2                    # 2^19 negatives per anchor: what try_count 8 against 9 needs at density 0.5
+
+
+def link_graph(n_src, n_dst, density, seed):
+    """A relation in which each ordered pair (s, d), s != d, is an edge independently with probability `density`, so
+    edge(s -> d) and edge(d -> s) differ on about half the pairs at 0.5; of the equal-id pairs only 0, 1, 2 are edges (the
+    self-loops when both ends are one type), so the `s == d` rule decides every other cell of the diagonal.
+    -> (ptrs, indices) of its CSC, M bool [n_src, n_dst]"""
+    M = np.random.default_rng(seed).random((n_src, n_dst)) < density
+    k = min(n_src, n_dst)
+    M[np.arange(k), np.arange(k)] = np.arange(k) < 3
+    ptrs = np.concatenate([[0], np.cumsum(M.sum(0))]).astype(np.int64)
+    return ptrs, np.nonzero(M.T)[1].astype(np.int64), M
+
+
+def link_power(wrong, right, admissible, N):
+    """the chance that a link-seed test rejects N negatives of the law `wrong`: that of the more powerful of its two
+    chi-square tests, the cells' law and the [admissible, inadmissible] fold of it (the unverified total's law; an
+    inadmissible cell is rare and pools with its neighbours, so an error in the number of attempts shows in the fold)"""
+    adm = np.asarray(admissible, dtype=bool).ravel()
+    fold = lambda P: np.array([P[adm].sum(), P[~adm].sum()])
+    return max(power(wrong, right, N), power(fold(wrong), fold(right), N))
+
+
+def link_seed(kind, density):
+    """generator seed of the link_graph of a GPU configuration"""
+    return (100 if kind == "homo" else 200) + int(round(100 * density))
+
+
+def link_anchors(M):
+    """triplet anchors: source ids 1 (equal-id pair an edge), 4 (not one), and the sources with the fewest and the most
+    out-edges among the others"""
+    deg = M.sum(1).astype(np.int64)
+    deg[[1, 4]] = -1
+    rest = np.flatnonzero(deg >= 0)
+    return [1, 4, int(rest[np.argmin(deg[rest])]), int(rest[np.argmax(deg[rest])])]
+
+
+def wedge_graph():
+    """9 vertices, every one with two or more out-edges: the triangle 0-1-2, open wedges (0-3-4, 1-5-6, ...) and two
+    one-way edges 5 -> 0 and 2 -> 7, so has_edge(next, prev) and has_edge(prev, next) differ (from 0 over 1 to 5: 5 -> 0
+    is an edge, 0 -> 5 is not).  -> (ptrs, col, 9), rows ascending"""
+    und = [(0, 1), (0, 2), (1, 2), (0, 3), (3, 4), (1, 5), (5, 6), (2, 6), (4, 7), (7, 8), (6, 8), (3, 8), (4, 5)]
+    rows = {v: set() for v in range(9)}
+    for a, b in und:
+        rows[a].add(b)
+        rows[b].add(a)
+    rows[5].add(0)
+    rows[2].add(7)
+    ptrs = np.concatenate([[0], np.cumsum([len(rows[v]) for v in range(9)])]).astype(np.int64)
+    return ptrs, np.array([u for v in range(9) for u in sorted(rows[v])], dtype=np.int64), 9
+
+
+MP_COUNTS = (5, 7)                           # node types A, B of the chain test's metapath A-B-A
+MP_SINK = 3                                  # the B node without out-edges
+
+
+def metapath_graph():
+    """dense bipartite pair: A -> B where (a + 2 b) mod 5 != 0, B -> A where (a + b) mod 4 != 0, B node MP_SINK without
+    out-edges -> [(ptrs, col) of A -> B, (ptrs, col) of B -> A] (CSR, rows ascending)"""
+    nA, nB = MP_COUNTS
+    ab = [[b for b in range(nB) if (a + 2 * b) % 5] for a in range(nA)]
+    ba = [[a for a in range(nA) if (a + b) % 4 and b != MP_SINK] for b in range(nB)]
+    out = []
+    for rows in (ab, ba):
+        ptrs = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        out.append((ptrs, np.array([v for r in rows for v in r], dtype=np.int64)))
+    return out
+
+
+WALK_SHAPE = (256, 64, 64)                   # B, R, G: G * R * B = N_WALK walkers per launch, K = 1 negative row per walker
+WALK_STEPS = 3                               # x_1, x_2, x_3 of every walker (the temporal walk: two steps, 36 rank pairs)
+NEG_NODES = 31                               # range of the skip-gram negatives; the metapath's types have 31 and 17 nodes
+NEG_MP_COUNTS = (31, 17)
+NEG_SHAPE = (256, 16, 16, 4, 4)              # B, R, K, G, T: U = R K B = 2^16 rows of L = 5 words per mini-batch, G U (L-1) = N_NEG

@@ -2,7 +2,9 @@
 oracle's philox-mode (the counter-addressed restatements the kernels share) against those laws on long columns, and the
 power of the test against named wrong laws at the sample sizes tests/test_gpu_exact_laws.py and
 tests/test_gpu_exact_laws_typed.py use.  The typed samplers (hgt_sampling, budget_sampling) have their enumeration, oracle and
-power tests here as well."""
+power tests here as well, and so have the batch kernels of tests/test_gpu_exact_laws_batches.py (link seed rows, skip-gram
+negatives, consecutive walk steps): enumeration of the sequential loops, the NumPy models of tests/helpers_*.py against the
+laws, and the power at that file's sample sizes."""
 from collections import Counter
 from fractions import Fraction
 from itertools import product
@@ -552,3 +554,393 @@ def test_power_budget_and_edge_phase_without_the_quirk():
     wrong[1 << 16:] = 0.0                                               # a position cut to 16 bits: nothing past 65 535
     wrong[50:] *= (1 - wrong[49]) / wrong[50:].sum()
     assert L.power(wrong, right, L.EDGE_OUTCOMES[70000]) >= 0.999
+
+
+# ---------------------------------------------------------------- link seed rows, skip-gram negatives, consecutive steps
+# closed forms == enumeration of the sequential loops
+def _edge_sets(ptrs, indices):
+    return {(int(s), d) for d in range(len(ptrs) - 1) for s in indices[ptrs[d]:ptrs[d + 1]]}
+
+
+def _enumerate_kept_attempt(cells, accepted, tries):
+    """negative_sampling.rs:33-43 with tg_link_seeds' fixed-shape rule, every sequence of `tries` candidates equally
+    likely: the first accepted one is kept, else the last; tries = 1 keeps attempt 0 unchecked.
+    -> ({cell: probability}, P(unverified)) in rationals"""
+    P, unv = {c: Fraction(0) for c in cells}, Fraction(0)
+    w = Fraction(1, len(cells) ** tries)
+    for seq in product(cells, repeat=tries):
+        kept = seq[0] if tries == 1 else next((c for c in seq if accepted(c)), None)
+        if kept is None:
+            kept, unv = seq[-1], unv + w
+        P[kept] += w
+    return P, unv
+
+
+TOY_RELATIONS = {                                                        # name -> (n_src, n_dst, edges s -> d, same_type)
+    "square": (4, 4, [(0, 1), (1, 0), (2, 1), (3, 3), (0, 2), (3, 0)], True),        # one self-loop, 0 <-> 1 both ways
+    "rect": (3, 4, [(0, 0), (1, 0), (2, 3), (0, 2), (1, 1)], False),                 # equal ids (0, 0), (1, 1) are edges
+    "full-row": (4, 4, [(2, 0), (2, 1), (2, 3), (0, 1)], True),                      # source 2 has no admissible d
+}
+
+
+@pytest.mark.parametrize("tries", [1, 2, 3])
+@pytest.mark.parametrize("name", list(TOY_RELATIONS))
+def test_link_laws_equal_enumeration(name, tries):
+    import helpers_link as hl
+    n_src, n_dst, edges, same = TOY_RELATIONS[name]
+    ptrs, idx = hl.csc_of(edges, n_dst)
+    E = _edge_sets(ptrs, idx)
+    assert E == set(edges)
+    accepted = lambda c: c not in E and not (same and c[0] == c[1])      # !has_edge(v, w) && v != w
+    adm = L.link_admissible(ptrs, idx, n_src, same)
+    cells = [(s, d) for s in range(n_src) for d in range(n_dst)]
+    assert [bool(adm[c]) for c in cells] == [accepted(c) for c in cells]
+    P, unv = _enumerate_kept_attempt(cells, accepted, tries)
+    assert sum(P.values()) == 1
+    assert np.allclose(L.link_binary_law(n_src, n_dst, adm, tries), [float(P[c]) for c in cells], atol=1e-15, rtol=0)
+    assert np.allclose(L.link_unverified_law(adm, tries), [float(1 - unv), float(unv)], atol=1e-15, rtol=0)
+    for s in range(n_src):                                               # triplet: the anchor's row alone
+        row = [(s, d) for d in range(n_dst)]
+        P, unv = _enumerate_kept_attempt(row, accepted, tries)
+        assert np.allclose(L.link_triplet_law(n_dst, adm[s], tries), [float(P[c]) for c in row], atol=1e-15, rtol=0)
+        assert np.allclose(L.link_unverified_law(adm[s], tries), [float(1 - unv), float(unv)], atol=1e-15, rtol=0)
+    if tries > 1 and adm.any():                                          # the named wrong law keeps accepted attempts only
+        keep = {c: p for c, p in _enumerate_kept_attempt(cells, accepted, tries)[0].items() if accepted(c)}
+        tot = sum(keep.values())
+        assert np.allclose(L.link_binary_law(n_src, n_dst, adm, tries, drop_last=True),
+                           [float(keep.get(c, 0) / tot) for c in cells], atol=1e-15, rtol=0)
+
+
+def _enumerate_chain(step, start, m):
+    """the walk loop of random_walk.rs:43-71, every choice of every step enumerated: step(prev, cur) -> [(next,
+    probability)], empty at a dead end (`break`: the later columns keep their padding).  -> {path: probability}, None = ended"""
+    out = Counter()
+
+    def go(prev, cur, path, pr):
+        if len(path) == m:
+            out[path] += pr
+            return
+        nxt = step(prev, cur) if cur is not None else []
+        if not nxt:
+            out[path + (None,) * (m - len(path))] += pr
+            return
+        for v, t in nxt:
+            go(cur, v, path + (v,), pr * t)
+    go(-1, start, (), Fraction(1))
+    return out
+
+
+def _chain_equals(P, exact):
+    sizes = [s - 1 for s in P.shape]
+    Q = np.zeros(P.shape)
+    for path, pr in exact.items():
+        Q[tuple(s if v is None else v for v, s in zip(path, sizes))] += float(pr)
+    assert sum(exact.values()) == 1
+    assert np.allclose(P, Q, atol=1e-14, rtol=0) and np.array_equal(P == 0, Q == 0)
+
+
+TOY_ROWS = {0: [1, 2, 3], 1: [0, 2], 2: [3, 3, 0], 3: []}               # a multiplicity (2 -> 3 twice) and a dead end
+
+
+def _toy_csr(rows, n):
+    ptrs = np.concatenate([[0], np.cumsum([len(rows[v]) for v in range(n)])]).astype(np.int64)
+    return ptrs, np.array([u for v in range(n) for u in rows[v]], dtype=np.int64)
+
+
+@pytest.mark.parametrize("m", [2, 3])
+def test_chain_law_of_uniform_steps_equals_enumeration(m):
+    ptrs, col = _toy_csr(TOY_ROWS, 4)
+    uniform = lambda prev, cur: [(v, Fraction(1, len(TOY_ROWS[cur]))) for v in TOY_ROWS[cur]]   # neighbors[gen_range(0..len)]
+    for start in (0, 1):
+        P = L.chain_law([L.csr_step(ptrs, col, 4)] * m, start)
+        assert P.shape == (5,) * m
+        _chain_equals(P, _enumerate_chain(uniform, start, m))
+    assert L.chain_law([L.csr_step(ptrs, col, 4)] * m, 3, sizes=(4,) * m)[(4,) * m] == 1.0          # a start without out-edges
+
+
+def test_chain_law_of_node2vec_steps_equals_enumeration():
+    """acceptance weights as exact rationals of the f32 values; the rejection loop's law is weight / sum (shown above);
+    step 1 has prev = -1, which is no vertex: every proposal has prob2"""
+    rows = {0: [1, 2], 1: [0, 2, 3], 2: [0, 1], 3: [1, 0]}                # 3 -> 0 is one-way: has_edge(3, 0), not (0, 3)
+    ptrs, col = _toy_csr(rows, 4)
+    p, q = 0.5, 4.0
+    p0, p1, p2 = (Fraction(x) for x in L.node2vec_probs(p, q))
+
+    def step(prev, cur):
+        acc = [p0 if v == prev else p1 if prev in rows.get(v, []) else p2 for v in rows[cur]]
+        return [(v, a / sum(acc)) for v, a in zip(rows[cur], acc)]
+    exact = _enumerate_chain(step, 0, 3)
+    _chain_equals(L.chain_law([L.node2vec_step(ptrs, col, 4, p, q)] * 3, 0), exact)
+    assert exact[(1, 3, 0)] != exact[(1, 3, 1)]                          # from 0 over 1 to 3: back to 1 (prob0) or on to 0 (prob1)
+    swapped = L.chain_law([L.node2vec_step(ptrs, col, 4, p, q, swap_lookup=True)] * 3, 0)
+    assert not np.allclose(swapped, L.chain_law([L.node2vec_step(ptrs, col, 4, p, q)] * 3, 0))
+    first = L.chain_law([L.node2vec_step(ptrs, col, 4, p, q)], 0)
+    assert np.allclose(first, [0, 0.5, 0.5, 0, 0])                       # step 1 is uniform
+
+
+def test_chain_law_of_temporal_steps_equals_enumeration():
+    """the one-slot reservoir (the literal loop with k = 1, enumerated) at every step of the complete graph on 4 vertices,
+    every edge admissible; as ranks the joint law is one_slot_walk_law(3) x itself"""
+    ptrs, col = L.complete_csr(4)
+    rows = {v: col[ptrs[v]:ptrs[v + 1]].tolist() for v in range(4)}
+    lit = law_reference_loop(3, 1)
+    step = lambda prev, cur: [(rows[cur][c], lit[(c,)]) for c in range(3) if lit.get((c,), 0)]
+    P = L.chain_law([L.csr_step(ptrs, col, 4, L.one_slot_walk_law)] * 2, 0)
+    _chain_equals(P, _enumerate_chain(step, 0, 2))
+    R = np.zeros((3, 3))
+    for x1 in range(4):
+        for x2 in range(4):
+            if P[x1, x2]:
+                R[rows[0].index(x1), rows[x1].index(x2)] += P[x1, x2]
+    assert np.allclose(R, np.outer(L.one_slot_walk_law(3), L.one_slot_walk_law(3)), atol=1e-15, rtol=0)
+
+
+def test_metapath_chain_with_a_sink_equals_enumeration():
+    (pa, ca), (pb, cb) = L.metapath_graph()
+    rows = [{a: ca[pa[a]:pa[a + 1]].tolist() for a in range(5)}, {b: cb[pb[b]:pb[b + 1]].tolist() for b in range(7)}]
+    assert rows[1][L.MP_SINK] == [] and all(rows[0][a] for a in range(5)) and sum(1 for b in range(7) if not rows[1][b]) == 1
+    exact = Counter()
+    for x1 in rows[0][0]:                                                # csrs[l mod 2]: A -> B, B -> A, A -> B
+        t1 = Fraction(1, len(rows[0][0]))
+        if not rows[1][x1]:
+            exact[(x1, None, None)] += t1
+            continue
+        for x2 in rows[1][x1]:
+            t2 = t1 / len(rows[1][x1])
+            for x3 in rows[0][x2]:
+                exact[(x1, x2, x3)] += t2 / len(rows[0][x2])
+    laws = [L.csr_step(pa, ca, 7), L.csr_step(pb, cb, 5), L.csr_step(pa, ca, 7)]
+    P = L.chain_law(laws, 0, sizes=(7, 5, 7))
+    _chain_equals(P, exact)
+    assert P[L.MP_SINK, 5, 7] == pytest.approx(1 / 5) and P[L.MP_SINK, :5, :].sum() == 0   # ended: padding in every later column
+
+
+def test_pair_laws_equal_enumeration():
+    for n_a, n_b in ((3, 2), (5, 7), (7, 7)):
+        D = 4 * n_a * n_b                                                # a draw of log2(D) bits, every value once
+        got = np.zeros((n_a, n_b))
+        for a in range(D):
+            got[a * n_a // D, a * n_b // D] += 1.0 / D
+        assert np.allclose(L.shared_draw_pair_law(n_a, n_b), got.ravel(), atol=1e-15, rtol=0)
+        assert np.allclose(L.product_uniform_law(n_a, n_b), np.outer(np.full(n_a, 1 / n_a), np.full(n_b, 1 / n_b)).ravel())
+    ptrs, col = _toy_csr(TOY_ROWS, 4)                                    # one draw for every step: rows of 3, 2, 3, 0 entries
+    P = L.shared_draw_chain_law([(ptrs, col)], 0, 2, (4, 4))
+    exact = Counter()
+    for j in range(6):
+        x1 = TOY_ROWS[0][j * 3 // 6]
+        exact[(x1, TOY_ROWS[x1][j * len(TOY_ROWS[x1]) // 6] if TOY_ROWS[x1] else None)] += Fraction(1, 6)
+    _chain_equals(P, exact)
+
+
+# ---------------------------------------------------------------- the NumPy models of the batch kernels against the laws
+def _neg_pairs(rows, E, K, mode):
+    import helpers_link as hl
+    pr = hl.pairs(rows, E, K, mode)
+    return pr[:, 0, E:], pr[:, 1, E:]                                    # [G, K E] negative sources and destinations
+
+
+@pytest.mark.parametrize("tries", [1, 2])
+def test_link_model_binary_follows_the_exact_law(tries):
+    import helpers_link as hl
+    n = 13
+    ptrs, idx, _ = L.link_graph(n, n, 0.5, 31)
+    adm = L.link_admissible(ptrs, idx, n, True)
+    G, E, K = 4, 25, 60
+    src, dst = np.zeros((G, E), dtype=np.int64), np.ones((G, E), dtype=np.int64)
+    rows, unv = hl.seed_rows(ptrs, idx, src, dst, K, hl.BINARY, tries, 0xF1, 5, n)
+    s, d = _neg_pairs(rows, E, K, hl.BINARY)
+    assert L.chi2_gof(np.bincount((s * n + d).ravel(), minlength=n * n), L.link_binary_law(n, n, adm, tries),
+                      "link model binary")[1] > 0
+    bad = int((~adm[s, d]).sum())
+    assert int(unv.sum()) == (bad if tries > 1 else 0)
+    L.chi2_gof([G * E * K - int(unv.sum()), int(unv.sum())], L.link_unverified_law(adm, tries), "link model unverified")
+
+
+def test_link_model_triplet_follows_the_exact_law():
+    import helpers_link as hl
+    n, tries = 13, 3
+    ptrs, idx, M = L.link_graph(n, n, 0.5, 32)
+    adm = L.link_admissible(ptrs, idx, n, True)
+    G, E, K = 4, 10, 50
+    anchors = [1, 4, 7, 10]
+    src = np.repeat(np.array(anchors, dtype=np.int64)[:, None], E, axis=1)
+    rows, unv = hl.seed_rows(ptrs, idx, src, np.zeros_like(src), K, hl.TRIPLET, tries, 0xF2, 5, n)
+    s, d = _neg_pairs(rows, E, K, hl.TRIPLET)
+    for g, a in enumerate(anchors):
+        assert np.all(s[g] == a)
+        L.chi2_gof(np.bincount(d[g], minlength=n), L.link_triplet_law(n, adm[a], tries), "link model triplet anchor %d" % a)
+        assert int(unv[g]) == int((~adm[a, d[g]]).sum())
+        L.chi2_gof([E * K - int(unv[g]), int(unv[g])], L.link_unverified_law(adm[a], tries), "link model unverified")
+
+
+@pytest.mark.parametrize("same_type", [0, 1])
+def test_typed_link_model_follows_the_exact_law(same_type):
+    import helpers_link as hl
+    import helpers_link_typed as hlt
+    (n_src, n_dst), tries = ((7, 7) if same_type else (5, 7)), 2
+    ptrs, idx, M = L.link_graph(n_src, n_dst, 0.5, 33 + same_type)
+    adm = L.link_admissible(ptrs, idx, n_src, same_type)
+    assert same_type or (adm[3, 3] and not adm[0, 0] and M[0, 0])                    # equal ids of two types: eligible unless an edge
+    G, E, K = 2, 25, 60
+    src, dst = np.zeros((G, E), dtype=np.int64), np.ones((G, E), dtype=np.int64)
+    srows, drows, unv = hlt.seed_rows(ptrs, idx, src, dst, K, hlt.BINARY, tries, 0xF3, 5, n_src, n_dst, same_type)
+    s, d = srows[:, E:], drows[:, E:]
+    assert s.max() < n_src and d.max() < n_dst and s.min() >= 0 and d.min() >= 0
+    got = np.bincount((s * n_dst + d).ravel(), minlength=n_src * n_dst)
+    L.chi2_gof(got, L.link_binary_law(n_src, n_dst, adm, tries), "typed link model same_type=%d" % same_type)
+    if not same_type:
+        assert got[3 * n_dst + 3] > 0
+    assert int(unv.sum()) == int((~adm[s, d]).sum())
+    if same_type:                                                        # the homogeneous model, word for word
+        rows, unv1 = hl.seed_rows(ptrs, idx, src, dst, K, hl.BINARY, tries, 0xF3, 5, n_src)
+        assert np.array_equal(hlt.joined(srows, drows), rows) and np.array_equal(unv, unv1)
+
+
+def test_skipgram_negative_model_follows_the_exact_law():
+    import helpers_skipgram as hs
+    n, Lc, B, R, K = 7, 3, 50, 4, 10
+    seeds = np.arange(B, dtype=np.int64) % n
+    x = [hs.negatives(0xF4, 9 + g, seeds, R, K, Lc, n) for g in range(2)]
+    for g in range(2):
+        assert np.array_equal(x[g][:, 0], np.tile(seeds, R * K))
+        for m in (1, 2):
+            L.chi2_gof(np.bincount(x[g][:, m], minlength=n), np.full(n, 1 / n), "negative model word %d" % m)
+        L.chi2_gof(np.bincount(x[g][:, 1] * n + x[g][:, 2], minlength=n * n), L.product_uniform_law(n, n), "words 1, 2")
+    both = np.concatenate([x[0][:, m] * n + x[1][:, m] for m in (1, 2)])
+    L.chi2_gof(np.bincount(both, minlength=n * n), L.product_uniform_law(n, n), "negative model, call ids c and c + 1")
+
+
+def test_metapath_model_follows_the_exact_laws():
+    import helpers_metapath as hm
+    csrs = L.metapath_graph()
+    (pa, ca), (pb, cb) = csrs
+    nA, nB = L.MP_COUNTS
+    W = 3000
+    w = hm.walks(0xF5, 3, csrs, [0, 1], [1, 0], np.zeros(W // 4, dtype=np.int64), 4, 3)
+    assert w.shape == (W, 4) and np.all(w[:, 0] == 0)
+    sizes = (nB, nA, nB)
+    cat = np.zeros(W, dtype=np.int64)
+    for c, s in enumerate(sizes):
+        x = np.where(w[:, c + 1] < 0, s, w[:, c + 1])
+        assert np.all((x >= 0) & (x <= s))
+        cat = cat * (s + 1) + x
+    P = L.chain_law([L.csr_step(pa, ca, nB), L.csr_step(pb, cb, nA), L.csr_step(pa, ca, nB)], 0, sizes=sizes)
+    assert L.chi2_gof(np.bincount(cat, minlength=P.size), P.ravel(), "metapath model walks")[1] > 0
+    U = 2000
+    x = hm.negatives(0xF5, 3, [0, 1], [1, 0], np.zeros(U // 4, dtype=np.int64), 2, 2, 3, [nA, nB])
+    assert x.shape == (U, 3) and x[:, 1].max() < nB and x[:, 2].max() < nA
+    L.chi2_gof(np.bincount(x[:, 1] * nA + x[:, 2], minlength=nA * nB), L.product_uniform_law(nB, nA), "metapath model negatives")
+
+
+# ---------------------------------------------------------------- power at the sample sizes of test_gpu_exact_laws_batches.py
+def _show(wrong, right, N, seed):
+    """the file's demonstration: a multinomial draw from the wrong law is rejected, one from the right law is not"""
+    _reject(np.random.default_rng(seed).multinomial(N, wrong), right)
+    L.chi2_gof(np.random.default_rng(seed).multinomial(N, right), right, "right law")
+
+
+def link_wrong_laws(M, ptrs, idx, n_src, n_dst, same_type, tries, row=None):
+    """name -> wrong law of one negative of the relation M (row: the triplet anchor), for every named error that exists at
+    this configuration"""
+    adm = L.link_admissible(ptrs, idx, n_src, same_type)
+    law = (lambda a, t, **kw: L.link_binary_law(n_src, n_dst, a, t, **kw)) if row is None else \
+        (lambda a, t, **kw: L.link_triplet_law(n_dst, a[row], t, **kw))
+    wrong = {"one attempt too many": law(adm, tries + 1)}
+    if tries > 1:
+        wrong["one attempt too few"] = law(adm, tries - 1)
+        if (adm if row is None else adm[row]).any():
+            wrong["the last attempt dropped"] = law(adm, tries, drop_last=True)
+        flipped = ~M if same_type else ~M & ~np.eye(n_src, n_dst, dtype=bool)
+        wrong["s == d %s" % ("not rejected within one type" if same_type else "rejected across two types")] = law(flipped, tries)
+        if n_src == n_dst:
+            back = ~M.T
+            if same_type:
+                back = back & ~np.eye(n_src, dtype=bool)
+            wrong["look-up direction swapped"] = law(back, tries)
+    return wrong
+
+
+def _link_power_cases():
+    n = L.LINK_N
+    for density in L.LINK_DENSITIES:
+        for tries in L.LINK_TRIES:
+            yield "homo", n, n, 1, density, tries
+            yield "typed", L.LINK_TYPED[0], L.LINK_TYPED[1], 0, density, tries
+
+
+@pytest.mark.parametrize("kind,n_src,n_dst,same,density,tries", list(_link_power_cases()))
+def test_power_link_seed_laws(kind, n_src, n_dst, same, density, tries):
+    ptrs, idx, M = L.link_graph(n_src, n_dst, density, L.link_seed(kind, density))
+    adm = L.link_admissible(ptrs, idx, n_src, same)
+    right = L.link_binary_law(n_src, n_dst, adm, tries)
+    for name, wrong in link_wrong_laws(M, ptrs, idx, n_src, n_dst, same, tries).items():
+        assert L.link_power(wrong, right, adm, N_NEG) >= 0.999, (name, L.link_power(wrong, right, adm, N_NEG))
+    if tries == 2:
+        for name, wrong in link_wrong_laws(M, ptrs, idx, n_src, n_dst, same, tries).items():
+            _show(wrong, right, N_NEG, 11)
+    N_a = L.LINK_TRIPLET_LAUNCHES * N_NEG // L.LINK_ANCHORS              # triplet: every anchor's row law at its own N
+    for a in L.link_anchors(M):
+        right = L.link_triplet_law(n_dst, adm[a], tries)
+        for name, wrong in link_wrong_laws(M, ptrs, idx, n_src, n_dst, same, tries, row=a).items():
+            if np.allclose(wrong, right, atol=1e-15, rtol=0):
+                continue                                                 # the error does not touch this anchor's row
+            assert L.link_power(wrong, right, adm[a], N_a) >= 0.999, (name, a, L.link_power(wrong, right, adm[a], N_a))
+    if tries > 1:                                                        # the unverified total against an attempt more or fewer
+        for t in (tries - 1, tries + 1):
+            if t > 1:
+                assert L.power(L.link_unverified_law(adm, t), L.link_unverified_law(adm, tries), N_NEG) >= 0.999
+
+
+def _walk_chain(name):
+    """-> (right law, {name: wrong law}) of the walk configurations of the GPU file"""
+    m = L.WALK_STEPS
+    if name == "complete":
+        ptrs, col = L.complete_csr(7)
+        right = L.chain_law([L.csr_step(ptrs, col, 7)] * m, 0)
+        return right, {"steps share one draw": L.shared_draw_chain_law([(ptrs, col)], 0, m, (7,) * m)}
+    if name == "wedge":
+        ptrs, col, n = L.wedge_graph()
+        mk = lambda p, q, **kw: L.chain_law([L.node2vec_step(ptrs, col, n, p, q, **kw)] * m, 0, sizes=(n,) * m)
+        return mk(0.5, 4.0), {"p and q swapped": mk(4.0, 0.5), "prev ignored": mk(1.0, 1.0),
+                              "look-up direction swapped": mk(0.5, 4.0, swap_lookup=True)}
+    if name == "metapath":
+        (pa, ca), (pb, cb) = L.metapath_graph()
+        nA, nB = L.MP_COUNTS
+        right = L.chain_law([L.csr_step(pa, ca, nB), L.csr_step(pb, cb, nA), L.csr_step(pa, ca, nB)], 0, sizes=(nB, nA, nB))
+        return right, {"steps share one draw": L.shared_draw_chain_law([(pa, ca), (pb, cb)], 0, m, (nB, nA, nB))}
+    ptrs, col = L.complete_csr(7)                                        # temporal: two steps, the rank of step 2 = step 1's
+    step = L.csr_step(ptrs, col, 7, L.one_slot_walk_law)
+    right = L.chain_law([step] * 2, 0)
+    wrong = np.zeros_like(right)
+    for r, pr in enumerate(L.one_slot_walk_law(6)):
+        x1 = col[ptrs[0] + r]
+        wrong[x1, col[ptrs[x1] + r]] += pr
+    return right, {"steps share one draw": wrong}
+
+
+@pytest.mark.parametrize("name", ["complete", "wedge", "metapath", "temporal"])
+def test_power_consecutive_steps(name):
+    right, wrongs = _walk_chain(name)
+    assert abs(right.sum() - 1) < 1e-12
+    for what, wrong in wrongs.items():
+        assert abs(wrong.sum() - 1) < 1e-12
+        assert L.power(wrong.ravel(), right.ravel(), N_WALK) >= 0.999, what
+        _show(wrong.ravel(), right.ravel(), N_WALK, 12)
+
+
+def test_power_negative_words_sharing_one_draw():
+    """two words from one draw (columns m and m + 1, mini-batches g and g + 1, launches, or the walk's and the negatives'
+    stream) at the smallest N any of those pair tests counts"""
+    B, R, K, G, T = L.NEG_SHAPE
+    U = R * K * B
+    assert G * U * T == N_NEG
+    N = U * T                                                            # one pair of mini-batches, every (u, m)
+    n = L.NEG_NODES
+    for a, b in ((n, n), L.NEG_MP_COUNTS, L.NEG_MP_COUNTS[::-1]):
+        right, wrong = L.product_uniform_law(a, b), L.shared_draw_pair_law(a, b)
+        assert L.power(wrong, right, N) >= 0.999 and L.power(wrong, right, U) >= 0.999
+        _show(wrong, right, U, 13)
+    for a, b in ((6, n), (3, n), (5, n), (5, 7)):                        # walker w's x_1 (a rank of its start's row) and word 1 of
+        assert L.power(L.shared_draw_pair_law(a, b), L.product_uniform_law(a, b), N_WALK) >= 0.999   # its negative row
+    short = np.concatenate([np.full(17, 1 / 17), np.zeros(n - 17)])      # a word bounded by the other type's count
+    assert L.power(short, np.full(n, 1 / n), G * U) >= 0.999
