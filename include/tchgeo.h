@@ -70,6 +70,21 @@ typedef struct {
 #define TG_SAMPLER_UNIFORM 0      /* UnweightedSampler<false> -- the default (python.rs:215) */
 #define TG_SAMPLER_UNIFORM_REPL 1 /* UnweightedSampler<true> */
 #define TG_SAMPLER_WEIGHTED 2     /* WeightedSampler<f64> */
+/* Additive (the reference has no such sampler; PyG calls it temporal_strategy="last"): the k MOST RECENT admitted edges.
+ * For a frontier vertex w with filter state s, column [ptrs[w], ptrs[w+1]) and fan-out k:
+ *   admitted  the edges the temporal filter passes (TG_FILTER_NONE: all; STATIC / RELATIVE / DYNAMIC with `forward`
+ *             exactly as neighbor_sampling.rs:55-67, in wrapping int64 arithmetic like the other filtered kernels);
+ *   rank      forward == 0: the larger timestamp first; forward == 1: the smaller timestamp first (under TG_FILTER_NONE
+ *             the configuration's `forward` still selects the direction); ties: the smaller edge pointer first; the
+ *             comparison is on the full int64 timestamp;
+ *   output    the first min(k, n_admitted) edges in rank order, with the per-vertex bookkeeping of
+ *             neighbor_sampling.rs:210-218; a sample's state is the filter's `mutate` (the edge's timestamp under DYNAMIC,
+ *             s otherwise; without a filter no states are kept and `states` may be NULL).
+ * No random draw is made: rng, id_base, ids and call_ids do not influence the result.  Fan-outs 1..64 per hop,
+ * tg_graph.timestamps required, columns of fewer than 2^32 - 1 edges (checked against the graph's sizes: a graph of
+ * 2^32 - 1 edges or more must state tg_graph.max_degree, and that must be below the limit); anything else is TG_ERR_INVALID.  Taken by
+ * tg_ns_hop_recent and, with a workspace, tg_ns_homo_batched_ws; every other entry point rejects or ignores the id. */
+#define TG_SAMPLER_RECENT 3
 /* Filter variants of python.rs:218-249 */
 #define TG_FILTER_NONE (-1)
 #define TG_FILTER_STATIC 0   /* TEMPORAL_SAMPLE_STATIC   (neighbor_sampling.rs:32) */
@@ -174,7 +189,10 @@ TG_API int tg_ns_homo_workspace_bytes_for(const tg_graph *csc, int64_t n_batches
  * launch then runs hop by hop over the whole device (tg_ns_hop_scan / tg_ns_hop_weighted_groups on all batches' frontiers
  * at once) instead of one workgroup per batch: 64 weighted batches of 1 024 seeds on RMAT-24 53 -> 15 ms, temporal 5.5 ->
  * 2.3 ms; 8 batches 47 -> 2.2 / 5.2 -> 0.55 ms.  Results are tg_ns_homo_batched's bit for bit (the per-batch kernel runs behind the flat path whenever that could
- * not finish: a column-group bound reached, a non-positive weight sum).  0 bytes: the launch takes no workspace. */
+ * not finish: a column-group bound reached, a non-positive weight sum).  0 bytes: the launch takes no workspace.
+ * TG_SAMPLER_RECENT (with or without a filter) has no per-batch kernel: it takes the flat path at ANY batch count with
+ * tg_ns_hop_recent as the hop, nothing can overflow and nothing is queued behind it; the workspace is REQUIRED
+ * (tg_ns_homo_batched, a null, short or misaligned workspace, and seed_ids / seed_call_ids are TG_ERR_INVALID). */
 TG_API int tg_ns_homo_batched_workspace_bytes(const tg_graph *csc, int64_t n_batches, int64_t n_seeds, const int64_t *fanout,
                                        int32_t n_hops, const tg_ns_config *cfg, int64_t *n_bytes);
 TG_API int tg_ns_homo_batched_ws(const tg_graph *csc, const int64_t *seeds, int64_t n_batches, int64_t n_seeds,
@@ -273,7 +291,7 @@ typedef struct {
     int64_t m;
     int64_t id_base;
     int32_t fanout;
-    int32_t sampler;  /* TG_SAMPLER_UNIFORM or TG_SAMPLER_UNIFORM_REPL */
+    int32_t sampler;  /* TG_SAMPLER_UNIFORM or TG_SAMPLER_UNIFORM_REPL (tg_ns_hop_recent: TG_SAMPLER_RECENT) */
     uint32_t rng_tag; /* 0 = TG_TAG_NS_HOMO */
     uint32_t _reserved;
 } tg_hop_in;
@@ -308,6 +326,16 @@ TG_API int tg_ns_hop_scan_workspace_bytes(int64_t m, int32_t fanout, int64_t gro
 TG_API int tg_ns_hop_scan(const tg_graph *csc, const tg_hop_in *in, const tg_hop_filter *filter, const tg_rng *rng,
                           const tg_hop_out *out, int64_t *states_out, int32_t *status, void *workspace,
                           int64_t workspace_bytes, int64_t group_cap, void *stream);
+
+/* The flat hop of TG_SAMPLER_RECENT (in->sampler must say so; semantics at the define): one wavefront per frontier vertex
+ * streams the column's timestamps 64 at a time and keeps the best 64 one per lane; a chunk none of whose admitted edges
+ * beats the current k-th entry is skipped after one ballot.  A hub column is scanned by ONE wavefront.  `filter` NULL =
+ * no filter, most recent first; a filter with filter_mode = TG_FILTER_NONE admits every edge and carries `forward`.
+ * Outputs as tg_ns_hop_scan's (cnt, offsets with offsets[m] the total, neighbors / edge_ptrs / parents grouped by frontier
+ * vertex, here in RANK order); states_out [m * fanout] may be NULL without a filter and is then not written.  Vertices < 0
+ * are empty slots.  No workspace, no status word (nothing can overflow), no synchronisation; fan-outs 1..64. */
+TG_API int tg_ns_hop_recent(const tg_graph *csc, const tg_hop_in *in, const tg_hop_filter *filter, const tg_hop_out *out,
+                            int64_t *states_out, void *stream);
 
 /* The flat hop for the WEIGHTED sampler (sampling.rs:28-55), with or without a temporal filter (filter = NULL or
  * filter_mode = TG_FILTER_NONE: none).  One wavefront per frontier vertex all over the device; a column's

@@ -17,6 +17,8 @@
 // a column-group bound that was too low, a weighted column whose sum is not positive (the batch's counts[0] = -1) -- raise
 // a status word; the per-batch kernel is launched BEHIND the flat path and returns at once unless that word is set, so the
 // result is always the per-batch kernel's, bit for bit.
+// TG_SAMPLER_RECENT (the k most recent admitted edges, ns_hop_recent.hip) runs the same driver with tg_ns_hop_recent as the
+// hop, at ANY batch count: it has no per-batch kernel, nothing can overflow, and nothing is queued behind it.
 #include <algorithm>
 
 #include "tg_device.h"
@@ -59,23 +61,30 @@ __global__ void flat_begin_kernel(const FlatParams p) {
     }
 }
 
-// boff = exclusive prefix of the batches' frontier lengths (n_batches <= 256: one workgroup, one pass)
+// boff = exclusive prefix of the batches' frontier lengths: one workgroup, 256 batches per pass with a running carry
+// (the filtered / weighted launches bring at most 256 batches, TG_SAMPLER_RECENT any number)
 __global__ void __launch_bounds__(256) flat_offsets_kernel(const FlatParams p) {
     __shared__ int64_t wave_tot[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t len = tid < p.n_batches ? p.st[tid].end - p.st[tid].begin : 0;
-    int64_t incl = len;
+    int64_t base = 0;
+    for (int64_t b0 = 0; b0 < p.n_batches; b0 += 256) {
+        const int64_t b = b0 + tid;
+        const int64_t len = b < p.n_batches ? p.st[b].end - p.st[b].begin : 0;
+        int64_t incl = len;
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t u = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += u;
+        for (int off = 1; off < 64; off <<= 1) {
+            const int64_t u = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += u;
+        }
+        if (lane == 63) wave_tot[wave] = incl;
+        __syncthreads();
+        int64_t carry = base;
+        for (int w = 0; w < wave; ++w) carry += wave_tot[w];
+        if (b < p.n_batches) p.boff[b] = carry + incl - len;
+        base += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+        __syncthreads(); // the totals are rewritten by the next pass
     }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int64_t carry = 0;
-    for (int w = 0; w < wave; ++w) carry += wave_tot[w];
-    if (tid < p.n_batches) p.boff[tid] = carry + incl - len;
-    if (tid == p.n_batches - 1) p.boff[p.n_batches] = carry + incl;
+    if (tid == 0) p.boff[p.n_batches] = base;
 }
 
 __global__ void flat_frontier_kernel(const FlatParams p) {
@@ -140,8 +149,15 @@ struct FlatLayout {
     int64_t m_max, out_max, group_cap, hop_ws_bytes;
 };
 
+// the hop a launch runs over the flat frontier
+enum FlatHop { FLAT_HOP_SCAN, FLAT_HOP_WEIGHTED, FLAT_HOP_RECENT };
+static FlatHop flat_hop_of(const tg_ns_config *cfg) {
+    if (cfg->sampler == TG_SAMPLER_RECENT) return FLAT_HOP_RECENT;
+    return cfg->sampler == TG_SAMPLER_WEIGHTED ? FLAT_HOP_WEIGHTED : FLAT_HOP_SCAN;
+}
+
 static int flat_layout(const tg_graph *csc, int64_t n_batches, int64_t n_seeds, const int64_t *fanout, int32_t n_hops,
-                       bool weighted, FlatLayout *L) {
+                       FlatHop hop, FlatLayout *L) {
     int64_t layer = n_seeds, m_max = n_seeds, out_max = 0;
     int32_t kmax = 1;
     for (int h = 0; h < n_hops; ++h) {
@@ -158,9 +174,10 @@ static int flat_layout(const tg_graph *csc, int64_t n_batches, int64_t n_seeds, 
     // per-batch kernel
     L->group_cap = std::max<int64_t>({1024, csc->n_edges / 512 + 2 * L->m_max + 2,
                                       std::min<int64_t>(16 * L->m_max, (int64_t)1 << 26)});
-    int64_t hb = 0;
-    const int rc = weighted ? tg_ns_hop_weighted_workspace_bytes(L->m_max, kmax, L->group_cap, &hb)
-                            : tg_ns_hop_scan_workspace_bytes(L->m_max, kmax, L->group_cap, &hb);
+    int64_t hb = 0; // tg_ns_hop_recent takes no workspace
+    const int rc = hop == FLAT_HOP_RECENT     ? TG_OK
+                   : hop == FLAT_HOP_WEIGHTED ? tg_ns_hop_weighted_workspace_bytes(L->m_max, kmax, L->group_cap, &hb)
+                                              : tg_ns_hop_scan_workspace_bytes(L->m_max, kmax, L->group_cap, &hb);
     if (rc != TG_OK) return rc;
     L->hop_ws_bytes = hb;
     size_t at = 0;
@@ -210,15 +227,32 @@ static bool flat_applies(const tg_graph *csc, int64_t n_batches, int64_t n_seeds
     return true;
 }
 
+// TG_SAMPLER_RECENT has no per-batch kernel: the flat path is its only one, at any batch count
+static int recent_check(const int64_t *fanout, int32_t n_hops, const char *who) {
+    for (int h = 0; h < n_hops; ++h)
+        TG_REQUIRE(fanout[h] >= 1 && fanout[h] <= 64, "%s: TG_SAMPLER_RECENT takes fan-outs 1..64, fanout[%d] = %lld", who, h,
+                   (long long)fanout[h]);
+    return TG_OK;
+}
+
 extern "C" int tg_ns_homo_batched_workspace_bytes(const tg_graph *csc, int64_t n_batches, int64_t n_seeds,
                                                   const int64_t *fanout, int32_t n_hops, const tg_ns_config *cfg,
                                                   int64_t *n_bytes) {
     TG_REQUIRE(csc && n_bytes && n_batches >= 0 && n_seeds >= 0 && n_hops >= 0 && n_hops <= TG_MAX_HOPS &&
                    (fanout || n_hops == 0),
                "tg_ns_homo_batched_workspace_bytes: bad arguments");
+    if (cfg && cfg->sampler == TG_SAMPLER_RECENT) {
+        int rc = recent_check(fanout, n_hops, "tg_ns_homo_batched_workspace_bytes");
+        if (rc != TG_OK) return rc;
+        tg::FlatLayout L;
+        rc = tg::flat_layout(csc, n_batches, n_seeds, fanout, n_hops, tg::FLAT_HOP_RECENT, &L);
+        if (rc != TG_OK) return rc;
+        *n_bytes = (int64_t)L.total;
+        return TG_OK;
+    }
     if (flat_applies(csc, n_batches, n_seeds, fanout, n_hops, cfg)) {
         tg::FlatLayout L;
-        const int rc = tg::flat_layout(csc, n_batches, n_seeds, fanout, n_hops, cfg->sampler == TG_SAMPLER_WEIGHTED, &L);
+        const int rc = tg::flat_layout(csc, n_batches, n_seeds, fanout, n_hops, tg::flat_hop_of(cfg), &L);
         if (rc != TG_OK) return rc;
         *n_bytes = (int64_t)L.total;
         return TG_OK;
@@ -229,6 +263,90 @@ extern "C" int tg_ns_homo_batched_workspace_bytes(const tg_graph *csc, int64_t n
         return TG_OK;
     }
     return tg_ns_homo_workspace_bytes_for(csc, n_batches, n_seeds, fanout, n_hops, n_bytes);
+}
+
+// The driver of the flat path: per hop flat_offsets / flat_frontier / the hop / flat_emit over every batch at once.
+// *status (the scan and weighted hops' overflow word) is zeroed first; what runs behind the last hop is the caller's.
+static int flat_run(const tg_graph *csc, const int64_t *seeds, int64_t n_batches, int64_t n_seeds, const int64_t *fanout,
+                    int32_t n_hops, const tg_ns_config *cfg, const tg_rng *rng, const tg_ns_out *out, void *ws,
+                    const tg::FlatLayout &L, tg::FlatHop hop, int32_t **status_out, hipStream_t stream) {
+    using namespace tg;
+    const bool filtered = cfg->filter_mode != TG_FILTER_NONE;
+    unsigned char *w = static_cast<unsigned char *>(ws);
+    FlatParams p;
+    p.seeds = seeds;
+    p.seeds_state = cfg->seeds_state;
+    p.n_seeds = n_seeds;
+    p.n_batches = n_batches;
+    p.cap_nodes = out->cap_nodes;
+    p.cap_edges = out->cap_edges;
+    p.id_base = cfg->id_base;
+    p.n_hops = n_hops;
+    p.call_id = rng->call_id;
+    p.samples = out->samples;
+    p.rows = out->rows;
+    p.cols = out->cols;
+    p.edge_index = out->edge_index;
+    p.layer_offsets = out->layer_offsets;
+    p.counts = out->counts;
+    p.states = filtered ? out->states : nullptr;
+    p.st = reinterpret_cast<FlatState *>(w + L.st);
+    int32_t *status = reinterpret_cast<int32_t *>(w + L.status);
+    *status_out = status;
+    p.boff = reinterpret_cast<int64_t *>(w + L.boff);
+    p.vertices = reinterpret_cast<int64_t *>(w + L.vertices);
+    p.ids = reinterpret_cast<int64_t *>(w + L.ids);
+    p.call_ids = reinterpret_cast<int64_t *>(w + L.call_ids);
+    p.fstates = reinterpret_cast<int64_t *>(w + L.fstates);
+    p.cnt = reinterpret_cast<int64_t *>(w + L.cnt);
+    p.offsets = reinterpret_cast<int64_t *>(w + L.offsets);
+    p.neighbors = reinterpret_cast<int64_t *>(w + L.neighbors);
+    p.edge_ptrs = reinterpret_cast<int64_t *>(w + L.edge_ptrs);
+    p.parents = reinterpret_cast<int64_t *>(w + L.parents);
+    p.states_out = reinterpret_cast<int64_t *>(w + L.states_out);
+    TG_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), stream));
+    hipLaunchKernelGGL(flat_begin_kernel, dim3((unsigned)n_batches), dim3(256), 0, stream, p);
+    TG_LAUNCH_CHECK();
+    int64_t pitch = n_seeds;
+    for (int h = 0; h < n_hops; ++h) {
+        p.hop = h;
+        p.pitch = pitch;
+        const int64_t m = n_batches * pitch;
+        hipLaunchKernelGGL(flat_offsets_kernel, dim3(1), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL(flat_frontier_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((m + 255) / 256, 8192))),
+                           dim3(256), 0, stream, p);
+        TG_LAUNCH_CHECK();
+        tg_hop_in in{};
+        in.vertices = p.vertices;
+        in.ids = p.ids;
+        in.call_ids = p.call_ids;
+        in.m = m;
+        in.id_base = 0;
+        in.fanout = (int32_t)fanout[h];
+        in.sampler = hop == FLAT_HOP_WEIGHTED ? TG_SAMPLER_UNIFORM : cfg->sampler;
+        in.rng_tag = cfg->rng_tag;
+        tg_hop_out ho{p.cnt, p.offsets, p.neighbors, p.edge_ptrs, p.parents};
+        tg_hop_filter flt{};
+        flt.filter_mode = cfg->filter_mode;
+        flt.forward = cfg->forward;
+        flt.win_lo = cfg->win_lo;
+        flt.win_hi = cfg->win_hi;
+        flt.states = p.fstates;
+        int rc;
+        if (hop == FLAT_HOP_RECENT)
+            rc = tg_ns_hop_recent(csc, &in, &flt, &ho, p.states_out, stream);
+        else if (hop == FLAT_HOP_WEIGHTED)
+            rc = tg_ns_hop_weighted_groups(csc, &in, filtered ? &flt : nullptr, rng, &ho, p.states_out, status, w + L.hop_ws,
+                                           L.hop_ws_bytes, L.group_cap, stream);
+        else
+            rc = tg_ns_hop_scan(csc, &in, &flt, rng, &ho, p.states_out, status, w + L.hop_ws, L.hop_ws_bytes, L.group_cap,
+                                stream);
+        if (rc != TG_OK) return rc;
+        hipLaunchKernelGGL(flat_emit_kernel, dim3((unsigned)n_batches), dim3(512), 0, stream, p);
+        TG_LAUNCH_CHECK();
+        pitch *= fanout[h];
+    }
+    return TG_OK;
 }
 
 // -> 1 when the launch took the flat path (the caller returns), 0 when it does not apply (the caller goes on), < 0 never;
@@ -242,84 +360,43 @@ int tg_ns_homo_flat_launch(const tg_graph *csc, const int64_t *seeds, int64_t n_
     const bool weighted = cfg->sampler == TG_SAMPLER_WEIGHTED, filtered = cfg->filter_mode != TG_FILTER_NONE;
     if ((weighted && !csc->weights) || (filtered && (!csc->timestamps || !cfg->seeds_state || !out->states))) return 0; // the per-batch launch reports it
     FlatLayout L;
-    if (flat_layout(csc, n_batches, n_seeds, fanout, n_hops, weighted, &L) != TG_OK || ws_bytes < (int64_t)L.total ||
+    if (flat_layout(csc, n_batches, n_seeds, fanout, n_hops, flat_hop_of(cfg), &L) != TG_OK || ws_bytes < (int64_t)L.total ||
         ((uintptr_t)ws & 255) != 0)
         return 0;
     auto run = [&]() -> int {
-        unsigned char *w = static_cast<unsigned char *>(ws);
-        FlatParams p;
-        p.seeds = seeds;
-        p.seeds_state = cfg->seeds_state;
-        p.n_seeds = n_seeds;
-        p.n_batches = n_batches;
-        p.cap_nodes = out->cap_nodes;
-        p.cap_edges = out->cap_edges;
-        p.id_base = cfg->id_base;
-        p.n_hops = n_hops;
-        p.call_id = rng->call_id;
-        p.samples = out->samples;
-        p.rows = out->rows;
-        p.cols = out->cols;
-        p.edge_index = out->edge_index;
-        p.layer_offsets = out->layer_offsets;
-        p.counts = out->counts;
-        p.states = filtered ? out->states : nullptr;
-        p.st = reinterpret_cast<FlatState *>(w + L.st);
-        int32_t *status = reinterpret_cast<int32_t *>(w + L.status);
-        p.boff = reinterpret_cast<int64_t *>(w + L.boff);
-        p.vertices = reinterpret_cast<int64_t *>(w + L.vertices);
-        p.ids = reinterpret_cast<int64_t *>(w + L.ids);
-        p.call_ids = reinterpret_cast<int64_t *>(w + L.call_ids);
-        p.fstates = reinterpret_cast<int64_t *>(w + L.fstates);
-        p.cnt = reinterpret_cast<int64_t *>(w + L.cnt);
-        p.offsets = reinterpret_cast<int64_t *>(w + L.offsets);
-        p.neighbors = reinterpret_cast<int64_t *>(w + L.neighbors);
-        p.edge_ptrs = reinterpret_cast<int64_t *>(w + L.edge_ptrs);
-        p.parents = reinterpret_cast<int64_t *>(w + L.parents);
-        p.states_out = reinterpret_cast<int64_t *>(w + L.states_out);
-        TG_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), stream));
-        hipLaunchKernelGGL(flat_begin_kernel, dim3((unsigned)n_batches), dim3(256), 0, stream, p);
-        TG_LAUNCH_CHECK();
-        int64_t pitch = n_seeds;
-        for (int h = 0; h < n_hops; ++h) {
-            p.hop = h;
-            p.pitch = pitch;
-            const int64_t m = n_batches * pitch;
-            hipLaunchKernelGGL(flat_offsets_kernel, dim3(1), dim3(256), 0, stream, p);
-            hipLaunchKernelGGL(flat_frontier_kernel, dim3((unsigned)std::min<int64_t>((m + 255) / 256, 8192)), dim3(256), 0,
-                               stream, p);
-            TG_LAUNCH_CHECK();
-            tg_hop_in in{};
-            in.vertices = p.vertices;
-            in.ids = p.ids;
-            in.call_ids = p.call_ids;
-            in.m = m;
-            in.id_base = 0;
-            in.fanout = (int32_t)fanout[h];
-            in.sampler = weighted ? TG_SAMPLER_UNIFORM : cfg->sampler;
-            in.rng_tag = cfg->rng_tag;
-            tg_hop_out ho{p.cnt, p.offsets, p.neighbors, p.edge_ptrs, p.parents};
-            tg_hop_filter flt{};
-            flt.filter_mode = cfg->filter_mode;
-            flt.forward = cfg->forward;
-            flt.win_lo = cfg->win_lo;
-            flt.win_hi = cfg->win_hi;
-            flt.states = p.fstates;
-            int rc;
-            if (weighted)
-                rc = tg_ns_hop_weighted_groups(csc, &in, filtered ? &flt : nullptr, rng, &ho, p.states_out, status, w + L.hop_ws,
-                                               L.hop_ws_bytes, L.group_cap, stream);
-            else
-                rc = tg_ns_hop_scan(csc, &in, &flt, rng, &ho, p.states_out, status, w + L.hop_ws, L.hop_ws_bytes, L.group_cap,
-                                    stream);
-            if (rc != TG_OK) return rc;
-            hipLaunchKernelGGL(flat_emit_kernel, dim3((unsigned)n_batches), dim3(512), 0, stream, p);
-            TG_LAUNCH_CHECK();
-            pitch *= fanout[h];
-        }
+        int32_t *status = nullptr;
+        const int rc = flat_run(csc, seeds, n_batches, n_seeds, fanout, n_hops, cfg, rng, out, ws, L, flat_hop_of(cfg), &status,
+                                stream);
+        if (rc != TG_OK) return rc;
         // the per-batch kernel behind it: returns at once unless the status word says the flat path could not finish
         return tg_ns_homo_filtered_launch_if(csc, seeds, n_batches, n_seeds, fanout, n_hops, cfg, rng, out, status, stream);
     };
     *rc_out = run();
     return 1;
+}
+
+// TG_SAMPLER_RECENT: the same driver with tg_ns_hop_recent as the hop.  Nothing can overflow, so nothing is queued behind
+// it; what the launch cannot take is an error, not another path.
+int tg_ns_homo_recent_launch(const tg_graph *csc, const int64_t *seeds, int64_t n_batches, int64_t n_seeds,
+                             const int64_t *fanout, int32_t n_hops, const tg_ns_config *cfg, const tg_rng *rng,
+                             const tg_ns_out *out, void *ws, int64_t ws_bytes, hipStream_t stream) {
+    using namespace tg;
+    const char *who = "tg_ns_homo_batched_ws";
+    TG_REQUIRE(csc->timestamps || csc->n_edges == 0, "%s: TG_SAMPLER_RECENT needs edge timestamps (tg_graph.timestamps)", who);
+    TG_REQUIRE(recent_columns_fit(csc),
+               "%s: TG_SAMPLER_RECENT takes columns shorter than 2^32 - 1 edges (a graph this large has to state max_degree)", who);
+    int rc = recent_check(fanout, n_hops, who);
+    if (rc != TG_OK) return rc;
+    TG_REQUIRE(!cfg->seed_ids && !cfg->seed_call_ids, "%s: TG_SAMPLER_RECENT does not take seed_ids / seed_call_ids", who);
+    TG_REQUIRE(cfg->filter_mode == TG_FILTER_NONE || (cfg->seeds_state && out->states),
+               "%s: a temporal filter needs seeds_state and out->states", who);
+    TG_REQUIRE(ws, "TG_SAMPLER_RECENT needs a workspace: tg_ns_homo_batched_ws with tg_ns_homo_batched_workspace_bytes");
+    FlatLayout L;
+    rc = flat_layout(csc, n_batches, n_seeds, fanout, n_hops, FLAT_HOP_RECENT, &L);
+    if (rc != TG_OK) return rc;
+    TG_REQUIRE(ws_bytes >= (int64_t)L.total, "%s: workspace too small for TG_SAMPLER_RECENT (%lld < %lld bytes)", who,
+               (long long)ws_bytes, (long long)L.total);
+    TG_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+    int32_t *status = nullptr;
+    return flat_run(csc, seeds, n_batches, n_seeds, fanout, n_hops, cfg, rng, out, ws, L, FLAT_HOP_RECENT, &status, stream);
 }

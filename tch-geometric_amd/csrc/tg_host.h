@@ -23,6 +23,13 @@ inline bool ns_rows_prefilled(const tg_ns_out *out, int64_t n_seeds) {
     return out->rows_prefilled != 0 && out->rows_prefilled == n_seeds + 1;
 }
 
+// TG_SAMPLER_RECENT keeps a 32-bit position inside the column, 2^32 - 1 marking an empty entry: every column must be
+// shorter than that.  A graph with fewer edges cannot have such a column; a larger one has to state its longest column.
+inline bool recent_columns_fit(const tg_graph *g) {
+    const int64_t limit = 0xFFFFFFFFll;
+    return g->n_edges < limit || (g->max_degree > 0 && g->max_degree < limit);
+}
+
 } // namespace tg
 
 #define TG_REQUIRE(cond, ...)                                                                                          \

@@ -36,6 +36,7 @@ namespace {
 struct SamplerArg {
     int kind = TG_SAMPLER_UNIFORM; // python.rs:215 default
     py::object weights;            // Tensor (homogeneous) or dict[str, Tensor]
+    py::object timestamps;         // TG_SAMPLER_RECENT: the edge timestamps the ranking reads
 };
 SamplerArg parse_sampler(const py::object &o) {
     SamplerArg s;
@@ -45,14 +46,20 @@ SamplerArg parse_sampler(const py::object &o) {
     } else if (py::hasattr(o, "weights")) {
         s.kind = TG_SAMPLER_WEIGHTED;
         s.weights = o.attr("weights");
+    } else if (py::hasattr(o, "temporal_strategy")) { // additive: utils.RecentEdgeSampler (the reference has none)
+        if (o.attr("temporal_strategy").cast<std::string>() != "last")
+            throw py::value_error("sampler.temporal_strategy must be \"last\"");
+        s.kind = TG_SAMPLER_RECENT;
+        s.timestamps = o.attr("timestamps");
     } else {
-        throw py::type_error("sampler must expose `.with_replacement` or `.weights`");
+        throw py::type_error("sampler must expose `.with_replacement`, `.weights` or `.temporal_strategy`");
     }
     return s;
 }
 struct FilterArg {
     int mode = TG_FILTER_NONE;
     bool forward = false;
+    bool forward_given = false; // as the caller wrote it: TG_SAMPLER_RECENT ranks by it under a STATIC filter too
     int64_t win_lo = 0, win_hi = 0;
     py::object timestamps; // Tensor or dict
     py::object state;      // Tensor or dict
@@ -65,7 +72,7 @@ FilterArg parse_filter(const py::object &o) {
     py::object ft = t[0];
     auto window = ft.attr("window").cast<std::pair<int64_t, int64_t>>();
     const int64_t mode = ft.attr("mode").cast<int64_t>();
-    f.forward = ft.attr("forward").cast<bool>();
+    f.forward = f.forward_given = ft.attr("forward").cast<bool>();
     if (mode < 0 || mode > 2) return f; // python.rs:249: any other mode falls through to IdentityFilter
     f.mode = (int)mode;
     if (mode == TG_FILTER_STATIC) f.forward = true; // python.rs:219-224 builds <true, STATIC> for both
@@ -231,14 +238,15 @@ NsResult run_ns_filtered_flat(const c10::Device &dev, const Tensor &ptrs, const 
     NsResult r;
     const int64_t n_seeds = seeds.numel();
     const bool weighted = s.kind == TG_SAMPLER_WEIGHTED, filtered = f.mode != TG_FILTER_NONE;
+    const bool recent = s.kind == TG_SAMPLER_RECENT; // ranks by the timestamps with or without a filter
     tg_graph g{};
     g.ptrs = ptrs.data_ptr<int64_t>();
     g.indices = indices.numel() ? indices.data_ptr<int64_t>() : nullptr;
-    g.timestamps = filtered ? timestamps.data_ptr<int64_t>() : nullptr;
+    g.timestamps = (filtered || recent) ? timestamps.data_ptr<int64_t>() : nullptr;
     g.weights = weighted ? weights.data_ptr<double>() : nullptr;
     g.n_major = ptrs.numel() - 1;
     g.n_edges = indices.numel();
-    if ((weighted || filtered) && id_base == 0 &&
+    if (!recent && (weighted || filtered) && id_base == 0 &&
         run_ns_filtered_device(r, dev, g, seeds, seeds_state, fanout, s, f, rng, tag, unchecked_seeds))
         return r;
     if (unchecked_seeds) {
@@ -268,14 +276,17 @@ NsResult run_ns_filtered_flat(const c10::Device &dev, const Tensor &ptrs, const 
         in.rng_tag = tag;
         tg_hop_filter flt{};
         flt.filter_mode = f.mode;
-        flt.forward = f.forward ? 1 : 0;
+        flt.forward = (recent ? f.forward_given : f.forward) ? 1 : 0;
         flt.win_lo = f.win_lo;
         flt.win_hi = f.win_hi;
         flt.states = filtered ? fstate.data_ptr<int64_t>() : nullptr;
         tg_hop_out out{cnt.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(), nbr.data_ptr<int64_t>(),
                        ep.data_ptr<int64_t>(), par.data_ptr<int64_t>()};
         int64_t group_cap = std::max<int64_t>(1024, indices.numel() / 512 + 2 * m + 2), total = 0;
-        if (!weighted && !filtered) { // plain uniform samplers over a large frontier: the whole-device hop of ns_hop.hip
+        if (recent) { // the k most recent admitted edges: a wavefront per frontier vertex, no workspace
+            check_rc(tg_ns_hop_recent(&g, &in, &flt, &out, filtered ? st_out.data_ptr<int64_t>() : nullptr, stream_of(dev)));
+            total = read_scalar<int64_t>(offsets[m]);
+        } else if (!weighted && !filtered) { // plain uniform samplers over a large frontier: the whole-device hop of ns_hop.hip
             int64_t ws_bytes = 0;
             check_rc(tg_ns_hop_workspace_bytes(m, &ws_bytes));
             Tensor ws = at::empty({ws_bytes / 8 + 1}, i64(dev));
@@ -344,8 +355,15 @@ NsResult run_ns(const c10::Device &dev, const Tensor &ptrs, const Tensor &indice
     int64_t max_k = 1;
     for (int64_t k : fanout) max_k = std::max(max_k, k);
     // ... or more hops than the one-launch kernel's TG_MAX_HOPS (the reference takes any number: neighbor_sampling.rs:188)
-    if (f.mode != TG_FILTER_NONE || s.kind == TG_SAMPLER_WEIGHTED || seeds.numel() > 2048 || max_k > 128 ||
-        fanout.size() > (size_t)TG_MAX_HOPS) {
+    // the most-recent-k sampler: one launch of the batched flat driver (a batch has ONE workgroup for its seeds and its
+    // emit pass), or, like the others, hop by hop when the call brings more seeds than a workgroup should walk alone
+    const bool recent = s.kind == TG_SAMPLER_RECENT;
+    if (recent && max_k > 64) throw py::value_error("RecentEdgeSampler: num_neighbors above 64 is not supported");
+    if (recent && fanout.size() > (size_t)TG_MAX_HOPS)
+        throw py::value_error("RecentEdgeSampler: more hops than TG_MAX_HOPS are not supported");
+    if (recent ? seeds.numel() > 2048
+               : (f.mode != TG_FILTER_NONE || s.kind == TG_SAMPLER_WEIGHTED || seeds.numel() > 2048 || max_k > 128 ||
+                  fanout.size() > (size_t)TG_MAX_HOPS)) {
         return run_ns_filtered_flat(dev, ptrs, indices, weights, timestamps, seeds, seeds_state, fanout, s, f, rng, tag,
                                     id_base, unchecked_seeds);
     }
@@ -379,7 +397,7 @@ NsResult run_ns(const c10::Device &dev, const Tensor &ptrs, const Tensor &indice
     tg_ns_config cfg{};
     cfg.sampler = s.kind;
     cfg.filter_mode = f.mode;
-    cfg.forward = f.forward ? 1 : 0;
+    cfg.forward = (recent ? f.forward_given : f.forward) ? 1 : 0;
     cfg.rng_tag = tag;
     cfg.win_lo = f.win_lo;
     cfg.win_hi = f.win_hi;
@@ -395,8 +413,18 @@ NsResult run_ns(const c10::Device &dev, const Tensor &ptrs, const Tensor &indice
     out.states = r.states.defined() ? r.states.data_ptr<int64_t>() : nullptr;
     out.cap_nodes = r.samples.numel();
     out.cap_edges = r.rows.numel();
-    check_rc(tg_ns_homo_batched(&g, seeds_ok.numel() ? seeds_ok.data_ptr<int64_t>() : nullptr, 1, seeds_ok.numel(),
-                                fanout.data(), H, &cfg, &rng, &out, stream_of(dev)));
+    if (recent) { // the most-recent-k sampler runs hop by hop over the whole device and needs its workspace
+        int64_t ws_bytes = 0;
+        check_rc(tg_ns_homo_batched_workspace_bytes(&g, 1, seeds_ok.numel(), fanout.data(), H, &cfg, &ws_bytes));
+        Tensor ws = at::empty({ws_bytes / 8 + 32}, i64(dev));
+        int64_t *wp = ws.data_ptr<int64_t>();
+        wp += ((256 - ((uintptr_t)wp & 255)) & 255) / 8;
+        check_rc(tg_ns_homo_batched_ws(&g, seeds_ok.numel() ? seeds_ok.data_ptr<int64_t>() : nullptr, 1, seeds_ok.numel(),
+                                       fanout.data(), H, &cfg, &rng, &out, wp, ws_bytes, TG_NS_FORM_AUTO, stream_of(dev)));
+    } else {
+        check_rc(tg_ns_homo_batched(&g, seeds_ok.numel() ? seeds_ok.data_ptr<int64_t>() : nullptr, 1, seeds_ok.numel(),
+                                    fanout.data(), H, &cfg, &rng, &out, stream_of(dev)));
+    }
     Tensor th = to_host(tail); // the only synchronisation of the call
     const int64_t *l = th.data_ptr<int64_t>();
     if (unchecked_seeds) raise_if_flagged(l[lo_words + 2], unchecked_seeds);
@@ -463,8 +491,18 @@ py::tuple neighbor_sampling_homogenous(const Tensor &col_ptrs, const Tensor &row
     Tensor seeds = on(inputs, dev, at::kLong).reshape({-1});
     Tensor w, ts, st;
     if (s.kind == TG_SAMPLER_WEIGHTED) w = on_graph(as_homogeneous(s.weights), dev, at::kDouble); // python.rs:214
+    if (s.kind == TG_SAMPLER_RECENT) {
+        const Tensor sts = as_homogeneous(s.timestamps);
+        if (f.mode != TG_FILTER_NONE) { // one graph view carries one timestamp array: ranking and filter read the same
+            const Tensor fts = as_homogeneous(f.timestamps);
+            if (fts.data_ptr() != sts.data_ptr() || fts.scalar_type() != sts.scalar_type() || fts.numel() != sts.numel())
+                throw py::value_error("RecentEdgeSampler: the filter's timestamps must be the sampler's tensor");
+        }
+        ts = on_graph(sts, dev, at::kLong);
+        if (ts.numel() != idx.numel()) throw py::value_error("RecentEdgeSampler: one timestamp per edge");
+    }
     if (f.mode != TG_FILTER_NONE) {
-        ts = on_graph(as_homogeneous(f.timestamps), dev, at::kLong); // python.rs:149
+        if (s.kind != TG_SAMPLER_RECENT) ts = on_graph(as_homogeneous(f.timestamps), dev, at::kLong); // python.rs:149
         st = on(as_homogeneous(f.state), dev, at::kLong).reshape({-1});
         if (st.numel() != seeds.numel()) throw py::value_error("filter state must have one entry per input");
     }
@@ -491,6 +529,7 @@ py::tuple neighbor_sampling_heterogenous(const std::vector<std::string> &node_ty
                                          const py::dict &num_neighbors, int64_t num_hops, const py::object &sampler,
                                          const py::object &filter) {
     const SamplerArg s = parse_sampler(sampler);
+    if (s.kind == TG_SAMPLER_RECENT) throw py::value_error("RecentEdgeSampler: homogeneous sampling only");
     const FilterArg f = parse_filter(filter);
     const size_t T = node_types.size();
     std::map<std::string, size_t> tix;

@@ -12,4 +12,4 @@ from .tch_geometric import (PanicException, backend_version, graph_cache_clear, 
 from .loader import (HeteroLinkNeighborLoader, LinkNeighborLoader, MetaPath2VecLoader, Node2VecLoader,  # noqa: F401
                      TemporalWalkLoader)
 from .utils import (TEMPORAL_SAMPLE_DYNAMIC, TEMPORAL_SAMPLE_RELATIVE, TEMPORAL_SAMPLE_STATIC,  # noqa: F401
-                    TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler)
+                    RecentEdgeSampler, TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler)

@@ -15,6 +15,7 @@ TG_OK = 0
 TG_MAX_HOPS = 8
 TG_MAX_FANOUT = 32
 SAMPLER_UNIFORM, SAMPLER_UNIFORM_REPL, SAMPLER_WEIGHTED = 0, 1, 2
+SAMPLER_RECENT = 3   # additive: the k most recent admitted edges (tchgeo.h TG_SAMPLER_RECENT); deterministic
 PART_REPLY_PACKED, PART_REPLY_PAIRS, PART_REPLY_TRIPLES, PART_REPLY_PACKED_STATE = 1, 2, 3, 4   # tchgeo.h TG_PART_REPLY_*
 FILTER_NONE, FILTER_STATIC, FILTER_RELATIVE, FILTER_DYNAMIC = -1, 0, 1, 2
 
@@ -41,7 +42,7 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_rw_skipgram_form", "tg_rw_skipgram_workspace_bytes", "tg_rw_skipgram", "tg_ns_rows_fill",
            "tg_link_seeds_capacity", "tg_link_seeds", "tg_link_seeds_typed", "tg_mp_skipgram_capacity",
            "tg_mp_skipgram_form", "tg_mp_skipgram_workspace_bytes", "tg_mp_skipgram", "tg_tempo_skipgram_capacity",
-           "tg_tempo_skipgram_lds_bytes", "tg_tempo_skipgram"]
+           "tg_tempo_skipgram_lds_bytes", "tg_tempo_skipgram", "tg_ns_hop_recent"]
 
 
 class TgGraph(C.Structure):
@@ -1650,3 +1651,24 @@ def ns_hop_scan(graph, vertices, states, fanout, seed, filter_mode, window, forw
     check(lib.tg_ns_hop_scan(C.byref(graph), C.byref(hin), C.byref(flt), C.byref(rng), C.byref(hout), ptr(st_out),
                              ptr(status), ptr(ws), C.c_int64(nbytes.value), C.c_int64(group_cap), stream_ptr(dev)))
     return cnt[:m], offsets, nbr, ep, par, st_out, status
+
+
+def ns_hop_recent(graph, vertices, fanout, states=None, filter_mode=FILTER_NONE, window=(0, 0), forward=False):
+    """One flat hop of the most-recent-k sampler (tg_ns_hop_recent; the graph view carries the edge timestamps).  `states`
+    [m] is the filter state of every frontier vertex (None without a filter; `forward` then still picks the direction).
+    -> (cnt[m], offsets[m+1], neighbors, edge_ptrs, parents, states_out or None) -- no host synchronisation."""
+    m, dev = vertices.numel(), vertices.device
+    o = dict(dtype=torch.int64, device=dev)
+    cnt, offsets = torch.empty(max(m, 1), **o), torch.empty(m + 1, **o)
+    nbr, ep, par = (torch.empty(max(m * fanout, 1), **o) for _ in range(3))
+    st_out = torch.empty(max(m * fanout, 1), **o) if filter_mode != FILTER_NONE else None
+    hin, hout, flt = TgHopIn(), TgHopOut(), TgHopFilter()
+    hin.vertices = vertices.data_ptr() if m else None
+    hin.m, hin.fanout, hin.sampler = m, fanout, SAMPLER_RECENT
+    hout.cnt, hout.offsets = cnt.data_ptr(), offsets.data_ptr()
+    hout.neighbors, hout.edge_ptrs, hout.parents = nbr.data_ptr(), ep.data_ptr(), par.data_ptr()
+    flt.filter_mode, flt.forward = filter_mode, int(bool(forward))
+    flt.win_lo, flt.win_hi = window
+    flt.states = states.data_ptr() if (m and states is not None) else None
+    check(lib.tg_ns_hop_recent(C.byref(graph), C.byref(hin), C.byref(flt), C.byref(hout), ptr(st_out), stream_ptr(dev)))
+    return cnt[:m], offsets, nbr, ep, par, st_out

@@ -7,7 +7,8 @@ every mini-batch equals what `neighbor_sampling_homogenous` returns for that (se
 `tg_gather_rows` launch per attribute fetches the feature rows of all their nodes, and the mini-batches are handed
 out as lazily built views of that `SuperBatch` (or the super-batch itself: `NeighborLoader.super_batches()`).
 Everything stays in HBM; the host learns only the per-batch sizes (one read-back per launch, taken from pinned memory
-behind a launch that runs one super-batch ahead on a side stream).
+behind a launch that runs one super-batch ahead on a side stream).  With `time_attr` / `input_time` the same launches run
+under a backward temporal filter, uniformly or taking the most recent admitted edges (TG_SAMPLER_RECENT).
 
 The typed-graph loaders (HeteroNeighborLoader, HGTLoader, BudgetLoader, NegativeLoader) are one program, _TypedLoader:
 `prefetch` mini-batches of one node type's seeds per launch of a batched operator, one read-back of the counts, every
@@ -64,12 +65,14 @@ class SuperBatch:
     the loader really works in.  `n_id` [sum nodes], `edge_index` [2, sum edges] (batch-local numbering), `e_id`
     [sum edges] (COO edge ids of the source graph), one flat tensor per node / edge attribute, `node_ptr` / `edge_ptr`
     (python lists, length G + 1), `layer_offsets` [G][hops] triples, `call_id0`; from a `unique=True` loader also
-    `layer_nodes` [G][hops] (unique nodes known when a hop starts; else None).  Iterating (or indexing) yields the
+    `layer_nodes` [G][hops] (unique nodes known when a hop starts; else None); from a temporal loader `input_time`
+    [G, batch_size] (the seeds' times) and `node_time` [sum nodes] (the filter state of every node of n_id: its root's
+    time; else None).  Iterating (or indexing) yields the
     mini-batches as `MiniBatch` views; a consumer that can take the whole super-batch (a model over a batch of
     sub-graphs with `ptr` offsets) pays no per-mini-batch host work at all."""
     __slots__ = ("n_id", "edge_index", "_e_id", "_e_ptr", "_perm", "node_attrs", "edge_attrs", "node_ptr", "edge_ptr",
                  "layer_offsets", "layer_nodes", "layer_edges", "seed_counts", "batch_size", "call_id0", "n_hops", "_views",
-                 "_index")
+                 "_index", "input_time", "node_time")
 
     @property
     def e_id(self):
@@ -113,6 +116,9 @@ class SuperBatch:
     @property
     def num_edges(self):
         return self.edge_ptr[-1]
+
+
+TIME_FIELDS = ("input_time", "node_time")   # what a temporal NeighborLoader adds to a mini-batch
 
 
 class MiniBatch:
@@ -170,6 +176,15 @@ class MiniBatch:
 
     def __getattr__(self, name):  # node / edge attributes of the source graph (x, y, edge_attr, ...)
         sb = object.__getattribute__(self, "_sb")
+        # a temporal loader's mini-batches also carry input_time [batch_size] (the seeds' times) and node_time [num_nodes]
+        # (the time every node of n_id was sampled under: its root's).  Not class attributes: from an untimed loader the
+        # two names stay what they were, attributes of the source graph if it has them (a temporal loader refuses such a graph)
+        if name in TIME_FIELDS and sb.input_time is not None:
+            j = object.__getattribute__(self, "_j")
+            if name == "input_time":
+                return sb.input_time[j]
+            a = sb.node_ptr[j]
+            return sb.node_time.narrow(0, a, sb.node_ptr[j + 1] - a)
         if name in sb.node_attrs or name in sb.edge_attrs:
             views = self._all()
             return views[sb._index[name]]
@@ -199,19 +214,58 @@ class NeighborLoader(_Loader):
     other sizes: still one wait per launch), tg_ns_induced_emit on the caller's stream straight into the flat `edge_index`;
     the workspace the two passes share belongs to the slab set.  `edge_index`, `num_edges`, `e_id` and the edge attributes
     are the induced edges'; `layer_edges[h]` counts those whose target is among the first `layer_nodes[h]` nodes, a prefix
-    of `edge_index`; `layer_offsets` is None.  Induced edges are not filtered."""
+    of `edge_index`; `layer_offsets` is None.  Induced edges are not filtered.
+
+    Temporal (PyG's time_attr / input_time): `time_attr` names an int64 [E] tensor on `data` in edge_index order (carried
+    into CSC order once), `input_time` holds one int64 per input node and is sliced and shuffled with input_nodes.  An edge
+    of time t is admitted for a seed of time T when 0 <= T - t <= hi (TG_FILTER_RELATIVE, backward; `time_window` = (lo, hi),
+    default (0, 2**62)), and the whole subtree of a seed keeps the seed's time.  temporal_strategy="uniform" draws with the
+    loader's sampler among the admitted edges (`replace` honoured); "last" takes the num_neighbors most recent ones
+    (TG_SAMPLER_RECENT: deterministic, fan-outs <= 64).  Mini-batches gain `input_time` [batch_size] and `node_time`
+    [num_nodes]; a `data` that has node or edge attributes of those names is refused (from an untimed loader the names
+    stay the graph's attributes, as before).  unique=True is refused: deduplication would merge slots that carry different seed times."""
 
     def __init__(self, data, num_neighbors: List[int], input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
                  prefetch: int = 16, replace: bool = False, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0, unique: bool = False,
-                 induced: bool = False):
+                 induced: bool = False, time_attr: Optional[str] = None, input_time: Optional[Tensor] = None,
+                 temporal_strategy: str = "uniform", time_window=None):
         if induced and not unique:
             raise ValueError("induced=True needs unique=True: the induced edges are numbered against the unique node list")
+        if temporal_strategy not in ("uniform", "last"):
+            raise ValueError("temporal_strategy must be 'uniform' or 'last', got %r" % (temporal_strategy,))
+        if (time_attr is None) != (input_time is None):
+            raise ValueError("time_attr and input_time come together: edge times need seed times and the reverse")
+        if temporal_strategy == "last" and time_attr is None:
+            raise ValueError("temporal_strategy='last' needs time_attr and input_time")
+        if time_window is not None and time_attr is None:
+            raise ValueError("time_window needs time_attr and input_time")
+        self.temporal = time_attr is not None
+        if self.temporal:                   # everything that can be refused is refused before any device work
+            if unique:
+                raise ValueError("a temporal loader with unique=True is not offered: deduplication would merge slots that "
+                                 "carry different seed times")
+            times = getattr(data, time_attr, None)
+            n_edges = int(data.edge_index.shape[1])
+            if not isinstance(times, Tensor) or times.dtype != torch.int64 or times.numel() != n_edges:
+                raise ValueError("data.%s must be an int64 tensor with one entry per edge (%d)" % (time_attr, n_edges))
+            n_inputs = _num_nodes(data) if input_nodes is None else input_nodes.numel()
+            if input_time.dtype != torch.int64 or input_time.numel() != n_inputs:
+                raise ValueError("input_time must be int64 with one entry per input node (%d)" % n_inputs)
+            if temporal_strategy == "last" and any(int(k) > 64 for k in num_neighbors):
+                raise ValueError("temporal_strategy='last' takes num_neighbors up to 64")
+            for key, value in _tensor_items(data):   # the mini-batches' own input_time / node_time would hide them
+                if key in TIME_FIELDS and _attr_kind(key, value, _num_nodes(data), n_edges) in ("node", "edge"):
+                    raise ValueError("a temporal loader's mini-batches carry their own `%s`: rename data.%s" % (key, key))
+            self.time_window = (0, 2 ** 62) if time_window is None else (int(time_window[0]), int(time_window[1]))
+        self.temporal_strategy = temporal_strategy
         self.induced = bool(induced)
         self.data, self.fanout = data, [int(k) for k in num_neighbors]
         self.device = torch.device(device)
         self.batch_size, self.prefetch = int(batch_size), max(1, int(prefetch))
         self.sampler = _cabi.SAMPLER_UNIFORM_REPL if replace else _cabi.SAMPLER_UNIFORM
+        if temporal_strategy == "last":
+            self.sampler = _cabi.SAMPLER_RECENT
         self.shuffle, self.drop_last, self.seed, self.call_id0 = shuffle, drop_last, int(seed), int(call_id0)
         self.form = int(form)               # of many-batch launches (ns_homo_batched's `form`): 0 = by launch size
         self.unique = bool(unique)
@@ -224,8 +278,14 @@ class NeighborLoader(_Loader):
         self._ptr32 = self.col_ptrs.to(torch.int32) if small else None
         # the longest column (one read-back) sets the stage slots' bit widths: without it they assume n_edges, and the
         # slots of a large graph come out two chunks wide, which the staged pipeline of many-batch launches refuses
-        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, indices32=self._idx32, ptrs32=self._ptr32,
-                                       max_degree="auto")
+        self.edge_time = self.input_time = None
+        if self.temporal:                   # the edge times in CSC order, once
+            times = getattr(data, time_attr).to(self.device).reshape(-1)
+            self.edge_time = times[self.perm].contiguous() if times.numel() else times
+            self.input_time = input_time.to(self.device).reshape(-1)
+        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, timestamps=self.edge_time, indices32=self._idx32,
+                                       ptrs32=self._ptr32, max_degree="auto")
+        self._time_ws = {}                  # temporal launches: the workspace per launch shape (full / ragged), kept
         nodes = torch.arange(self.n_nodes, device=self.device) if input_nodes is None else input_nodes.to(self.device)
         self.input_nodes = _checked_inputs(nodes, self.n_nodes)
         self._n_edges = int(data.edge_index.shape[1])
@@ -259,7 +319,7 @@ class NeighborLoader(_Loader):
         return SuperBatch()
 
     # ---- stage 1 (side stream): sample G mini-batches into slab set `which`, sizes -> pinned host memory
-    def _sample(self, slabs, which, seeds: Tensor, first_batch: int):
+    def _sample(self, slabs, which, seeds: Tensor, first_batch: int, times: Optional[Tensor] = None):
         """`slabs` is the iterator's own set: slots 0 / 1 for full launches (one consumed, one sampled), "ragged" for the
         epoch's last, narrower mini-batch -- so that one neither replaces the big slabs nor is replaced by them"""
         G, B = seeds.shape[0], self._seed_width(seeds.shape[1])
@@ -267,7 +327,7 @@ class NeighborLoader(_Loader):
         slab = slabs.get(which)
         if slab is None or slab["out"].n_batches < G or slab["out"].n_seeds != B:
             cap = G if which == "ragged" else max(G, min(self.prefetch, len(self)))
-            slab = {"out": _cabi.NsBatchedOut(cap, B, self.fanout, self.device),
+            slab = {"out": _cabi.NsBatchedOut(cap, B, self.fanout, self.device, with_states=self.temporal),
                     "counts": torch.empty((cap, 2), dtype=torch.int64).pin_memory(),
                     "lo": torch.empty((cap, max(H, 1), 3), dtype=torch.int64).pin_memory(),
                     "free": None}
@@ -275,7 +335,15 @@ class NeighborLoader(_Loader):
                 slab["uniq"] = _cabi.NsUniqueOut(slab["out"], in_place=True, with_inverse=self.WITH_INVERSE)
                 slab["ln"] = torch.empty((cap, max(H, 1)), dtype=torch.int64).pin_memory()
             slabs[which] = slab
-        if G >= 2048 and self._ws is None:   # many batches per launch: the window-ordered form pays
+        time_ws = None
+        if self.temporal:                    # the workspace of THIS sampler / filter, sized for the slab set's full launch
+            key = (slab["out"].n_batches, B)
+            if key not in self._time_ws:
+                self._time_ws[key] = _cabi.ns_homo_batched_workspace(self._graph, key[0], B, self.fanout, self.device,
+                                                                     sampler=self.sampler,
+                                                                     filter_mode=_cabi.FILTER_RELATIVE)
+            time_ws = self._time_ws[key]
+        if G >= 2048 and self._ws is None and not self.temporal:   # many batches per launch: the window-ordered form pays
             self._ws = _cabi.ns_homo_workspace(max(G, min(self.prefetch, len(self))), B, self.fanout, self.device,
                                                graph=self._graph)
         cur = torch.cuda.current_stream(self.device)
@@ -289,8 +357,14 @@ class NeighborLoader(_Loader):
             items = seeds.contiguous()
             seeds = self._seed_rows(slab, items, first_batch)
             out = slab["out"]
-            _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
-                                  sampler=self.sampler, ws=self._ws if G >= 2048 else None, form=self.form)
+            if self.temporal:                # backward RELATIVE filter: 0 <= seed time - edge time <= hi, state kept down the tree
+                times = times.contiguous()
+                _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
+                                      sampler=self.sampler, filter_mode=_cabi.FILTER_RELATIVE, forward=False,
+                                      window=self.time_window, seeds_state=times, ws=time_ws)
+            else:
+                _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
+                                      sampler=self.sampler, ws=self._ws if G >= 2048 else None, form=self.form)
             sizes = out
             if self.unique:                  # dedup + relabel directly behind the sampler; the host reads the unique counts
                 sizes = uniq = slab["uniq"]
@@ -313,11 +387,13 @@ class NeighborLoader(_Loader):
             done = torch.cuda.Event()
             done.record(side)
         items.record_stream(side)
-        return (slab, G, B, first_batch, done)
+        if times is not None:
+            times.record_stream(side)
+        return (slab, G, B, first_batch, done, times)
 
     # ---- stage 2 (caller's stream): flatten, gather the attribute rows
     def _finish(self, ticket) -> SuperBatch:
-        slab, G, B, first_batch, done = ticket
+        slab, G, B, first_batch, done, times = ticket
         out = slab["out"]
         done.synchronize()                   # the host needs the sizes; the device work it waits for is long done
         cur = torch.cuda.current_stream(self.device)
@@ -334,6 +410,10 @@ class NeighborLoader(_Loader):
         else:
             n_id, edge_index, e_ptr = _cabi.ns_homo_compact(src, G, counts, stacked=True)   # copies: the slabs go back to the sampler
         sb = self._new_super_batch(slab, G)
+        sb.input_time = sb.node_time = None
+        if self.temporal:                    # the states slab trimmed like samples (a copy: the slab goes back)
+            sb.input_time = times
+            sb.node_time = _flat_rows(out.states[:G], out.counts[:G, 0], sum(n_nodes))
         free = torch.cuda.Event()
         free.record(cur)
         slab["free"] = free
@@ -367,15 +447,19 @@ class NeighborLoader(_Loader):
         nodes = self.input_nodes
         epoch = self.epoch                                      # captured: a second iterator is the next epoch
         self.epoch += 1
-        if self.shuffle:
-            gen = torch.Generator(device=self.device)
-            gen.manual_seed(self.seed * 1000003 + epoch)
-            nodes = nodes[torch.randperm(nodes.numel(), device=self.device, generator=gen)]
         B = self.batch_size
         # every epoch draws afresh, as the reference's global stream does (utils/random.rs:19-22): mini-batch j of
         # epoch e uses call id call_id0 + e * len(self) + j -- reproducible for a fixed (seed, epoch)
         batch0 = epoch * len(self)
-        work = [(nodes[start:start + G * width].reshape(G, width), batch0 + start // B)
+        times = self.input_time
+        if self.shuffle:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(self.seed * 1000003 + epoch)
+            order = torch.randperm(nodes.numel(), device=self.device, generator=gen)
+            nodes = nodes[order]
+            times = times[order] if times is not None else None
+        cut = lambda t, start, G, width: t[start:start + G * width].reshape(G, width)
+        work = [(cut(nodes, start, G, width), batch0 + start // B) + ((cut(times, start, G, width),) if times is not None else ())
                 for start, G, width in _epoch_plan(nodes.numel(), B, self.prefetch, self.drop_last)]
         # this iterator's own slabs (two iterators alive at once -- zip(loader, loader), a restart after an abandoned
         # epoch -- must not sample into each other's); they go back to the pool when the iterator ends or is dropped
@@ -1219,7 +1303,9 @@ class LinkNeighborLoader(NeighborLoader):
                  edge_label: Optional[Tensor] = None, neg_sampling_ratio: int = 1, neg_sampling: str = "binary",
                  try_count: int = 8, batch_size: int = 1024, prefetch: int = 16, replace: bool = False, shuffle: bool = False,
                  drop_last: bool = False, seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0,
-                 unique: bool = False, edge_set: bool = False):
+                 unique: bool = False, edge_set: bool = False, time_attr: Optional[str] = None):
+        if time_attr is not None:
+            raise ValueError("LinkNeighborLoader takes no time_attr: seed times per label edge (edge_label_time) are not offered")
         if neg_sampling not in ("binary", "triplet"):
             raise ValueError("neg_sampling must be 'binary' or 'triplet'")
         K = int(neg_sampling_ratio)

@@ -7,7 +7,11 @@ Limits the reference does not have: per-hop fan-out at most 4096 for the unweigh
 1024 under a temporal filter or the weighted sampler (ValueError beyond; the C ABI's batched launch tg_ns_homo_batched
 takes fan-outs up to 255 and 8 hops, TG_MAX_HOPS: the operators route larger fan-outs to the flat per-hop kernels and
 deeper calls hop by hop); heterogeneous sampling at most 8 node types / 16 relations in the fused launch (more fall back
-to one launch per relation and hop).
+to one launch per relation and hop).  RecentEdgeSampler (additive: the reference has no such class; the k most recent
+admitted edges, PyG's temporal_strategy="last", deterministic) takes fan-outs up to 64 and at most 8 hops, homogeneous
+sampling only; a filter passed with it must carry the sampler's own timestamps tensor (ValueError otherwise).  A call of
+up to 2048 inputs is one launch of the batched driver; a larger one runs hop by hop (tg_ns_hop_recent, one size read-back
+per hop), as the other samplers do.
 
 neighbor_sampling_homogenous returns the reference's forest (a vertex reached along two paths holds two slots of
 `samples`, rows[e] == n_seeds + e).  The PyG-style form -- each node once, edges numbered against that list -- is made
@@ -26,18 +30,27 @@ graph, with ids offset into one embedding table (PyG's MetaPath2Vec: start / end
 Link-level mini-batches -- positive edges, checked negatives, the neighbourhood of all their endpoints, and
 edge_label_index numbered against n_id -- come from LinkNeighborLoader (exported by the package; tg_link_seeds,
 csrc/link_seeds.hip), and for one relation (A, rel, B) of a typed graph from HeteroLinkNeighborLoader
-(tg_link_seeds_typed): edge_label_index's two rows are numbered against the n_id of A and of B."""
+(tg_link_seeds_typed): edge_label_index's two rows are numbered against the n_id of A and of B.
+
+Node-level temporal mini-batches come from loader.NeighborLoader(..., time_attr=None, input_time=None,
+temporal_strategy="uniform", time_window=None): `time_attr` names an int64 [E] tensor on `data` (edge_index order),
+`input_time` one int64 per input node; an edge of time t is admitted for a seed of time T when 0 <= T - t <= hi
+(time_window = (lo, hi), default (0, 2**62)) and a seed's whole subtree keeps its time.  "uniform" draws among the admitted
+edges (replace honoured), "last" takes the num_neighbors most recent (RecentEdgeSampler's kernel).  Mini-batches gain
+input_time [batch_size] and node_time [num_nodes] (a graph with attributes of those names is refused; from an untimed
+loader the names stay the graph's own attributes).  unique=True with times, and time_attr on LinkNeighborLoader, raise
+ValueError."""
 from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor
 
-from .utils import TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler
+from .utils import RecentEdgeSampler, TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler
 
 NodeType = str
 RelType = str
 EdgeType = Tuple[str, str, str]
 LayerOffset = Tuple[int, int, int]
-EdgeSampler = Union[UniformEdgeSampler, WeightedEdgeSampler]
+EdgeSampler = Union[UniformEdgeSampler, WeightedEdgeSampler, RecentEdgeSampler]   # the last one is additive
 HomoFilter = Tuple[TemporalEdgeFilter, Tensor]
 HeteroFilter = Tuple[TemporalEdgeFilter, Dict[NodeType, Tensor]]
 

@@ -51,3 +51,15 @@ class TemporalEdgeFilter:
 
     def validate(self, hetero: bool = False) -> None:
         _check(self.timestamps, hetero, torch.int64)
+
+
+@dataclass
+class RecentEdgeSampler:
+    """The k most recent admitted edges of every frontier vertex (PyG's temporal_strategy="last"), deterministic.
+    Additive: the reference has no such sampler.  The native module recognises it by `temporal_strategy`, tried after
+    `with_replacement` and `weights`.  Homogeneous sampling only; a filter passed with it must use the same timestamps."""
+    timestamps: MixedData
+    temporal_strategy = "last"
+
+    def validate(self, hetero: bool = False) -> None:
+        _check(self.timestamps, hetero, torch.int64)
