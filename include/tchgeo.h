@@ -1157,6 +1157,40 @@ TG_API int tg_ns_homo_unique(const tg_ns_out *in, int64_t n_batches, int64_t n_s
                              const tg_ns_unique_out *out, void *workspace, int64_t workspace_bytes, int32_t form,
                              void *stream);
 
+/* ---- per-batch, per-GROUP node dedup and relabel: one subgraph per group of seeds (PyG's disjoint=True) ------------------
+ * tg_ns_homo_unique with a group dimension.  seed_group (device int32 [n_seeds], shared by all batches; NULL = the
+ * identity, and then n_groups must equal n_seeds) puts every seed position in a group of [0, n_groups).  Per batch:
+ *   root(p)   = p for p < n_seeds, else root(in.cols[p - n_seeds]): the forest contract rows[e] == n_seeds + e,
+ *               cols[e] < n_seeds + e (see rows_prefilled) ends a chase after at most n_hops parents
+ *   group(p)  = seed_group[root(p)]
+ *   nodes[b]  the ids of the distinct PAIRS (group(p), samples[b][p]), p < n, ordered by the position of their first
+ *             occurrence; group[b][u] = the group of nodes[b][u] (pitch in.cap_nodes; PyG's `batch` vector)
+ *   inverse, rows, cols, counts, layer_nodes: as tg_ns_homo_unique defines them, over the pair instead of the id.
+ * The same node under two groups is two entries; inside one group (two seeds of it included) it is one.  The hash key is
+ * group * id_bound + id: 32-bit keys when n_groups * id_bound <= 2^31, else 64-bit ones; n_groups * id_bound >= 2^63 is
+ * refused.  Forms, rounds and the workspace rule are tg_ns_homo_unique's (the LDS form also holds a u16 group word per
+ * position, so it needs n_groups <= 65 536; the flat form's workspace holds a u32 one).  out.rows / out.cols may be
+ * in.rows / in.cols: every group is found before any edge is relabelled.  A batch that breaks the forest contract (a cols
+ * word that is no earlier position, a chase longer than n_hops) gets unspecified values, nothing out of bounds, no spin.
+ * Bad arguments are refused with TG_ERR_INVALID before anything is launched; no synchronisation, no read-back. */
+typedef struct {
+    int64_t *nodes;
+    int64_t *inverse;     /* or NULL */
+    int64_t *rows;
+    int64_t *cols;
+    int64_t *counts;
+    int64_t *layer_nodes; /* or NULL */
+    int64_t *group;       /* [n_batches * cap_nodes] */
+} tg_ns_unique_grouped_out;
+TG_API int tg_ns_homo_unique_grouped_form(int64_t cap_nodes, int64_t id_bound, int64_t n_groups, int64_t lds_limit_bytes,
+                                          int32_t *form, int64_t *lds_bytes);
+TG_API int tg_ns_homo_unique_grouped_workspace_bytes(int64_t cap_nodes, int64_t id_bound, int64_t n_groups,
+                                                     int64_t n_batches, int64_t *bytes, int64_t *bytes_min);
+TG_API int tg_ns_homo_unique_grouped(const tg_ns_out *in, int64_t n_batches, int64_t n_seeds, int32_t n_hops,
+                                     int64_t id_bound, const int32_t *seed_group, int64_t n_groups,
+                                     const tg_ns_unique_grouped_out *out, void *workspace, int64_t workspace_bytes,
+                                     int32_t form, void *stream);
+
 /* ---- per-batch, per-type node dedup and relabel of the typed slabs (tg_ns_hetero_batched's layout) ---------------------
  * tg_ns_homo_unique with a type dimension.  Input: per node type t a `samples` slab [n_batches * pitch_nodes[t]], per
  * relation r `rows` / `cols` slabs [n_batches * pitch_edges[r]] -- rows index positions of samples[rel_src[r]], cols

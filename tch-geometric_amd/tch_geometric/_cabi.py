@@ -42,7 +42,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_rw_skipgram_form", "tg_rw_skipgram_workspace_bytes", "tg_rw_skipgram", "tg_ns_rows_fill",
            "tg_link_seeds_capacity", "tg_link_seeds", "tg_link_seeds_typed", "tg_mp_skipgram_capacity",
            "tg_mp_skipgram_form", "tg_mp_skipgram_workspace_bytes", "tg_mp_skipgram", "tg_tempo_skipgram_capacity",
-           "tg_tempo_skipgram_lds_bytes", "tg_tempo_skipgram", "tg_ns_hop_recent"]
+           "tg_tempo_skipgram_lds_bytes", "tg_tempo_skipgram", "tg_ns_hop_recent", "tg_ns_homo_unique_grouped_form",
+           "tg_ns_homo_unique_grouped_workspace_bytes", "tg_ns_homo_unique_grouped"]
 
 
 class TgGraph(C.Structure):
@@ -1266,12 +1267,14 @@ class NsUniqueOut:
     """Output slabs of tg_ns_homo_unique for the slabs `src` (an NsBatchedOut or another object with its fields): nodes,
     inverse [n_batches, cap_nodes], rows, cols [n_batches, cap_edges] (src's own under in_place), counts [n_batches, 2],
     layer_nodes [n_batches, n_hops].  struct() is a tg_ns_out view (samples = nodes, the relabelled rows / cols, src's
-    edge_index and layer_offsets, the unique counts) that ns_homo_compact accepts."""
+    edge_index and layer_offsets, the unique counts) that ns_homo_compact accepts.  with_group: also `group`
+    [n_batches, cap_nodes], the output slab of tg_ns_homo_unique_grouped (the group of every entry of nodes: PyG's `batch`)."""
 
-    def __init__(self, src, in_place=False, with_inverse=True):
+    def __init__(self, src, in_place=False, with_inverse=True, with_group=False):
         self.src, self.n_batches, self.n_seeds, self.n_hops = src, src.samples.shape[0], src.n_seeds, src.n_hops
         o = dict(dtype=torch.int64, device=src.samples.device)
         self.samples = self.nodes = torch.empty_like(src.samples)
+        self.group = torch.empty_like(src.samples) if with_group else None   # tg_ns_homo_unique_grouped: PyG's `batch`
         self.inverse = torch.empty_like(src.samples) if with_inverse else None
         self.rows = src.rows if in_place else torch.empty_like(src.rows)
         self.cols = src.cols if in_place else torch.empty_like(src.cols)
@@ -1292,6 +1295,14 @@ class NsUniqueOut:
         u.layer_nodes = self.layer_nodes.data_ptr() if self.n_hops else None
         return u
 
+    def grouped_struct(self):
+        u = TgNsUniqueGroupedOut()
+        u.nodes, u.rows, u.cols, u.counts = self.nodes.data_ptr(), self.rows.data_ptr(), self.cols.data_ptr(), self.counts.data_ptr()
+        u.inverse = self.inverse.data_ptr() if self.inverse is not None else None
+        u.layer_nodes = self.layer_nodes.data_ptr() if self.n_hops else None
+        u.group = self.group.data_ptr()
+        return u
+
 
 def ns_homo_unique(out, n_batches, id_bound, form=0, ws=None, in_place=False, result=None, with_inverse=True):
     """Per-batch node dedup and relabel of the first n_batches batches of `out` (an NsBatchedOut, or a NsUniqueOut-like
@@ -1308,6 +1319,66 @@ def ns_homo_unique(out, n_batches, id_bound, form=0, ws=None, in_place=False, re
                                 C.c_int64(id_bound), C.byref(su), ptr(ws), C.c_int64(ws.numel() * 8 if ws is not None else 0),
                                 C.c_int32(form), stream_ptr(out.samples.device)))
     res._ws = ws                              # the launch borrows it: alive as long as the result
+    return res
+
+
+class TgNsUniqueGroupedOut(C.Structure):
+    _fields_ = TgNsUniqueOut._fields_ + [("group", C.c_void_p)]
+
+
+def ns_homo_unique_grouped_form(cap_nodes, id_bound, n_groups, lds_limit_bytes=0):
+    """-> (form, lds_bytes): the form an auto tg_ns_homo_unique_grouped call takes for slabs of pitch cap_nodes and keys
+    group * id_bound + id (1 = LDS, 2 = flat) and the LDS the LDS form asks for.  lds_limit_bytes > 0: taken as the
+    workgroup's limit, no device is touched; otherwise the current device is asked."""
+    form, nbytes = C.c_int32(-1), C.c_int64(0)
+    check(lib.tg_ns_homo_unique_grouped_form(C.c_int64(cap_nodes), C.c_int64(id_bound), C.c_int64(n_groups),
+                                             C.c_int64(lds_limit_bytes), C.byref(form), C.byref(nbytes)))
+    return form.value, nbytes.value
+
+
+def ns_homo_unique_grouped_workspace_bytes(cap_nodes, id_bound, n_groups, n_batches):
+    """-> (bytes, bytes_min) of tg_ns_homo_unique_grouped, as ns_homo_unique_workspace_bytes: a batch's part also holds a
+    group word per position."""
+    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_ns_homo_unique_grouped_workspace_bytes(C.c_int64(cap_nodes), C.c_int64(id_bound), C.c_int64(n_groups),
+                                                        C.c_int64(n_batches), C.byref(nbytes), C.byref(bmin)))
+    return nbytes.value, bmin.value
+
+
+def ns_homo_unique_grouped_workspace(cap_nodes, id_bound, n_groups, n_batches, device, form=0):
+    """The workspace of ns_homo_unique_grouped for n_batches batches at once as an int64 tensor; None where the call takes
+    none (the LDS form).  form=2 sizes it for the flat form whatever auto would take."""
+    nbytes, bmin = ns_homo_unique_grouped_workspace_bytes(cap_nodes, id_bound, n_groups, n_batches)
+    if form == 2:
+        nbytes = bmin * n_batches
+    return torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device) if nbytes > 0 and form != 1 else None
+
+
+def ns_homo_unique_grouped(out, n_batches, id_bound, seed_group=None, n_groups=None, form=0, ws=None, in_place=False,
+                           result=None, with_inverse=True):
+    """ns_homo_unique per GROUP of seeds (tg_ns_homo_unique_grouped; PyG's disjoint=True): seed_group, an int32 device
+    tensor [out.n_seeds] with values in [0, n_groups), puts every seed in a group (None: every seed its own, n_groups =
+    out.n_seeds); a node is listed once per group that reaches it, and result.group [n_batches, cap_nodes] names the group
+    of every entry of result.nodes.  The other arguments and the result are ns_homo_unique's; id_bound * n_groups < 2^63."""
+    if seed_group is None:
+        n_groups = out.n_seeds if n_groups is None else n_groups
+    else:
+        if seed_group.dtype != torch.int32 or seed_group.numel() != out.n_seeds or not seed_group.is_contiguous():
+            raise ValueError("seed_group must be a contiguous int32 tensor with one entry per seed (%d)" % out.n_seeds)
+        if n_groups is None:
+            raise ValueError("seed_group comes with n_groups")
+    res = result if result is not None else NsUniqueOut(out, in_place, with_inverse, with_group=True)
+    if res.group is None:
+        raise ValueError("result carries no group slab: NsUniqueOut(..., with_group=True)")
+    if ws is None:
+        ws = ns_homo_unique_grouped_workspace(out.samples.shape[1], id_bound, n_groups, n_batches, out.samples.device, form)
+    si, su = out.struct(), res.grouped_struct()
+    ns_rows_unmark(res.rows)                  # written through the raw pointer (under in_place: out's own slab)
+    check(lib.tg_ns_homo_unique_grouped(C.byref(si), C.c_int64(n_batches), C.c_int64(out.n_seeds), C.c_int32(out.n_hops),
+                                        C.c_int64(id_bound), ptr(seed_group), C.c_int64(n_groups), C.byref(su), ptr(ws),
+                                        C.c_int64(ws.numel() * 8 if ws is not None else 0), C.c_int32(form),
+                                        stream_ptr(out.samples.device)))
+    res._ws, res._seed_group = ws, seed_group  # the launch borrows them: alive as long as the result
     return res
 
 

@@ -67,12 +67,13 @@ class SuperBatch:
     (python lists, length G + 1), `layer_offsets` [G][hops] triples, `call_id0`; from a `unique=True` loader also
     `layer_nodes` [G][hops] (unique nodes known when a hop starts; else None); from a temporal loader `input_time`
     [G, batch_size] (the seeds' times) and `node_time` [sum nodes] (the filter state of every node of n_id: its root's
-    time; else None).  Iterating (or indexing) yields the
+    time; else None); from a disjoint loader `batch` [sum nodes] (the subgraph -- the seed group -- every node of n_id
+    belongs to, numbered inside its mini-batch; else None).  Iterating (or indexing) yields the
     mini-batches as `MiniBatch` views; a consumer that can take the whole super-batch (a model over a batch of
     sub-graphs with `ptr` offsets) pays no per-mini-batch host work at all."""
     __slots__ = ("n_id", "edge_index", "_e_id", "_e_ptr", "_perm", "node_attrs", "edge_attrs", "node_ptr", "edge_ptr",
                  "layer_offsets", "layer_nodes", "layer_edges", "seed_counts", "batch_size", "call_id0", "n_hops", "_views",
-                 "_index", "input_time", "node_time")
+                 "_index", "input_time", "node_time", "batch")
 
     @property
     def e_id(self):
@@ -119,6 +120,7 @@ class SuperBatch:
 
 
 TIME_FIELDS = ("input_time", "node_time")   # what a temporal NeighborLoader adds to a mini-batch
+DISJOINT_FIELDS = ("batch",)                # what a disjoint one adds (PyG's `batch` vector)
 
 
 class MiniBatch:
@@ -185,9 +187,17 @@ class MiniBatch:
                 return sb.input_time[j]
             a = sb.node_ptr[j]
             return sb.node_time.narrow(0, a, sb.node_ptr[j + 1] - a)
+        # a disjoint loader's mini-batches carry batch [num_nodes], the subgraph of every node of n_id; from any other loader
+        # the name stays the graph's attribute if it has one, else None
+        if name in DISJOINT_FIELDS and sb.batch is not None:
+            j = object.__getattribute__(self, "_j")
+            a = sb.node_ptr[j]
+            return sb.batch.narrow(0, a, sb.node_ptr[j + 1] - a)
         if name in sb.node_attrs or name in sb.edge_attrs:
             views = self._all()
             return views[sb._index[name]]
+        if name in DISJOINT_FIELDS:
+            return None
         raise AttributeError(name)
 
     def tensor_items(self):
@@ -223,13 +233,23 @@ class NeighborLoader(_Loader):
     loader's sampler among the admitted edges (`replace` honoured); "last" takes the num_neighbors most recent ones
     (TG_SAMPLER_RECENT: deterministic, fan-outs <= 64).  Mini-batches gain `input_time` [batch_size] and `node_time`
     [num_nodes]; a `data` that has node or edge attributes of those names is refused (from an untimed loader the names
-    stay the graph's attributes, as before).  unique=True is refused: deduplication would merge slots that carry different seed times."""
+    stay the graph's attributes, as before).
+
+    disjoint=True (needs unique=True; PyG's disjoint): every seed keeps its own subgraph.  tg_ns_homo_unique_grouped runs in
+    tg_ns_homo_unique's place and dedups by (subgraph, node): a node reached from two seeds is listed twice, once per
+    subgraph, and `batch` [num_nodes] names the subgraph (here: the seed's position in the mini-batch) of every node of
+    n_id, so both ends of every edge share `batch` and `batch_size` is the seed count.  It buys the contract, not speed:
+    inside one seed's tree there is little to merge.  A temporal loader takes unique=True only together with disjoint=True
+    -- the same node under two seeds of different times is two samples, so plain deduplication stays refused -- and its
+    `node_time` is then input_time[batch].  (PyG turns disjoint on by itself when times are given; here it is asked for by
+    name, so that unique=True alone keeps meaning the plain dedup.)  A `data` with a node or edge attribute named `batch` is
+    refused; induced=True with disjoint is out of scope and refused."""
 
     def __init__(self, data, num_neighbors: List[int], input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
                  prefetch: int = 16, replace: bool = False, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0, unique: bool = False,
                  induced: bool = False, time_attr: Optional[str] = None, input_time: Optional[Tensor] = None,
-                 temporal_strategy: str = "uniform", time_window=None):
+                 temporal_strategy: str = "uniform", time_window=None, disjoint: bool = False):
         if induced and not unique:
             raise ValueError("induced=True needs unique=True: the induced edges are numbered against the unique node list")
         if temporal_strategy not in ("uniform", "last"):
@@ -241,17 +261,27 @@ class NeighborLoader(_Loader):
         if time_window is not None and time_attr is None:
             raise ValueError("time_window needs time_attr and input_time")
         self.temporal = time_attr is not None
+        if disjoint and not unique:
+            raise ValueError("disjoint=True needs unique=True: without deduplication every seed's tree is apart already")
+        self.disjoint = bool(disjoint)
+        if self.temporal and unique and not self.disjoint:
+            raise ValueError("a temporal loader with unique=True needs disjoint=True: plain deduplication would merge slots "
+                             "that carry different seed times")
+        if self.disjoint and induced:
+            raise ValueError("induced=True with disjoint subgraphs is out of scope: the induced edges are found per "
+                             "mini-batch, not per subgraph")
+        if self.disjoint:
+            for key, value in _tensor_items(data):   # the mini-batches' own `batch` would hide it
+                if key in DISJOINT_FIELDS and _attr_kind(key, value, _num_nodes(data), int(data.edge_index.shape[1])) in ("node", "edge"):
+                    raise ValueError("a disjoint loader's mini-batches carry their own `%s`: rename data.%s" % (key, key))
         if self.temporal:                   # everything that can be refused is refused before any device work
-            if unique:
-                raise ValueError("a temporal loader with unique=True is not offered: deduplication would merge slots that "
-                                 "carry different seed times")
             times = getattr(data, time_attr, None)
             n_edges = int(data.edge_index.shape[1])
             if not isinstance(times, Tensor) or times.dtype != torch.int64 or times.numel() != n_edges:
                 raise ValueError("data.%s must be an int64 tensor with one entry per edge (%d)" % (time_attr, n_edges))
             n_inputs = _num_nodes(data) if input_nodes is None else input_nodes.numel()
-            if input_time.dtype != torch.int64 or input_time.numel() != n_inputs:
-                raise ValueError("input_time must be int64 with one entry per input node (%d)" % n_inputs)
+            if not isinstance(input_time, Tensor) or input_time.dtype != torch.int64 or input_time.numel() != n_inputs:
+                raise ValueError("%s must be an int64 tensor with one entry per %s (%d)" % (self.TIME_ARG + (n_inputs,)))
             if temporal_strategy == "last" and any(int(k) > 64 for k in num_neighbors):
                 raise ValueError("temporal_strategy='last' takes num_neighbors up to 64")
             for key, value in _tensor_items(data):   # the mini-batches' own input_time / node_time would hide them
@@ -303,6 +333,7 @@ class NeighborLoader(_Loader):
 
     # ---- what a loader whose work items are not the seeds themselves fills in (LinkNeighborLoader)
     WITH_INVERSE = False            # unique=True: keep tg_ns_homo_unique's `inverse` slab (forest position -> n_id position)
+    TIME_ARG = ("input_time", "input node")   # what the work items' times are called in a refusal
 
     def _seed_width(self, width: int) -> int:
         """Seeds of a mini-batch of `width` work items."""
@@ -313,10 +344,25 @@ class NeighborLoader(_Loader):
         first_batch; called on the side stream, directly ahead of the sampler."""
         return items
 
+    def _seed_times(self, slab, times: Tensor) -> Tensor:
+        """The [G, seeds] times the sampler filters under for the work items' times [G, width]; called on the side stream
+        next to _seed_rows."""
+        return times
+
+    def _seed_groups(self, seeds: int):
+        """disjoint: (seed_group, n_groups) of a seed row of this width -- the int32 device map seed position -> subgraph,
+        None for the identity (one subgraph per seed)."""
+        return None, seeds
+
     def _new_super_batch(self, slab, G: int) -> SuperBatch:
         """The launch's container; called on the caller's stream while the slab set is still the launch's (whatever a
         subclass needs from it is copied here)."""
         return SuperBatch()
+
+    def _times_of(self, sb, slab, G: int, times: Tensor):
+        """-> (input_time [G, seeds], the subgraphs' times [G, n_groups]) of a temporal launch, for the super-batch; called
+        on the caller's stream behind _new_super_batch."""
+        return times, times
 
     # ---- stage 1 (side stream): sample G mini-batches into slab set `which`, sizes -> pinned host memory
     def _sample(self, slabs, which, seeds: Tensor, first_batch: int, times: Optional[Tensor] = None):
@@ -332,7 +378,8 @@ class NeighborLoader(_Loader):
                     "lo": torch.empty((cap, max(H, 1), 3), dtype=torch.int64).pin_memory(),
                     "free": None}
             if self.unique:
-                slab["uniq"] = _cabi.NsUniqueOut(slab["out"], in_place=True, with_inverse=self.WITH_INVERSE)
+                slab["uniq"] = _cabi.NsUniqueOut(slab["out"], in_place=True, with_inverse=self.WITH_INVERSE,
+                                                 with_group=self.disjoint)
                 slab["ln"] = torch.empty((cap, max(H, 1)), dtype=torch.int64).pin_memory()
             slabs[which] = slab
         time_ws = None
@@ -359,19 +406,29 @@ class NeighborLoader(_Loader):
             out = slab["out"]
             if self.temporal:                # backward RELATIVE filter: 0 <= seed time - edge time <= hi, state kept down the tree
                 times = times.contiguous()
+                seed_times = self._seed_times(slab, times)
                 _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
                                       sampler=self.sampler, filter_mode=_cabi.FILTER_RELATIVE, forward=False,
-                                      window=self.time_window, seeds_state=times, ws=time_ws)
+                                      window=self.time_window, seeds_state=seed_times, ws=time_ws)
             else:
                 _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
                                       sampler=self.sampler, ws=self._ws if G >= 2048 else None, form=self.form)
             sizes = out
             if self.unique:                  # dedup + relabel directly behind the sampler; the host reads the unique counts
                 sizes = uniq = slab["uniq"]
-                need, least = _cabi.ns_homo_unique_workspace_bytes(out.cap_nodes, self.n_nodes, out.n_batches)
+                if self.disjoint:            # the dedup key is (subgraph, node): one subgraph per group of seeds
+                    seed_group, n_groups = self._seed_groups(B)
+                    need, least = _cabi.ns_homo_unique_grouped_workspace_bytes(out.cap_nodes, self.n_nodes, n_groups,
+                                                                               out.n_batches)
+                else:
+                    need, least = _cabi.ns_homo_unique_workspace_bytes(out.cap_nodes, self.n_nodes, out.n_batches)
                 if need and (self._unique_ws is None or self._unique_ws.numel() * 8 < least):
                     self._unique_ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=self.device)
-                _cabi.ns_homo_unique(out, G, self.n_nodes, ws=self._unique_ws if need else None, result=uniq)
+                if self.disjoint:
+                    _cabi.ns_homo_unique_grouped(out, G, self.n_nodes, seed_group=seed_group, n_groups=n_groups,
+                                                 ws=self._unique_ws if need else None, result=uniq)
+                else:
+                    _cabi.ns_homo_unique(out, G, self.n_nodes, ws=self._unique_ws if need else None, result=uniq)
                 if H:
                     slab["ln"][:G].copy_(uniq.layer_nodes[:G], non_blocking=True)
                 if self.induced:             # pass 1: the edge counts join the sizes the host waits for
@@ -410,10 +467,18 @@ class NeighborLoader(_Loader):
         else:
             n_id, edge_index, e_ptr = _cabi.ns_homo_compact(src, G, counts, stacked=True)   # copies: the slabs go back to the sampler
         sb = self._new_super_batch(slab, G)
-        sb.input_time = sb.node_time = None
-        if self.temporal:                    # the states slab trimmed like samples (a copy: the slab goes back)
-            sb.input_time = times
-            sb.node_time = _flat_rows(out.states[:G], out.counts[:G, 0], sum(n_nodes))
+        sb.input_time = sb.node_time = sb.batch = None
+        total = sum(n_nodes)
+        if self.disjoint:                    # the group slab trimmed like nodes (a copy: the slab goes back)
+            sb.batch = _flat_rows(src.group[:G], src.counts[:G, 0], total)
+        if self.temporal:
+            sb.input_time, group_times = self._times_of(sb, slab, G, times)
+            if self.disjoint:                # time is a function of the subgraph: mini-batch g's node u has group_times[g][batch[u]]
+                first = torch.arange(G, device=self.device) * group_times.shape[1]
+                first = torch.repeat_interleave(first, src.counts[:G, 0], output_size=total)
+                sb.node_time = group_times.reshape(-1)[first + sb.batch]
+            else:                            # the states slab trimmed like samples (a copy: the slab goes back)
+                sb.node_time = _flat_rows(out.states[:G], out.counts[:G, 0], total)
         free = torch.cuda.Event()
         free.record(cur)
         slab["free"] = free
@@ -1247,9 +1312,10 @@ class LinkSuperBatch(SuperBatch):
     """A SuperBatch of a LinkNeighborLoader: the G mini-batches of ONE tg_link_seeds + tg_ns_homo_batched launch, plus the
     link fields as batch-major tensors (row g is mini-batch g's, numbered against ITS n_id): `input_id` [G, E],
     `neg_unverified` [G], `batch_size` = E; binary: `edge_label_index` [G, 2, P], `edge_label` [G, P]; triplet:
-    `src_index`, `dst_pos_index` [G, E], `dst_neg_index` [G, E, K] (`edge_label` [G, E] only when the user gave labels)."""
+    `src_index`, `dst_pos_index` [G, E], `dst_neg_index` [G, E, K] (`edge_label` [G, E] only when the user gave labels); from a
+    temporal loader `edge_label_time` [G, P] (triplet: [G, E]; else None)."""
     __slots__ = ("neg_sampling", "edge_label_index", "edge_label", "src_index", "dst_pos_index", "dst_neg_index", "input_id",
-                 "neg_unverified")
+                 "neg_unverified", "edge_label_time")
 
     def __getitem__(self, j):
         if j < 0:
@@ -1283,6 +1349,7 @@ class LinkMiniBatch(MiniBatch):
     dst_neg_index = _row_of("dst_neg_index")
     input_id = _row_of("input_id")
     neg_unverified = _row_of("neg_unverified")
+    edge_label_time = _row_of("edge_label_time")
 
 
 class LinkNeighborLoader(NeighborLoader):
@@ -1296,16 +1363,29 @@ class LinkNeighborLoader(NeighborLoader):
     Numbering against n_id: under unique=False seed p sits at n_id[p], so the index tensors are constants shared by all
     mini-batches of one width; under unique=True they are tg_ns_homo_unique's `inverse` of the seed positions, copied out of
     the slab before the sampler gets it back.  `edge_label` (user labels [N]) is carried through only when K = 0.
-    `edge_set=True` builds the CSC's edge set once (one probe per check instead of a binary search) when the ids fit."""
+    `edge_set=True` builds the CSC's edge set once (one probe per check instead of a binary search) when the ids fit.
+
+    Temporal (PyG's time_attr / edge_label_time): `edge_label_time` holds one int64 per label edge and is sliced and
+    shuffled with the edges; `time_attr`, `temporal_strategy` and `time_window` are NeighborLoader's.  Both endpoints of
+    pair j sample under the pair's time; negative u belongs to positive u // K (in binary mode as in triplet mode) and takes
+    its time.  Negatives are still checked against the WHOLE graph, not against time: a pair that becomes an edge only
+    after its time is not drawn as a negative.  Mini-batches gain `edge_label_time` [P] (the pairs' times; triplet: [E], the
+    positives'), `input_time` [S] (per seed) and `node_time`.  unique=False hands out the temporal forest; unique=True the
+    disjoint contract (implied by the times, as in PyG; `disjoint=True` asks for it without times): one subgraph per pair -- binary: seed s belongs to
+    subgraph s mod P; triplet: src i, dst_pos i and dst_neg u to subgraphs i, i and u // K -- so src_j and dst_j share a
+    subgraph, `batch` names every node's, and edge_label_index and friends come from `inverse` as before."""
     WITH_INVERSE = True
+    TIME_ARG = ("edge_label_time", "label edge")
 
     def __init__(self, data, num_neighbors: List[int], edge_label_index: Optional[Tensor] = None,
                  edge_label: Optional[Tensor] = None, neg_sampling_ratio: int = 1, neg_sampling: str = "binary",
                  try_count: int = 8, batch_size: int = 1024, prefetch: int = 16, replace: bool = False, shuffle: bool = False,
                  drop_last: bool = False, seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0,
-                 unique: bool = False, edge_set: bool = False, time_attr: Optional[str] = None):
-        if time_attr is not None:
-            raise ValueError("LinkNeighborLoader takes no time_attr: seed times per label edge (edge_label_time) are not offered")
+                 unique: bool = False, edge_set: bool = False, time_attr: Optional[str] = None,
+                 edge_label_time: Optional[Tensor] = None, temporal_strategy: str = "uniform", time_window=None,
+                 disjoint: bool = False):
+        if (time_attr is None) != (edge_label_time is None):
+            raise ValueError("time_attr and edge_label_time come together: edge times need a time per label edge and the reverse")
         if neg_sampling not in ("binary", "triplet"):
             raise ValueError("neg_sampling must be 'binary' or 'triplet'")
         K = int(neg_sampling_ratio)
@@ -1319,15 +1399,23 @@ class LinkNeighborLoader(NeighborLoader):
         eli = data.edge_index if edge_label_index is None else edge_label_index
         if eli.dim() != 2 or eli.shape[0] != 2:
             raise ValueError("edge_label_index must be [2, N]")
+        if edge_label_time is not None and (not isinstance(edge_label_time, Tensor) or edge_label_time.dtype != torch.int64
+                                            or edge_label_time.numel() != eli.shape[1]):
+            raise ValueError("edge_label_time must be an int64 tensor with one entry per label edge (%d)" % eli.shape[1])
+        if disjoint and not unique:
+            raise ValueError("disjoint=True needs unique=True: without deduplication every seed's tree is apart already")
         eli = eli.to(dev).to(torch.int64).contiguous()
         n_nodes = _num_nodes(data)
         if eli.numel() and (int(eli.min()) < 0 or int(eli.max()) >= n_nodes):   # once, as _checked_inputs: no launch yet
             raise IndexError("edge_label_index outside [0, %d)" % n_nodes)
         if edge_label is not None and edge_label.shape[0] != eli.shape[1]:
             raise ValueError("edge_label must have one entry per edge of edge_label_index")
-        super().__init__(data, num_neighbors, input_nodes=eli.new_empty(0), batch_size=batch_size, prefetch=prefetch,
-                         replace=replace, shuffle=shuffle, drop_last=drop_last, seed=seed, call_id0=call_id0, device=dev,
-                         form=form, unique=unique)
+        # the base class sees the work items only as a count (for the times' length); the real ones are set below
+        super().__init__(data, num_neighbors, input_nodes=eli.new_zeros(eli.shape[1] if time_attr is not None else 0),
+                         batch_size=batch_size, prefetch=prefetch, replace=replace, shuffle=shuffle, drop_last=drop_last,
+                         seed=seed, call_id0=call_id0, device=dev, form=form, unique=unique, time_attr=time_attr,
+                         input_time=edge_label_time, temporal_strategy=temporal_strategy, time_window=time_window,
+                         disjoint=bool(disjoint) or (time_attr is not None and bool(unique)))   # as PyG: times force disjoint
         self.edge_label_index = eli
         self.edge_label = None if edge_label is None else edge_label.to(dev)
         self.input_nodes = torch.arange(eli.shape[1], device=dev)    # the work items: positions in edge_label_index
@@ -1363,6 +1451,45 @@ class LinkNeighborLoader(NeighborLoader):
             c = self._consts[E] = (local, label)
         return c
 
+    def _group_constants(self, E: int):
+        """What all mini-batches of E positives share under times or disjoint subgraphs: (seed_group int32 [S], n_groups,
+        of_positive int64 [S]) -- the subgraph of every seed of the row and the positive whose time it samples under.  Pair
+        j < E is positive j, negative u = j - E belongs to positive u // K; binary: the row is [src of P pairs | dst of P
+        pairs], a subgraph per pair; triplet: [src | dst_pos | dst_neg], a subgraph per positive."""
+        c = self._consts.get(("groups", E))
+        if c is None:
+            K = self.K
+            of_pair = torch.cat([torch.arange(E, device=self.device),
+                                 torch.div(torch.arange(E * K, device=self.device), max(K, 1), rounding_mode="floor")])
+            if self.mode == _cabi.LINK_BINARY:
+                P = E + E * K
+                group, of_positive, n_groups = torch.arange(P, device=self.device).repeat(2), of_pair.repeat(2), P
+            else:
+                group = of_positive = torch.cat([torch.arange(E, device=self.device), of_pair])
+                n_groups = E
+            c = self._consts[("groups", E)] = (group.to(torch.int32).contiguous(), n_groups, of_positive.contiguous())
+        return c
+
+    def _seed_groups(self, seeds: int):
+        per = 2 * (1 + self.K) if self.mode == _cabi.LINK_BINARY else 2 + self.K    # seeds per positive: _seed_width's inverse
+        group, n_groups, _ = self._group_constants(seeds // per)
+        return group, n_groups
+
+    def _seed_times(self, slab, times: Tensor) -> Tensor:
+        G, E = times.shape
+        _, _, of_positive = self._group_constants(E)
+        S, cap = of_positive.numel(), slab["out"].n_batches
+        rows = slab.get("seed_times")
+        if rows is None or rows.shape != (cap, S):
+            rows = slab["seed_times"] = torch.empty((cap, S), dtype=torch.int64, device=self.device)
+        slab["label_times"] = times
+        torch.index_select(times, 1, of_positive, out=rows[:G])     # one gather on the side stream, ahead of the sampler
+        return rows[:G]
+
+    def _times_of(self, sb, slab, G: int, times: Tensor):
+        # a copy: the seed-time rows go back to the sampler with the slab set
+        return slab["seed_times"][:G].clone(), sb.edge_label_time
+
     def _new_super_batch(self, slab, G: int) -> LinkSuperBatch:
         sb = LinkSuperBatch()
         items = slab["items"]
@@ -1375,7 +1502,12 @@ class LinkNeighborLoader(NeighborLoader):
             local = const.expand(G, S)
         sb.neg_sampling, sb.input_id = self.neg_sampling, items
         sb.neg_unverified = slab["unv"][:G].clone()
-        sb.edge_label_index = sb.edge_label = sb.src_index = sb.dst_pos_index = sb.dst_neg_index = None
+        sb.edge_label_index = sb.edge_label = sb.src_index = sb.dst_pos_index = sb.dst_neg_index = sb.edge_label_time = None
+        if self.temporal:                    # the pairs' times (triplet: the positives'): the subgraphs' either way
+            times = slab["label_times"]
+            if self.mode == _cabi.LINK_BINARY:
+                times = times.index_select(1, self._group_constants(E)[2][:P])
+            sb.edge_label_time = times
         if self.mode == _cabi.LINK_BINARY:
             sb.edge_label_index = local.view(G, 2, P)
             sb.edge_label = label.expand(G, P)

@@ -38,8 +38,25 @@ temporal_strategy="uniform", time_window=None): `time_attr` names an int64 [E] t
 (time_window = (lo, hi), default (0, 2**62)) and a seed's whole subtree keeps its time.  "uniform" draws among the admitted
 edges (replace honoured), "last" takes the num_neighbors most recent (RecentEdgeSampler's kernel).  Mini-batches gain
 input_time [batch_size] and node_time [num_nodes] (a graph with attributes of those names is refused; from an untimed
-loader the names stay the graph's own attributes).  unique=True with times, and time_attr on LinkNeighborLoader, raise
-ValueError."""
+loader the names stay the graph's own attributes).
+
+Disjoint mini-batches (PyG's disjoint=True: one subgraph per seed, the dedup key is (subgraph, node), `batch` [num_nodes]
+names every node's subgraph) come from loader.NeighborLoader(..., unique=True, disjoint=True), with or without times; a
+temporal NeighborLoader with unique=True and no disjoint=True raises ValueError (plain dedup would merge seed times).  The operator is tg_ns_homo_unique_grouped (csrc/ns_unique_grouped.hip):
+_cabi.ns_homo_unique_grouped(out, n_batches, id_bound, seed_group=None, n_groups=None, form=0, ws=None, in_place=False,
+result=None, with_inverse=True) -> an NsUniqueOut(..., with_group=True) whose `group` slab is the batch vector, with
+_cabi.ns_homo_unique_grouped_form(cap_nodes, id_bound, n_groups, lds_limit_bytes=0) -> (form, lds_bytes),
+_cabi.ns_homo_unique_grouped_workspace_bytes(cap_nodes, id_bound, n_groups, n_batches) -> (bytes, bytes_min) and
+_cabi.ns_homo_unique_grouped_workspace(cap_nodes, id_bound, n_groups, n_batches, device, form=0); for one call
+transforms.unique_nodes(samples, rows, cols, id_bound=None, seed_group=None, n_seeds=None) -> with seed_group (an int
+tensor [n_seeds]) (nodes, rows_u, cols_u, inverse, batch), without it the four-tuple as before.
+
+Temporal link-level mini-batches come from LinkNeighborLoader(..., time_attr=None, edge_label_time=None,
+temporal_strategy="uniform", time_window=None, disjoint=False): `edge_label_time` holds one int64 per label edge; both
+endpoints of a pair sample under the pair's time, a negative under its positive's (negative u belongs to positive u // K);
+negatives are checked against the whole graph, not against time.  Mini-batches gain edge_label_time [P] (triplet: [E]),
+input_time [S], node_time and, under unique=True (one subgraph per pair; triplet: per positive), batch.  induced=True
+with disjoint subgraphs raises ValueError."""
 from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor

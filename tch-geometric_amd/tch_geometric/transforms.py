@@ -167,19 +167,69 @@ class _OneCallSlabs:
     struct = _cabi.NsBatchedOut.struct
 
 
-def unique_nodes(samples: Tensor, rows: Tensor, cols: Tensor, id_bound: Optional[int] = None):
+def _unique_nodes_grouped(samples: Tensor, rows: Tensor, cols: Tensor, id_bound, seed_group: Tensor, n_seeds):
+    """unique_nodes per group of seeds: -> (nodes, rows_u, cols_u, inverse, batch)."""
+    n, m = samples.numel(), rows.numel()
+    n_seeds = seed_group.numel() if n_seeds is None else int(n_seeds)
+    if seed_group.dtype not in (torch.int32, torch.int64) or seed_group.numel() != n_seeds:
+        raise ValueError("seed_group must be an int32 or int64 tensor with one entry per seed (%d)" % n_seeds)
+    if n != n_seeds + m:
+        raise ValueError("a forest of %d seeds and %d edges has %d samples, got %d" % (n_seeds, m, n_seeds + m, n))
+    seed_group = seed_group.reshape(-1)
+    if n_seeds and (int(seed_group.min()) < 0):
+        raise ValueError("seed_group holds a negative group")
+    n_groups = int(seed_group.max()) + 1 if n_seeds else 1
+    if n == 0:
+        return samples, rows, cols, samples, samples
+    if not samples.is_cuda:
+        cols = cols.cpu()
+        if m and (bool((cols < 0).any()) or bool((cols >= torch.arange(n_seeds, n)).any())):
+            raise ValueError("cols[e] must be a position before n_seeds + e")
+        root = torch.cat([torch.arange(n_seeds), cols])
+        while bool((root >= n_seeds).any()):                       # pointer jumping: a parent sits before its child
+            root = root[root]
+        group = seed_group.cpu().to(torch.int64)[root]
+        pairs, inv = torch.unique(torch.stack([group, samples], 1), dim=0, return_inverse=True)
+        first = torch.full((pairs.shape[0],), n, dtype=torch.int64).scatter_reduce_(0, inv, torch.arange(n), "amin")
+        order = torch.argsort(first)
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(order.numel())
+        inverse = rank[inv]
+        return pairs[order, 1], inverse[rows], inverse[cols], inverse, pairs[order, 0]
+    dev = samples.device
+    if id_bound is None:                                           # the pair key needs a real bound: one read-back
+        id_bound = int(samples.max()) + 1 if n else 1
+    slabs = _OneCallSlabs(samples, rows.to(dev), cols.to(dev))
+    slabs.n_seeds, slabs.n_hops = n_seeds, _cabi.TG_MAX_HOPS       # the hop count is not known here: the deepest forest
+    slabs.layer_offsets = torch.zeros((1, _cabi.TG_MAX_HOPS, 3), dtype=torch.int64, device=dev)
+    u = _cabi.ns_homo_unique_grouped(slabs, 1, int(id_bound), seed_group=seed_group.to(dev).to(torch.int32).contiguous(),
+                                     n_groups=n_groups)
+    n_unique = int(u.counts[0, 0])
+    return u.nodes[0, :n_unique], u.rows[0, :m], u.cols[0, :m], u.inverse[0, :n], u.group[0, :n_unique]
+
+
+def unique_nodes(samples: Tensor, rows: Tensor, cols: Tensor, id_bound: Optional[int] = None,
+                 seed_group: Optional[Tensor] = None, n_seeds: Optional[int] = None):
     """Node dedup and relabel of ONE sampled batch (what neighbor_sampling_homogenous returns: a forest, a vertex reached
     along two paths holds two slots) -> (nodes, rows_u, cols_u, inverse): `nodes` lists each value of `samples` once, in
     order of first occurrence (distinct seeds stay first, in order), nodes[inverse] == samples, rows_u = inverse[rows],
     cols_u = inverse[cols]; edges are not merged.  Device tensors run tg_ns_homo_unique (csrc/ns_unique.hip; one read-back
     of the unique count); CPU tensors take a torch implementation of the same rule.  id_bound: every id is in
-    [0, id_bound) (at most 2^31 takes 32-bit hash keys); None assumes nothing beyond non-negative int64 ids."""
+    [0, id_bound) (at most 2^31 takes 32-bit hash keys); None assumes nothing beyond non-negative int64 ids.
+
+    seed_group (int tensor [n_seeds], values >= 0; n_seeds defaults to its length) asks for the disjoint form, PyG's
+    disjoint=True: the first n_seeds samples are the seeds, edge e made sample n_seeds + e from the earlier position
+    cols[e] (what the sampler returns), every sample belongs to the group of the seed its parents lead to, and a node is
+    listed once per GROUP that reaches it -> (nodes, rows_u, cols_u, inverse, batch), batch[u] the group of nodes[u]
+    (tg_ns_homo_unique_grouped, csrc/ns_unique_grouped.hip; forests of up to TG_MAX_HOPS hops)."""
     for t in (samples, rows, cols):
         if t.dtype != torch.int64:
             raise ValueError("Tensor must be a is of invalid type. Expected Int64 but got %s" % t.dtype)
     samples, rows, cols = samples.reshape(-1), rows.reshape(-1), cols.reshape(-1)
     if rows.numel() != cols.numel():
         raise ValueError("rows and cols differ in length")
+    if seed_group is not None:
+        return _unique_nodes_grouped(samples, rows, cols, id_bound, seed_group, n_seeds)
     if not samples.is_cuda:
         n = samples.numel()
         values, inv = torch.unique(samples, return_inverse=True)
