@@ -1300,6 +1300,50 @@ TG_API int tg_ns_induced_emit(const tg_graph *csc, const tg_ns_induced_in *in, i
                               const int64_t *edge_off, int64_t *rows, int64_t *cols, int64_t *edge_index,
                               void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- induced edges per SUBGRAPH of a disjoint list (ShaDow-GNN's k-hop sampler; subgraph_type="induced" under times) -----
+ * The pair above with a group dimension, behind tg_ns_homo_unique_grouped.  Per batch b (n as above):
+ *   local(g, v) = the FIRST position p < n with (group[p], nodes[p]) == (g, v)
+ *   for i in 0 .. n-1, g = group[i], for e in ptrs[nodes[i]] .. ptrs[nodes[i]+1]-1 ascending:
+ *       j = local(g, indices[e]);  if j exists and the edge is admitted: emit (row = j, col = i, edge_index = e)
+ * Order is (i, e) ascending, parallel edges and self loops are kept, both ends of every triple share a group.  Admitted:
+ * always when group_time is NULL (csc->timestamps is then not looked at); else the backward TG_FILTER_RELATIVE predicate of
+ * the filtered hops, window_lo <= group_time[b][g] - csc->timestamps[e] <= window_hi in wrapping int64 arithmetic
+ * (csc->timestamps NULL is then refused).  The timestamp is read only behind a table hit; both passes evaluate the same
+ * predicate.  The hash key is group * id_bound + id as in tg_ns_homo_unique_grouped: 32-bit while n_groups * id_bound <=
+ * 2^31, else 64-bit, >= 2^63 refused; n_groups in [1, 2^31).
+ * status: bit 1 as above; a group word outside [0, n_groups) makes its position a column of length 0 that is no `local` of
+ * anything and raises bit 2 (value 4).
+ * Capacity: columns of a disjoint list are NOT disjoint (a hub reached from many seeds is one entry per seed), so the
+ * caller states how many chunks per batch the workspace holds: chunk_cap (<= 0: the ungrouped bound pitch_nodes +
+ * ceil(n_edges / 512); at most 2^31).  chunks[b] (device int64 [n_batches], or NULL) always receives the batch's exact
+ * chunk count, the sum over positions of ceil(column length / 512).  A batch with chunks[b] > chunk_cap raises status bit 0,
+ * gets m_b = 0 and nothing from pass 2; other batches are unaffected; the caller may repeat both passes with chunk_cap =
+ * max(chunks) in a workspace of that size.  edge_marks, the two exact passes, the untouched workspace between them, no
+ * allocation / synchronisation / read-back and refusals with TG_ERR_INVALID before any launch are the ungrouped pair's. */
+typedef struct {
+    const int64_t *nodes;       /* device [n_batches * pitch_nodes]: tg_ns_unique_grouped_out.nodes */
+    const int64_t *group;       /* device [n_batches * pitch_nodes]: tg_ns_unique_grouped_out.group */
+    int64_t pitch_nodes;
+    const int64_t *counts;
+    int64_t counts_stride;
+    const int64_t *node_marks;  /* as tg_ns_induced_in */
+    int32_t n_marks;
+    int64_t n_groups;
+    const int64_t *group_time;  /* device [n_batches * n_groups] or NULL: no time filter */
+    int64_t window_lo, window_hi;
+    int64_t chunk_cap;          /* chunks per batch the workspace holds; <= 0: pitch_nodes + ceil(n_edges / 512) */
+} tg_ns_induced_grouped_in;
+
+TG_API int tg_ns_induced_grouped_workspace_bytes(const tg_graph *csc, int64_t pitch_nodes, int64_t id_bound, int64_t n_groups,
+                                                 int64_t chunk_cap, int64_t n_batches, int64_t *bytes,
+                                                 int64_t *bytes_min /* one batch */);
+TG_API int tg_ns_induced_grouped_count(const tg_graph *csc, const tg_ns_induced_grouped_in *in, int64_t n_batches,
+                                       int64_t id_bound, int64_t *n_edges, int64_t *edge_marks, int64_t *chunks,
+                                       int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+TG_API int tg_ns_induced_grouped_emit(const tg_graph *csc, const tg_ns_induced_grouped_in *in, int64_t n_batches,
+                                      int64_t id_bound, const int64_t *edge_off, int64_t *rows, int64_t *cols,
+                                      int64_t *edge_index, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Ragged rows of an int64 slab -> one flat array: dst[offsets[r] + i] = src[r * pitch + i] for
  * i < lens[r * lens_stride] (lens, offsets: device arrays).  The per-type / per-relation slabs of
  * tg_ns_hetero_batched are flattened with it (tch_geometric/loader.py). */

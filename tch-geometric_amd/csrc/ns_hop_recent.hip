@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "tg_device.h"
+#include "tg_filter.h"
 #include "tg_host.h"
 #include "tg_scan.h"
 
@@ -62,10 +63,7 @@ __device__ __forceinline__ RcEntry rc_exchange(const RcEntry &v, int j, bool kee
 }
 
 __device__ __forceinline__ bool rc_pass(const RecentParams &p, int64_t state, int64_t t) { // neighbor_sampling.rs:55-67
-    if (p.filter_mode == TG_FILTER_NONE) return true;
-    const uint64_t d = (uint64_t)t - (uint64_t)state; // wrapping, like the reference's release build
-    const int64_t x = (p.filter_mode == TG_FILTER_STATIC) ? t : (p.forward ? (int64_t)d : (int64_t)(0 - d));
-    return p.win_lo <= x && x <= p.win_hi;
+    return tg_filter_pass(p.filter_mode, p.forward, p.win_lo, p.win_hi, state, t);
 }
 
 __global__ void __launch_bounds__(256) recent_select_kernel(const RecentParams p) {

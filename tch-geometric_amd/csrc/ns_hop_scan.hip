@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "tg_device.h"
+#include "tg_filter.h"
 #include "tg_host.h"
 #include "tg_scan.h"
 
@@ -92,9 +93,7 @@ __device__ __forceinline__ int hs_seg_of(const HsSeg *S, int n_seg, int64_t v) {
 }
 
 __device__ __forceinline__ bool hs_pass(const HopScanParams &p, int64_t state, int64_t t) { // neighbor_sampling.rs:55-67
-    if (p.filter_mode == TG_FILTER_NONE) return true;
-    const int64_t x = (p.filter_mode == TG_FILTER_STATIC) ? t : (p.forward ? (t - state) : -(t - state));
-    return p.win_lo <= x && x <= p.win_hi;
+    return tg_filter_pass(p.filter_mode, p.forward, p.win_lo, p.win_hi, state, t);
 }
 
 __global__ void hs_groups_kernel(const HopScanParams p) {

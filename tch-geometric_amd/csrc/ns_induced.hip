@@ -29,9 +29,19 @@
 // Infinity Cache hits at best, and only wavefronts in flight hide them -- 8 waves per SIMD, no LDS, few registers.
 // An id outside [0, n_major) is a column of length 0, is not inserted and raises status bit 1.  Probe loops are capped at
 // the table size.
+//
+// The GROUPED pair (tg_ns_induced_grouped_count / _emit: induced edges per subgraph of a disjoint list, ShaDow's k-hop
+// sampler) is the same kernels with G = true: the table key is group * id_bound + id (tg_ns_homo_unique_grouped's), the
+// scan reads the position's group -- and, under times, the group's time -- once per chunk in the unit's look-up lanes, and
+// a table hit is kept only where tg_filter_pass admits the edge's timestamp (loaded behind the hit, the same expression in
+// both passes).  Columns of such a list are not disjoint, so the chunk capacity is the caller's (chunk_cap), the exact
+// chunk count goes to chunks[b], and the comparison still happens in the node apply kernel.  A group word outside
+// [0, n_groups) is a column of length 0, is not inserted and raises status bit 2.  The G = false instances are what the
+// ungrouped exports launch: no group word is read, no key is widened, no timestamp is looked at.
 #include <algorithm>
 
 #include "ns_unique.h"
+#include "tg_filter.h"
 
 namespace tg {
 
@@ -60,6 +70,11 @@ struct NsiArgs {
     int64_t batch_bytes, vals_off, npref_off, ntile_off, cpref_off, ctile_off, chunk_bound;
     int64_t table_cap, chunk_tiles;
     uint32_t cap_mask, hash_shift;
+    // the grouped pair
+    const int64_t *group, *group_time, *timestamps; // group: batch 0 of the launch; group_time: [n_groups] per batch or null
+    int64_t n_groups, win_lo, win_hi;
+    uint64_t key_mul;                               // id_bound: key = group * key_mul + id
+    int64_t *chunks;                                // [batches] the exact chunk counts, or null
 };
 
 template <typename K> struct NsiBatch {
@@ -130,7 +145,7 @@ template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_clear_k
 }
 
 // a tile of positions: insert, chunks per position, their exclusive prefix inside the tile and the tile's sum
-template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_insert_kernel(const NsiArgs a) {
+template <typename K, bool G> __global__ void __launch_bounds__(NSI_THREADS) nsi_insert_kernel(const NsiArgs a) {
     __shared__ unsigned long long s_wave[NSI_THREADS / 64];
     const int64_t b = blockIdx.y;
     const int64_t n = nsu_clamp(a.counts[b * a.counts_stride], a.pitch);
@@ -138,27 +153,37 @@ template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_insert_
     if (tile0 >= n && blockIdx.x != 0) return; // uniform
     const NsiBatch<K> t(a, b);
     const int64_t *nodes = a.nodes + b * a.pitch;
+    const int64_t *group = G ? a.group + b * a.pitch : nullptr;
     const int64_t p0 = tile0 + (int64_t)threadIdx.x * NSU_PER;
     unsigned long long c[NSU_PER], mine = 0;
-    bool outside = false;
+    bool outside = false, no_group = false;
 #pragma unroll
     for (int k = 0; k < NSU_PER; ++k) {
         c[k] = 0;
         const int64_t p = p0 + k;
         if (p < n) {
             const int64_t v = nodes[p];
-            if ((uint64_t)v < (uint64_t)a.n_major) {
-                const uint32_t s = nsu_insert<K>(t.keys, a.cap_mask, a.hash_shift, (K)v);
+            K key = (K)v;
+            bool grouped = true;
+            if (G) {
+                const int64_t g = group[p];
+                grouped = (uint64_t)g < (uint64_t)a.n_groups;
+                no_group |= !grouped;
+                key += (K)g * (K)a.key_mul;
+            }
+            if ((uint64_t)v >= (uint64_t)a.n_major) {
+                outside = true;
+            } else if (grouped) {
+                const uint32_t s = nsu_insert<K>(t.keys, a.cap_mask, a.hash_shift, key);
                 atomicMin(&t.vals[s], (uint32_t)p);
                 const int64_t deg = nsi_ptr(a, v + 1) - nsi_ptr(a, v);
                 if (deg > 0) c[k] = (unsigned long long)((deg + NSI_CHUNK - 1) / NSI_CHUNK);
-            } else {
-                outside = true;
             }
         }
         mine += c[k];
     }
     if (outside) atomicOr(a.status, 2);
+    if (G && no_group) atomicOr(a.status, 4);
     unsigned long long total;
     unsigned long long run = nsi_scan64(mine, s_wave, &total);
 #pragma unroll
@@ -187,6 +212,7 @@ template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_node_ap
     if (tile0 + NSI_TILE >= n && threadIdx.x == 0) { // the batch's last tile (tile 0 of an empty batch)
         const unsigned long long total = base + t.ntile[blockIdx.x];
         t.npref[n] = total;
+        if (a.chunks) a.chunks[b] = (int64_t)total;
         if (total > (unsigned long long)a.chunk_bound) {
             atomicOr(a.status, 1);
             t.hdr[0] = 0;
@@ -197,7 +223,8 @@ template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_node_ap
 }
 
 // EMIT = false: hits per chunk (and their sum per tile of chunks); true: the hits themselves
-template <typename K, bool I32, bool EMIT> __global__ void __launch_bounds__(NSI_THREADS) nsi_scan_kernel(const NsiArgs a) {
+template <typename K, bool I32, bool EMIT, bool G>
+__global__ void __launch_bounds__(NSI_THREADS) nsi_scan_kernel(const NsiArgs a) {
     const int64_t b = blockIdx.y;
     const NsiBatch<K> t(a, b);
     const unsigned long long n_chunks = t.hdr[0];
@@ -214,8 +241,9 @@ template <typename K, bool I32, bool EMIT> __global__ void __launch_bounds__(NSI
     const int64_t out0 = EMIT ? a.edge_off[b] : 0;
     for (unsigned long long u = (unsigned long long)blockIdx.x * waves + wave; u < n_units; u += (unsigned long long)gridDim.x * waves) {
         const unsigned long long c = u * unit + lane;
-        long long my_i = 0, my_e0 = 0;
+        long long my_i = 0, my_e0 = 0, my_time = 0;
         int my_len = 0;
+        uint32_t my_group = 0;
         if (lane < unit && c < n_chunks) {
             // the last position whose prefix is <= c: npref[0] = 0 <= c < n_chunks = npref[n]
             int64_t lo = 0, hi = n;
@@ -228,6 +256,10 @@ template <typename K, bool I32, bool EMIT> __global__ void __launch_bounds__(NSI
             my_i = lo;
             my_e0 = col0 + (int64_t)(c - t.npref[lo]) * NSI_CHUNK;
             my_len = (int)std::min<int64_t>(NSI_CHUNK, col1 - my_e0);
+            if (G) { // the position has chunks, so its group word is in range
+                my_group = (uint32_t)a.group[b * a.pitch + lo];
+                if (a.group_time) my_time = a.group_time[b * a.n_groups + my_group];
+            }
         }
         unsigned long long unit_hits = 0;
         for (int q = 0; q < unit; ++q) {
@@ -235,14 +267,19 @@ template <typename K, bool I32, bool EMIT> __global__ void __launch_bounds__(NSI
             if (cq >= n_chunks) break; // uniform
             const long long i = __shfl(my_i, q), e0 = __shfl(my_e0, q);
             const int len = __shfl(my_len, q);
+            const K key0 = G ? (K)__shfl(my_group, q) * (K)a.key_mul : (K)0;
+            const long long time = G ? __shfl(my_time, q) : 0;
             const int64_t out = EMIT ? out0 + (int64_t)t.cpref[cq] : 0;
             uint32_t cnt = 0;
             for (int s = 0; s < len; s += 64) {
                 const int64_t e = e0 + s + lane;
                 uint32_t pos = NSU_UNSEEN;
                 if (s + lane < len) {
-                    const K key = I32 ? (K)a.indices32[e] : (K)a.indices[e];
+                    const K key = key0 + (I32 ? (K)a.indices32[e] : (K)a.indices[e]);
                     pos = nsi_find<K>(t.keys, t.vals, a.cap_mask, a.hash_shift, key);
+                    if (G && pos != NSU_UNSEEN && a.group_time &&
+                        !tg_filter_pass(TG_FILTER_RELATIVE, 0, a.win_lo, a.win_hi, time, a.timestamps[e]))
+                        pos = NSU_UNSEEN;
                 }
                 const unsigned long long hits = __ballot(pos != NSU_UNSEEN);
                 if (EMIT && pos != NSU_UNSEEN) {
@@ -316,16 +353,29 @@ struct NsiPlan {
     int64_t vals_off, npref_off, ntile_off, cpref_off, ctile_off, batch_bytes;
 };
 
-static int nsi_plan(const tg_graph *csc, int64_t pitch, int64_t id_bound, const char *who, NsiPlan &pl) {
+// n_groups = 0: the ungrouped pair (key = id, the chunk bound is the graph's); else key = group * id_bound + id and
+// chunk_cap > 0 is the caller's capacity
+static int nsi_plan(const tg_graph *csc, int64_t pitch, int64_t id_bound, int64_t n_groups, int64_t chunk_cap, const char *who,
+                    NsiPlan &pl) {
     TG_REQUIRE(csc, "%s: null graph", who);
     TG_REQUIRE(csc->n_major >= 0 && csc->n_edges >= 0, "%s: negative graph size (n_major = %lld, n_edges = %lld)", who,
                (long long)csc->n_major, (long long)csc->n_edges);
     TG_REQUIRE(pitch >= 0 && pitch <= NSU_MAX_NODES, "%s: pitch_nodes = %lld outside [0, 2^30]", who, (long long)pitch);
-    if (const int rc = nsu_plan(pitch, id_bound, who, pl.table)) return rc; // id_bound >= 1, the key width, the table
+    TG_REQUIRE(id_bound >= 1, "%s: id_bound = %lld, at least 1 expected", who, (long long)id_bound);
+    int64_t key_bound = id_bound;
+    if (n_groups) {
+        TG_REQUIRE(n_groups <= 0x7fffffff, "%s: n_groups = %lld does not fit a 31-bit group word", who, (long long)n_groups);
+        TG_REQUIRE(id_bound <= INT64_MAX / n_groups, "%s: n_groups * id_bound = %lld * %lld reaches 2^63: no key holds the pair",
+                   who, (long long)n_groups, (long long)id_bound);
+        key_bound = n_groups * id_bound;
+    }
+    if (const int rc = nsu_plan(pitch, key_bound, who, pl.table)) return rc; // the key width, the table
     TG_REQUIRE(id_bound >= csc->n_major, "%s: id_bound = %lld below n_major = %lld", who, (long long)id_bound,
                (long long)csc->n_major);
-    // distinct nodes have disjoint columns: every column ends in at most one ragged chunk
-    pl.chunk_bound = pitch + (csc->n_edges + NSI_CHUNK - 1) / NSI_CHUNK;
+    TG_REQUIRE(chunk_cap <= NSI_MAX_CHUNKS, "%s: chunk_cap = %lld, at most 2^31 expected", who, (long long)chunk_cap);
+    // distinct nodes have disjoint columns: every column ends in at most one ragged chunk.  A disjoint list has no such
+    // property; there this is only the default a caller may raise
+    pl.chunk_bound = chunk_cap > 0 ? chunk_cap : pitch + (csc->n_edges + NSI_CHUNK - 1) / NSI_CHUNK;
     TG_REQUIRE(pl.chunk_bound <= NSI_MAX_CHUNKS, "%s: %lld chunks per batch, at most 2^31 expected", who, (long long)pl.chunk_bound);
     pl.node_tiles = pitch > 0 ? (pitch + NSI_TILE - 1) / NSI_TILE : 1;
     pl.chunk_tiles = pl.chunk_bound / NSI_TILE + 1;
@@ -339,11 +389,17 @@ static int nsi_plan(const tg_graph *csc, int64_t pitch, int64_t id_bound, const 
 }
 
 // what both passes check alike, and the kernel arguments of batch 0
-static int nsi_common(const tg_graph *csc, const tg_ns_induced_in *in, int64_t n_batches, int64_t id_bound, void *workspace,
-                      int64_t workspace_bytes, const char *who, NsiPlan &pl, NsiArgs &a) {
+static int nsi_common(const tg_graph *csc, const tg_ns_induced_in *in, const tg_ns_induced_grouped_in *gin, int64_t n_batches,
+                      int64_t id_bound, void *workspace, int64_t workspace_bytes, const char *who, NsiPlan &pl, NsiArgs &a) {
     TG_REQUIRE(csc && in, "%s: null argument", who);
     TG_REQUIRE(n_batches >= 0 && n_batches <= 0x7fffffff, "%s: n_batches = %lld outside [0, 2^31)", who, (long long)n_batches);
-    if (const int rc = nsi_plan(csc, in->pitch_nodes, id_bound, who, pl)) return rc;
+    if (gin) TG_REQUIRE(gin->n_groups >= 1, "%s: n_groups = %lld, at least 1 expected", who, (long long)gin->n_groups);
+    if (const int rc = nsi_plan(csc, in->pitch_nodes, id_bound, gin ? gin->n_groups : 0, gin ? gin->chunk_cap : 0, who, pl))
+        return rc;
+    if (gin) {
+        TG_REQUIRE(gin->group, "%s: null group", who);
+        TG_REQUIRE(!gin->group_time || csc->timestamps, "%s: group_time given, but the graph has no timestamps", who);
+    }
     TG_REQUIRE(in->counts_stride >= 1, "%s: counts_stride = %lld, at least 1 expected", who, (long long)in->counts_stride);
     TG_REQUIRE(in->n_marks >= 0 && in->n_marks <= TG_MAX_HOPS, "%s: n_marks = %d outside [0, %d]", who, in->n_marks, TG_MAX_HOPS);
     TG_REQUIRE(workspace_bytes >= 0, "%s: workspace_bytes = %lld is negative", who, (long long)workspace_bytes);
@@ -364,13 +420,31 @@ static int nsi_common(const tg_graph *csc, const tg_ns_induced_in *in, int64_t n
     a.table_cap = pl.table.table_cap, a.chunk_tiles = pl.chunk_tiles;
     a.cap_mask = (uint32_t)(pl.table.table_cap - 1);
     a.hash_shift = 32u - (uint32_t)__builtin_ctzll((unsigned long long)pl.table.table_cap);
+    if (gin) {
+        a.group = gin->group, a.group_time = gin->group_time, a.timestamps = csc->timestamps;
+        a.n_groups = gin->n_groups, a.win_lo = gin->window_lo, a.win_hi = gin->window_hi;
+        a.key_mul = (uint64_t)id_bound;
+    }
     return TG_OK;
+}
+
+// the ungrouped fields of a grouped input
+static tg_ns_induced_in nsi_plain(const tg_ns_induced_grouped_in *g) {
+    tg_ns_induced_in in{};
+    if (g) {
+        in.nodes = g->nodes, in.pitch_nodes = g->pitch_nodes, in.counts = g->counts, in.counts_stride = g->counts_stride;
+        in.node_marks = g->node_marks, in.n_marks = g->n_marks;
+    }
+    return in;
 }
 
 // the arguments of the launch that starts at batch b0
 static NsiArgs nsi_at(const NsiArgs &a0, int64_t b0) {
     NsiArgs a = a0;
     a.nodes += b0 * a.pitch, a.counts += b0 * a.counts_stride, a.ws += b0 * a.batch_bytes;
+    if (a.group) a.group += b0 * a.pitch;
+    if (a.group_time) a.group_time += b0 * a.n_groups;
+    if (a.chunks) a.chunks += b0;
     if (a.node_marks) a.node_marks += b0 * a.n_marks;
     if (a.edge_marks) a.edge_marks += b0 * a.n_marks;
     if (a.n_edges) a.n_edges += b0;
@@ -380,33 +454,56 @@ static NsiArgs nsi_at(const NsiArgs &a0, int64_t b0) {
 
 static inline unsigned nsi_scan_grid(int64_t nb) { return (unsigned)std::max<int64_t>(1, NSI_SCAN_BLOCKS / nb); }
 
-template <typename K> static int nsi_launch_count(const NsiArgs &a, const NsiPlan &pl, int64_t nb_, hipStream_t stream) {
+template <typename K, bool G> static int nsi_launch_count(const NsiArgs &a, const NsiPlan &pl, int64_t nb_, hipStream_t stream) {
     const unsigned nb = (unsigned)nb_;
     const dim3 block(NSI_THREADS);
     const int64_t clear_blocks = (pl.table.table_cap + NSI_THREADS - 1) / NSI_THREADS;
     hipLaunchKernelGGL(nsi_clear_kernel<K>, dim3((unsigned)std::min<int64_t>(clear_blocks, 1024), nb), block, 0, stream, a);
     TG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(nsi_insert_kernel<K>, dim3((unsigned)pl.node_tiles, nb), block, 0, stream, a);
+    hipLaunchKernelGGL((nsi_insert_kernel<K, G>), dim3((unsigned)pl.node_tiles, nb), block, 0, stream, a);
     TG_LAUNCH_CHECK();
     hipLaunchKernelGGL(nsi_node_apply_kernel<K>, dim3((unsigned)pl.node_tiles, nb), block, 0, stream, a);
     TG_LAUNCH_CHECK();
     if (a.indices32)
-        hipLaunchKernelGGL((nsi_scan_kernel<K, true, false>), dim3(nsi_scan_grid(nb_), nb), block, 0, stream, a);
+        hipLaunchKernelGGL((nsi_scan_kernel<K, true, false, G>), dim3(nsi_scan_grid(nb_), nb), block, 0, stream, a);
     else
-        hipLaunchKernelGGL((nsi_scan_kernel<K, false, false>), dim3(nsi_scan_grid(nb_), nb), block, 0, stream, a);
+        hipLaunchKernelGGL((nsi_scan_kernel<K, false, false, G>), dim3(nsi_scan_grid(nb_), nb), block, 0, stream, a);
     TG_LAUNCH_CHECK();
     hipLaunchKernelGGL(nsi_chunk_apply_kernel<K>, dim3((unsigned)pl.chunk_tiles, nb), block, 0, stream, a);
     TG_LAUNCH_CHECK();
     return TG_OK;
 }
 
-template <typename K> static int nsi_launch_emit(const NsiArgs &a, int64_t nb_, hipStream_t stream) {
+template <typename K, bool G> static int nsi_launch_emit(const NsiArgs &a, int64_t nb_, hipStream_t stream) {
     const dim3 grid(nsi_scan_grid(nb_), (unsigned)nb_), block(NSI_THREADS);
     if (a.indices32)
-        hipLaunchKernelGGL((nsi_scan_kernel<K, true, true>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((nsi_scan_kernel<K, true, true, G>), grid, block, 0, stream, a);
     else
-        hipLaunchKernelGGL((nsi_scan_kernel<K, false, true>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((nsi_scan_kernel<K, false, true, G>), grid, block, 0, stream, a);
     TG_LAUNCH_CHECK();
+    return TG_OK;
+}
+
+// pass 1 of either pair over launches of at most NSI_GRID_Y batches
+template <bool G> static int nsi_count(const NsiArgs &a0, const NsiPlan &pl, int64_t n_batches, hipStream_t stream) {
+    for (int64_t b0 = 0; b0 < n_batches; b0 += NSI_GRID_Y) {
+        const NsiArgs a = nsi_at(a0, b0);
+        const int64_t nb = std::min(NSI_GRID_Y, n_batches - b0);
+        if (const int rc = pl.table.key_bytes == 4 ? nsi_launch_count<nsu_k32, G>(a, pl, nb, stream)
+                                                   : nsi_launch_count<nsu_k64, G>(a, pl, nb, stream))
+            return rc;
+    }
+    return TG_OK;
+}
+
+template <bool G> static int nsi_emit(const NsiArgs &a0, const NsiPlan &pl, int64_t n_batches, hipStream_t stream) {
+    for (int64_t b0 = 0; b0 < n_batches; b0 += NSI_GRID_Y) {
+        const NsiArgs a = nsi_at(a0, b0);
+        const int64_t nb = std::min(NSI_GRID_Y, n_batches - b0);
+        if (const int rc = pl.table.key_bytes == 4 ? nsi_launch_emit<nsu_k32, G>(a, nb, stream)
+                                                   : nsi_launch_emit<nsu_k64, G>(a, nb, stream))
+            return rc;
+    }
     return TG_OK;
 }
 
@@ -419,7 +516,7 @@ extern "C" int tg_ns_induced_workspace_bytes(const tg_graph *csc, int64_t pitch_
     TG_REQUIRE(bytes && bytes_min, "%s: null output", who);
     TG_REQUIRE(n_batches >= 0 && n_batches <= 0x7fffffff, "%s: n_batches = %lld outside [0, 2^31)", who, (long long)n_batches);
     NsiPlan pl;
-    if (const int rc = nsi_plan(csc, pitch_nodes, id_bound, who, pl)) return rc;
+    if (const int rc = nsi_plan(csc, pitch_nodes, id_bound, 0, 0, who, pl)) return rc;
     *bytes_min = pl.batch_bytes;
     *bytes = pl.batch_bytes * n_batches;
     return TG_OK;
@@ -432,19 +529,11 @@ extern "C" int tg_ns_induced_count(const tg_graph *csc, const tg_ns_induced_in *
     const char *who = "tg_ns_induced_count";
     NsiPlan pl;
     NsiArgs a0;
-    if (const int rc = nsi_common(csc, in, n_batches, id_bound, workspace, workspace_bytes, who, pl, a0)) return rc;
+    if (const int rc = nsi_common(csc, in, nullptr, n_batches, id_bound, workspace, workspace_bytes, who, pl, a0)) return rc;
     TG_REQUIRE(n_edges && status, "%s: null n_edges / status", who);
     a0.n_edges = n_edges, a0.status = status;
     a0.edge_marks = in->n_marks > 0 && in->node_marks ? edge_marks : nullptr;
-    hipStream_t stream = (hipStream_t)stream_;
-    for (int64_t b0 = 0; b0 < n_batches; b0 += NSI_GRID_Y) {
-        const NsiArgs a = nsi_at(a0, b0);
-        const int64_t nb = std::min(NSI_GRID_Y, n_batches - b0);
-        if (const int rc = pl.table.key_bytes == 4 ? nsi_launch_count<nsu_k32>(a, pl, nb, stream)
-                                                   : nsi_launch_count<nsu_k64>(a, pl, nb, stream))
-            return rc;
-    }
-    return TG_OK;
+    return nsi_count<false>(a0, pl, n_batches, (hipStream_t)stream_);
 }
 
 extern "C" int tg_ns_induced_emit(const tg_graph *csc, const tg_ns_induced_in *in, int64_t n_batches, int64_t id_bound,
@@ -454,16 +543,54 @@ extern "C" int tg_ns_induced_emit(const tg_graph *csc, const tg_ns_induced_in *i
     const char *who = "tg_ns_induced_emit";
     NsiPlan pl;
     NsiArgs a0;
-    if (const int rc = nsi_common(csc, in, n_batches, id_bound, workspace, workspace_bytes, who, pl, a0)) return rc;
+    if (const int rc = nsi_common(csc, in, nullptr, n_batches, id_bound, workspace, workspace_bytes, who, pl, a0)) return rc;
     TG_REQUIRE(edge_off && rows && cols && edge_index, "%s: null edge_off / rows / cols / edge_index", who);
     a0.edge_off = edge_off, a0.rows = rows, a0.cols = cols, a0.edge_index = edge_index;
-    hipStream_t stream = (hipStream_t)stream_;
-    for (int64_t b0 = 0; b0 < n_batches; b0 += NSI_GRID_Y) {
-        const NsiArgs a = nsi_at(a0, b0);
-        const int64_t nb = std::min(NSI_GRID_Y, n_batches - b0);
-        if (const int rc = pl.table.key_bytes == 4 ? nsi_launch_emit<nsu_k32>(a, nb, stream)
-                                                   : nsi_launch_emit<nsu_k64>(a, nb, stream))
-            return rc;
-    }
+    return nsi_emit<false>(a0, pl, n_batches, (hipStream_t)stream_);
+}
+
+extern "C" int tg_ns_induced_grouped_workspace_bytes(const tg_graph *csc, int64_t pitch_nodes, int64_t id_bound,
+                                                     int64_t n_groups, int64_t chunk_cap, int64_t n_batches, int64_t *bytes,
+                                                     int64_t *bytes_min) {
+    using namespace tg;
+    const char *who = "tg_ns_induced_grouped_workspace_bytes";
+    TG_REQUIRE(bytes && bytes_min, "%s: null output", who);
+    TG_REQUIRE(n_batches >= 0 && n_batches <= 0x7fffffff, "%s: n_batches = %lld outside [0, 2^31)", who, (long long)n_batches);
+    TG_REQUIRE(n_groups >= 1, "%s: n_groups = %lld, at least 1 expected", who, (long long)n_groups);
+    NsiPlan pl;
+    if (const int rc = nsi_plan(csc, pitch_nodes, id_bound, n_groups, chunk_cap, who, pl)) return rc;
+    *bytes_min = pl.batch_bytes;
+    *bytes = pl.batch_bytes * n_batches;
     return TG_OK;
+}
+
+extern "C" int tg_ns_induced_grouped_count(const tg_graph *csc, const tg_ns_induced_grouped_in *in, int64_t n_batches,
+                                           int64_t id_bound, int64_t *n_edges, int64_t *edge_marks, int64_t *chunks,
+                                           int32_t *status, void *workspace, int64_t workspace_bytes, void *stream_) {
+    using namespace tg;
+    const char *who = "tg_ns_induced_grouped_count";
+    NsiPlan pl;
+    NsiArgs a0;
+    const tg_ns_induced_in plain = nsi_plain(in);
+    if (const int rc = nsi_common(csc, in ? &plain : nullptr, in, n_batches, id_bound, workspace, workspace_bytes, who, pl, a0))
+        return rc;
+    TG_REQUIRE(n_edges && status, "%s: null n_edges / status", who);
+    a0.n_edges = n_edges, a0.status = status, a0.chunks = chunks;
+    a0.edge_marks = in->n_marks > 0 && in->node_marks ? edge_marks : nullptr;
+    return nsi_count<true>(a0, pl, n_batches, (hipStream_t)stream_);
+}
+
+extern "C" int tg_ns_induced_grouped_emit(const tg_graph *csc, const tg_ns_induced_grouped_in *in, int64_t n_batches,
+                                          int64_t id_bound, const int64_t *edge_off, int64_t *rows, int64_t *cols,
+                                          int64_t *edge_index, void *workspace, int64_t workspace_bytes, void *stream_) {
+    using namespace tg;
+    const char *who = "tg_ns_induced_grouped_emit";
+    NsiPlan pl;
+    NsiArgs a0;
+    const tg_ns_induced_in plain = nsi_plain(in);
+    if (const int rc = nsi_common(csc, in ? &plain : nullptr, in, n_batches, id_bound, workspace, workspace_bytes, who, pl, a0))
+        return rc;
+    TG_REQUIRE(edge_off && rows && cols && edge_index, "%s: null edge_off / rows / cols / edge_index", who);
+    a0.edge_off = edge_off, a0.rows = rows, a0.cols = cols, a0.edge_index = edge_index;
+    return nsi_emit<true>(a0, pl, n_batches, (hipStream_t)stream_);
 }

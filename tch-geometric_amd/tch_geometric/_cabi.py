@@ -43,7 +43,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_link_seeds_capacity", "tg_link_seeds", "tg_link_seeds_typed", "tg_mp_skipgram_capacity",
            "tg_mp_skipgram_form", "tg_mp_skipgram_workspace_bytes", "tg_mp_skipgram", "tg_tempo_skipgram_capacity",
            "tg_tempo_skipgram_lds_bytes", "tg_tempo_skipgram", "tg_ns_hop_recent", "tg_ns_homo_unique_grouped_form",
-           "tg_ns_homo_unique_grouped_workspace_bytes", "tg_ns_homo_unique_grouped"]
+           "tg_ns_homo_unique_grouped_workspace_bytes", "tg_ns_homo_unique_grouped",
+           "tg_ns_induced_grouped_workspace_bytes", "tg_ns_induced_grouped_count", "tg_ns_induced_grouped_emit"]
 
 
 class TgGraph(C.Structure):
@@ -1443,7 +1444,94 @@ def induced_status_check(status, who):
     """the status word of tg_ns_induced_count after its read-back: non-zero raises"""
     if status:
         raise RuntimeError("%s: status %d (%s)" % (who, status, " and ".join(
-            t for bit, t in ((1, "a list with repeats exceeds the chunk bound"), (2, "a node id outside the graph")) if status & bit)))
+            t for bit, t in ((1, "a list with repeats exceeds the chunk bound"), (2, "a node id outside the graph"),
+                             (4, "a group word outside [0, n_groups)")) if status & bit)))
+
+
+class TgNsInducedGroupedIn(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("group", C.c_void_p), ("pitch_nodes", C.c_int64), ("counts", C.c_void_p),
+                ("counts_stride", C.c_int64), ("node_marks", C.c_void_p), ("n_marks", C.c_int32), ("n_groups", C.c_int64),
+                ("group_time", C.c_void_p), ("window_lo", C.c_int64), ("window_hi", C.c_int64), ("chunk_cap", C.c_int64)]
+
+
+def ns_induced_grouped_workspace_bytes(graph, pitch_nodes, id_bound, n_groups, chunk_cap, n_batches):
+    """-> (bytes, bytes_min) of the grouped induced pair: as ns_induced_workspace_bytes with the pair key's table and room
+    for chunk_cap chunks per batch (<= 0: the ungrouped bound pitch_nodes + ceil(n_edges / 512)).  No device is touched."""
+    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_ns_induced_grouped_workspace_bytes(C.byref(graph), C.c_int64(pitch_nodes), C.c_int64(id_bound),
+                                                    C.c_int64(n_groups), C.c_int64(chunk_cap), C.c_int64(n_batches),
+                                                    C.byref(nbytes), C.byref(bmin)))
+    return nbytes.value, bmin.value
+
+
+def ns_induced_default_chunk_cap(graph, pitch_nodes):
+    """the capacity chunk_cap <= 0 stands for: the ungrouped pair's bound"""
+    return int(pitch_nodes) + (int(graph.n_edges) + 511) // 512
+
+
+class NsInducedGrouped:
+    """The grouped induced pair (tg_ns_induced_grouped_count / _emit) over `nodes` / `group` slabs [>= n_batches, pitch]:
+    NsInduced with a group word per entry, n_groups groups per batch, optional group_time [n_batches, n_groups] with
+    time_window = (lo, hi) (the graph view then carries timestamps), and chunk_cap chunks of workspace per batch (None: the
+    ungrouped bound).  `state` holds n_edges [n_batches], edge_marks [n_batches, n_marks], chunks [n_batches] and the status
+    word, so one copy reads everything back; a batch whose chunks exceed chunk_cap has status bit 0 and n_edges 0."""
+
+    def __init__(self, graph, nodes, group, counts, counts_stride, n_batches, id_bound, n_groups, node_marks=None,
+                 group_time=None, time_window=None, chunk_cap=None, ws=None):
+        dev = nodes.device
+        self.graph, self.n_batches, self.id_bound, self.n_groups = graph, int(n_batches), int(id_bound), int(n_groups)
+        self.nodes, self.group, self.counts, self.node_marks, self.group_time = nodes, group, counts, node_marks, group_time
+        si = self.struct = TgNsInducedGroupedIn()
+        si.nodes, si.group, si.pitch_nodes = nodes.data_ptr(), group.data_ptr(), nodes.shape[-1]
+        si.counts, si.counts_stride = counts.data_ptr(), int(counts_stride)
+        self.n_marks = 0 if node_marks is None else int(node_marks.shape[-1])
+        si.node_marks, si.n_marks = (node_marks.data_ptr() if self.n_marks else None), self.n_marks
+        si.n_groups = self.n_groups
+        si.group_time = group_time.data_ptr() if group_time is not None else None
+        if group_time is not None and time_window is None:
+            raise ValueError("group_time comes with a time_window")
+        si.window_lo, si.window_hi = (int(time_window[0]), int(time_window[1])) if time_window is not None else (0, 0)
+        self.chunk_cap = ns_induced_default_chunk_cap(graph, si.pitch_nodes) if chunk_cap is None or chunk_cap <= 0 else int(chunk_cap)
+        si.chunk_cap = self.chunk_cap
+        need = ns_induced_grouped_workspace_bytes(graph, si.pitch_nodes, self.id_bound, self.n_groups, self.chunk_cap,
+                                                  self.n_batches)[0]
+        if ws is None or ws.numel() * 8 < need:
+            ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+        self.ws = ws
+        nb, nm = self.n_batches, self.n_marks
+        self.state = torch.zeros(nb * (2 + nm) + 1, dtype=torch.int64, device=dev)
+        self.n_edges = self.state[:nb]
+        self.edge_marks = self.state[nb:nb * (1 + nm)].view(nb, nm)
+        self.chunks = self.state[nb * (1 + nm):nb * (2 + nm)]
+        self.status = self.state[-1:].view(torch.int32)[:1]
+
+    def count(self, n_batches=None):
+        """pass 1 over the first n_batches batches (all when None); emit() then runs the same ones"""
+        self.live = self.n_batches if n_batches is None else int(n_batches)
+        self.state[-1:].zero_()
+        check(lib.tg_ns_induced_grouped_count(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live),
+                                              C.c_int64(self.id_bound), ptr(self.n_edges),
+                                              ptr(self.edge_marks) if self.n_marks else None, ptr(self.chunks),
+                                              ptr(self.status), ptr(self.ws), C.c_int64(self.ws.numel() * 8),
+                                              stream_ptr(self.nodes.device)))
+        return self
+
+    def emit(self, edge_off, rows, cols, edge_index):
+        """pass 2 into the caller's flat arrays; edge_off: device [n_batches], the exclusive prefix of n_edges"""
+        check(lib.tg_ns_induced_grouped_emit(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live),
+                                             C.c_int64(self.id_bound), ptr(edge_off), ptr(rows), ptr(cols), ptr(edge_index),
+                                             ptr(self.ws), C.c_int64(self.ws.numel() * 8), stream_ptr(self.nodes.device)))
+
+    def chunks_of(self, state_host):
+        """the chunk counts inside a host copy of `state`"""
+        nb, nm = self.n_batches, self.n_marks
+        return state_host[nb * (1 + nm):nb * (2 + nm)].tolist()
+
+    def grown(self, chunk_cap):
+        """a launch object over the same slabs with room for chunk_cap chunks per batch"""
+        return NsInducedGrouped(self.graph, self.nodes, self.group, self.counts, self.struct.counts_stride, self.n_batches,
+                                self.id_bound, self.n_groups, self.node_marks, self.group_time,
+                                (self.struct.window_lo, self.struct.window_hi), chunk_cap)
 
 
 def ns_induced_count(graph, nodes, counts, counts_stride, n_batches, id_bound, node_marks=None, ws=None):

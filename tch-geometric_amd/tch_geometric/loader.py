@@ -9,6 +9,8 @@ out as lazily built views of that `SuperBatch` (or the super-batch itself: `Neig
 Everything stays in HBM; the host learns only the per-batch sizes (one read-back per launch, taken from pinned memory
 behind a launch that runs one super-batch ahead on a side stream).  With `time_attr` / `input_time` the same launches run
 under a backward temporal filter, uniformly or taking the most recent admitted edges (TG_SAMPLER_RECENT).
+ShaDowKHopLoader is NeighborLoader with one subgraph per seed and every edge of the graph inside each (ShaDow-GNN's k-hop
+sampler): tg_ns_induced_grouped_count / _emit behind the grouped dedup.
 
 The typed-graph loaders (HeteroNeighborLoader, HGTLoader, BudgetLoader, NegativeLoader) are one program, _TypedLoader:
 `prefetch` mini-batches of one node type's seeds per launch of a batched operator, one read-back of the counts, every
@@ -73,7 +75,7 @@ class SuperBatch:
     sub-graphs with `ptr` offsets) pays no per-mini-batch host work at all."""
     __slots__ = ("n_id", "edge_index", "_e_id", "_e_ptr", "_perm", "node_attrs", "edge_attrs", "node_ptr", "edge_ptr",
                  "layer_offsets", "layer_nodes", "layer_edges", "seed_counts", "batch_size", "call_id0", "n_hops", "_views",
-                 "_index", "input_time", "node_time", "batch")
+                 "_index", "input_time", "node_time", "batch", "root_n_id")
 
     @property
     def e_id(self):
@@ -121,6 +123,7 @@ class SuperBatch:
 
 TIME_FIELDS = ("input_time", "node_time")   # what a temporal NeighborLoader adds to a mini-batch
 DISJOINT_FIELDS = ("batch",)                # what a disjoint one adds (PyG's `batch` vector)
+SHADOW_FIELDS = ("root_n_id",)              # what ShaDowKHopLoader adds (PyG's ShaDowKHopSampler: every seed's own entry)
 
 
 class MiniBatch:
@@ -193,6 +196,9 @@ class MiniBatch:
             j = object.__getattribute__(self, "_j")
             a = sb.node_ptr[j]
             return sb.batch.narrow(0, a, sb.node_ptr[j + 1] - a)
+        # ShaDowKHopLoader's mini-batches carry root_n_id [batch_size], the position of every seed's own entry in n_id
+        if name in SHADOW_FIELDS and getattr(sb, "root_n_id", None) is not None:
+            return sb.root_n_id
         if name in sb.node_attrs or name in sb.edge_attrs:
             views = self._all()
             return views[sb._index[name]]
@@ -243,7 +249,7 @@ class NeighborLoader(_Loader):
     -- the same node under two seeds of different times is two samples, so plain deduplication stays refused -- and its
     `node_time` is then input_time[batch].  (PyG turns disjoint on by itself when times are given; here it is asked for by
     name, so that unique=True alone keeps meaning the plain dedup.)  A `data` with a node or edge attribute named `batch` is
-    refused; induced=True with disjoint is out of scope and refused."""
+    refused; induced=True with disjoint is out of scope and refused here: induced edges per subgraph are ShaDowKHopLoader's."""
 
     def __init__(self, data, num_neighbors: List[int], input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
                  prefetch: int = 16, replace: bool = False, shuffle: bool = False, drop_last: bool = False,
@@ -267,7 +273,7 @@ class NeighborLoader(_Loader):
         if self.temporal and unique and not self.disjoint:
             raise ValueError("a temporal loader with unique=True needs disjoint=True: plain deduplication would merge slots "
                              "that carry different seed times")
-        if self.disjoint and induced:
+        if self.disjoint and induced and not self.INDUCED_PER_SUBGRAPH:
             raise ValueError("induced=True with disjoint subgraphs is out of scope: the induced edges are found per "
                              "mini-batch, not per subgraph")
         if self.disjoint:
@@ -330,6 +336,8 @@ class NeighborLoader(_Loader):
         self._ws = None
         self._side = None
         self.epoch = 0
+
+    INDUCED_PER_SUBGRAPH = False    # induced=True with disjoint=True: only a subclass built for it (ShaDowKHopLoader) gets past
 
     # ---- what a loader whose work items are not the seeds themselves fills in (LinkNeighborLoader)
     WITH_INVERSE = False            # unique=True: keep tg_ns_homo_unique's `inverse` slab (forest position -> n_id position)
@@ -433,7 +441,18 @@ class NeighborLoader(_Loader):
                     slab["ln"][:G].copy_(uniq.layer_nodes[:G], non_blocking=True)
                 if self.induced:             # pass 1: the edge counts join the sizes the host waits for
                     ind = slab.get("ind")
-                    if ind is None:
+                    if self.disjoint:        # per subgraph: the grouped pair, under times with the subgraphs' times
+                        if ind is None or ind.chunk_cap < self.chunk_cap:
+                            if self.temporal and "gt" not in slab:
+                                slab["gt"] = torch.empty((out.n_batches, n_groups), dtype=torch.int64, device=self.device)
+                            ind = slab["ind"] = _cabi.NsInducedGrouped(
+                                self._graph, uniq.nodes, uniq.group, uniq.counts, 2, out.n_batches, self.n_nodes, n_groups,
+                                node_marks=uniq.layer_nodes if H else None, group_time=slab.get("gt"),
+                                time_window=self.time_window if self.temporal else None, chunk_cap=self.chunk_cap)
+                            slab["ist"] = torch.empty(ind.state.numel(), dtype=torch.int64).pin_memory()
+                        if self.temporal:
+                            slab["gt"][:G].copy_(self._group_times(slab, seed_times))
+                    elif ind is None:
                         ind = slab["ind"] = _cabi.NsInduced(self._graph, uniq.nodes, uniq.counts, 2, out.n_batches,
                                                             self.n_nodes, node_marks=uniq.layer_nodes if H else None)
                         slab["ist"] = torch.empty(ind.state.numel(), dtype=torch.int64).pin_memory()
@@ -460,14 +479,16 @@ class NeighborLoader(_Loader):
         src = slab["uniq"] if self.unique else out                 # unique: the deduplicated, relabelled view of the slabs
         if self.induced:                     # pass 2 writes the flat arrays itself: no edge slab, no edge compaction
             ind, ist = slab["ind"], slab["ist"]
-            _cabi.induced_status_check(int(ist[-1]) & 0xFFFFFFFF, "NeighborLoader(induced=True)")
+            if self.disjoint and int(ist[-1]) & 1:   # a mini-batch needs more chunks than the workspace holds: the slow path
+                ind, ist = self._grow_induced(slab, G)
+            _cabi.induced_status_check(int(ist[-1]) & 0xFFFFFFFF, "%s(induced=True)" % type(self).__name__)
             n_edges = ist[:G].tolist()
             n_id = _flat_rows(src.nodes[:G], src.counts[:G, 0], sum(n_nodes))
             edge_index, e_ptr, _ = _cabi.ns_induced_emit(ind, n_edges)
         else:
             n_id, edge_index, e_ptr = _cabi.ns_homo_compact(src, G, counts, stacked=True)   # copies: the slabs go back to the sampler
         sb = self._new_super_batch(slab, G)
-        sb.input_time = sb.node_time = sb.batch = None
+        sb.input_time = sb.node_time = sb.batch = sb.root_n_id = None
         total = sum(n_nodes)
         if self.disjoint:                    # the group slab trimmed like nodes (a copy: the slab goes back)
             sb.batch = _flat_rows(src.group[:G], src.counts[:G, 0], total)
@@ -506,6 +527,23 @@ class NeighborLoader(_Loader):
             sb.seed_counts = [ln[0] for ln in sb.layer_nodes] if H else n_nodes
         sb.batch_size, sb.call_id0, sb.n_hops = B, self.call_id0 + first_batch, len(self.fanout)
         return sb
+
+    def _group_times(self, slab, seed_times: Tensor) -> Tensor:
+        """The [G, n_groups] subgraph times of a launch whose seeds' times are seed_times [G, seeds]; called on the side
+        stream.  One subgraph per seed: the seeds' own."""
+        return seed_times
+
+    def _grow_induced(self, slab, G: int):
+        """The grouped induced count of a launch overflowed its chunk capacity: a launch object with room for the largest
+        mini-batch it reported replaces the slab set's (and sets the capacity of every later one), and pass 1 runs again on
+        the caller's stream while the slab set is still the launch's.  One more wait; taken at most a few times per loader."""
+        old = slab["ind"]
+        self.chunk_cap = max(self.chunk_cap, max(old.chunks_of(slab["ist"])[:G]))
+        ind = slab["ind"] = old.grown(self.chunk_cap)
+        ind.count(G)
+        slab["ist"].copy_(ind.state, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return ind, slab["ist"]
 
     def super_batches(self) -> Iterator[SuperBatch]:
         """The epoch as super-batches of up to `prefetch` mini-batches; the next one is sampled while this one is used."""
@@ -553,6 +591,59 @@ def _flat_rows(slab: Tensor, lens: Tensor, total: int) -> Tensor:
     if total == 0:
         return torch.empty(0, dtype=torch.int64, device=slab.device)
     return _cabi.compact_rows(slab, lens, total)
+
+
+class ShaDowKHopLoader(NeighborLoader):
+    """ShaDow-GNN's k-hop sampler (PyG's ShaDowKHopSampler) as a loader: every seed gets its own bounded neighbourhood --
+    `depth` hops of at most `num_neighbors` sampled neighbours each -- and the mini-batch holds EVERY edge of the graph
+    inside each neighbourhood.  It is NeighborLoader([num_neighbors] * depth, unique=True, disjoint=True, induced=True), the
+    one combination NeighborLoader itself refuses: tg_ns_induced_grouped_count runs on the side stream behind
+    tg_ns_homo_unique_grouped (node list, group words and, under times, the subgraphs' times), tg_ns_induced_grouped_emit
+    writes the flat `edge_index` on the caller's stream.
+
+    Mini-batches carry what the disjoint loader's carry (`n_id`, `batch`, node attributes, under times `node_time` and
+    `input_time`), `edge_index` / `e_id` / edge attributes / `layer_edges` of the per-subgraph induced edges (both ends of
+    every edge share `batch`; ordered by target position, then CSC offset), `root_n_id` [batch_size] -- the position of
+    every seed's own entry in `n_id` -- and `batch_size`, the seed count.  Under times (time_attr / input_time /
+    temporal_strategy / time_window as NeighborLoader's) the sampled neighbourhood AND the induced edges are admitted only up
+    to the seed's time: lo <= T_seed - t_edge <= hi.
+
+    Columns of a disjoint node list are not disjoint (a hub reached from many seeds is scanned once per seed), so the
+    induced pair's workspace has a capacity in chunks of 512 column entries per mini-batch: `chunk_cap` (None: the
+    ungrouped pair's bound, num nodes + ceil(E / 512)).  A launch that needs more is counted again with the capacity it
+    reported and the larger workspace is kept: one extra wait, taken at most a few times per loader.
+
+    Out of scope: the link-level counterpart (enclosing subgraphs around a label edge; tg_ns_induced_grouped_* already takes
+    arbitrary groups, so that loader needs no new kernel) and the typed graphs."""
+    INDUCED_PER_SUBGRAPH = True
+
+    def __init__(self, data, depth: int, num_neighbors: int, input_nodes: Optional[Tensor] = None, replace: bool = False,
+                 batch_size: int = 1024, prefetch: int = 16, shuffle: bool = False, drop_last: bool = False, seed: int = 0,
+                 call_id0: int = 0, device="cuda", time_attr: Optional[str] = None, input_time: Optional[Tensor] = None,
+                 temporal_strategy: str = "uniform", time_window=None, chunk_cap: Optional[int] = None):
+        if int(depth) < 1:
+            raise ValueError("depth must be at least 1, got %r" % (depth,))
+        if int(num_neighbors) < 1:
+            raise ValueError("num_neighbors must be at least 1, got %r" % (num_neighbors,))
+        if temporal_strategy == "last" and int(num_neighbors) > 64:
+            raise ValueError("temporal_strategy='last' takes num_neighbors up to 64")
+        if chunk_cap is not None and not 1 <= int(chunk_cap) <= 2 ** 31:
+            raise ValueError("chunk_cap must be in [1, 2^31], got %r" % (chunk_cap,))
+        for key, value in _tensor_items(data):       # the mini-batches' own root_n_id would hide it (`batch`: the parent's check)
+            if key in SHADOW_FIELDS and _attr_kind(key, value, _num_nodes(data), int(data.edge_index.shape[1])) in ("node", "edge"):
+                raise ValueError("a ShaDowKHopLoader's mini-batches carry their own `%s`: rename data.%s" % (key, key))
+        self.depth, self.num_neighbors = int(depth), int(num_neighbors)
+        self.chunk_cap = int(chunk_cap) if chunk_cap is not None else 0   # 0: the launch object's default; grows on overflow
+        super().__init__(data, [self.num_neighbors] * self.depth, input_nodes=input_nodes, batch_size=batch_size,
+                         prefetch=prefetch, replace=replace, shuffle=shuffle, drop_last=drop_last, seed=seed,
+                         call_id0=call_id0, device=device, unique=True, induced=True, disjoint=True, time_attr=time_attr,
+                         input_time=input_time, temporal_strategy=temporal_strategy, time_window=time_window)
+
+    def _finish(self, ticket) -> SuperBatch:
+        sb = super()._finish(ticket)
+        # one subgraph per seed and the pair (subgraph, seed) first occurs at the seed's own position: the seeds lead n_id
+        sb.root_n_id = torch.arange(sb.batch_size, device=self.device)
+        return sb
 
 
 def _rows_of(table: Tensor, index: Tensor) -> Tensor:

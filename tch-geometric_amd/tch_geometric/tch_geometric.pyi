@@ -56,7 +56,19 @@ temporal_strategy="uniform", time_window=None, disjoint=False): `edge_label_time
 endpoints of a pair sample under the pair's time, a negative under its positive's (negative u belongs to positive u // K);
 negatives are checked against the whole graph, not against time.  Mini-batches gain edge_label_time [P] (triplet: [E]),
 input_time [S], node_time and, under unique=True (one subgraph per pair; triplet: per positive), batch.  induced=True
-with disjoint subgraphs raises ValueError."""
+with disjoint subgraphs raises ValueError.
+
+Induced edges per subgraph (ShaDow-GNN's k-hop sampler, PyG's ShaDowKHopSampler) come from ShaDowKHopLoader(data, depth,
+num_neighbors, input_nodes=None, replace=False, batch_size=1024, prefetch=16, ..., time_attr=None, input_time=None,
+temporal_strategy="uniform", time_window=None, chunk_cap=None) (exported by the package): NeighborLoader's unique=True,
+disjoint=True, induced=True in one, which NeighborLoader itself refuses.  Mini-batches carry the disjoint loader's fields,
+the induced edges of every seed's own neighbourhood (both ends of an edge share `batch`; under times only edges with
+lo <= T_seed - t <= hi) and root_n_id [batch_size].  The operators are tg_ns_induced_grouped_count / _emit
+(csrc/ns_induced.hip): _cabi.NsInducedGrouped(graph, nodes, group, counts, counts_stride, n_batches, id_bound, n_groups,
+node_marks=None, group_time=None, time_window=None, chunk_cap=None, ws=None) with count() / emit() / grown(chunk_cap) and
+_cabi.ns_induced_grouped_workspace_bytes(graph, pitch_nodes, id_bound, n_groups, chunk_cap, n_batches) -> (bytes,
+bytes_min); for one list transforms.induced_subgraph(nodes, col_ptrs, row_indices, id_bound=None, group=None,
+group_time=None, edge_time=None, time_window=None) -> (rows, cols, edge_index)."""
 from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor

@@ -245,7 +245,9 @@ def unique_nodes(samples: Tensor, rows: Tensor, cols: Tensor, id_bound: Optional
     return u.nodes[0, :n_unique], u.rows[0, :m], u.cols[0, :m], u.inverse[0, :samples.numel()]
 
 
-def induced_subgraph(nodes: Tensor, col_ptrs: Tensor, row_indices: Tensor, id_bound: Optional[int] = None):
+def induced_subgraph(nodes: Tensor, col_ptrs: Tensor, row_indices: Tensor, id_bound: Optional[int] = None,
+                     group: Optional[Tensor] = None, group_time: Optional[Tensor] = None, edge_time: Optional[Tensor] = None,
+                     time_window: Optional[Tuple[int, int]] = None):
     """Every edge of the CSC graph (col_ptrs, row_indices) between two nodes of ONE list (PyG's directed=False /
     subgraph_type="induced") -> (rows, cols, edge_index): for every position i of `nodes` in order and every CSC offset e of
     column nodes[i] in ascending order, (local(row_indices[e]), i, e) where local(v), the FIRST position of v in `nodes`,
@@ -253,7 +255,15 @@ def induced_subgraph(nodes: Tensor, col_ptrs: Tensor, row_indices: Tensor, id_bo
     repeats every position scans its column.  Device tensors run tg_ns_induced_count / tg_ns_induced_emit as a single-batch
     launch (csrc/ns_induced.hip; one read-back of the edge count); CPU tensors take a torch implementation of the same
     rule.  An id outside the graph raises IndexError.  id_bound: every id is in [0, id_bound) (at most 2^31 takes 32-bit
-    hash keys); None takes the graph's node count."""
+    hash keys); None takes the graph's node count.
+
+    group (int64, one word per entry of `nodes`, values >= 0) makes the list a DISJOINT one, one subgraph per group
+    (unique_nodes' grouped form, ShaDow's k-hop sampler): local(g, v) is the first position of the PAIR, position i looks up
+    (group[i], row_indices[e]), so both ends of every edge share a group and the same node under two groups is two entries.
+    With group_time (int64 [max(group) + 1]), edge_time (int64, one per CSC offset) and time_window = (lo, hi), an edge is
+    kept only where lo <= group_time[group[i]] - edge_time[e] <= hi (wrapping int64: the backward relative filter of the
+    temporal hops).  Device tensors run tg_ns_induced_grouped_count / _emit; if the list needs more chunks than the default
+    capacity, the count is repeated once with the exact capacity it reported."""
     for t in (nodes, col_ptrs, row_indices):
         if t.dtype != torch.int64:
             raise ValueError("Tensor must be a is of invalid type. Expected Int64 but got %s" % t.dtype)
@@ -261,6 +271,11 @@ def induced_subgraph(nodes: Tensor, col_ptrs: Tensor, row_indices: Tensor, id_bo
     n, n_major = nodes.numel(), col_ptrs.numel() - 1
     if n and (int(nodes.min()) < 0 or int(nodes.max()) >= n_major):
         raise IndexError("induced_subgraph: node id outside [0, %d)" % n_major)
+    if group is not None:
+        return _induced_subgraph_grouped(nodes, col_ptrs, row_indices, n_major if id_bound is None else int(id_bound),
+                                         group, group_time, edge_time, time_window)
+    if group_time is not None or edge_time is not None or time_window is not None:
+        raise ValueError("induced_subgraph: group_time / edge_time / time_window come with group")
     if not nodes.is_cuda:
         begin = col_ptrs[nodes]
         deg = col_ptrs[nodes + 1] - begin
@@ -280,6 +295,51 @@ def induced_subgraph(nodes: Tensor, col_ptrs: Tensor, row_indices: Tensor, id_bo
     counts = torch.tensor([n], dtype=torch.int64).to(dev)
     launch = _cabi.ns_induced_count(graph, nodes.contiguous().view(1, -1), counts, 1, 1,
                                     n_major if id_bound is None else int(id_bound))
+    rc, edge_index, _ = _cabi.ns_induced_emit(launch)
+    return rc[0], rc[1], edge_index
+
+
+def _induced_subgraph_grouped(nodes, col_ptrs, row_indices, id_bound, group, group_time, edge_time, time_window):
+    """induced_subgraph with a group word per entry (see there)"""
+    n, n_major, dev = nodes.numel(), col_ptrs.numel() - 1, nodes.device
+    group = group.reshape(-1)
+    if group.dtype != torch.int64 or group.numel() != n or group.device != dev:
+        raise ValueError("induced_subgraph: group must be an int64 tensor with one word per node, on the nodes' device")
+    timed = group_time is not None
+    if timed != (edge_time is not None) or timed != (time_window is not None):
+        raise ValueError("induced_subgraph: group_time, edge_time and time_window come together")
+    if timed and (edge_time.dtype != torch.int64 or edge_time.numel() != row_indices.numel() or group_time.dtype != torch.int64):
+        raise ValueError("induced_subgraph: edge_time is int64 with one entry per CSC offset, group_time is int64")
+    if n and int(group.min()) < 0:
+        raise IndexError("induced_subgraph: negative group")
+    n_groups = int(group.max()) + 1 if n else 1
+    if timed and group_time.numel() < n_groups:
+        raise IndexError("induced_subgraph: group_time has %d entries, %d groups" % (group_time.numel(), n_groups))
+    if n == 0:
+        return tuple(torch.empty(0, dtype=torch.int64, device=dev) for _ in range(3))
+    if not nodes.is_cuda:
+        begin = col_ptrs[nodes]
+        deg = col_ptrs[nodes + 1] - begin
+        cols = torch.repeat_interleave(torch.arange(n), deg)
+        edge = torch.arange(cols.numel()) - torch.repeat_interleave(torch.cumsum(deg, 0) - deg, deg) + begin[cols]
+        values, inv = torch.unique(group * n_major + nodes, return_inverse=True)
+        first = torch.full((values.numel(),), n, dtype=torch.int64).scatter_reduce_(0, inv, torch.arange(n), "amin")
+        src = group[cols] * n_major + row_indices[edge]
+        at = torch.searchsorted(values, src).clamp_(max=values.numel() - 1)
+        keep = values[at] == src
+        if timed:
+            x = group_time.reshape(-1)[group[cols]] - edge_time.reshape(-1)[edge]      # int64 wraps
+            keep &= (x >= int(time_window[0])) & (x <= int(time_window[1]))
+        return first[at[keep]], cols[keep], edge[keep]
+    col_ptrs, row_indices = col_ptrs.to(dev).contiguous(), row_indices.to(dev).contiguous()
+    graph = _cabi.graph_view(col_ptrs, row_indices, timestamps=edge_time.to(dev).contiguous().view(-1) if timed else None)
+    counts = torch.tensor([n], dtype=torch.int64).to(dev)
+    gt = group_time.to(dev).contiguous().view(-1)[:n_groups].contiguous().view(1, -1) if timed else None
+    launch = _cabi.NsInducedGrouped(graph, nodes.contiguous().view(1, -1), group.contiguous().view(1, -1), counts, 1, 1,
+                                    id_bound, n_groups, group_time=gt, time_window=time_window).count()
+    state = launch.state.cpu()
+    if int(state[-1:].view(torch.int32)[0]) & 1:                                       # the default capacity is no bound here
+        launch = launch.grown(int(launch.chunks_of(state)[0])).count()
     rc, edge_index, _ = _cabi.ns_induced_emit(launch)
     return rc[0], rc[1], edge_index
 
