@@ -1344,6 +1344,56 @@ TG_API int tg_ns_induced_grouped_emit(const tg_graph *csc, const tg_ns_induced_g
                                       int64_t id_bound, const int64_t *edge_off, int64_t *rows, int64_t *cols,
                                       int64_t *edge_index, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- GraphSAINT's random-walk sampler: a SUBGRAPH per mini-batch (PyG's GraphSAINTRandomWalkSampler) ---------------------
+ * tg_saint_rw_nodes: one launch takes G = n_batches mini-batches of B = batch_size roots (roots: device [G, B]); every
+ * root walks T = walk_length >= 1 uniform steps over csr.  Per mini-batch g: walker i starts at roots[g][i] and its
+ * vertices x_i[0..T] are, value for value, row i of tg_random_walk(start = roots[g], n = B, T, p = q = 1, seed, call id =
+ * rng->call_id + g); a walker that meets a vertex without out-edges stops there (tg_random_walk's -1 padding is no visit).
+ * The visit x_i[l] has position p = l * B + i (step-major: the distinct roots lead); nodes[g] = the distinct visited
+ * vertices ordered by the position of their first occurrence, counts[g * counts_stride] = their number n_unique; words
+ * past n_unique are not written.  pitch_nodes >= P = B * (T + 1).  nodes / pitch_nodes / counts / counts_stride go
+ * straight into tg_ns_induced_in.  A root outside [0, csr->n_major) contributes nothing, raises bit 1 (value 2) of the
+ * caller-zeroed device word `status` and never indexes ptrs.
+ * form: 0 auto, 1 LDS (one workgroup walks and dedups one mini-batch in LDS: a table of 2^k >= 4P/3 slots of 8 bytes plus
+ * 2 bytes per position, P <= 12 288 in 160 KiB, where a CU holds one such workgroup; no workspace), 2 flat (any P; visit
+ * lists and tables in `workspace`: bytes = n_batches * bytes_min runs all mini-batches at once, anything from bytes_min up
+ * runs them in rounds).  Both forms write identical words.  tg_saint_rw_form / _workspace_bytes: lds_limit_bytes > 0
+ * replaces the device's limit (no device is touched); a forced form asks no device either.
+ * Limits: csr->n_major <= 2^31 (else TG_ERR_UNSUPPORTED), P <= 2^30; indices32 / ptrs32 are used when given, with equal
+ * results.  Null buffers, T < 1, B < 0, a short pitch, counts_stride < 1, a forced form 1 that does not fit, a short or
+ * misaligned (8 bytes) workspace are refused with TG_ERR_INVALID before any launch; G = 0 or B = 0 launches nothing.  The
+ * call does not synchronise, allocate or read back. */
+typedef struct {
+    int64_t *nodes;        /* device [n_batches * pitch_nodes] */
+    int64_t pitch_nodes;
+    int64_t *counts;       /* device: n_unique of mini-batch g at counts[g * counts_stride] */
+    int64_t counts_stride;
+} tg_saint_rw_out;
+
+TG_API int tg_saint_rw_capacity(int64_t batch_size, int64_t walk_length, int64_t *positions);
+TG_API int tg_saint_rw_form(int64_t batch_size, int64_t walk_length, int64_t lds_limit_bytes, int32_t *form,
+                            int64_t *lds_bytes);
+TG_API int tg_saint_rw_workspace_bytes(int64_t n_batches, int64_t batch_size, int64_t walk_length, int32_t form,
+                                       int64_t *bytes, int64_t *bytes_min /* one mini-batch */);
+TG_API int tg_saint_rw_nodes(const tg_graph *csr, const int64_t *roots, int64_t n_batches, int64_t batch_size,
+                             int64_t walk_length, const tg_rng *rng, const tg_saint_rw_out *out, int32_t *status,
+                             void *workspace, int64_t workspace_bytes, int32_t form, void *stream);
+
+/* GraphSAINT's coverage counters: node_count[v] += 1 for every listed node of every mini-batch (nodes / pitch_nodes /
+ * counts / counts_stride as above, n clamped to the pitch), edge_count[e] += 1 for every entry of the flat edge_ids (the
+ * edge_index words of tg_ns_induced_emit: CSC offsets).  Both tables are device int64, updated with atomic adds: the
+ * caller zeroes them once and may call repeatedly.  An id outside its table is skipped and raises status bit 1 (value 2). */
+TG_API int tg_saint_coverage_add(const int64_t *nodes, int64_t pitch_nodes, const int64_t *counts, int64_t counts_stride,
+                                 int64_t n_batches, const int64_t *edge_ids, int64_t n_edge_ids, int64_t *node_count,
+                                 int64_t n_nodes, int64_t *edge_count, int64_t n_edges, int32_t *status, void *stream);
+/* The two normalisation vectors (float32) of n_samples pre-sampled mini-batches:
+ *   edge_norm[e], e in column c of csc (c = the edge's target): r = (float)node_count[c] / (float)edge_count[e];
+ *                 NaN (0/0) -> 0.1f, otherwise min(max(r, 0), 1e4f) (x/0 = inf -> 1e4f)
+ *   node_norm[v] = ((float)n_samples / d) / (float)n_major, d = (float)node_count[v], 0.1f where the count is 0
+ * The edge pass runs over chunks of consecutive CSC offsets, so a hub column is shared by many wavefronts. */
+TG_API int tg_saint_norm(const tg_graph *csc, const int64_t *node_count, const int64_t *edge_count, int64_t n_samples,
+                         float *node_norm, float *edge_norm, void *stream);
+
 /* Ragged rows of an int64 slab -> one flat array: dst[offsets[r] + i] = src[r * pitch + i] for
  * i < lens[r * lens_stride] (lens, offsets: device arrays).  The per-type / per-relation slabs of
  * tg_ns_hetero_batched are flattened with it (tch_geometric/loader.py). */

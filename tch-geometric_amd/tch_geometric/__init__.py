@@ -9,7 +9,7 @@ from . import _cabi  # noqa: F401  (raises if lib/libtchgeo_hip.so is missing)
 from .tch_geometric import *  # noqa: F401,F403
 from .tch_geometric import (PanicException, backend_version, graph_cache_clear, graph_cache_info,  # noqa: F401
                             rng_state, seed, set_rng_state)
-from .loader import (HeteroLinkNeighborLoader, LinkNeighborLoader, MetaPath2VecLoader, Node2VecLoader,  # noqa: F401
-                     ShaDowKHopLoader, TemporalWalkLoader)
+from .loader import (GraphSAINTRandomWalkLoader, HeteroLinkNeighborLoader, LinkNeighborLoader,  # noqa: F401
+                     MetaPath2VecLoader, Node2VecLoader, ShaDowKHopLoader, TemporalWalkLoader)
 from .utils import (TEMPORAL_SAMPLE_DYNAMIC, TEMPORAL_SAMPLE_RELATIVE, TEMPORAL_SAMPLE_STATIC,  # noqa: F401
                     RecentEdgeSampler, TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler)

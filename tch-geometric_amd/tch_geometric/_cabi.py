@@ -44,7 +44,9 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_mp_skipgram_form", "tg_mp_skipgram_workspace_bytes", "tg_mp_skipgram", "tg_tempo_skipgram_capacity",
            "tg_tempo_skipgram_lds_bytes", "tg_tempo_skipgram", "tg_ns_hop_recent", "tg_ns_homo_unique_grouped_form",
            "tg_ns_homo_unique_grouped_workspace_bytes", "tg_ns_homo_unique_grouped",
-           "tg_ns_induced_grouped_workspace_bytes", "tg_ns_induced_grouped_count", "tg_ns_induced_grouped_emit"]
+           "tg_ns_induced_grouped_workspace_bytes", "tg_ns_induced_grouped_count", "tg_ns_induced_grouped_emit",
+           "tg_saint_rw_capacity", "tg_saint_rw_form", "tg_saint_rw_workspace_bytes", "tg_saint_rw_nodes",
+           "tg_saint_coverage_add", "tg_saint_norm"]
 
 
 class TgGraph(C.Structure):
@@ -1557,6 +1559,99 @@ def ns_induced_emit(launch, n_edges_host=None):
         edge_off = torch.cumsum(launch.n_edges, 0) - launch.n_edges
         launch.emit(edge_off, rc[0], rc[1], eidx)
     return rc, eidx, off
+
+
+class TgSaintRwOut(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("pitch_nodes", C.c_int64), ("counts", C.c_void_p), ("counts_stride", C.c_int64)]
+
+
+def saint_rw_capacity(batch_size, walk_length):
+    """-> positions of a mini-batch, batch_size * (walk_length + 1): the least pitch of tg_saint_rw_nodes' node slab."""
+    positions = C.c_int64(-1)
+    check(lib.tg_saint_rw_capacity(C.c_int64(batch_size), C.c_int64(walk_length), C.byref(positions)))
+    return positions.value
+
+
+def saint_rw_form(batch_size, walk_length, lds_limit_bytes=0):
+    """-> (form, lds_bytes): the form an auto tg_saint_rw_nodes call takes (1 = one workgroup per mini-batch with the table
+    in LDS, 2 = flat through a workspace) and the LDS the LDS form asks for.  lds_limit_bytes > 0: taken as the workgroup's
+    limit, no device is touched; otherwise the current device is asked."""
+    form, nbytes = C.c_int32(-1), C.c_int64(0)
+    check(lib.tg_saint_rw_form(C.c_int64(batch_size), C.c_int64(walk_length), C.c_int64(lds_limit_bytes), C.byref(form),
+                               C.byref(nbytes)))
+    return form.value, nbytes.value
+
+
+def saint_rw_workspace_bytes(n_batches, batch_size, walk_length, form=0):
+    """-> (bytes, bytes_min): the workspace of n_batches mini-batches at once in this form (0: the one auto takes on the
+    current device; 0 bytes for the LDS form) and of one mini-batch of the flat form, the least a flat call runs with."""
+    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_saint_rw_workspace_bytes(C.c_int64(n_batches), C.c_int64(batch_size), C.c_int64(walk_length), C.c_int32(form),
+                                          C.byref(nbytes), C.byref(bmin)))
+    return nbytes.value, bmin.value
+
+
+def saint_rw_nodes(graph, roots, walk_length, seed, call_id, form=0, ws=None, out=None, status=None):
+    """GraphSAINT's random-walk node lists (tg_saint_rw_nodes) of the G mini-batches roots[G, B] in one launch on the current
+    stream -> (nodes [G, pitch], counts [G]): nodes[g, :counts[g]] = the distinct vertices the walks of roots[g] visit
+    (walk_length uniform steps over the CSR `graph`, call id call_id + g), first visit first; words past counts[g] are not
+    written.  form: 0 auto, 1 LDS, 2 flat; ws: the flat form's workspace (an int64 tensor; from bytes_min up it runs in
+    rounds), allocated here when needed and not given; out: (nodes [G, pitch >= B * (walk_length + 1)], counts [G]) of an
+    earlier call, reused; status: a zeroed device int32 word, bit 1 (value 2) = a root outside the graph (allocated here
+    when not given; not read back)."""
+    if roots.dim() != 2 or roots.dtype != torch.int64 or not roots.is_contiguous():
+        raise ValueError("saint_rw_nodes: roots must be a contiguous int64 [n_batches, batch_size] tensor")
+    G, B = roots.shape
+    dev = roots.device
+    P = saint_rw_capacity(B, walk_length)
+    if out is None:
+        out = (torch.empty((G, P), dtype=torch.int64, device=dev), torch.empty(G, dtype=torch.int64, device=dev))
+    nodes, counts = out
+    if nodes.dim() != 2 or nodes.shape[0] < G or nodes.stride(1) != 1 or counts.dim() != 1 or counts.numel() < G \
+            or nodes.dtype != torch.int64 or counts.dtype != torch.int64:
+        raise ValueError("saint_rw_nodes: out must be (int64 nodes [>= n_batches, pitch], int64 counts [>= n_batches])")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    need = saint_rw_workspace_bytes(G, B, walk_length, form)[0]
+    if need and ws is None:
+        ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    o = TgSaintRwOut(nodes.data_ptr(), nodes.stride(0), counts.data_ptr(), counts.stride(0))
+    rng = TgRng(seed, call_id)
+    check(lib.tg_saint_rw_nodes(C.byref(graph), ptr(roots), C.c_int64(G), C.c_int64(B), C.c_int64(walk_length), C.byref(rng),
+                                C.byref(o), ptr(status), ptr(ws), C.c_int64(ws.numel() * ws.element_size() if ws is not None else 0),
+                                C.c_int32(form), stream_ptr(dev)))
+    return nodes, counts
+
+
+def saint_coverage_add(nodes, counts, node_count, edge_count, edge_ids=None, status=None, n_batches=None):
+    """GraphSAINT's coverage counters (tg_saint_coverage_add) on the current stream: node_count[v] += 1 for every node of
+    nodes[g, :counts[g]], g < n_batches (all rows when None), edge_count[e] += 1 for every entry of the flat edge_ids (CSC
+    offsets, or None).  Both tables are int64 device tensors the caller zeroed.  -> status: a device int32 word (the one
+    given, else a fresh zeroed one), bit 1 (value 2) = an id outside its table was skipped."""
+    dev = node_count.device
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    G = nodes.shape[0] if n_batches is None else int(n_batches)
+    n_ids = 0 if edge_ids is None else edge_ids.numel()
+    if edge_ids is not None:
+        edge_ids = edge_ids.contiguous()
+    check(lib.tg_saint_coverage_add(ptr(nodes), C.c_int64(nodes.stride(0)), ptr(counts), C.c_int64(counts.stride(0)),
+                                    C.c_int64(G), ptr(edge_ids) if n_ids else None, C.c_int64(n_ids), ptr(node_count),
+                                    C.c_int64(node_count.numel()), ptr(edge_count), C.c_int64(edge_count.numel()),
+                                    ptr(status), stream_ptr(dev)))
+    return status
+
+
+def saint_norm(graph, node_count, edge_count, n_samples):
+    """GraphSAINT's normalisation vectors (tg_saint_norm) of n_samples pre-sampled mini-batches over the CSC `graph` ->
+    (node_norm [n_major], edge_norm [n_edges], float32, edge_norm in CSC order)."""
+    dev = node_count.device
+    node_norm = torch.empty(graph.n_major, dtype=torch.float32, device=dev)
+    edge_norm = torch.empty(graph.n_edges, dtype=torch.float32, device=dev)
+    check(lib.tg_saint_norm(C.byref(graph), ptr(node_count), ptr(edge_count), C.c_int64(n_samples),
+                            ptr(node_norm) if graph.n_major else None, ptr(edge_norm) if graph.n_edges else None,
+                            stream_ptr(dev)))
+    return node_norm, edge_norm
 
 
 class TgNsTypedIn(C.Structure):

@@ -21,6 +21,9 @@ tensors of the relation's two node types directly ahead of the sampler.
 Node2VecLoader, MetaPath2VecLoader and TemporalWalkLoader hand out skip-gram batches (context windows of walks plus negative
 rows; the temporal one also the windows' timestamps) of one tg_rw_skipgram / tg_mp_skipgram / tg_tempo_skipgram launch per
 `prefetch` mini-batches; nothing is read back.
+GraphSAINTRandomWalkLoader hands out subgraphs: the distinct nodes that short random walks from random roots visit
+(tg_saint_rw_nodes) with every edge of the graph between them (the induced pair), and with sample_coverage the two
+normalisation vectors of a pre-sample (tg_saint_coverage_add, tg_saint_norm).
 """
 from typing import Iterator, List, Optional
 
@@ -1775,3 +1778,188 @@ class HeteroLinkNeighborLoader(HeteroNeighborLoader):
             items = items[torch.randperm(items.numel(), device=self.device, generator=gen)]
         for start, G, width in _epoch_plan(items.numel(), B, self.prefetch, self.drop_last):
             yield from self._emit(items[start:start + G * width].reshape(G, width), None, batch0 + start // B)
+
+
+SAINT_FIELDS = ("node_norm", "edge_norm")   # what GraphSAINTRandomWalkLoader(sample_coverage > 0) adds to a mini-batch
+SAINT_PRESAMPLE_CALL_ID0 = 1 << 62          # the pre-sample's call ids: a range no epoch reaches
+
+
+class GraphSAINTRandomWalkLoader(_Loader):
+    """GraphSAINT's random-walk sampler (PyG's GraphSAINTRandomWalkSampler) as a loader: a mini-batch is a SUBGRAPH -- the
+    distinct nodes that `walk_length`-step uniform walks from `batch_size` random roots visit, and every edge of the graph
+    between them.  An epoch is `num_steps` mini-batches; mini-batch j of epoch e has call id c = call_id0 + e * num_steps + j,
+    its roots are tg_seed_batches(seed, c, 1, batch_size, N) and its walks draw with (seed, c).  A launch takes `prefetch`
+    consecutive mini-batches (the epoch's last launch may be narrower): tg_seed_batches, tg_saint_rw_nodes (walks and the
+    first-occurrence dedup in one step, `form` as there), tg_ns_induced_count, ONE read-back of the node and edge counts
+    and the status words, tg_ns_induced_emit into flat arrays, tg_gather_rows per attribute -- all on the caller's stream.
+    The walks follow out-edges on a CSR built once with the device ingest; symmetric=True states that the graph is
+    symmetric and walks on the CSC the loader already holds.
+
+    Mini-batches are `MiniBatch` views of a `SuperBatch` (`super_batches()` hands those out): `n_id` (first visit first, so
+    the distinct roots lead), `edge_index` (row = source, col = target, numbered against n_id; ordered by target position,
+    then CSC offset), `e_id`, node and edge attributes; `batch_size` is the root count.
+
+    sample_coverage > 0: the constructor pre-samples whole launches (call ids from 1 << 62) until the node lists' sizes add
+    up to N * sample_coverage, counts how often every node and edge was sampled (tg_saint_coverage_add) and turns the
+    counts into GraphSAINT's two normalisation vectors (tg_saint_norm, n_samples = the mini-batches pre-sampled);
+    mini-batches then carry `node_norm` [num_nodes] and `edge_norm` [num_edges] like attributes.  A `data` that has node or
+    edge attributes of those names is refused."""
+
+    def __init__(self, data, batch_size: int, walk_length: int, num_steps: int, sample_coverage: int = 0, prefetch: int = 16,
+                 seed: int = 0, call_id0: int = 0, device="cuda", symmetric: bool = False, form: int = 0):
+        B, T, S = int(batch_size), int(walk_length), int(num_steps)
+        if B < 1:                            # everything that can be refused is refused before any device work
+            raise ValueError("batch_size must be at least 1, got %r" % (batch_size,))
+        if T < 1:
+            raise ValueError("walk_length must be at least 1, got %r" % (walk_length,))
+        if S < 1:
+            raise ValueError("num_steps must be at least 1, got %r" % (num_steps,))
+        if int(sample_coverage) < 0:
+            raise ValueError("sample_coverage must not be negative, got %r" % (sample_coverage,))
+        if int(prefetch) < 1:
+            raise ValueError("prefetch must be at least 1, got %r" % (prefetch,))
+        if int(form) not in (0, 1, 2):
+            raise ValueError("form must be 0 (auto), 1 (LDS) or 2 (flat), got %r" % (form,))
+        if B * (T + 1) > 2 ** 30:
+            raise ValueError("batch_size * (walk_length + 1) = %d positions exceed 2^30" % (B * (T + 1)))
+        if not 0 <= int(call_id0) < SAINT_PRESAMPLE_CALL_ID0 // 2:
+            raise ValueError("call_id0 must be in [0, 2^61), got %r" % (call_id0,))
+        N, E = _num_nodes(data), int(data.edge_index.shape[1])
+        if not 1 <= N <= 2 ** 31:
+            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
+        if int(sample_coverage) > 0:
+            for key, value in _tensor_items(data):   # the mini-batches' own node_norm / edge_norm would hide them
+                if key in SAINT_FIELDS and _attr_kind(key, value, N, E) in ("node", "edge"):
+                    raise ValueError("a GraphSAINT loader's mini-batches carry their own `%s`: rename data.%s" % (key, key))
+        self.data, self.batch_size, self.walk_length, self.num_steps = data, B, T, S
+        self.sample_coverage, self.prefetch = int(sample_coverage), int(prefetch)
+        self.seed, self.call_id0, self.form, self.symmetric = int(seed), int(call_id0), int(form), bool(symmetric)
+        self.device = torch.device(device)
+        self.n_nodes, self._n_edges = N, E
+        self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
+        small = E < 2 ** 31
+        shadows = lambda ptrs, idx: dict(indices32=idx.to(torch.int32), ptrs32=ptrs.to(torch.int32)) if small else {}
+        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, **shadows(self.col_ptrs, self.row_indices))
+        if self.symmetric:                   # the caller's word: in-edges are out-edges
+            self._walk_graph = self._graph
+        else:                                # out-edges: the CSR, built once
+            ei = data.edge_index.to(self.device)
+            row_ptrs, col_indices, _ = _cabi.coo_to_csx(ei[0], ei[1], N, N, False)
+            self._walk_graph = _cabi.graph_view(row_ptrs, col_indices, **shadows(row_ptrs, col_indices))
+        self._node_attrs, self._edge_attrs = [], []
+        for key, value in _tensor_items(data):
+            kind = _attr_kind(key, value, N, E)
+            if kind == "node":
+                self._node_attrs.append((key, value.to(self.device)))
+            elif kind == "edge":
+                self._edge_attrs.append((key, value.to(self.device)))
+        self.positions = _cabi.saint_rw_capacity(B, T)
+        self._pool = []                      # slab sets of finished iterators (each live iterator owns its own)
+        self.slab_allocations = 0            # slab sets made so far: a second epoch makes none
+        self.epoch = 0
+        self.node_norm = self.edge_norm = None
+        self.presampled_launches = self.presampled_batches = 0
+        if self.sample_coverage > 0:
+            self._presample()
+
+    def __len__(self) -> int:
+        return self.num_steps
+
+    def _new_slab(self):
+        """what a launch of up to `prefetch` mini-batches writes (an epoch's launches may be narrower; the pre-sample's are
+        always `prefetch` wide, so that is the size whatever num_steps is): the node slab, counts + the walk's status
+        word in one tensor, the induced pair's launch object (its counts, status and workspace), the flat form's workspace
+        and the pinned image of everything the host reads back"""
+        cap, dev = self.prefetch, self.device
+        self.slab_allocations += 1
+        nodes = torch.empty((cap, self.positions), dtype=torch.int64, device=dev)
+        state = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+        counts, status = state[:cap], state[-1:].view(torch.int32)[:1]
+        need = _cabi.saint_rw_workspace_bytes(cap, self.batch_size, self.walk_length, self.form)[0]
+        ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev) if need else None
+        ind = _cabi.NsInduced(self._graph, nodes, counts, 1, cap, self.n_nodes)
+        host = torch.empty(state.numel() + ind.state.numel(), dtype=torch.int64).pin_memory()
+        return dict(nodes=nodes, state=state, counts=counts, status=status, ws=ws, ind=ind, host=host)
+
+    def _launch(self, slab, call_id: int, G: int):
+        """mini-batches call_id .. call_id + G - 1 into the slab set -> (node counts, edge counts) as python lists, after the
+        launch's one read-back; pass 2 of the induced pair has not run yet"""
+        cap = self.prefetch
+        roots = _cabi.seed_batches(self.seed, call_id, G, self.batch_size, self.n_nodes, self.device)
+        slab["state"][-1:].zero_()
+        _cabi.saint_rw_nodes(self._walk_graph, roots, self.walk_length, self.seed, call_id, form=self.form, ws=slab["ws"],
+                             out=(slab["nodes"], slab["counts"]), status=slab["status"])
+        ind = slab["ind"].count(G)
+        host = slab["host"]
+        host[:cap + 1].copy_(slab["state"], non_blocking=True)
+        host[cap + 1:].copy_(ind.state, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        who = type(self).__name__
+        if int(host[cap:cap + 1].view(torch.int32)[0]):
+            raise RuntimeError("%s: a root outside the graph" % who)
+        _cabi.induced_status_check(int(host[-1:].view(torch.int32)[0]), who)
+        return host[:G].tolist(), host[cap + 1:cap + 1 + G].tolist()
+
+    def _presample(self):
+        """whole launches under call ids from 1 << 62 until the node lists' sizes reach N * sample_coverage; their nodes
+        and induced edges are counted on the device, the counts become the two norms"""
+        dev, G = self.device, self.prefetch
+        node_count = torch.zeros(self.n_nodes, dtype=torch.int64, device=dev)
+        edge_count = torch.zeros(self._n_edges, dtype=torch.int64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        slab = self._new_slab()
+        covered, launches = 0, 0
+        while covered < self.n_nodes * self.sample_coverage:
+            n_nodes, n_edges = self._launch(slab, SAINT_PRESAMPLE_CALL_ID0 + launches * G, G)
+            _, offsets, _ = _cabi.ns_induced_emit(slab["ind"], n_edges)
+            _cabi.saint_coverage_add(slab["nodes"], slab["counts"], node_count, edge_count, edge_ids=offsets, status=status,
+                                     n_batches=G)
+            covered += sum(n_nodes)
+            launches += 1
+        self._pool.append(slab)
+        self.presampled_launches, self.presampled_batches = launches, launches * G
+        self.node_norm, self.edge_norm = _cabi.saint_norm(self._graph, node_count, edge_count, launches * G)
+        if int(status.item()):
+            raise RuntimeError("%s: an id outside the coverage tables" % type(self).__name__)
+
+    def _finish(self, slab, call_id: int, G: int, n_nodes, n_edges) -> SuperBatch:
+        edge_index, e_ptr, _ = _cabi.ns_induced_emit(slab["ind"], n_edges)
+        total = sum(n_nodes)
+        n_id = _flat_rows(slab["nodes"][:G], slab["counts"][:G], total)   # copies: the slabs go back to the sampler
+        sb = SuperBatch()
+        sb.input_time = sb.node_time = sb.batch = sb.root_n_id = None
+        sb.n_id, sb.edge_index = n_id, edge_index
+        sb._e_id, sb._e_ptr, sb._perm = None, e_ptr, self.perm
+        sb.node_attrs = {k: _rows_of(v, n_id) for k, v in self._node_attrs}
+        sb.edge_attrs = {k: _rows_of(v, sb.e_id) for k, v in self._edge_attrs}
+        if self.node_norm is not None:       # like attributes: the view machinery cuts them per mini-batch
+            sb.node_attrs["node_norm"] = _rows_of(self.node_norm, n_id)
+            sb.edge_attrs["edge_norm"] = _rows_of(self.edge_norm, e_ptr)
+        ptr_n, ptr_e, a, e = [0], [0], 0, 0
+        for x, y in zip(n_nodes, n_edges):
+            a += x
+            e += y
+            ptr_n.append(a)
+            ptr_e.append(e)
+        sb.node_ptr, sb.edge_ptr = ptr_n, ptr_e
+        sb.layer_offsets = sb.layer_nodes = sb.layer_edges = sb.seed_counts = None
+        sb.batch_size, sb.call_id0, sb.n_hops = self.batch_size, call_id, 0
+        return sb
+
+    def super_batches(self) -> Iterator[SuperBatch]:
+        """The epoch as super-batches of up to `prefetch` mini-batches."""
+        epoch = self.epoch                   # captured: a second iterator is the next epoch
+        self.epoch += 1
+        first = self.call_id0 + epoch * self.num_steps
+        slab = self._pool.pop() if self._pool else self._new_slab()
+        try:
+            for j in range(0, self.num_steps, self.prefetch):
+                G = min(self.prefetch, self.num_steps - j)
+                n_nodes, n_edges = self._launch(slab, first + j, G)
+                yield self._finish(slab, first + j, G, n_nodes, n_edges)
+        finally:
+            self._pool.append(slab)
+
+    def __iter__(self) -> Iterator[MiniBatch]:
+        for sb in self.super_batches():
+            yield from sb
