@@ -85,6 +85,30 @@ typedef struct {
  * 2^32 - 1 edges or more must state tg_graph.max_degree, and that must be below the limit); anything else is TG_ERR_INVALID.  Taken by
  * tg_ns_hop_recent and, with a workspace, tg_ns_homo_batched_ws; every other entry point rejects or ignores the id. */
 #define TG_SAMPLER_RECENT 3
+/* Additive: LAYER-NEIGHBOR sampling (LABOR-0, Balin & Catalyurek, NeurIPS 2023; DGL's LaborSampler, GraphBolt's
+ * sample_layer_neighbor).  Every graph vertex t gets ONE variate per call id and layer, shared by every frontier vertex
+ * of that call; a frontier vertex keeps the k admitted edges whose neighbours have the smallest variates.  For ONE
+ * frontier vertex with distinct neighbours this is a uniform k-subset (the rank order of iid keys is a uniform
+ * permutation); ACROSS frontier vertices of a mini-batch the choices are maximally correlated, so fewer distinct vertices
+ * are sampled.  For a frontier vertex v holding graph vertex w, with call id c (call_ids[v], else rng.call_id; in a
+ * batched launch rng.call_id + b), filter state s, fan-out k, hop h:
+ *   admitted  as TG_SAMPLER_RECENT: tg_filter_pass in wrapping int64, every edge under TG_FILTER_NONE;
+ *   key       of edge pointer e with t = indices[e]: a >> 1, a = the low 64 bits of the draw (call key of (rng.seed, c,
+ *             tag), id = t, d0 = layer, d1 = 0); layer = h for TG_SAMPLER_LABOR, 0 for TG_SAMPLER_LABOR_SHARED (the same
+ *             variates at every hop: LABOR's layer dependency); tag = rng_tag, 0 meaning TG_TAG_LABOR.  A 63-bit
+ *             non-negative int64: an empty entry (INT64_MAX, position 2^32 - 1) ranks behind every edge;
+ *   rank      the smaller key first; ties (parallel edges to the same t) to the smaller edge pointer;
+ *   output    the first min(k, n_admitted) edges in rank order; bookkeeping and the filter's mutate as TG_SAMPLER_RECENT.
+ * ids and id_base do not influence the result; weights are ignored; timestamps are needed only under a filter.  Fan-outs
+ * 1..64, columns shorter than 2^32 - 1 edges (TG_SAMPLER_RECENT's check), no seed_ids / seed_call_ids; anything else is
+ * TG_ERR_INVALID before any launch.  Taken by tg_ns_hop_labor and, with a workspace, tg_ns_homo_batched_ws; every other
+ * entry point rejects the ids. */
+#define TG_SAMPLER_LABOR 4         /* fresh variates per hop      */
+#define TG_SAMPLER_LABOR_SHARED 5  /* the same variates at every hop (LABOR's layer dependency) */
+#define TG_TAG_LABOR 14u           /* first number no TAG_* uses */
+/* tg_ns_hop_labor: a column of more than this many edges is scanned by one workgroup of 16 wavefronts, not by one
+ * wavefront.  Results do not depend on the value. */
+#define TG_LABOR_LONG_COLUMN 32768
 /* Filter variants of python.rs:218-249 */
 #define TG_FILTER_NONE (-1)
 #define TG_FILTER_STATIC 0   /* TEMPORAL_SAMPLE_STATIC   (neighbor_sampling.rs:32) */
@@ -192,7 +216,9 @@ TG_API int tg_ns_homo_workspace_bytes_for(const tg_graph *csc, int64_t n_batches
  * not finish: a column-group bound reached, a non-positive weight sum).  0 bytes: the launch takes no workspace.
  * TG_SAMPLER_RECENT (with or without a filter) has no per-batch kernel: it takes the flat path at ANY batch count with
  * tg_ns_hop_recent as the hop, nothing can overflow and nothing is queued behind it; the workspace is REQUIRED
- * (tg_ns_homo_batched, a null, short or misaligned workspace, and seed_ids / seed_call_ids are TG_ERR_INVALID). */
+ * (tg_ns_homo_batched, a null, short or misaligned workspace, and seed_ids / seed_call_ids are TG_ERR_INVALID).
+ * TG_SAMPLER_LABOR / TG_SAMPLER_LABOR_SHARED likewise, with tg_ns_hop_labor as the hop (hop h passes layer h, or 0 when
+ * shared) and its long-column list inside the workspace; tg_ns_homo_batched_form reports TG_NS_FORM_FUSED for them. */
 TG_API int tg_ns_homo_batched_workspace_bytes(const tg_graph *csc, int64_t n_batches, int64_t n_seeds, const int64_t *fanout,
                                        int32_t n_hops, const tg_ns_config *cfg, int64_t *n_bytes);
 TG_API int tg_ns_homo_batched_ws(const tg_graph *csc, const int64_t *seeds, int64_t n_batches, int64_t n_seeds,
@@ -291,8 +317,9 @@ typedef struct {
     int64_t m;
     int64_t id_base;
     int32_t fanout;
-    int32_t sampler;  /* TG_SAMPLER_UNIFORM or TG_SAMPLER_UNIFORM_REPL (tg_ns_hop_recent: TG_SAMPLER_RECENT) */
-    uint32_t rng_tag; /* 0 = TG_TAG_NS_HOMO */
+    int32_t sampler;  /* TG_SAMPLER_UNIFORM or TG_SAMPLER_UNIFORM_REPL (tg_ns_hop_recent: TG_SAMPLER_RECENT;
+                         tg_ns_hop_labor: TG_SAMPLER_LABOR / _LABOR_SHARED) */
+    uint32_t rng_tag; /* 0 = TG_TAG_NS_HOMO (tg_ns_hop_labor: TG_TAG_LABOR) */
     uint32_t _reserved;
 } tg_hop_in;
 
@@ -336,6 +363,21 @@ TG_API int tg_ns_hop_scan(const tg_graph *csc, const tg_hop_in *in, const tg_hop
  * are empty slots.  No workspace, no status word (nothing can overflow), no synchronisation; fan-outs 1..64. */
 TG_API int tg_ns_hop_recent(const tg_graph *csc, const tg_hop_in *in, const tg_hop_filter *filter, const tg_hop_out *out,
                             int64_t *states_out, void *stream);
+
+/* The flat hop of TG_SAMPLER_LABOR / TG_SAMPLER_LABOR_SHARED (in->sampler must be one of them; semantics at the defines;
+ * `layer` is the d0 of the key's address and is used as given: the caller passes the hop for TG_SAMPLER_LABOR and 0 for
+ * _SHARED).  tg_ns_hop_recent's shape with a Philox draw of the neighbour's id as the key: one wavefront per frontier
+ * vertex for columns of up to TG_LABOR_LONG_COLUMN edges; longer ones are listed in the workspace (m + 32 words:
+ * tg_ns_hop_labor_workspace_bytes) and taken by a second kernel, one workgroup of 16 wavefronts per long vertex, whose 16
+ * partial lists meet in LDS.  Same result word for word either way.  `filter` NULL or filter_mode = TG_FILTER_NONE: every
+ * edge is admitted and the timestamps are not read.  Outputs as tg_ns_hop_recent's.  No status word, no synchronisation. */
+TG_API int tg_ns_hop_labor_workspace_bytes(int64_t m, int64_t *bytes);
+TG_API int tg_ns_hop_labor(const tg_graph *csc, const tg_hop_in *in, const tg_hop_filter *filter, const tg_rng *rng,
+                           int32_t layer, const tg_hop_out *out, int64_t *states_out, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+/* Measurement and tests only: the long-column threshold of later tg_ns_hop_labor launches of this process (0 restores
+ * TG_LABOR_LONG_COLUMN); *previous (optional) = the value it replaces.  Results do not depend on it. */
+TG_API int tg_ns_hop_labor_long_column(int64_t edges, int64_t *previous);
 
 /* The flat hop for the WEIGHTED sampler (sampling.rs:28-55), with or without a temporal filter (filter = NULL or
  * filter_mode = TG_FILTER_NONE: none).  One wavefront per frontier vertex all over the device; a column's

@@ -355,6 +355,9 @@ int tg_ns_homo_flat_launch(const tg_graph *csc, const int64_t *seeds, int64_t n_
 int tg_ns_homo_recent_launch(const tg_graph *csc, const int64_t *seeds, int64_t n_batches, int64_t n_seeds,
                              const int64_t *fanout, int32_t n_hops, const tg_ns_config *cfg, const tg_rng *rng,
                              const tg_ns_out *out, void *ws, int64_t ws_bytes, hipStream_t stream); // ns_homo_flat.hip
+int tg_ns_homo_labor_launch(const tg_graph *csc, const int64_t *seeds, int64_t n_batches, int64_t n_seeds,
+                            const int64_t *fanout, int32_t n_hops, const tg_ns_config *cfg, const tg_rng *rng,
+                            const tg_ns_out *out, void *ws, int64_t ws_bytes, hipStream_t stream); // ns_homo_flat.hip
 int tg_ns_homo_windowed_applicable(const tg_graph *csc, int64_t n_batches, int64_t n_seeds, const int64_t *fanout,
                                    int32_t n_hops, const tg_ns_config *cfg, const tg_ns_out *out,
                                    int32_t mode); // ns_homo_win.hip
@@ -386,12 +389,15 @@ static int ns_homo_batched_impl(const tg_graph *csc, const int64_t *seeds, int64
 
     const int sampler = cfg ? cfg->sampler : TG_SAMPLER_UNIFORM;
     const int filter = cfg ? cfg->filter_mode : TG_FILTER_NONE;
-    TG_REQUIRE(sampler >= TG_SAMPLER_UNIFORM && sampler <= TG_SAMPLER_RECENT, "tg_ns_homo_batched: bad sampler %d",
+    TG_REQUIRE(sampler >= TG_SAMPLER_UNIFORM && sampler <= TG_SAMPLER_LABOR_SHARED, "tg_ns_homo_batched: bad sampler %d",
                sampler);
     TG_REQUIRE(filter >= TG_FILTER_NONE && filter <= TG_FILTER_DYNAMIC, "tg_ns_homo_batched: bad filter %d", filter);
     if (sampler == TG_SAMPLER_RECENT) // the k most recent admitted edges: hop by hop over the whole device, always
         return tg_ns_homo_recent_launch(csc, seeds, n_batches, n_seeds, fanout, n_hops, cfg, rng, out, ws, ws_bytes,
                                         (hipStream_t)stream);
+    if (sampler == TG_SAMPLER_LABOR || sampler == TG_SAMPLER_LABOR_SHARED) // layer-neighbor sampling: the same driver
+        return tg_ns_homo_labor_launch(csc, seeds, n_batches, n_seeds, fanout, n_hops, cfg, rng, out, ws, ws_bytes,
+                                       (hipStream_t)stream);
     if (sampler == TG_SAMPLER_WEIGHTED || filter != TG_FILTER_NONE) {
         int rc_flat = TG_OK; // few batches + a workspace: hop by hop over the whole device (ns_homo_flat.hip)
         if (tg_ns_homo_flat_launch(csc, seeds, n_batches, n_seeds, fanout, n_hops, cfg, rng, out, ws, ws_bytes, mode,

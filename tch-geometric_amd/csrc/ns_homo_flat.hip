@@ -19,6 +19,8 @@
 // result is always the per-batch kernel's, bit for bit.
 // TG_SAMPLER_RECENT (the k most recent admitted edges, ns_hop_recent.hip) runs the same driver with tg_ns_hop_recent as the
 // hop, at ANY batch count: it has no per-batch kernel, nothing can overflow, and nothing is queued behind it.
+// TG_SAMPLER_LABOR / _LABOR_SHARED (layer-neighbor sampling, ns_hop_labor.hip) do the same with tg_ns_hop_labor, whose
+// long-column list is the hop's workspace; the hop number (or 0 for _SHARED) is the layer of its keys' address.
 #include <algorithm>
 
 #include "tg_device.h"
@@ -150,9 +152,11 @@ struct FlatLayout {
 };
 
 // the hop a launch runs over the flat frontier
-enum FlatHop { FLAT_HOP_SCAN, FLAT_HOP_WEIGHTED, FLAT_HOP_RECENT };
+enum FlatHop { FLAT_HOP_SCAN, FLAT_HOP_WEIGHTED, FLAT_HOP_RECENT, FLAT_HOP_LABOR };
+static bool is_labor(int sampler) { return sampler == TG_SAMPLER_LABOR || sampler == TG_SAMPLER_LABOR_SHARED; }
 static FlatHop flat_hop_of(const tg_ns_config *cfg) {
     if (cfg->sampler == TG_SAMPLER_RECENT) return FLAT_HOP_RECENT;
+    if (is_labor(cfg->sampler)) return FLAT_HOP_LABOR;
     return cfg->sampler == TG_SAMPLER_WEIGHTED ? FLAT_HOP_WEIGHTED : FLAT_HOP_SCAN;
 }
 
@@ -176,6 +180,7 @@ static int flat_layout(const tg_graph *csc, int64_t n_batches, int64_t n_seeds, 
                                       std::min<int64_t>(16 * L->m_max, (int64_t)1 << 26)});
     int64_t hb = 0; // tg_ns_hop_recent takes no workspace
     const int rc = hop == FLAT_HOP_RECENT     ? TG_OK
+                   : hop == FLAT_HOP_LABOR    ? tg_ns_hop_labor_workspace_bytes(L->m_max, &hb)
                    : hop == FLAT_HOP_WEIGHTED ? tg_ns_hop_weighted_workspace_bytes(L->m_max, kmax, L->group_cap, &hb)
                                               : tg_ns_hop_scan_workspace_bytes(L->m_max, kmax, L->group_cap, &hb);
     if (rc != TG_OK) return rc;
@@ -228,9 +233,9 @@ static bool flat_applies(const tg_graph *csc, int64_t n_batches, int64_t n_seeds
 }
 
 // TG_SAMPLER_RECENT has no per-batch kernel: the flat path is its only one, at any batch count
-static int recent_check(const int64_t *fanout, int32_t n_hops, const char *who) {
+static int recent_check(const int64_t *fanout, int32_t n_hops, const char *who, const char *what = "TG_SAMPLER_RECENT") {
     for (int h = 0; h < n_hops; ++h)
-        TG_REQUIRE(fanout[h] >= 1 && fanout[h] <= 64, "%s: TG_SAMPLER_RECENT takes fan-outs 1..64, fanout[%d] = %lld", who, h,
+        TG_REQUIRE(fanout[h] >= 1 && fanout[h] <= 64, "%s: %s takes fan-outs 1..64, fanout[%d] = %lld", who, what, h,
                    (long long)fanout[h]);
     return TG_OK;
 }
@@ -241,11 +246,12 @@ extern "C" int tg_ns_homo_batched_workspace_bytes(const tg_graph *csc, int64_t n
     TG_REQUIRE(csc && n_bytes && n_batches >= 0 && n_seeds >= 0 && n_hops >= 0 && n_hops <= TG_MAX_HOPS &&
                    (fanout || n_hops == 0),
                "tg_ns_homo_batched_workspace_bytes: bad arguments");
-    if (cfg && cfg->sampler == TG_SAMPLER_RECENT) {
-        int rc = recent_check(fanout, n_hops, "tg_ns_homo_batched_workspace_bytes");
+    if (cfg && (cfg->sampler == TG_SAMPLER_RECENT || tg::is_labor(cfg->sampler))) {
+        int rc = recent_check(fanout, n_hops, "tg_ns_homo_batched_workspace_bytes",
+                              tg::is_labor(cfg->sampler) ? "TG_SAMPLER_LABOR" : "TG_SAMPLER_RECENT");
         if (rc != TG_OK) return rc;
         tg::FlatLayout L;
-        rc = tg::flat_layout(csc, n_batches, n_seeds, fanout, n_hops, tg::FLAT_HOP_RECENT, &L);
+        rc = tg::flat_layout(csc, n_batches, n_seeds, fanout, n_hops, tg::flat_hop_of(cfg), &L);
         if (rc != TG_OK) return rc;
         *n_bytes = (int64_t)L.total;
         return TG_OK;
@@ -335,6 +341,9 @@ static int flat_run(const tg_graph *csc, const int64_t *seeds, int64_t n_batches
         int rc;
         if (hop == FLAT_HOP_RECENT)
             rc = tg_ns_hop_recent(csc, &in, &flt, &ho, p.states_out, stream);
+        else if (hop == FLAT_HOP_LABOR)
+            rc = tg_ns_hop_labor(csc, &in, &flt, rng, cfg->sampler == TG_SAMPLER_LABOR ? h : 0, &ho, p.states_out, w + L.hop_ws,
+                                 L.hop_ws_bytes, stream);
         else if (hop == FLAT_HOP_WEIGHTED)
             rc = tg_ns_hop_weighted_groups(csc, &in, filtered ? &flt : nullptr, rng, &ho, p.states_out, status, w + L.hop_ws,
                                            L.hop_ws_bytes, L.group_cap, stream);
@@ -399,4 +408,31 @@ int tg_ns_homo_recent_launch(const tg_graph *csc, const int64_t *seeds, int64_t 
     TG_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
     int32_t *status = nullptr;
     return flat_run(csc, seeds, n_batches, n_seeds, fanout, n_hops, cfg, rng, out, ws, L, FLAT_HOP_RECENT, &status, stream);
+}
+
+// TG_SAMPLER_LABOR / TG_SAMPLER_LABOR_SHARED: the same again with tg_ns_hop_labor as the hop (its long-column list is the
+// hop's workspace); timestamps are needed only under a filter.
+int tg_ns_homo_labor_launch(const tg_graph *csc, const int64_t *seeds, int64_t n_batches, int64_t n_seeds,
+                            const int64_t *fanout, int32_t n_hops, const tg_ns_config *cfg, const tg_rng *rng,
+                            const tg_ns_out *out, void *ws, int64_t ws_bytes, hipStream_t stream) {
+    using namespace tg;
+    const char *who = "tg_ns_homo_batched_ws";
+    TG_REQUIRE(cfg->filter_mode == TG_FILTER_NONE || csc->timestamps || csc->n_edges == 0,
+               "%s: TG_SAMPLER_LABOR under a filter needs edge timestamps (tg_graph.timestamps)", who);
+    TG_REQUIRE(recent_columns_fit(csc),
+               "%s: TG_SAMPLER_LABOR takes columns shorter than 2^32 - 1 edges (a graph this large has to state max_degree)", who);
+    int rc = recent_check(fanout, n_hops, who, "TG_SAMPLER_LABOR");
+    if (rc != TG_OK) return rc;
+    TG_REQUIRE(!cfg->seed_ids && !cfg->seed_call_ids, "%s: TG_SAMPLER_LABOR does not take seed_ids / seed_call_ids", who);
+    TG_REQUIRE(cfg->filter_mode == TG_FILTER_NONE || (cfg->seeds_state && out->states),
+               "%s: a temporal filter needs seeds_state and out->states", who);
+    TG_REQUIRE(ws, "TG_SAMPLER_LABOR needs a workspace: tg_ns_homo_batched_ws with tg_ns_homo_batched_workspace_bytes");
+    FlatLayout L;
+    rc = flat_layout(csc, n_batches, n_seeds, fanout, n_hops, FLAT_HOP_LABOR, &L);
+    if (rc != TG_OK) return rc;
+    TG_REQUIRE(ws_bytes >= (int64_t)L.total, "%s: workspace too small for TG_SAMPLER_LABOR (%lld < %lld bytes)", who,
+               (long long)ws_bytes, (long long)L.total);
+    TG_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+    int32_t *status = nullptr;
+    return flat_run(csc, seeds, n_batches, n_seeds, fanout, n_hops, cfg, rng, out, ws, L, FLAT_HOP_LABOR, &status, stream);
 }

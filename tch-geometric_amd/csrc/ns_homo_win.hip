@@ -1467,6 +1467,7 @@ int tg_ns_homo_windowed_applicable(const tg_graph *csc, int64_t n_batches, int64
     const int sampler = cfg ? cfg->sampler : TG_SAMPLER_UNIFORM;
     const int filter = cfg ? cfg->filter_mode : TG_FILTER_NONE;
     if (sampler == TG_SAMPLER_WEIGHTED || filter != TG_FILTER_NONE) return 0;
+    if (sampler == TG_SAMPLER_LABOR || sampler == TG_SAMPLER_LABOR_SHARED) return 0; // the flat path only (ns_homo_flat.hip)
     if (cfg && (cfg->seed_ids || cfg->seed_call_ids)) return 0;
     if (n_hops < 1 || n_batches < 1 || n_seeds < 1) return 0;
     int kmax = 1;
@@ -1665,6 +1666,7 @@ extern "C" int tg_ns_homo_batched_form(const tg_graph *csc, int64_t n_batches, i
     const int sampler = cfg ? cfg->sampler : TG_SAMPLER_UNIFORM;
     const int filter = cfg ? cfg->filter_mode : TG_FILTER_NONE;
     if (sampler == TG_SAMPLER_WEIGHTED || filter != TG_FILTER_NONE) return TG_OK; // the scanning kernels: neither form
+    if (sampler == TG_SAMPLER_LABOR || sampler == TG_SAMPLER_LABOR_SHARED) return TG_OK; // the flat path: neither form
     if (workspace_bytes <= 0 || !tg_ns_homo_windowed_applicable(csc, n_batches, n_seeds, fanout, n_hops, cfg, out, mode))
         return TG_OK;
     if ((int64_t)tg::win_layout(csc, n_batches, n_seeds, fanout, n_hops).total_push > workspace_bytes) return TG_OK; // the launch would refuse

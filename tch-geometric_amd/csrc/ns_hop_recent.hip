@@ -18,13 +18,12 @@
 #include "tg_device.h"
 #include "tg_filter.h"
 #include "tg_host.h"
+#include "ns_topk.h"
 #include "tg_scan.h"
 
 namespace tg {
 
 constexpr int RC_UNROLL = 8;                     // 64-edge chunks of a block; two blocks' timestamps are in flight together
-constexpr uint32_t RC_NO_POS = 0xFFFFFFFFu;      // an empty entry: ranks behind every edge (columns have < 2^32 - 1 edges)
-constexpr int64_t RC_NO_KEY = INT64_MAX;
 
 struct RecentParams {
     const int64_t *ptrs, *indices, *timestamps;
@@ -36,31 +35,7 @@ struct RecentParams {
     int64_t *cnt, *offsets, *neighbors, *edge_ptrs, *parents, *states_out;
 };
 
-struct RcEntry {
-    int64_t key;  // forward: t, else ~t (= -t - 1: order reversed, no overflow): the smaller key ranks first
-    uint32_t pos; // position inside the column: the smaller edge pointer ranks first among equal timestamps
-};
-
-__device__ __forceinline__ bool rc_before(const RcEntry &a, const RcEntry &b) {
-    return a.key < b.key || (a.key == b.key && a.pos < b.pos);
-}
-__device__ __forceinline__ RcEntry rc_shfl_xor(const RcEntry &a, int j) {
-    RcEntry r;
-    r.key = __shfl_xor(a.key, j, 64);
-    r.pos = __shfl_xor(a.pos, j, 64);
-    return r;
-}
-__device__ __forceinline__ RcEntry rc_shfl(const RcEntry &a, int src) {
-    RcEntry r;
-    r.key = __shfl(a.key, src, 64);
-    r.pos = __shfl(a.pos, src, 64);
-    return r;
-}
-// one compare-exchange step with the lane `j` away: this lane keeps the better entry of the pair iff keep_better
-__device__ __forceinline__ RcEntry rc_exchange(const RcEntry &v, int j, bool keep_better) {
-    const RcEntry o = rc_shfl_xor(v, j);
-    return (rc_before(o, v) == keep_better) ? o : v;
-}
+// RcEntry: key = forward ? t : ~t (= -t - 1: order reversed, no overflow), pos = position inside the column (ns_topk.h)
 
 __device__ __forceinline__ bool rc_pass(const RecentParams &p, int64_t state, int64_t t) { // neighbor_sampling.rs:55-67
     return tg_filter_pass(p.filter_mode, p.forward, p.win_lo, p.win_hi, state, t);
@@ -108,18 +83,10 @@ __global__ void __launch_bounds__(256) recent_select_kernel(const RecentParams p
                 const bool cand = q < deg && rc_pass(p, st, tsv[u]) && rc_before(c, kth);
                 if (__ballot(cand) == 0) continue; // wave-uniform
                 if (!cand) c = RcEntry{RC_NO_KEY, RC_NO_POS};
-                // bitonic sort of the 64 candidates, best first
-#pragma unroll
-                for (int size = 2; size <= 64; size <<= 1) {
-                    const bool up = (lane & size) == 0;
-#pragma unroll
-                    for (int j = size >> 1; j > 0; j >>= 1) c = rc_exchange(c, j, ((lane & j) == 0) == up);
-                }
-                // best 64 of kept (ascending) and candidates (reversed): a bitonic sequence; six steps order it
-                const RcEntry r = rc_shfl(c, 63 - lane);
-                if (rc_before(r, kept)) kept = r;
-#pragma unroll
-                for (int j = 32; j > 0; j >>= 1) kept = rc_exchange(kept, j, (lane & j) == 0);
+                // bitonic sort of the 64 candidates, best first; best 64 of kept (ascending) and candidates (reversed): a
+                // bitonic sequence; six steps order it (ns_topk.h)
+                c = rc_sort64(c, lane);
+                kept = rc_merge_reversed(kept, rc_shfl(c, 63 - lane), lane);
             }
 #pragma unroll
             for (int u = 0; u < RC_UNROLL; ++u) tsv[u] = nxt[u];

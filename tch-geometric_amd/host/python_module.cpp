@@ -51,8 +51,11 @@ SamplerArg parse_sampler(const py::object &o) {
             throw py::value_error("sampler.temporal_strategy must be \"last\"");
         s.kind = TG_SAMPLER_RECENT;
         s.timestamps = o.attr("timestamps");
+    } else if (py::hasattr(o, "layer_dependency")) { // additive: utils.LaborEdgeSampler (layer-neighbor sampling)
+        s.kind = o.attr("layer_dependency").cast<bool>() ? TG_SAMPLER_LABOR_SHARED : TG_SAMPLER_LABOR;
     } else {
-        throw py::type_error("sampler must expose `.with_replacement`, `.weights` or `.temporal_strategy`");
+        throw py::type_error(
+            "sampler must expose `.with_replacement`, `.weights`, `.temporal_strategy` or `.layer_dependency`");
     }
     return s;
 }
@@ -239,6 +242,7 @@ NsResult run_ns_filtered_flat(const c10::Device &dev, const Tensor &ptrs, const 
     const int64_t n_seeds = seeds.numel();
     const bool weighted = s.kind == TG_SAMPLER_WEIGHTED, filtered = f.mode != TG_FILTER_NONE;
     const bool recent = s.kind == TG_SAMPLER_RECENT; // ranks by the timestamps with or without a filter
+    const bool labor = s.kind == TG_SAMPLER_LABOR || s.kind == TG_SAMPLER_LABOR_SHARED;
     tg_graph g{};
     g.ptrs = ptrs.data_ptr<int64_t>();
     g.indices = indices.numel() ? indices.data_ptr<int64_t>() : nullptr;
@@ -246,7 +250,7 @@ NsResult run_ns_filtered_flat(const c10::Device &dev, const Tensor &ptrs, const 
     g.weights = weighted ? weights.data_ptr<double>() : nullptr;
     g.n_major = ptrs.numel() - 1;
     g.n_edges = indices.numel();
-    if (!recent && (weighted || filtered) && id_base == 0 &&
+    if (!recent && !labor && (weighted || filtered) && id_base == 0 &&
         run_ns_filtered_device(r, dev, g, seeds, seeds_state, fanout, s, f, rng, tag, unchecked_seeds))
         return r;
     if (unchecked_seeds) {
@@ -258,7 +262,9 @@ NsResult run_ns_filtered_flat(const c10::Device &dev, const Tensor &ptrs, const 
     if (filtered) states.push_back(seeds_state);
     Tensor frontier = seeds, fstate = seeds_state;
     int64_t ne = 0, slot0 = 0;
+    int32_t hop = -1;
     for (int64_t k : fanout) {
+        ++hop;
         r.layer_offsets.emplace_back(n_seeds + ne, ne, n_seeds + ne); // neighbor_sampling.rs:193
         const int64_t m = frontier.numel();
         if (m == 0) continue;
@@ -285,6 +291,14 @@ NsResult run_ns_filtered_flat(const c10::Device &dev, const Tensor &ptrs, const 
         int64_t group_cap = std::max<int64_t>(1024, indices.numel() / 512 + 2 * m + 2), total = 0;
         if (recent) { // the k most recent admitted edges: a wavefront per frontier vertex, no workspace
             check_rc(tg_ns_hop_recent(&g, &in, &flt, &out, filtered ? st_out.data_ptr<int64_t>() : nullptr, stream_of(dev)));
+            total = read_scalar<int64_t>(offsets[m]);
+        } else if (labor) { // layer-neighbor sampling: the hop is the layer of the variates' address (0 when shared)
+            int64_t ws_bytes = 0;
+            check_rc(tg_ns_hop_labor_workspace_bytes(m, &ws_bytes));
+            Tensor ws = at::empty({ws_bytes / 8 + 1}, i64(dev));
+            check_rc(tg_ns_hop_labor(&g, &in, &flt, &rng, s.kind == TG_SAMPLER_LABOR ? hop : 0, &out,
+                                     filtered ? st_out.data_ptr<int64_t>() : nullptr, ws.data_ptr<int64_t>(), ws_bytes,
+                                     stream_of(dev)));
             total = read_scalar<int64_t>(offsets[m]);
         } else if (!weighted && !filtered) { // plain uniform samplers over a large frontier: the whole-device hop of ns_hop.hip
             int64_t ws_bytes = 0;
@@ -357,11 +371,16 @@ NsResult run_ns(const c10::Device &dev, const Tensor &ptrs, const Tensor &indice
     // ... or more hops than the one-launch kernel's TG_MAX_HOPS (the reference takes any number: neighbor_sampling.rs:188)
     // the most-recent-k sampler: one launch of the batched flat driver (a batch has ONE workgroup for its seeds and its
     // emit pass), or, like the others, hop by hop when the call brings more seeds than a workgroup should walk alone
+    // layer-neighbor sampling (LaborEdgeSampler) takes the same two routes
+    const bool labor = s.kind == TG_SAMPLER_LABOR || s.kind == TG_SAMPLER_LABOR_SHARED;
+    if (labor && max_k > 64) throw py::value_error("LaborEdgeSampler: num_neighbors above 64 is not supported");
+    if (labor && fanout.size() > (size_t)TG_MAX_HOPS)
+        throw py::value_error("LaborEdgeSampler: more hops than TG_MAX_HOPS are not supported");
     const bool recent = s.kind == TG_SAMPLER_RECENT;
     if (recent && max_k > 64) throw py::value_error("RecentEdgeSampler: num_neighbors above 64 is not supported");
     if (recent && fanout.size() > (size_t)TG_MAX_HOPS)
         throw py::value_error("RecentEdgeSampler: more hops than TG_MAX_HOPS are not supported");
-    if (recent ? seeds.numel() > 2048
+    if ((recent || labor) ? seeds.numel() > 2048
                : (f.mode != TG_FILTER_NONE || s.kind == TG_SAMPLER_WEIGHTED || seeds.numel() > 2048 || max_k > 128 ||
                   fanout.size() > (size_t)TG_MAX_HOPS)) {
         return run_ns_filtered_flat(dev, ptrs, indices, weights, timestamps, seeds, seeds_state, fanout, s, f, rng, tag,
@@ -413,7 +432,7 @@ NsResult run_ns(const c10::Device &dev, const Tensor &ptrs, const Tensor &indice
     out.states = r.states.defined() ? r.states.data_ptr<int64_t>() : nullptr;
     out.cap_nodes = r.samples.numel();
     out.cap_edges = r.rows.numel();
-    if (recent) { // the most-recent-k sampler runs hop by hop over the whole device and needs its workspace
+    if (recent || labor) { // these samplers run hop by hop over the whole device and need their workspace
         int64_t ws_bytes = 0;
         check_rc(tg_ns_homo_batched_workspace_bytes(&g, 1, seeds_ok.numel(), fanout.data(), H, &cfg, &ws_bytes));
         Tensor ws = at::empty({ws_bytes / 8 + 32}, i64(dev));
@@ -530,6 +549,8 @@ py::tuple neighbor_sampling_heterogenous(const std::vector<std::string> &node_ty
                                          const py::object &filter) {
     const SamplerArg s = parse_sampler(sampler);
     if (s.kind == TG_SAMPLER_RECENT) throw py::value_error("RecentEdgeSampler: homogeneous sampling only");
+    if (s.kind == TG_SAMPLER_LABOR || s.kind == TG_SAMPLER_LABOR_SHARED)
+        throw py::value_error("LaborEdgeSampler: homogeneous sampling only");
     const FilterArg f = parse_filter(filter);
     const size_t T = node_types.size();
     std::map<std::string, size_t> tix;

@@ -12,4 +12,4 @@ from .tch_geometric import (PanicException, backend_version, graph_cache_clear, 
 from .loader import (GraphSAINTRandomWalkLoader, HeteroLinkNeighborLoader, LinkNeighborLoader,  # noqa: F401
                      MetaPath2VecLoader, Node2VecLoader, ShaDowKHopLoader, TemporalWalkLoader)
 from .utils import (TEMPORAL_SAMPLE_DYNAMIC, TEMPORAL_SAMPLE_RELATIVE, TEMPORAL_SAMPLE_STATIC,  # noqa: F401
-                    RecentEdgeSampler, TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler)
+                    LaborEdgeSampler, RecentEdgeSampler, TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler)

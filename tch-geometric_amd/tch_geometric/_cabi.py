@@ -17,6 +17,8 @@ TG_MAX_FANOUT = 32
 SAMPLER_UNIFORM, SAMPLER_UNIFORM_REPL, SAMPLER_WEIGHTED = 0, 1, 2
 SAMPLER_RECENT = 3   # additive: the k most recent admitted edges (tchgeo.h TG_SAMPLER_RECENT); deterministic
 PART_REPLY_PACKED, PART_REPLY_PAIRS, PART_REPLY_TRIPLES, PART_REPLY_PACKED_STATE = 1, 2, 3, 4   # tchgeo.h TG_PART_REPLY_*
+SAMPLER_LABOR, SAMPLER_LABOR_SHARED = 4, 5   # additive: layer-neighbor sampling (tchgeo.h TG_SAMPLER_LABOR[_SHARED])
+LABOR_LONG_COLUMN = 32768   # tchgeo.h TG_LABOR_LONG_COLUMN: longer columns go to the 16-wavefront kernel
 FILTER_NONE, FILTER_STATIC, FILTER_RELATIVE, FILTER_DYNAMIC = -1, 0, 1, 2
 
 EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_batched", "tg_random_walk",
@@ -46,7 +48,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_ns_homo_unique_grouped_workspace_bytes", "tg_ns_homo_unique_grouped",
            "tg_ns_induced_grouped_workspace_bytes", "tg_ns_induced_grouped_count", "tg_ns_induced_grouped_emit",
            "tg_saint_rw_capacity", "tg_saint_rw_form", "tg_saint_rw_workspace_bytes", "tg_saint_rw_nodes",
-           "tg_saint_coverage_add", "tg_saint_norm"]
+           "tg_saint_coverage_add", "tg_saint_norm", "tg_ns_hop_labor_workspace_bytes", "tg_ns_hop_labor",
+           "tg_ns_hop_labor_long_column"]
 
 
 class TgGraph(C.Structure):
@@ -1926,3 +1929,40 @@ def ns_hop_recent(graph, vertices, fanout, states=None, filter_mode=FILTER_NONE,
     flt.states = states.data_ptr() if (m and states is not None) else None
     check(lib.tg_ns_hop_recent(C.byref(graph), C.byref(hin), C.byref(flt), C.byref(hout), ptr(st_out), stream_ptr(dev)))
     return cnt[:m], offsets, nbr, ep, par, st_out
+
+
+def ns_hop_labor(graph, vertices, fanout, seed, call_id, layer=0, call_ids=None, states=None, filter_mode=FILTER_NONE,
+                 window=(0, 0), forward=False, sampler=SAMPLER_LABOR, rng_tag=0):
+    """One flat hop of layer-neighbor sampling (tg_ns_hop_labor): every frontier vertex keeps the `fanout` admitted edges
+    whose neighbours have the smallest variates of (seed, call id, layer).  `call_ids` [m] names a call id per frontier
+    vertex (else `call_id`); `states` [m] is the filter state (None without a filter).
+    -> (cnt[m], offsets[m+1], neighbors, edge_ptrs, parents, states_out or None) -- no host synchronisation."""
+    m, dev = vertices.numel(), vertices.device
+    o = dict(dtype=torch.int64, device=dev)
+    cnt, offsets = torch.empty(max(m, 1), **o), torch.empty(m + 1, **o)
+    nbr, ep, par = (torch.empty(max(m * fanout, 1), **o) for _ in range(3))
+    st_out = torch.empty(max(m * fanout, 1), **o) if filter_mode != FILTER_NONE else None
+    hin, hout, flt = TgHopIn(), TgHopOut(), TgHopFilter()
+    hin.vertices = vertices.data_ptr() if m else None
+    hin.call_ids = call_ids.data_ptr() if call_ids is not None else None
+    hin.m, hin.fanout, hin.sampler, hin.rng_tag = m, fanout, sampler, rng_tag
+    hout.cnt, hout.offsets = cnt.data_ptr(), offsets.data_ptr()
+    hout.neighbors, hout.edge_ptrs, hout.parents = nbr.data_ptr(), ep.data_ptr(), par.data_ptr()
+    flt.filter_mode, flt.forward = filter_mode, int(bool(forward))
+    flt.win_lo, flt.win_hi = window
+    flt.states = states.data_ptr() if (m and states is not None) else None
+    nbytes = C.c_int64(0)
+    check(lib.tg_ns_hop_labor_workspace_bytes(C.c_int64(m), C.byref(nbytes)))
+    ws = torch.empty(nbytes.value // 8, **o)
+    rng = TgRng(seed, call_id)
+    check(lib.tg_ns_hop_labor(C.byref(graph), C.byref(hin), C.byref(flt), C.byref(rng), C.c_int32(layer), C.byref(hout),
+                              ptr(st_out), ptr(ws), C.c_int64(nbytes.value), stream_ptr(dev)))
+    return cnt[:m], offsets, nbr, ep, par, st_out
+
+
+def ns_hop_labor_long_column(edges=0):
+    """Measurement and tests: the long-column threshold of later tg_ns_hop_labor launches (0 = LABOR_LONG_COLUMN).
+    -> the value it replaces."""
+    prev = C.c_int64(0)
+    check(lib.tg_ns_hop_labor_long_column(C.c_int64(edges), C.byref(prev)))
+    return prev.value

@@ -214,6 +214,22 @@ class MiniBatch:
         return [(k, views[i]) for k, i in self._sb._index.items()] + [("e_id", self.e_id)]
 
 
+def _check_labor(labor, layer_dependency, replace, temporal_strategy, disjoint, num_neighbors):
+    """What layer-neighbor sampling (labor=True, TG_SAMPLER_LABOR) cannot take: refused before any device work."""
+    if layer_dependency and not labor:
+        raise ValueError("layer_dependency=True needs labor=True: it is an option of layer-neighbor sampling")
+    if not labor:
+        return
+    if replace:
+        raise ValueError("labor=True samples without replacement: replace=True is not supported")
+    if temporal_strategy == "last":
+        raise ValueError("labor=True does not combine with temporal_strategy='last': the most recent edges are not drawn")
+    if disjoint:
+        raise ValueError("labor=True does not combine with disjoint=True: nothing is shared between subgraphs")
+    if any(int(k) > 64 for k in num_neighbors):
+        raise ValueError("labor=True takes num_neighbors up to 64")
+
+
 class NeighborLoader(_Loader):
     """One launch samples `prefetch` mini-batches; while the caller consumes super-batch i, super-batch i + 1 is already
     being sampled on a side stream into the other of two slab sets (its sizes travel to pinned host memory behind the
@@ -252,13 +268,24 @@ class NeighborLoader(_Loader):
     -- the same node under two seeds of different times is two samples, so plain deduplication stays refused -- and its
     `node_time` is then input_time[batch].  (PyG turns disjoint on by itself when times are given; here it is asked for by
     name, so that unique=True alone keeps meaning the plain dedup.)  A `data` with a node or edge attribute named `batch` is
-    refused; induced=True with disjoint is out of scope and refused here: induced edges per subgraph are ShaDowKHopLoader's."""
+    refused; induced=True with disjoint is out of scope and refused here: induced edges per subgraph are ShaDowKHopLoader's.
+
+    labor=True samples with layer-neighbor sampling (LABOR-0; TG_SAMPLER_LABOR): every vertex gets one random variate per
+    mini-batch and hop, shared by all seeds of the mini-batch, and a frontier vertex keeps the num_neighbors admitted
+    neighbours with the smallest ones.  One vertex's neighbours are a uniform subset as without the option; across the
+    mini-batch the same vertices are picked again and again, so `n_id` under unique=True is shorter and fewer feature rows
+    are gathered.  layer_dependency=True uses the same variates at every hop (fewer distinct nodes still).  The forest has
+    the shape it always has, so unique, induced and time_attr (temporal_strategy="uniform") work unchanged; replace=True,
+    temporal_strategy="last", disjoint=True and num_neighbors above 64 are refused."""
 
     def __init__(self, data, num_neighbors: List[int], input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
                  prefetch: int = 16, replace: bool = False, shuffle: bool = False, drop_last: bool = False,
                  seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0, unique: bool = False,
                  induced: bool = False, time_attr: Optional[str] = None, input_time: Optional[Tensor] = None,
-                 temporal_strategy: str = "uniform", time_window=None, disjoint: bool = False):
+                 temporal_strategy: str = "uniform", time_window=None, disjoint: bool = False, labor: bool = False,
+                 layer_dependency: bool = False):
+        _check_labor(labor, layer_dependency, replace, temporal_strategy, disjoint, num_neighbors)
+        self.labor, self.layer_dependency = bool(labor), bool(layer_dependency)
         if induced and not unique:
             raise ValueError("induced=True needs unique=True: the induced edges are numbered against the unique node list")
         if temporal_strategy not in ("uniform", "last"):
@@ -305,6 +332,8 @@ class NeighborLoader(_Loader):
         self.sampler = _cabi.SAMPLER_UNIFORM_REPL if replace else _cabi.SAMPLER_UNIFORM
         if temporal_strategy == "last":
             self.sampler = _cabi.SAMPLER_RECENT
+        if self.labor:
+            self.sampler = _cabi.SAMPLER_LABOR_SHARED if self.layer_dependency else _cabi.SAMPLER_LABOR
         self.shuffle, self.drop_last, self.seed, self.call_id0 = shuffle, drop_last, int(seed), int(call_id0)
         self.form = int(form)               # of many-batch launches (ns_homo_batched's `form`): 0 = by launch size
         self.unique = bool(unique)
@@ -324,7 +353,7 @@ class NeighborLoader(_Loader):
             self.input_time = input_time.to(self.device).reshape(-1)
         self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, timestamps=self.edge_time, indices32=self._idx32,
                                        ptrs32=self._ptr32, max_degree="auto")
-        self._time_ws = {}                  # temporal launches: the workspace per launch shape (full / ragged), kept
+        self._time_ws = {}                  # temporal and labor launches: the workspace per launch shape (full / ragged), kept
         nodes = torch.arange(self.n_nodes, device=self.device) if input_nodes is None else input_nodes.to(self.device)
         self.input_nodes = _checked_inputs(nodes, self.n_nodes)
         self._n_edges = int(data.edge_index.shape[1])
@@ -394,14 +423,14 @@ class NeighborLoader(_Loader):
                 slab["ln"] = torch.empty((cap, max(H, 1)), dtype=torch.int64).pin_memory()
             slabs[which] = slab
         time_ws = None
-        if self.temporal:                    # the workspace of THIS sampler / filter, sized for the slab set's full launch
+        if self.temporal or self.labor:      # the workspace of THIS sampler / filter, sized for the slab set's full launch
             key = (slab["out"].n_batches, B)
             if key not in self._time_ws:
+                mode = _cabi.FILTER_RELATIVE if self.temporal else _cabi.FILTER_NONE
                 self._time_ws[key] = _cabi.ns_homo_batched_workspace(self._graph, key[0], B, self.fanout, self.device,
-                                                                     sampler=self.sampler,
-                                                                     filter_mode=_cabi.FILTER_RELATIVE)
+                                                                     sampler=self.sampler, filter_mode=mode)
             time_ws = self._time_ws[key]
-        if G >= 2048 and self._ws is None and not self.temporal:   # many batches per launch: the window-ordered form pays
+        if G >= 2048 and self._ws is None and not self.temporal and not self.labor:   # many batches per launch: the window-ordered form pays
             self._ws = _cabi.ns_homo_workspace(max(G, min(self.prefetch, len(self))), B, self.fanout, self.device,
                                                graph=self._graph)
         cur = torch.cuda.current_stream(self.device)
@@ -421,6 +450,9 @@ class NeighborLoader(_Loader):
                 _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
                                       sampler=self.sampler, filter_mode=_cabi.FILTER_RELATIVE, forward=False,
                                       window=self.time_window, seeds_state=seed_times, ws=time_ws)
+            elif self.labor:                 # layer-neighbor sampling: the flat path with its workspace, at any launch size
+                _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
+                                      sampler=self.sampler, ws=time_ws)
             else:
                 _cabi.ns_homo_batched(self._graph, seeds, self.fanout, self.seed, self.call_id0 + first_batch, out,
                                       sampler=self.sampler, ws=self._ws if G >= 2048 else None, form=self.form)
@@ -1477,7 +1509,9 @@ class LinkNeighborLoader(NeighborLoader):
                  drop_last: bool = False, seed: int = 0, call_id0: int = 0, device="cuda", form: int = 0,
                  unique: bool = False, edge_set: bool = False, time_attr: Optional[str] = None,
                  edge_label_time: Optional[Tensor] = None, temporal_strategy: str = "uniform", time_window=None,
-                 disjoint: bool = False):
+                 disjoint: bool = False, labor: bool = False, layer_dependency: bool = False):
+        _check_labor(labor, layer_dependency, replace, temporal_strategy,
+                     bool(disjoint) or (time_attr is not None and bool(unique)), num_neighbors)
         if (time_attr is None) != (edge_label_time is None):
             raise ValueError("time_attr and edge_label_time come together: edge times need a time per label edge and the reverse")
         if neg_sampling not in ("binary", "triplet"):
@@ -1509,7 +1543,8 @@ class LinkNeighborLoader(NeighborLoader):
                          batch_size=batch_size, prefetch=prefetch, replace=replace, shuffle=shuffle, drop_last=drop_last,
                          seed=seed, call_id0=call_id0, device=dev, form=form, unique=unique, time_attr=time_attr,
                          input_time=edge_label_time, temporal_strategy=temporal_strategy, time_window=time_window,
-                         disjoint=bool(disjoint) or (time_attr is not None and bool(unique)))   # as PyG: times force disjoint
+                         disjoint=bool(disjoint) or (time_attr is not None and bool(unique)),   # as PyG: times force disjoint
+                         labor=labor, layer_dependency=layer_dependency)
         self.edge_label_index = eli
         self.edge_label = None if edge_label is None else edge_label.to(dev)
         self.input_nodes = torch.arange(eli.shape[1], device=dev)    # the work items: positions in edge_label_index

@@ -11,7 +11,12 @@ to one launch per relation and hop).  RecentEdgeSampler (additive: the reference
 admitted edges, PyG's temporal_strategy="last", deterministic) takes fan-outs up to 64 and at most 8 hops, homogeneous
 sampling only; a filter passed with it must carry the sampler's own timestamps tensor (ValueError otherwise).  A call of
 up to 2048 inputs is one launch of the batched driver; a larger one runs hop by hop (tg_ns_hop_recent, one size read-back
-per hop), as the other samplers do.
+per hop), as the other samplers do.  LaborEdgeSampler(layer_dependency=False) (additive: layer-neighbor sampling, LABOR-0;
+TG_SAMPLER_LABOR / _LABOR_SHARED, csrc/ns_hop_labor.hip) takes the same two routes under the same limits (fan-outs up to
+64, at most 8 hops, homogeneous only: ValueError otherwise): every vertex gets one variate per call and hop, an input keeps
+the num_neighbors admitted neighbours with the smallest ones.  loader.NeighborLoader(..., labor=False,
+layer_dependency=False) and LinkNeighborLoader take it per mini-batch; it works with unique, induced and time_attr
+(temporal_strategy="uniform") and refuses replace=True, temporal_strategy="last", disjoint=True and fan-outs above 64.
 
 neighbor_sampling_homogenous returns the reference's forest (a vertex reached along two paths holds two slots of
 `samples`, rows[e] == n_seeds + e).  The PyG-style form -- each node once, edges numbered against that list -- is made
@@ -73,13 +78,13 @@ from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor
 
-from .utils import RecentEdgeSampler, TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler
+from .utils import LaborEdgeSampler, RecentEdgeSampler, TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler
 
 NodeType = str
 RelType = str
 EdgeType = Tuple[str, str, str]
 LayerOffset = Tuple[int, int, int]
-EdgeSampler = Union[UniformEdgeSampler, WeightedEdgeSampler, RecentEdgeSampler]   # the last one is additive
+EdgeSampler = Union[UniformEdgeSampler, WeightedEdgeSampler, RecentEdgeSampler, LaborEdgeSampler]   # the last two are additive
 HomoFilter = Tuple[TemporalEdgeFilter, Tensor]
 HeteroFilter = Tuple[TemporalEdgeFilter, Dict[NodeType, Tensor]]
 

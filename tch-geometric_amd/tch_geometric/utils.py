@@ -63,3 +63,18 @@ class RecentEdgeSampler:
 
     def validate(self, hetero: bool = False) -> None:
         _check(self.timestamps, hetero, torch.int64)
+
+
+@dataclass
+class LaborEdgeSampler:
+    """Layer-neighbor sampling (LABOR-0, Balin & Catalyurek 2023; DGL's LaborSampler): every vertex gets one random variate
+    per call and hop, shared by all inputs of the call, and an input keeps the num_neighbors neighbours with the smallest
+    ones.  One input's neighbours are a uniform subset as with UniformEdgeSampler; across inputs the same vertices are
+    picked again and again, so a call samples fewer distinct vertices.  `layer_dependency` uses the same variates at
+    every hop.  Additive: the reference has no such sampler.  The native module recognises it by `layer_dependency`,
+    tried after `with_replacement`, `weights` and `temporal_strategy`.  Homogeneous sampling only, num_neighbors <= 64."""
+    layer_dependency: bool = False
+
+    def validate(self, hetero: bool = False) -> None:
+        if hetero:
+            raise ValueError("LaborEdgeSampler: homogeneous sampling only")
