@@ -1436,6 +1436,49 @@ TG_API int tg_saint_coverage_add(const int64_t *nodes, int64_t pitch_nodes, cons
 TG_API int tg_saint_norm(const tg_graph *csc, const int64_t *node_count, const int64_t *edge_count, int64_t n_samples,
                          float *node_norm, float *edge_norm, void *stream);
 
+/* ---- PinSAGE's importance sampler: random-walk neighbours (DGL's RandomWalkNeighborSampler / PinSAGESampler) ---------------
+ * tg_pinsage_hop: a flat hop over a frontier, shaped like tg_ns_hop_recent.  The neighbours of a frontier vertex are the
+ * vertices that R = n_walks short random walks from it visit most often; the visit counts are the weights.
+ *   walks     frontier slot i has draw id u = in->ids[i] (or in->id_base + i) and call id c = in->call_ids[i] (or
+ *             rng->call_id).  It starts R walks at in->vertices[i]; walk r is walker w = u * R + r (uint64 arithmetic).
+ *             Walker w takes up to T = walk_length uniform steps over walk_graph's rows: tg_random_walk's step with
+ *             p = q = 1 under tg_random_walk's call key of (rng->seed, c), so that WITHOUT termination its vertices are,
+ *             value for value, row w of tg_random_walk under call id c.  Pass the CSC to walk against edge direction, the
+ *             CSR to walk along it.
+ *   termination (DGL's restart_prob): the first step is always taken; before step l, 1 <= l < T, the walk ends if
+ *             u32_to_f32_01(draw(ck', w, l, 0).w[0]) < termination, ck' the call key of the same (seed, c) under the tag
+ *             in->rng_tag, 0 meaning TG_TAG_PINSAGE, and u32_to_f32_01(x) = float32 with the bits 0x3F800000 | x >> 9,
+ *             minus 1.  A vertex without out-edges ends the walk too.
+ *   visits    of slot i: the vertices after each step taken, x[1..] of all R walks; the start counts only where a walk
+ *             steps back onto it.
+ *   selection the distinct visited vertices ranked by visit count descending, then vertex id ascending; the first
+ *             min(in->fanout, distinct) are kept.  Fan-outs 1..64.
+ *   outputs   laid out as tg_ns_hop_recent's: cnt [m], offsets [m + 1] with offsets[m] the total, neighbors and parents
+ *             compact and grouped by frontier slot in rank order; `visits` runs parallel to neighbors and holds each one's
+ *             count as int64.  Words past offsets[m] are not written.  out->edge_ptrs must be NULL: a sampled neighbour is
+ *             not an edge of the graph.
+ *   slots     a vertex < 0 is an empty slot with cnt 0; a vertex >= n_major has cnt 0, raises bit 1 (value 2) of the
+ *             caller-zeroed device word `status` and never indexes ptrs.  in->sampler is ignored.
+ * Refused before any launch, without touching a device: with TG_ERR_INVALID a null graph, in, cfg, rng, out, and while
+ * m > 0 null vertices, cnt, offsets, neighbors, parents, visits or status; a non-NULL edge_ptrs; R < 1 or T < 1; a fan-out
+ * outside 1..64; termination outside [0, 1) or NaN; m < 0; a short or misaligned (8 bytes) workspace
+ * (tg_pinsage_hop_workspace_bytes: m * fanout words, where the winners wait for their offsets); with TG_ERR_UNSUPPORTED
+ * V = R * T > 4096 and n_major > 2^31.  m = 0 returns TG_OK and launches nothing.  The call does not allocate, synchronise
+ * or read back; ptrs32 / indices32 are used when given, with equal results.  The visits live in LDS only: a workgroup
+ * walks and selects a tile of consecutive slots (csrc/pinsage.hip); the result does not depend on the tile. */
+#define TG_TAG_PINSAGE 15u
+typedef struct {
+    int32_t n_walks;        /* R >= 1 walks per frontier vertex              */
+    int32_t walk_length;    /* T >= 1 steps per walk; V = R * T <= 4096      */
+    float   termination;    /* alpha in [0, 1): before every step l >= 1     */
+    int32_t _reserved;
+} tg_pinsage_config;
+
+TG_API int tg_pinsage_hop_workspace_bytes(int64_t m, int32_t fanout, int64_t *bytes);
+TG_API int tg_pinsage_hop(const tg_graph *walk_graph, const tg_hop_in *in, const tg_pinsage_config *cfg,
+                          const tg_rng *rng, const tg_hop_out *out, int64_t *visits, int32_t *status,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Ragged rows of an int64 slab -> one flat array: dst[offsets[r] + i] = src[r * pitch + i] for
  * i < lens[r * lens_stride] (lens, offsets: device arrays).  The per-type / per-relation slabs of
  * tg_ns_hetero_batched are flattened with it (tch_geometric/loader.py). */

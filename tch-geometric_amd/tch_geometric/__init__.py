@@ -10,6 +10,6 @@ from .tch_geometric import *  # noqa: F401,F403
 from .tch_geometric import (PanicException, backend_version, graph_cache_clear, graph_cache_info,  # noqa: F401
                             rng_state, seed, set_rng_state)
 from .loader import (GraphSAINTRandomWalkLoader, HeteroLinkNeighborLoader, LinkNeighborLoader,  # noqa: F401
-                     MetaPath2VecLoader, Node2VecLoader, ShaDowKHopLoader, TemporalWalkLoader)
+                     MetaPath2VecLoader, Node2VecLoader, PinSAGELoader, ShaDowKHopLoader, TemporalWalkLoader)
 from .utils import (TEMPORAL_SAMPLE_DYNAMIC, TEMPORAL_SAMPLE_RELATIVE, TEMPORAL_SAMPLE_STATIC,  # noqa: F401
                     LaborEdgeSampler, RecentEdgeSampler, TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler)

@@ -49,7 +49,7 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_ns_induced_grouped_workspace_bytes", "tg_ns_induced_grouped_count", "tg_ns_induced_grouped_emit",
            "tg_saint_rw_capacity", "tg_saint_rw_form", "tg_saint_rw_workspace_bytes", "tg_saint_rw_nodes",
            "tg_saint_coverage_add", "tg_saint_norm", "tg_ns_hop_labor_workspace_bytes", "tg_ns_hop_labor",
-           "tg_ns_hop_labor_long_column"]
+           "tg_ns_hop_labor_long_column", "tg_pinsage_hop_workspace_bytes", "tg_pinsage_hop"]
 
 
 class TgGraph(C.Structure):
@@ -1966,3 +1966,48 @@ def ns_hop_labor_long_column(edges=0):
     prev = C.c_int64(0)
     check(lib.tg_ns_hop_labor_long_column(C.c_int64(edges), C.byref(prev)))
     return prev.value
+
+
+TAG_PINSAGE = 15             # tchgeo.h TG_TAG_PINSAGE: the tag of the termination draws
+PINSAGE_MAX_VISITS = 4096    # n_walks * walk_length at most
+
+
+class TgPinsageConfig(C.Structure):
+    _fields_ = [("n_walks", C.c_int32), ("walk_length", C.c_int32), ("termination", C.c_float), ("_reserved", C.c_int32)]
+
+
+def pinsage_hop_workspace_bytes(m, fanout):
+    nbytes = C.c_int64(-1)
+    check(lib.tg_pinsage_hop_workspace_bytes(C.c_int64(m), C.c_int32(fanout), C.byref(nbytes)))
+    return nbytes.value
+
+
+def pinsage_hop(graph, vertices, fanout, n_walks, walk_length, termination, seed, call_id, call_ids=None, ids=None,
+                rng_tag=0, status=None):
+    """One flat hop of PinSAGE's random-walk neighbour sampler (tg_pinsage_hop): every frontier vertex starts `n_walks`
+    walks of up to `walk_length` uniform steps over the rows of `graph` (the CSC walks against edge direction, the CSR along
+    it), each ending before a step l >= 1 with probability `termination`; its neighbours are the `fanout` most visited
+    vertices, count descending then id ascending.  `ids` [m] names a draw id and `call_ids` [m] a call id per frontier
+    vertex (else the slot's index and `call_id`); status: a zeroed int32 device word (bit 1: a vertex outside the graph),
+    made here when None.  -> (cnt[m], offsets[m+1], neighbors, parents, visits) -- no host synchronisation."""
+    m, dev = vertices.numel(), vertices.device
+    o = dict(dtype=torch.int64, device=dev)
+    cnt = torch.empty(max(m, 1), **o)
+    offsets = torch.empty(m + 1, **o) if m else torch.zeros(1, **o)   # m = 0 launches nothing
+    nbr, par, vis = (torch.empty(max(m * fanout, 1), **o) for _ in range(3))
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    hin, hout = TgHopIn(), TgHopOut()
+    hin.vertices = vertices.data_ptr() if m else None
+    hin.ids = ids.data_ptr() if ids is not None else None
+    hin.call_ids = call_ids.data_ptr() if call_ids is not None else None
+    hin.m, hin.fanout, hin.rng_tag = m, fanout, rng_tag
+    hout.cnt, hout.offsets = cnt.data_ptr(), offsets.data_ptr()
+    hout.neighbors, hout.edge_ptrs, hout.parents = nbr.data_ptr(), None, par.data_ptr()
+    cfg = TgPinsageConfig(n_walks, walk_length, termination, 0)
+    nbytes = pinsage_hop_workspace_bytes(m, fanout)
+    ws = torch.empty(max(nbytes // 8, 1), **o)
+    rng = TgRng(seed, call_id)
+    check(lib.tg_pinsage_hop(C.byref(graph), C.byref(hin), C.byref(cfg), C.byref(rng), C.byref(hout), ptr(vis), ptr(status),
+                             ptr(ws), C.c_int64(nbytes), stream_ptr(dev)))
+    return cnt[:m], offsets, nbr, par, vis

@@ -24,6 +24,9 @@ rows; the temporal one also the windows' timestamps) of one tg_rw_skipgram / tg_
 GraphSAINTRandomWalkLoader hands out subgraphs: the distinct nodes that short random walks from random roots visit
 (tg_saint_rw_nodes) with every edge of the graph between them (the induced pair), and with sample_coverage the two
 normalisation vectors of a pre-sample (tg_saint_coverage_add, tg_saint_norm).
+PinSAGELoader hands out DGL-style blocks whose neighbours are the most visited nodes of short random walks with
+termination (tg_pinsage_hop), the visit counts as edge weights; a launch's frontiers are grown per mini-batch with the
+grouped dedup.
 """
 from typing import Iterator, List, Optional
 
@@ -1996,5 +1999,239 @@ class GraphSAINTRandomWalkLoader(_Loader):
             self._pool.append(slab)
 
     def __iter__(self) -> Iterator[MiniBatch]:
+        for sb in self.super_batches():
+            yield from sb
+
+
+class _PinSAGESlabs:
+    """A launch's frontier followed by a hop's neighbours, as the single-batch slabs tg_ns_homo_unique_grouped reads: the
+    counts stay on the device (n = frontier + E samples, E edges; E is the hop's offsets[m])."""
+
+    def __init__(self, frontier: Tensor, nbr: Tensor, par: Tensor, total: Tensor):
+        n, dev = frontier.numel(), frontier.device
+        self.samples = torch.cat([frontier, nbr]).view(1, -1)
+        self.rows = (n + torch.arange(nbr.numel(), dtype=torch.int64, device=dev)).view(1, -1)
+        self.cols = par.view(1, -1)
+        self.edge_index = self.rows
+        self.layer_offsets = torch.zeros((1, 1, 3), dtype=torch.int64, device=dev)
+        self.counts = torch.stack([total + n, total]).view(1, 2)
+        self.states, self.n_seeds, self.n_hops = None, n, 1
+
+    struct = _cabi.NsBatchedOut.struct
+
+
+class PinSAGEBlock:
+    """One layer of a PinSAGE mini-batch: `n_id` (the source nodes; its first `n_dst` entries are the destination nodes,
+    the previous frontier in order), `edge_index` [2, E] (row = position in n_id of the neighbour, col = position of the
+    destination) and `edge_weight` [E] int64, the visit counts."""
+    __slots__ = ("n_id", "n_dst", "edge_index", "edge_weight")
+
+    def __init__(self, n_id, n_dst, edge_index, edge_weight):
+        self.n_id, self.n_dst, self.edge_index, self.edge_weight = n_id, n_dst, edge_index, edge_weight
+
+    @property
+    def num_src_nodes(self):
+        return self.n_id.numel()
+
+    @property
+    def num_edges(self):
+        return self.edge_weight.numel()
+
+
+class PinSAGEBatch:
+    """Mini-batch j of a PinSAGESuperBatch: `blocks` outermost first as in DGL ([block_{L-1}, ..., block_0]), `n_id` = the
+    outermost block's source nodes, the node attributes of the data gathered by n_id, `input_nodes` (the seeds = the first
+    `batch_size` entries of n_id), `call_id` of layer 0."""
+
+    def __init__(self, sb, j):
+        self.batch_size = sb.seed_ptr[j + 1] - sb.seed_ptr[j]
+        self.input_nodes = sb.input_nodes[sb.seed_ptr[j]:sb.seed_ptr[j + 1]]
+        self.call_id = sb.call_id0 + j * sb.n_layers
+        self.blocks = []
+        for l in reversed(range(sb.n_layers)):
+            lay = sb.layers[l]
+            n0, n1 = lay["src_ptr"][j], lay["src_ptr"][j + 1]
+            e0, e1 = lay["edge_ptr"][j], lay["edge_ptr"][j + 1]
+            self.blocks.append(PinSAGEBlock(lay["n_id"][n0:n1], lay["dst_ptr"][j + 1] - lay["dst_ptr"][j],
+                                            lay["edge_index"][:, e0:e1], lay["edge_weight"][e0:e1]))
+        self.n_id = self.blocks[0].n_id
+        n0, n1 = sb.node_ptr[j], sb.node_ptr[j + 1]
+        self._attrs = {k: v[n0:n1] for k, v in sb.node_attrs.items()}
+
+    @property
+    def num_nodes(self):
+        return self.n_id.numel()
+
+    def __getattr__(self, name):
+        attrs = self.__dict__.get("_attrs", {})
+        if name in attrs:
+            return attrs[name]
+        raise AttributeError(name)
+
+
+class PinSAGESuperBatch:
+    """The mini-batches of ONE launch as flat batch-major device tensors: per layer l `layers[l]` = dict(n_id, src_ptr,
+    dst_ptr, edge_index (numbered inside each mini-batch), edge_weight, edge_ptr); `n_id` / `node_ptr` of the last layer,
+    `node_attrs` gathered once by it; `input_nodes` / `seed_ptr`; `call_id0` (layer 0 of mini-batch 0)."""
+
+    def __len__(self):
+        return len(self.node_ptr) - 1
+
+    def __getitem__(self, j):
+        if j < 0:
+            j += len(self)
+        if not 0 <= j < len(self):
+            raise IndexError(j)
+        return PinSAGEBatch(self, j)
+
+    def __iter__(self):
+        for j in range(len(self)):
+            yield PinSAGEBatch(self, j)
+
+
+class PinSAGELoader(_Loader):
+    """PinSAGE's importance sampler (DGL's PinSAGESampler / RandomWalkNeighborSampler) as a loader: the neighbours of a
+    node are the k_l nodes that `n_walks` random walks of up to `walk_length` steps from it visit most often (each walk
+    ends before a step l >= 1 with probability `termination`), the visit counts are the edge weights
+    (tg_pinsage_hop, csrc/pinsage.hip).  The walks follow in-edges on the CSC; walk_out_edges=True builds the CSR once and
+    walks along the edges; symmetric=True states that both are the same.
+
+    Mini-batch j of epoch e (0-based across launches) with distinct seeds F_0, for layer l = 0 .. L-1: one hop runs over
+    the flat concatenation of the launch's frontiers F_l with per-slot call ids call_id0 + (e * len(loader) + j) * L + l,
+    fan-out k_l and draw ids = the slot's index inside its own mini-batch's frontier -- a mini-batch's result does not
+    depend on what else is in the launch.  F_{l+1} = F_l followed by the neighbours not yet in F_l, in order of first
+    occurrence in the hop's output (tg_ns_homo_unique_grouped over the launch, one group per mini-batch).  Block l holds
+    n_id = F_{l+1}, n_dst = |F_l|, edge_index (row = index in n_id of the neighbour, col = index of the frontier slot) and
+    edge_weight.  A mini-batch (PinSAGEBatch) carries `blocks` outermost first, `n_id` = F_L, the node attributes of
+    `data` gathered by n_id (tg_gather_rows), `batch_size` and `input_nodes`; super_batches() hands out whole launches.
+
+    Host synchronisation: ONE read-back of sizes per layer and launch (the per-mini-batch node and edge counts), on the
+    caller's stream.  Duplicate input nodes inside one mini-batch are refused in the constructor (with shuffle=True any
+    duplicate); everything that can be refused is refused before any device work."""
+
+    def __init__(self, data, num_neighbors: List[int], input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
+                 n_walks: int = 10, walk_length: int = 2, termination: float = 0.5, prefetch: int = 16, seed: int = 0,
+                 call_id0: int = 0, shuffle: bool = False, drop_last: bool = False, symmetric: bool = False, device="cuda",
+                 walk_out_edges: bool = False):
+        fanout = [int(k) for k in num_neighbors]
+        if not fanout:
+            raise ValueError("num_neighbors must name at least one layer")
+        if any(not 1 <= k <= 64 for k in fanout):
+            raise ValueError("num_neighbors must be in 1..64 per layer, got %r" % (list(num_neighbors),))
+        B, R, T = int(batch_size), int(n_walks), int(walk_length)
+        if B < 1:
+            raise ValueError("batch_size must be at least 1, got %r" % (batch_size,))
+        if R < 1:
+            raise ValueError("n_walks must be at least 1, got %r" % (n_walks,))
+        if T < 1:
+            raise ValueError("walk_length must be at least 1, got %r" % (walk_length,))
+        if R * T > _cabi.PINSAGE_MAX_VISITS:
+            raise ValueError("n_walks * walk_length = %d visits per node exceed %d" % (R * T, _cabi.PINSAGE_MAX_VISITS))
+        alpha = float(termination)
+        if not 0.0 <= alpha < 1.0:                       # a NaN fails both comparisons
+            raise ValueError("termination must be in [0, 1), got %r" % (termination,))
+        if int(prefetch) < 1:
+            raise ValueError("prefetch must be at least 1, got %r" % (prefetch,))
+        if not 0 <= int(call_id0) < 2 ** 62:
+            raise ValueError("call_id0 must be in [0, 2^62), got %r" % (call_id0,))
+        N = _num_nodes(data)
+        if not 1 <= N <= 2 ** 31:
+            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
+        nodes = torch.arange(N) if input_nodes is None else input_nodes.detach().cpu().reshape(-1).to(torch.int64)
+        if nodes.numel() and (int(nodes.min()) < 0 or int(nodes.max()) >= N):
+            raise IndexError("input_nodes outside [0, %d)" % N)
+        if input_nodes is not None and nodes.numel():
+            # a frontier lists a node once: two equal seeds in one mini-batch would be two slots of F_0
+            batch_of = torch.zeros_like(nodes) if shuffle else torch.arange(nodes.numel()) // B
+            key = torch.sort(batch_of * N + nodes).values
+            if bool((key[1:] == key[:-1]).any()):
+                raise ValueError("input_nodes holds a node twice " + ("(shuffle=True: anywhere)" if shuffle else
+                                                                      "inside one mini-batch"))
+        self.data, self.fanout, self.batch_size = data, fanout, B
+        self.n_walks, self.walk_length, self.termination = R, T, alpha
+        self.prefetch, self.seed, self.call_id0 = int(prefetch), int(seed), int(call_id0)
+        self.shuffle, self.drop_last = bool(shuffle), bool(drop_last)
+        self.symmetric, self.walk_out_edges = bool(symmetric), bool(walk_out_edges)
+        self.device = torch.device(device)
+        self.n_nodes = N
+        self.input_nodes = nodes.to(self.device)
+        self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
+        E = int(data.edge_index.shape[1])
+        small = E < 2 ** 31
+        shadows = lambda ptrs, idx: dict(indices32=idx.to(torch.int32), ptrs32=ptrs.to(torch.int32)) if small else {}
+        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, **shadows(self.col_ptrs, self.row_indices))
+        if self.walk_out_edges and not self.symmetric:   # out-edges: the CSR, built once
+            ei = data.edge_index.to(self.device)
+            row_ptrs, col_indices, _ = _cabi.coo_to_csx(ei[0], ei[1], N, N, False)
+            self._csr = (row_ptrs, col_indices)
+            self._walk_graph = _cabi.graph_view(row_ptrs, col_indices, **shadows(row_ptrs, col_indices))
+        else:
+            self._walk_graph = self._graph
+        self._node_attrs = [(k, v.to(self.device)) for k, v in _tensor_items(data) if _attr_kind(k, v, N, E) == "node"]
+        self.epoch = 0
+
+    def _launch(self, seeds: Tensor, first_batch: int) -> PinSAGESuperBatch:
+        """seeds [G, width]: mini-batches first_batch .. first_batch + G - 1 of the run (epoch * len(self) + j)"""
+        dev, L = self.device, len(self.fanout)
+        G, width = seeds.shape
+        o = dict(dtype=torch.int64, device=dev)
+        arange = lambda n: torch.arange(n, **o)
+        sb = PinSAGESuperBatch()
+        sb.n_layers, sb.call_id0 = L, self.call_id0 + first_batch * L
+        sb.input_nodes = frontier = seeds.reshape(-1).contiguous()
+        sb.seed_ptr = ptr = [g * width for g in range(G + 1)]
+        group = arange(G).repeat_interleave(width)       # the mini-batch of every frontier slot: ascending
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        sb.layers = []
+        for l, k in enumerate(self.fanout):
+            n = frontier.numel()
+            start = torch.tensor(ptr, **o)
+            local = arange(n) - start[group]             # the slot's index inside its own mini-batch's frontier
+            call_ids = (self.call_id0 + first_batch * L + l) + group * L
+            cnt, offsets, nbr, par, vis = _cabi.pinsage_hop(self._walk_graph, frontier, k, self.n_walks, self.walk_length,
+                                                            self.termination, self.seed, 0, call_ids=call_ids, ids=local,
+                                                            status=status)
+            slabs = _PinSAGESlabs(frontier, nbr, par, offsets[n])
+            u = _cabi.ns_homo_unique_grouped(slabs, 1, self.n_nodes, seed_group=group.to(torch.int32), n_groups=G)
+            cap = slabs.samples.shape[1]
+            g_of = torch.where(arange(cap) < u.counts[0, 0], u.group[0], torch.full((), G, **o))
+            sizes = torch.zeros(G + 1, **o).scatter_add_(0, g_of, torch.ones(cap, **o))
+            host = torch.cat([sizes[:G], offsets[start], status.to(torch.int64)]).tolist()   # the layer's ONE read-back
+            if host[-1]:
+                raise RuntimeError("%s: a frontier node outside the graph" % type(self).__name__)
+            n_next, eptr = host[:G], host[G:2 * G + 1]
+            nptr = [0]
+            for x in n_next:
+                nptr.append(nptr[-1] + x)
+            total, n_edges = nptr[-1], eptr[-1]
+            order = torch.sort(g_of, stable=True).indices[:total]     # grouped by mini-batch, first occurrence first
+            rank = torch.empty(cap, **o)
+            rank[order] = arange(total)
+            n_id, next_group = u.nodes[0][order], g_of[order]
+            next_start = torch.tensor(nptr, **o)
+            par_e, e_group = par[:n_edges], group[par[:n_edges]]
+            row = rank[u.inverse[0, n:n + n_edges]] - next_start[e_group]
+            col = par_e - start[e_group]
+            sb.layers.append(dict(n_id=n_id, src_ptr=nptr, dst_ptr=ptr, edge_index=torch.stack([row, col]),
+                                  edge_weight=vis[:n_edges].clone(), edge_ptr=eptr))
+            frontier, group, ptr = n_id, next_group, nptr
+        sb.n_id, sb.node_ptr = frontier, ptr
+        sb.node_attrs = {k: _rows_of(v, frontier) for k, v in self._node_attrs}
+        return sb
+
+    def super_batches(self) -> Iterator[PinSAGESuperBatch]:
+        """The epoch as launches of up to `prefetch` mini-batches."""
+        nodes = self.input_nodes
+        epoch = self.epoch                               # captured: a second iterator is the next epoch
+        self.epoch += 1
+        batch0 = epoch * len(self)
+        if self.shuffle:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(self.seed * 1000003 + epoch)
+            nodes = nodes[torch.randperm(nodes.numel(), device=self.device, generator=gen)]
+        for start, G, width in _epoch_plan(nodes.numel(), self.batch_size, self.prefetch, self.drop_last):
+            yield self._launch(nodes[start:start + G * width].reshape(G, width), batch0 + start // self.batch_size)
+
+    def __iter__(self) -> Iterator[PinSAGEBatch]:
         for sb in self.super_batches():
             yield from sb
