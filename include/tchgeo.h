@@ -1386,6 +1386,62 @@ TG_API int tg_ns_induced_grouped_emit(const tg_graph *csc, const tg_ns_induced_g
                                       int64_t id_bound, const int64_t *edge_off, int64_t *rows, int64_t *cols,
                                       int64_t *edge_index, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- Cluster-GCN mini-batches: the induced subgraph of a UNION OF CLUSTERS (PyG's ClusterLoader, DGL's ClusterGCNSampler) --
+ * The nodes of csc are numbered so that cluster c of a fixed partition is the id range [partptr[c], partptr[c+1])
+ * (partptr ascends from 0 to csc->n_major: ranges of distinct clusters are disjoint).  For every batch b independently,
+ * with its cluster list c_0 .. c_{q-1} (q = n_clusters[b] clamped to [0, pitch_parts]; pitch_parts each without
+ * n_clusters):
+ *   size_k = partptr[c_k+1] - partptr[c_k];  base_k = size_0 + .. + size_{k-1};  n_b = base_q
+ *   position i in [base_k, base_k + size_k) is vertex v_i = partptr[c_k] + (i - base_k)
+ *   local(u) = base_k + (u - partptr[c_k]) for the FIRST k whose range holds u       (no such k: u is not in the batch)
+ *   for i in 0 .. n_b-1, for e in ptrs[v_i] .. ptrs[v_i+1]-1 ascending:
+ *       j = local(indices[e]);  if j exists: emit (row = j, col = i, edge_index = e)
+ * Output order is (i, e) ascending; parallel edges and self loops are emitted; m_b = the number of triples.  That is word
+ * for word tg_ns_induced_* over the list nodes[b] = (v_0 .. v_{n_b-1}), between-cluster edges included, and also where a
+ * cluster is named twice: every position scans its column, local is the first position.  What the partition saves: no
+ * hash table (the batch's distinct ranges, sorted, sit in LDS; a neighbour costs one search there), no idle lanes (a
+ * cluster's CSC entries are ONE offset range, scanned in chunks of 512 consecutive offsets that cross column boundaries;
+ * a hub column is still split over many chunks), no node list read (it is implied, and written once by pass 2).
+ * Two exact passes, as the induced pair: tg_cluster_count gives n_b and m_b, the caller computes the two exclusive
+ * prefixes, tg_cluster_emit writes; the workspace stays untouched between them; neither call allocates, synchronises or
+ * reads back.  The workspace holds all n_batches at once (bytes = n_batches * bytes_min), bounded by the graph: distinct
+ * clusters have disjoint offset ranges, so a batch has at most pitch_parts + ceil(csc->n_edges / 512) chunks.
+ * status (device int32, zeroed by the caller):
+ *   bit 1 (value 2): a cluster id outside [0, n_parts); the entry contributes no nodes.
+ *   bit 2 (value 4): a partptr pair that is inverted or leaves [0, csc->n_major]; the entry is treated as empty and never
+ *                    indexes ptrs out of range.  (A partptr that does not ascend elsewhere can make ranges overlap: the
+ *                    output is then still deterministic and in bounds, local(u) taken from the range with the greatest
+ *                    start <= u.)
+ *   bit 0 (value 1): a batch with more chunks than the bound (only possible with repeated clusters) or with n_b >= 2^31:
+ *                    it gets n_b = m_b = 0 and nothing from pass 2; other batches are unaffected.
+ * Limits: csc->n_major <= 2^31 (else TG_ERR_UNSUPPORTED); pitch_parts in [0, TG_CLUSTER_MAX_PARTS_PER_BATCH]; the chunk
+ * bound <= 2^31; indices32 / ptrs32 are used when given, with equal results.  Null buffers, negative sizes, a pitch above
+ * the limit and a short or misaligned (8 bytes) workspace are refused with TG_ERR_INVALID before anything is launched;
+ * n_batches = 0 launches nothing; more batches than one grid's y extent run in rounds. */
+#define TG_CLUSTER_MAX_PARTS_PER_BATCH 1024
+typedef struct {
+    const int64_t *partptr;     /* device [n_parts + 1]: cluster c = ids [partptr[c], partptr[c+1]) of csc */
+    int64_t n_parts;
+    const int64_t *clusters;    /* device [n_batches * pitch_parts]: batch b's cluster ids, in the caller's order */
+    int64_t pitch_parts;        /* 0 .. TG_CLUSTER_MAX_PARTS_PER_BATCH */
+    const int64_t *n_clusters;  /* device [n_batches] or NULL (= pitch_parts each); clamped to [0, pitch_parts] */
+    const int64_t *node_ids;    /* device [csc->n_major] or NULL: `nodes` receives node_ids[v] instead of v */
+} tg_cluster_in;
+
+TG_API int tg_cluster_workspace_bytes(const tg_graph *csc, int64_t n_parts, int64_t pitch_parts, int64_t n_batches,
+                                      int64_t *bytes, int64_t *bytes_min /* one batch */);
+/* pass 1: n_nodes[b] = n_b, n_edges[b] = m_b (device [n_batches] each); leaves the plan and the chunk prefixes in
+ * `workspace` for pass 2. */
+TG_API int tg_cluster_count(const tg_graph *csc, const tg_cluster_in *in, int64_t n_batches, int64_t *n_nodes,
+                            int64_t *n_edges, int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+/* pass 2, same arguments and the SAME untouched workspace: v_i (node_ids[v_i] when given) to nodes[node_off[b] + i] (nodes
+ * may be NULL: nothing is written for it), batch b's triples to rows / cols / edge_index[edge_off[b] .. edge_off[b] + m_b)
+ * of three FLAT arrays (node_off, edge_off: device [n_batches], the caller's exclusive prefixes of n_nodes and n_edges).
+ * Nothing outside those ranges is written. */
+TG_API int tg_cluster_emit(const tg_graph *csc, const tg_cluster_in *in, int64_t n_batches, const int64_t *node_off,
+                           const int64_t *edge_off, int64_t *nodes, int64_t *rows, int64_t *cols, int64_t *edge_index,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- GraphSAINT's random-walk sampler: a SUBGRAPH per mini-batch (PyG's GraphSAINTRandomWalkSampler) ---------------------
  * tg_saint_rw_nodes: one launch takes G = n_batches mini-batches of B = batch_size roots (roots: device [G, B]); every
  * root walks T = walk_length >= 1 uniform steps over csr.  Per mini-batch g: walker i starts at roots[g][i] and its

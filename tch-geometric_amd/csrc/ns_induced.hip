@@ -97,29 +97,6 @@ __device__ __forceinline__ int64_t nsi_ptr(const NsiArgs &a, int64_t v) {
     return a.ptrs32 ? (int64_t)a.ptrs32[v] : a.ptrs[v];
 }
 
-// exclusive prefix of `v` over the threads of the workgroup in thread order, *total = the sum.  Every thread calls it.
-__device__ __forceinline__ unsigned long long nsi_scan64(unsigned long long v, unsigned long long *s_wave,
-                                                         unsigned long long *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned long long carry = 0, sum = 0;
-    for (int w = 0; w < n_waves; ++w) {
-        const unsigned long long x = s_wave[w];
-        sum += x;
-        if (w < wave) carry += x;
-    }
-    __syncthreads(); // s_wave is free again
-    *total = sum;
-    return carry + incl - v;
-}
-
 // the first position of `key` in the batch's list, NSU_UNSEEN where it has none; at most one pass over the table
 template <typename K>
 __device__ __forceinline__ uint32_t nsi_find(const K *keys, const uint32_t *vals, uint32_t mask, uint32_t shift, K key) {
@@ -185,7 +162,7 @@ template <typename K, bool G> __global__ void __launch_bounds__(NSI_THREADS) nsi
     if (outside) atomicOr(a.status, 2);
     if (G && no_group) atomicOr(a.status, 4);
     unsigned long long total;
-    unsigned long long run = nsi_scan64(mine, s_wave, &total);
+    unsigned long long run = nsu_scan64(mine, s_wave, &total);
 #pragma unroll
     for (int k = 0; k < NSU_PER; ++k) {
         if (p0 + k < n) t.npref[p0 + k] = run;
@@ -204,7 +181,7 @@ template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_node_ap
     const NsiBatch<K> t(a, b);
     unsigned long long before = 0, base;
     for (uint32_t i = threadIdx.x; i < blockIdx.x; i += NSI_THREADS) before += t.ntile[i];
-    nsi_scan64(before, s_wave, &base);
+    nsu_scan64(before, s_wave, &base);
     const int64_t p0 = tile0 + (int64_t)threadIdx.x * NSU_PER;
 #pragma unroll
     for (int k = 0; k < NSU_PER; ++k)
@@ -310,7 +287,7 @@ template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_chunk_a
     if (tile0 >= n_chunks && blockIdx.x != 0) return; // uniform
     unsigned long long before = 0, base;
     for (uint32_t i = threadIdx.x; i < blockIdx.x; i += NSI_THREADS) before += t.ctile[i];
-    nsi_scan64(before, s_wave, &base);
+    nsu_scan64(before, s_wave, &base);
     const unsigned long long c0 = tile0 + (unsigned long long)threadIdx.x * NSU_PER;
     unsigned long long h[NSU_PER], mine = 0;
 #pragma unroll
@@ -319,7 +296,7 @@ template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_chunk_a
         mine += h[k];
     }
     unsigned long long total;
-    unsigned long long run = base + nsi_scan64(mine, s_wave, &total);
+    unsigned long long run = base + nsu_scan64(mine, s_wave, &total);
     unsigned long long pre[NSU_PER];
 #pragma unroll
     for (int k = 0; k < NSU_PER; ++k) {

@@ -61,6 +61,30 @@ __device__ __forceinline__ uint32_t nsu_scan(uint32_t cnt, uint32_t *s_wave, uin
     return carry + incl - cnt;
 }
 
+// exclusive prefix of `v` over the threads of the workgroup in thread order, *total = the sum.  Every thread calls it.  The 64-bit
+// form of nsu_scan: the induced pairs' chunk prefixes and tg_cluster_*'s plan step.
+__device__ __forceinline__ unsigned long long nsu_scan64(unsigned long long v, unsigned long long *s_wave,
+                                                         unsigned long long *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    unsigned long long incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long up = __shfl_up(incl, d);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    unsigned long long carry = 0, sum = 0;
+    for (int w = 0; w < n_waves; ++w) {
+        const unsigned long long x = s_wave[w];
+        sum += x;
+        if (w < wave) carry += x;
+    }
+    __syncthreads(); // s_wave is free again
+    *total = sum;
+    return carry + incl - v;
+}
+
 __device__ __forceinline__ int64_t nsu_clamp(int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 // the local id an edge end `r` (a position) maps to; -1 where r is no position of the batch (a contract violation)
 template <typename Lookup> __device__ __forceinline__ int64_t nsu_end(int64_t r, int64_t n, Lookup lookup) {

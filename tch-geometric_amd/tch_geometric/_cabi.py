@@ -49,7 +49,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_ns_induced_grouped_workspace_bytes", "tg_ns_induced_grouped_count", "tg_ns_induced_grouped_emit",
            "tg_saint_rw_capacity", "tg_saint_rw_form", "tg_saint_rw_workspace_bytes", "tg_saint_rw_nodes",
            "tg_saint_coverage_add", "tg_saint_norm", "tg_ns_hop_labor_workspace_bytes", "tg_ns_hop_labor",
-           "tg_ns_hop_labor_long_column", "tg_pinsage_hop_workspace_bytes", "tg_pinsage_hop"]
+           "tg_ns_hop_labor_long_column", "tg_pinsage_hop_workspace_bytes", "tg_pinsage_hop",
+           "tg_cluster_workspace_bytes", "tg_cluster_count", "tg_cluster_emit"]
 
 
 class TgGraph(C.Structure):
@@ -1451,6 +1452,113 @@ def induced_status_check(status, who):
         raise RuntimeError("%s: status %d (%s)" % (who, status, " and ".join(
             t for bit, t in ((1, "a list with repeats exceeds the chunk bound"), (2, "a node id outside the graph"),
                              (4, "a group word outside [0, n_groups)")) if status & bit)))
+
+
+CLUSTER_MAX_PARTS_PER_BATCH = 1024   # tchgeo.h TG_CLUSTER_MAX_PARTS_PER_BATCH
+
+
+class TgClusterIn(C.Structure):
+    _fields_ = [("partptr", C.c_void_p), ("n_parts", C.c_int64), ("clusters", C.c_void_p), ("pitch_parts", C.c_int64),
+                ("n_clusters", C.c_void_p), ("node_ids", C.c_void_p)]
+
+
+def cluster_workspace_bytes(graph, n_parts, pitch_parts, n_batches):
+    """-> (bytes, bytes_min): the workspace of the cluster pair for n_batches batches at once (n_batches * bytes_min) and
+    for one batch; graph: a tg_graph view (only n_major and n_edges are read)."""
+    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_cluster_workspace_bytes(C.byref(graph), C.c_int64(n_parts), C.c_int64(pitch_parts), C.c_int64(n_batches),
+                                         C.byref(nbytes), C.byref(bmin)))
+    return nbytes.value, bmin.value
+
+
+class ClusterInduced:
+    """The cluster pair (tg_cluster_count / tg_cluster_emit) over the cluster lists `clusters` [>= n_batches, pitch] of the
+    partition `partptr` [n_parts + 1] of `graph` (a CSC whose clusters are id ranges); n_clusters: [>= n_batches] entries
+    per batch or None (the pitch each); node_ids: [n_major] what `nodes` receives for a vertex, or None.  Owns what the
+    passes share: n_nodes, n_edges [n_batches each] and status [1] in one tensor `state` (a loader reads it back in one
+    copy) and the workspace (`ws`: an int64 tensor of an earlier launch, reused when large enough).  count(G) then
+    emit(...) run on the current stream over the first G batches; neither synchronises."""
+
+    def __init__(self, graph, partptr, clusters, n_clusters=None, node_ids=None, ws=None):
+        if clusters.dim() != 2 or clusters.dtype != torch.int64 or not clusters.is_contiguous():
+            raise ValueError("ClusterInduced: clusters must be a contiguous int64 [n_batches, pitch] tensor")
+        if partptr.dtype != torch.int64 or partptr.dim() != 1 or partptr.numel() < 1 or not partptr.is_contiguous():
+            raise ValueError("ClusterInduced: partptr must be a contiguous int64 [n_parts + 1] tensor")
+        for name, t in (("n_clusters", n_clusters), ("node_ids", node_ids)):
+            if t is not None and (t.dtype != torch.int64 or not t.is_contiguous()):
+                raise ValueError("ClusterInduced: %s must be a contiguous int64 tensor" % name)
+        if n_clusters is not None and n_clusters.numel() < clusters.shape[0]:
+            raise ValueError("ClusterInduced: n_clusters is shorter than the batches")
+        if node_ids is not None and node_ids.numel() < graph.n_major:
+            raise ValueError("ClusterInduced: node_ids is shorter than the graph")
+        dev = clusters.device
+        self.graph, self.partptr, self.clusters, self.n_clusters, self.node_ids = graph, partptr, clusters, n_clusters, node_ids
+        self.n_batches = self.live = int(clusters.shape[0])
+        si = self.struct = TgClusterIn()
+        si.partptr, si.n_parts = partptr.data_ptr(), partptr.numel() - 1
+        si.clusters, si.pitch_parts = clusters.data_ptr(), int(clusters.shape[1])
+        si.n_clusters = None if n_clusters is None else n_clusters.data_ptr()
+        si.node_ids = None if node_ids is None else node_ids.data_ptr()
+        need = cluster_workspace_bytes(graph, si.n_parts, si.pitch_parts, self.n_batches)[0]
+        if ws is None or ws.numel() * 8 < need:
+            ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+        self.ws = ws
+        self.state = torch.zeros(2 * self.n_batches + 1, dtype=torch.int64, device=dev)
+        self.n_nodes = self.state[:self.n_batches]
+        self.n_edges = self.state[self.n_batches:2 * self.n_batches]
+        self.status = self.state[-1:].view(torch.int32)[:1]
+
+    def count(self, G=None):
+        """pass 1 over the first G batches (all when None); emit() then runs the same ones"""
+        self.live = self.n_batches if G is None else int(G)
+        if not 0 <= self.live <= self.n_batches:
+            raise ValueError("ClusterInduced.count: G = %d outside [0, %d]" % (self.live, self.n_batches))
+        self.state[-1:].zero_()
+        check(lib.tg_cluster_count(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live), ptr(self.n_nodes),
+                                   ptr(self.n_edges), ptr(self.status), ptr(self.ws), C.c_int64(self.ws.numel() * 8),
+                                   stream_ptr(self.clusters.device)))
+        return self
+
+    def emit_into(self, node_off, edge_off, nodes, rows, cols, edge_index):
+        """pass 2 into the caller's flat arrays; node_off / edge_off: device [n_batches], the exclusive prefixes of n_nodes
+        / n_edges; nodes may be None"""
+        check(lib.tg_cluster_emit(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live), ptr(node_off),
+                                  ptr(edge_off), None if nodes is None else ptr(nodes), ptr(rows), ptr(cols),
+                                  ptr(edge_index), ptr(self.ws), C.c_int64(self.ws.numel() * 8),
+                                  stream_ptr(self.clusters.device)))
+
+    def emit(self, n_nodes_host=None, n_edges_host=None, with_nodes=True):
+        """pass 2 of a counted launch into exact flat arrays -> (nodes [sum n_b] or None, [2, M] rows over cols, edge_index
+        [M], node_off, edge_off [live + 1] as python lists).  n_nodes_host / n_edges_host: the counts already read back;
+        read here (one synchronisation) when not given, together with the status word, which raises when non-zero."""
+        G = self.live
+        if n_nodes_host is None or n_edges_host is None:
+            state = self.state.cpu()
+            cluster_status_check(int(state[-1:].view(torch.int32)[0]), "ClusterInduced.emit")
+            n_nodes_host = state[:G].tolist()
+            n_edges_host = state[self.n_batches:self.n_batches + G].tolist()
+        noff, eoff = [0], [0]
+        for n, m in zip(n_nodes_host, n_edges_host):
+            noff.append(noff[-1] + int(n))
+            eoff.append(eoff[-1] + int(m))
+        dev = self.clusters.device
+        nodes = torch.empty(noff[-1], dtype=torch.int64, device=dev) if with_nodes else None
+        rc = torch.empty((2, eoff[-1]), dtype=torch.int64, device=dev)
+        eidx = torch.empty(eoff[-1], dtype=torch.int64, device=dev)
+        if G and (noff[-1] or eoff[-1]):
+            node_off = torch.cumsum(self.n_nodes[:G], 0) - self.n_nodes[:G]
+            edge_off = torch.cumsum(self.n_edges[:G], 0) - self.n_edges[:G]
+            self.emit_into(node_off, edge_off, nodes, rc[0], rc[1], eidx)
+        return nodes, rc, eidx, noff, eoff
+
+
+def cluster_status_check(status, who):
+    """the status word of tg_cluster_count after its read-back: non-zero raises"""
+    if status:
+        raise RuntimeError("%s: status %d (%s)" % (who, status, " and ".join(
+            t for bit, t in ((1, "a batch with repeated clusters exceeds the chunk bound, or has 2^31 nodes or more"),
+                             (2, "a cluster id outside [0, n_parts)"),
+                             (4, "a partptr pair that is inverted or leaves the graph")) if status & bit)))
 
 
 class TgNsInducedGroupedIn(C.Structure):

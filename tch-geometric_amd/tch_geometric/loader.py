@@ -27,6 +27,9 @@ normalisation vectors of a pre-sample (tg_saint_coverage_add, tg_saint_norm).
 PinSAGELoader hands out DGL-style blocks whose neighbours are the most visited nodes of short random walks with
 termination (tg_pinsage_hop), the visit counts as edge weights; a launch's frontiers are grown per mini-batch with the
 grouped dedup.
+ClusterData / ClusterLoader hand out Cluster-GCN mini-batches: the union of `batch_size` clusters of a fixed node partition
+with every edge of the graph between its nodes (tg_cluster_count / tg_cluster_emit: a range table in LDS instead of the
+induced pair's hash table).
 """
 from typing import Iterator, List, Optional
 
@@ -2233,5 +2236,178 @@ class PinSAGELoader(_Loader):
             yield self._launch(nodes[start:start + G * width].reshape(G, width), batch0 + start // self.batch_size)
 
     def __iter__(self) -> Iterator[PinSAGEBatch]:
+        for sb in self.super_batches():
+            yield from sb
+
+
+def range_partition(num_nodes: int, num_parts: int) -> Tensor:
+    """part [N] (CPU int64): P contiguous id ranges whose sizes differ by at most one, node v in cluster v * P // N.  A
+    stand-in for a real partitioner in examples and tests; it knows nothing about the edges."""
+    N, P = int(num_nodes), int(num_parts)
+    if N < 0 or P < 1:
+        raise ValueError("range_partition: num_nodes >= 0 and num_parts >= 1 expected, got %r, %r" % (num_nodes, num_parts))
+    return (torch.arange(N, dtype=torch.int64) * P) // max(N, 1)
+
+
+def random_partition(num_nodes: int, num_parts: int, seed: int = 0) -> Tensor:
+    """part [N] (CPU int64): every node in a cluster drawn uniformly from [0, P) by a CPU generator seeded with `seed`."""
+    N, P = int(num_nodes), int(num_parts)
+    if N < 0 or P < 1:
+        raise ValueError("random_partition: num_nodes >= 0 and num_parts >= 1 expected, got %r, %r" % (num_nodes, num_parts))
+    g = torch.Generator()
+    g.manual_seed(int(seed))
+    return torch.randint(0, P, (N,), generator=g, dtype=torch.int64)
+
+
+def cluster_epoch_order(num_parts: int, seed: int, epoch: int, shuffle: bool = True) -> Tensor:
+    """The order ClusterLoader visits the clusters in during epoch `epoch` (CPU int64 [P]): torch.randperm from a CPU
+    generator seeded with (seed * 1000003 + epoch) mod 2^63, or arange without shuffle."""
+    if not shuffle:
+        return torch.arange(int(num_parts), dtype=torch.int64)
+    g = torch.Generator()
+    g.manual_seed((int(seed) * 1000003 + int(epoch)) % (1 << 63))
+    return torch.randperm(int(num_parts), generator=g)
+
+
+class ClusterData:
+    """A graph renumbered by a node partition (PyG's ClusterData without the partitioner): `part` [N] gives every node's
+    cluster in [0, num_parts) -- from METIS (pymetis, torch-sparse), a saved file, or range_partition / random_partition.
+    One-off setup on `device` with the plumbing that exists: a stable sort of `part` is `node_perm` (new id -> original id;
+    `node_inv` the other way), tg_ind2ptr over the sorted cluster ids is `partptr` (cluster c = new ids [partptr[c],
+    partptr[c+1])), the device ingest of the renumbered edge list gives the CSC (`col_ptrs`, `row_indices`) and `perm`
+    (CSC offset -> original edge number), with int32 shadows when E < 2^31.  Attributes stay in the original numbering:
+    mini-batches address them through n_id and e_id."""
+
+    def __init__(self, data, part: Tensor, num_parts: Optional[int] = None, device="cuda"):
+        N, E = _num_nodes(data), int(data.edge_index.shape[1])
+        if not 1 <= N <= 2 ** 31:                # everything that needs no device is refused before any device work
+            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
+        if not isinstance(part, Tensor) or part.dim() != 1 or part.is_floating_point() or part.dtype == torch.bool:
+            raise ValueError("part must be an integer tensor [num_nodes]")
+        if part.numel() != N:
+            raise ValueError("part has %d entries for %d nodes" % (part.numel(), N))
+        if num_parts is not None and int(num_parts) < 1:
+            raise ValueError("num_parts must be at least 1, got %r" % (num_parts,))
+        lo, hi = int(part.min()), int(part.max())    # on the device only when `part` lives there
+        P = hi + 1 if num_parts is None else int(num_parts)
+        if lo < 0 or hi >= P:
+            raise ValueError("part holds cluster ids outside [0, %d): min %d, max %d" % (P, lo, hi))
+        self.data, self.num_parts, self.n_nodes, self.n_edges = data, P, N, E
+        self.device = dev = torch.device(device)
+        part = part.to(dev, torch.int64)
+        sorted_part, self.node_perm = torch.sort(part, stable=True)
+        self.node_inv = torch.empty_like(self.node_perm)
+        self.node_inv[self.node_perm] = torch.arange(N, dtype=torch.int64, device=dev)
+        self.partptr = _cabi.ind2ptr(sorted_part.contiguous(), P)
+        ei = data.edge_index.to(dev)
+        self.col_ptrs, self.row_indices, self.perm = _cabi.coo_to_csx(self.node_inv[ei[0]], self.node_inv[ei[1]], N, N, True)
+        shadows = dict(indices32=self.row_indices.to(torch.int32), ptrs32=self.col_ptrs.to(torch.int32)) if E < 2 ** 31 else {}
+        self.graph = _cabi.graph_view(self.col_ptrs, self.row_indices, **shadows)
+        self.node_attrs, self.edge_attrs = [], []
+        for key, value in _tensor_items(data):
+            kind = _attr_kind(key, value, N, E)
+            if kind == "node":
+                self.node_attrs.append((key, value.to(dev)))
+            elif kind == "edge":
+                self.edge_attrs.append((key, value.to(dev)))
+
+    def __len__(self) -> int:
+        return self.num_parts
+
+
+class ClusterLoader(_Loader):
+    """Cluster-GCN's mini-batches (PyG's ClusterLoader, DGL's ClusterGCNSampler) over a ClusterData: a mini-batch is the
+    union of `batch_size` clusters with EVERY edge of the graph between its nodes, the between-cluster ones included.  An
+    epoch visits every cluster once, in cluster_epoch_order(P, seed, epoch, shuffle); mini-batch j takes
+    order[j * batch_size : (j + 1) * batch_size], the last one is shorter (dropped under drop_last).  A launch takes
+    `prefetch` consecutive mini-batches: tg_cluster_count, ONE read-back of the node and edge counts and the status word,
+    tg_cluster_emit into exact flat arrays, tg_gather_rows per attribute -- all on the caller's stream.
+
+    Mini-batches are `MiniBatch` views of a `SuperBatch` (`super_batches()` hands those out): `n_id` (ORIGINAL node ids,
+    cluster after cluster in the list's order, inside a cluster in the stable order of the partition), `edge_index` (row =
+    source, col = target, numbered against n_id; ordered by target position, then CSC offset), `e_id` (original edge
+    numbers), node and edge attributes; `batch_size` is the cluster count asked for."""
+
+    def __init__(self, cluster_data: ClusterData, batch_size: int = 1, shuffle: bool = True, drop_last: bool = False,
+                 prefetch: int = 16, seed: int = 0, device=None):
+        q = int(batch_size)
+        if q < 1:                            # everything that can be refused is refused before any device work
+            raise ValueError("batch_size must be at least 1 cluster, got %r" % (batch_size,))
+        if q > _cabi.CLUSTER_MAX_PARTS_PER_BATCH:
+            raise ValueError("batch_size must be at most %d clusters, got %r" % (_cabi.CLUSTER_MAX_PARTS_PER_BATCH, batch_size))
+        if int(prefetch) < 1:
+            raise ValueError("prefetch must be at least 1, got %r" % (prefetch,))
+        if not isinstance(cluster_data, ClusterData):
+            raise ValueError("cluster_data must be a ClusterData, got %s" % type(cluster_data).__name__)
+        cd = self.cluster_data = cluster_data
+        if device is not None and torch.device(device).type != cd.device.type:
+            raise ValueError("the ClusterData lives on %s, not on %s" % (cd.device, device))
+        self.device = cd.device
+        self.batch_size, self.shuffle, self.drop_last = q, bool(shuffle), bool(drop_last)
+        self.prefetch, self.seed = int(prefetch), int(seed)
+        self.input_nodes = torch.empty(cd.num_parts, dtype=torch.int8)   # _Loader.__len__: the inputs are the clusters
+        self._pool = []                      # slab sets of finished iterators (each live iterator owns its own)
+        self.slab_allocations = 0            # slab sets made so far: a second epoch makes none
+        self.epoch = 0
+
+    def _new_slab(self):
+        """what a launch of up to `prefetch` mini-batches needs: the cluster lists and their lengths on the device, the
+        pair's launch object (its counts, status and workspace) and the pinned images of what crosses the bus"""
+        cap, q, dev, cd = self.prefetch, self.batch_size, self.device, self.cluster_data
+        self.slab_allocations += 1
+        lists = torch.zeros(cap * q + cap, dtype=torch.int64, device=dev)   # lists and lengths: one upload
+        clusters, n_clusters = lists[:cap * q].view(cap, q), lists[cap * q:]
+        ind = _cabi.ClusterInduced(cd.graph, cd.partptr, clusters, n_clusters, cd.node_perm)
+        return dict(lists=lists, ind=ind, host_lists=torch.zeros(cap * q + cap, dtype=torch.int64).pin_memory(),
+                    host=torch.empty(ind.state.numel(), dtype=torch.int64).pin_memory())
+
+    def _launch(self, slab, order: Tensor, j0: int, G: int):
+        """mini-batches j0 .. j0 + G - 1 of the epoch -> (node counts, edge counts) as python lists, after the launch's one
+        read-back; pass 2 has not run yet"""
+        cap, q = self.prefetch, self.batch_size
+        hl = slab["host_lists"]              # its last upload is behind the last launch's read-back
+        hl.zero_()
+        part = order[j0 * q:(j0 + G) * q]
+        hl[:part.numel()] = part             # row g of the [cap, q] slab starts at g * q: full rows, then the ragged last
+        for g in range(G):
+            hl[cap * q + g] = min(q, order.numel() - (j0 + g) * q)
+        slab["lists"].copy_(hl, non_blocking=True)
+        ind = slab["ind"].count(G)
+        host = slab["host"]
+        host.copy_(ind.state, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        _cabi.cluster_status_check(int(host[-1:].view(torch.int32)[0]), type(self).__name__)
+        return host[:G].tolist(), host[cap:cap + G].tolist()
+
+    def _finish(self, slab, j0: int, G: int, n_nodes, n_edges) -> SuperBatch:
+        cd = self.cluster_data
+        n_id, edge_index, e_ptr, ptr_n, ptr_e = slab["ind"].emit(n_nodes, n_edges)
+        sb = SuperBatch()
+        sb.input_time = sb.node_time = sb.batch = sb.root_n_id = None
+        sb.n_id, sb.edge_index = n_id, edge_index
+        sb._e_id, sb._e_ptr, sb._perm = None, e_ptr, cd.perm
+        sb.node_attrs = {k: _rows_of(v, n_id) for k, v in cd.node_attrs}
+        sb.edge_attrs = {k: _rows_of(v, sb.e_id) for k, v in cd.edge_attrs}
+        sb.node_ptr, sb.edge_ptr = ptr_n, ptr_e
+        sb.layer_offsets = sb.layer_nodes = sb.layer_edges = sb.seed_counts = None
+        sb.batch_size, sb.call_id0, sb.n_hops = self.batch_size, j0, 0
+        return sb
+
+    def super_batches(self) -> Iterator[SuperBatch]:
+        """The epoch as super-batches of up to `prefetch` mini-batches."""
+        epoch = self.epoch                   # captured: a second iterator is the next epoch
+        self.epoch += 1
+        order = cluster_epoch_order(self.cluster_data.num_parts, self.seed, epoch, self.shuffle)
+        n_mb = len(self)
+        slab = self._pool.pop() if self._pool else self._new_slab()
+        try:
+            for j0 in range(0, n_mb, self.prefetch):
+                G = min(self.prefetch, n_mb - j0)
+                n_nodes, n_edges = self._launch(slab, order, j0, G)
+                yield self._finish(slab, j0, G, n_nodes, n_edges)
+        finally:
+            self._pool.append(slab)
+
+    def __iter__(self) -> Iterator[MiniBatch]:
         for sb in self.super_batches():
             yield from sb
