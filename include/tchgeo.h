@@ -1442,6 +1442,56 @@ TG_API int tg_cluster_emit(const tg_graph *csc, const tg_cluster_in *in, int64_t
                            const int64_t *edge_off, int64_t *nodes, int64_t *rows, int64_t *cols, int64_t *edge_index,
                            void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- full-neighbour hop: EVERY in-edge of a frontier (PyG's num_neighbors=[-1], DGL's MultiLayerFullNeighborSampler) -------
+ * The layer of layer-wise inference: no sampling, no fan-out limit, a ragged exact output.  For every batch b independently,
+ * with its frontier v_0 .. v_{n-1} = nodes[node_ptr[b] .. node_ptr[b+1]) (n clamped to [0, max_nodes]):
+ *   col(i) = the CSC column [ptrs[v_i], ptrs[v_i+1]); an id outside [0, csc->n_major) is a column of length 0 and raises
+ *            status bit 1 (value 2)
+ *   for i in 0 .. n-1, for e in col(i) ascending: triple k = (src_k = indices[e], col = i, edge_index = e)
+ *   m_b = the number of triples, the sum of the column lengths; parallel edges and self loops are each emitted
+ *   out_nodes = v_0 .. v_{n-1}, followed by every src that equals no earlier entry of out_nodes, in order of first
+ *               occurrence in triple order;  n_out_b = len(out_nodes)
+ *   row_k = the FIRST position of src_k in out_nodes
+ * A frontier with repeats stays deterministic and in bounds: every position emits its column, rows point to the first
+ * position.  Sources are expected inside [0, id_bound).
+ * Two exact passes.  tg_ns_full_count writes n_nodes[b] = n_out_b, n_edges[b] = m_b and chunks[b] (may be NULL) = the sum
+ * over positions of ceil(column length / 512), and leaves its tables and prefixes in `workspace`; the caller computes the
+ * exclusive prefixes node_off / edge_off; tg_ns_full_emit, with the same arguments and the SAME untouched workspace, writes
+ * out_nodes to nodes_out[node_off[b] ..) (nodes_out may be NULL: nothing is written for it) and the triples to rows / cols /
+ * edge_index[edge_off[b] .. edge_off[b] + m_b) of three flat arrays.  Nothing outside those ranges is written.  Pass 2
+ * leaves the new positions in the workspace's table: a second tg_ns_full_emit needs a second tg_ns_full_count.  Neither call
+ * allocates, synchronises or reads back.
+ * Capacity, decided per batch before any table work: a batch with n + min(m_b, id_bound) > node_cap, with chunks[b] >
+ * the chunk bound (chunk_cap; <= 0: max_nodes + ceil(csc->n_edges / 512), what a frontier of distinct nodes needs at most)
+ * or with m_b >= 2^31 is refused: status bit 0 (value 1), n_nodes[b] = 0, n_edges[b] and chunks[b] still exact, so the caller
+ * can repeat with a workspace of that size; pass 2 writes nothing for it; other batches are unaffected.
+ * Columns are scanned in chunks of 512 consecutive CSC offsets spread over the whole device (a hub column is many chunks);
+ * every entry is inserted into the batch's hash table with the index of its triple, so the first occurrence is decided
+ * across chunks.  Hash keys are 32-bit while id_bound (>= csc->n_major) <= 2^31, else 64-bit; indices32 / ptrs32 are used
+ * when given, with equal results.  Limits: max_nodes in [0, 2^30], node_cap in [max_nodes, 2^30], the chunk bound <= 2^31.
+ * Null buffers, negative sizes, id_bound < csc->n_major and a short or misaligned (8 bytes) workspace are refused with
+ * TG_ERR_INVALID before anything is launched; n_batches = 0 launches nothing; more batches than one grid's y extent run in
+ * rounds.  The workspace holds all n_batches at once (bytes = n_batches * bytes_min). */
+typedef struct {
+    const int64_t *nodes;     /* device, flat: batch b's frontier is nodes[node_ptr[b] .. node_ptr[b+1]) */
+    const int64_t *node_ptr;  /* device [n_batches + 1], ascending from any base */
+    int64_t max_nodes;        /* the caller's bound on node_ptr[b+1]-node_ptr[b]; a longer list is clamped to it */
+    int64_t node_cap;         /* distinct nodes (frontier + new sources) per batch the workspace's table holds */
+    int64_t chunk_cap;        /* chunks per batch the workspace holds; <= 0: max_nodes + ceil(n_edges / 512) */
+} tg_ns_full_in;
+
+/* only the sizes of `in` (max_nodes, node_cap, chunk_cap) are read */
+TG_API int tg_ns_full_workspace_bytes(const tg_graph *csc, const tg_ns_full_in *in, int64_t id_bound, int64_t n_batches,
+                                      int64_t *bytes, int64_t *bytes_min /* one batch */);
+/* pass 1: n_nodes, n_edges, chunks: device int64 [n_batches] (chunks may be NULL); status: device int32, zeroed by the caller */
+TG_API int tg_ns_full_count(const tg_graph *csc, const tg_ns_full_in *in, int64_t n_batches, int64_t id_bound,
+                            int64_t *n_nodes, int64_t *n_edges, int64_t *chunks, int32_t *status, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+/* pass 2: node_off, edge_off: device [n_batches], the caller's exclusive prefixes of n_nodes and n_edges */
+TG_API int tg_ns_full_emit(const tg_graph *csc, const tg_ns_full_in *in, int64_t n_batches, int64_t id_bound,
+                           const int64_t *node_off, const int64_t *edge_off, int64_t *nodes_out, int64_t *rows, int64_t *cols,
+                           int64_t *edge_index, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- GraphSAINT's random-walk sampler: a SUBGRAPH per mini-batch (PyG's GraphSAINTRandomWalkSampler) ---------------------
  * tg_saint_rw_nodes: one launch takes G = n_batches mini-batches of B = batch_size roots (roots: device [G, B]); every
  * root walks T = walk_length >= 1 uniform steps over csr.  Per mini-batch g: walker i starts at roots[g][i] and its

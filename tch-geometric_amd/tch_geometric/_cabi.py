@@ -50,7 +50,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_saint_rw_capacity", "tg_saint_rw_form", "tg_saint_rw_workspace_bytes", "tg_saint_rw_nodes",
            "tg_saint_coverage_add", "tg_saint_norm", "tg_ns_hop_labor_workspace_bytes", "tg_ns_hop_labor",
            "tg_ns_hop_labor_long_column", "tg_pinsage_hop_workspace_bytes", "tg_pinsage_hop",
-           "tg_cluster_workspace_bytes", "tg_cluster_count", "tg_cluster_emit"]
+           "tg_cluster_workspace_bytes", "tg_cluster_count", "tg_cluster_emit",
+           "tg_ns_full_workspace_bytes", "tg_ns_full_count", "tg_ns_full_emit"]
 
 
 class TgGraph(C.Structure):
@@ -1559,6 +1560,121 @@ def cluster_status_check(status, who):
             t for bit, t in ((1, "a batch with repeated clusters exceeds the chunk bound, or has 2^31 nodes or more"),
                              (2, "a cluster id outside [0, n_parts)"),
                              (4, "a partptr pair that is inverted or leaves the graph")) if status & bit)))
+
+
+class TgNsFullIn(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("node_ptr", C.c_void_p), ("max_nodes", C.c_int64), ("node_cap", C.c_int64),
+                ("chunk_cap", C.c_int64)]
+
+
+_P, _I64 = C.c_void_p, C.c_int64
+lib.tg_ns_full_workspace_bytes.argtypes = [_P, _P, _I64, _I64, _P, _P]
+lib.tg_ns_full_count.argtypes = [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _P]
+lib.tg_ns_full_emit.argtypes = [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _P]
+for _f in (lib.tg_ns_full_workspace_bytes, lib.tg_ns_full_count, lib.tg_ns_full_emit):
+    _f.restype = C.c_int
+NS_FULL_MAX_NODES = 1 << 30          # tchgeo.h: max_nodes and node_cap
+NS_FULL_MAX_CHUNKS = 1 << 31
+
+
+def _ns_full_sizes(who, graph, id_bound, max_nodes, node_cap, chunk_cap, n_batches):
+    """the refusals of the full-neighbour pair that need no device, as ValueError"""
+    id_bound, max_nodes, node_cap, chunk_cap, n_batches = (int(x) for x in (id_bound, max_nodes, node_cap, chunk_cap, n_batches))
+    if not 0 <= max_nodes <= NS_FULL_MAX_NODES:
+        raise ValueError("%s: max_nodes = %d outside [0, 2^30]" % (who, max_nodes))
+    if not max_nodes <= node_cap <= NS_FULL_MAX_NODES:
+        raise ValueError("%s: node_cap = %d outside [max_nodes = %d, 2^30]" % (who, node_cap, max_nodes))
+    if chunk_cap > NS_FULL_MAX_CHUNKS:
+        raise ValueError("%s: chunk_cap = %d above 2^31" % (who, chunk_cap))
+    if not 0 <= n_batches < 2 ** 31:
+        raise ValueError("%s: n_batches = %d outside [0, 2^31)" % (who, n_batches))
+    if id_bound < max(1, graph.n_major):
+        raise ValueError("%s: id_bound = %d below max(1, n_major = %d)" % (who, id_bound, graph.n_major))
+    return id_bound, max_nodes, node_cap, chunk_cap, n_batches
+
+
+def ns_full_workspace_bytes(graph, id_bound, max_nodes, node_cap, chunk_cap, n_batches):
+    """-> (bytes, bytes_min): the workspace of the full-neighbour pair for n_batches batches at once (n_batches * bytes_min)
+    and for one batch; graph: a tg_graph view (only n_major and n_edges are read).  No device is touched."""
+    si = TgNsFullIn(None, None, int(max_nodes), int(node_cap), int(chunk_cap))
+    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_ns_full_workspace_bytes(C.byref(graph), C.byref(si), int(id_bound), int(n_batches), C.byref(nbytes),
+                                         C.byref(bmin)))
+    return nbytes.value, bmin.value
+
+
+class NsFull:
+    """The full-neighbour pair (tg_ns_full_count / tg_ns_full_emit) for up to n_batches frontiers of at most max_nodes nodes
+    each over `graph` (a CSC view): a table for node_cap distinct nodes and room for chunk_cap chunks per batch (<= 0: the
+    bound of a frontier of distinct nodes).  Owns what the passes share: n_nodes, n_edges, chunks [n_batches each] and
+    status [1] in one tensor `state` (a loader reads it back in one copy) and the workspace (`ws`: an int64 tensor of an
+    earlier launch, reused when large enough).  count(nodes, node_ptr) then emit(...) run on the current stream over the
+    node_ptr.numel() - 1 lists; neither synchronises.  emit() consumes the workspace: count() again before another."""
+
+    def __init__(self, graph, id_bound, max_nodes, node_cap, chunk_cap, n_batches, device, ws=None):
+        self.id_bound, self.max_nodes, self.node_cap, self.chunk_cap, self.n_batches = _ns_full_sizes(
+            "NsFull", graph, id_bound, max_nodes, node_cap, chunk_cap, n_batches)
+        self.graph, self.device = graph, torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.struct = TgNsFullIn(None, None, self.max_nodes, self.node_cap, self.chunk_cap)
+        need = ns_full_workspace_bytes(graph, self.id_bound, self.max_nodes, self.node_cap, self.chunk_cap, self.n_batches)[0]
+        if ws is None or ws.numel() * 8 < need or ws.device != self.device:
+            ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=self.device)
+        self.ws = ws
+        G = self.n_batches
+        self.state = torch.zeros(3 * G + 1, dtype=torch.int64, device=self.device)
+        self.n_nodes, self.n_edges, self.chunks = self.state[:G], self.state[G:2 * G], self.state[2 * G:3 * G]
+        self.status = self.state[-1:].view(torch.int32)[:1]
+        self.live = None
+
+    def count(self, nodes, node_ptr):
+        """pass 1 over the lists nodes[node_ptr[b] : node_ptr[b + 1]] -> (n_nodes, n_edges, chunks [live each], status [1]),
+        device tensors; the caller reads them back"""
+        for name, t in (("nodes", nodes), ("node_ptr", node_ptr)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError("NsFull.count: %s must be a contiguous flat int64 tensor" % name)
+            if t.device != self.device:
+                raise ValueError("NsFull.count: %s is on %s, the launch on %s" % (name, t.device, self.device))
+        live = node_ptr.numel() - 1
+        if not 0 <= live <= self.n_batches:
+            raise ValueError("NsFull.count: node_ptr names %d lists, outside [0, %d]" % (live, self.n_batches))
+        self.live, self._lists = live, (nodes, node_ptr)
+        self.struct.nodes = nodes.data_ptr() if nodes.numel() else None
+        self.struct.node_ptr = node_ptr.data_ptr()
+        if self.max_nodes and not nodes.numel():
+            self.struct.nodes = self.ws.data_ptr()       # never read: every list is empty
+        self.state[-1:].zero_()
+        check(lib.tg_ns_full_count(C.byref(self.graph), C.byref(self.struct), live, self.id_bound, ptr(self.n_nodes),
+                                   ptr(self.n_edges), ptr(self.chunks), ptr(self.status), ptr(self.ws), self.ws.numel() * 8,
+                                   stream_ptr(self.device)))
+        return self.n_nodes[:live], self.n_edges[:live], self.chunks[:live], self.status
+
+    def emit(self, node_off, edge_off, nodes_out, rows, cols, edge_index):
+        """pass 2 into the caller's flat arrays; node_off / edge_off: device [live], the exclusive prefixes of n_nodes /
+        n_edges; nodes_out may be None"""
+        if self.live is None:
+            raise ValueError("NsFull.emit: no counted launch (emit() consumes the workspace: count() first)")
+        for name, t in (("node_off", node_off), ("edge_off", edge_off), ("nodes_out", nodes_out), ("rows", rows),
+                        ("cols", cols), ("edge_index", edge_index)):
+            if t is None and name in ("nodes_out", "node_off") and nodes_out is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("NsFull.emit: %s must be a contiguous int64 tensor on %s" % (name, self.device))
+        for name, t in (("node_off", node_off), ("edge_off", edge_off)):
+            if t is not None and t.numel() < self.live:
+                raise ValueError("NsFull.emit: %s is shorter than the %d counted lists" % (name, self.live))
+        live, self.live = self.live, None
+        check(lib.tg_ns_full_emit(C.byref(self.graph), C.byref(self.struct), live, self.id_bound, ptr(node_off),
+                                  ptr(edge_off), ptr(nodes_out), ptr(rows), ptr(cols), ptr(edge_index), ptr(self.ws),
+                                  self.ws.numel() * 8, stream_ptr(self.device)))
+
+
+def ns_full_status_check(status, who):
+    """the status word of tg_ns_full_count after its read-back: bit 1 raises (bit 0, a refused batch, is the caller's to
+    answer with a larger workspace)"""
+    if status & 2:
+        raise RuntimeError("%s: status %d (a frontier node outside the graph)" % (who, status))
 
 
 class TgNsInducedGroupedIn(C.Structure):

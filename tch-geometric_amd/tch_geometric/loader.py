@@ -30,6 +30,8 @@ grouped dedup.
 ClusterData / ClusterLoader hand out Cluster-GCN mini-batches: the union of `batch_size` clusters of a fixed node partition
 with every edge of the graph between its nodes (tg_cluster_count / tg_cluster_emit: a range table in LDS instead of the
 induced pair's hash table).
+FullNeighborLoader hands out blocks that hold EVERY in-edge of their destinations (layer-wise inference; PyG's
+num_neighbors=[-1]): tg_ns_full_count / tg_ns_full_emit, one read-back per layer and launch.
 """
 from typing import Iterator, List, Optional
 
@@ -2236,6 +2238,217 @@ class PinSAGELoader(_Loader):
             yield self._launch(nodes[start:start + G * width].reshape(G, width), batch0 + start // self.batch_size)
 
     def __iter__(self) -> Iterator[PinSAGEBatch]:
+        for sb in self.super_batches():
+            yield from sb
+
+
+class FullNeighborBlock:
+    """One layer of a full-neighbour mini-batch: `n_id` (the source nodes; its first `n_dst` entries are the destination
+    nodes, the previous frontier in order), `edge_index` [2, m] (row = position in n_id of the source, col = position of the
+    destination; EVERY in-edge of every destination, in (destination, CSC offset) order) and `e_id` [m], the edges' columns
+    in data.edge_index: data.edge_index[:, e_id] == n_id[edge_index]."""
+    __slots__ = ("n_id", "n_dst", "edge_index", "e_id")
+
+    def __init__(self, n_id, n_dst, edge_index, e_id):
+        self.n_id, self.n_dst, self.edge_index, self.e_id = n_id, n_dst, edge_index, e_id
+
+    @property
+    def num_src_nodes(self):
+        return self.n_id.numel()
+
+    @property
+    def num_edges(self):
+        return self.e_id.numel()
+
+
+class FullNeighborBatch:
+    """Mini-batch j of a FullNeighborSuperBatch: `blocks` outermost first as in DGL ([block_{L-1}, ..., block_0]), `n_id` =
+    the outermost block's source nodes, the node attributes of the data gathered by n_id, `batch_size` and `input_nodes`
+    (the seeds = the first `batch_size` entries of n_id)."""
+
+    def __init__(self, sb, j):
+        self.batch_size = sb.seed_ptr[j + 1] - sb.seed_ptr[j]
+        self.input_nodes = sb.input_nodes[sb.seed_ptr[j]:sb.seed_ptr[j + 1]]
+        self.blocks = []
+        for lay in reversed(sb.layers):
+            n0, n1 = lay["src_ptr"][j], lay["src_ptr"][j + 1]
+            e0, e1 = lay["edge_ptr"][j], lay["edge_ptr"][j + 1]
+            self.blocks.append(FullNeighborBlock(lay["n_id"][n0:n1], lay["dst_ptr"][j + 1] - lay["dst_ptr"][j],
+                                                 lay["edge_index"][:, e0:e1], lay["e_id"][e0:e1]))
+        self.n_id = self.blocks[0].n_id
+        n0, n1 = sb.node_ptr[j], sb.node_ptr[j + 1]
+        self._attrs = {k: v[n0:n1] for k, v in sb.node_attrs.items()}
+
+    @property
+    def num_nodes(self):
+        return self.n_id.numel()
+
+    def __getattr__(self, name):
+        attrs = self.__dict__.get("_attrs", {})
+        if name in attrs:
+            return attrs[name]
+        raise AttributeError(name)
+
+
+class FullNeighborSuperBatch:
+    """The mini-batches of ONE launch as flat batch-major device tensors with python pointer lists: per layer l `layers[l]` =
+    dict(n_id, src_ptr, dst_ptr, edge_index (numbered inside each mini-batch), e_id, edge_ptr); `n_id` / `node_ptr` of the
+    last layer, `node_attrs` gathered once by it; `input_nodes` / `seed_ptr`."""
+
+    def __len__(self):
+        return len(self.node_ptr) - 1
+
+    def __getitem__(self, j):
+        if j < 0:
+            j += len(self)
+        if not 0 <= j < len(self):
+            raise IndexError(j)
+        return FullNeighborBatch(self, j)
+
+    def __iter__(self):
+        for j in range(len(self)):
+            yield FullNeighborBatch(self, j)
+
+
+class FullNeighborLoader(_Loader):
+    """Every in-edge per layer: the loader of layer-wise inference (PyG's NeighborLoader(num_neighbors=[-1] * L), DGL's
+    MultiLayerFullNeighborSampler(L)) over tg_ns_full_count / tg_ns_full_emit (csrc/ns_full.hip).  Nothing is sampled:
+    a mini-batch is a function of the graph and its seeds.
+
+    Mini-batch j with distinct seeds F_0, for layer l = 0 .. L-1: one pair of calls runs over the flat concatenation of the
+    launch's frontiers F_l (one list per mini-batch).  F_{l+1} = F_l followed by the sources of its in-edges that are not
+    in it yet, in order of first occurrence in (destination, CSC offset) order; ALL of F_{l+1} is the next layer's
+    frontier.  Block l (FullNeighborBlock) holds n_id = F_{l+1}, n_dst = |F_l|, edge_index [2, m] and e_id with
+    data.edge_index[:, e_id] == n_id[edge_index]; every destination has its whole in-degree.  A mini-batch
+    (FullNeighborBatch) carries `blocks` outermost first, `n_id` = F_L, the node attributes of `data` gathered by n_id
+    (tg_gather_rows), `batch_size` and `input_nodes`; super_batches() hands out whole launches (`prefetch` mini-batches)
+    as flat tensors with pointer lists.
+
+    Host synchronisation: ONE read-back per layer and launch (node counts, edge counts, chunk counts and the status word in
+    one copy, between the two passes), on the caller's stream.  The table and chunk capacities of a layer are kept from
+    launch to launch; a launch that needs more than the kept capacity repeats the layer's first pass ONCE, sized by the
+    exact counts it has just read plus a quarter (a second read-back for that layer; `growths` counts them).  A mini-batch whose layer has 2^31
+    edges or more, or more than 2^30 nodes, raises RuntimeError naming the mini-batch.
+
+    Out of scope: a -1 inside NeighborLoader's num_neighbors and mixed fan-outs such as [-1, 10] (NeighborLoader is
+    unchanged and keeps refusing fan-outs <= 0 and > 255), temporal filters, typed graphs.  Duplicate input nodes inside
+    one mini-batch are refused in the constructor (with shuffle=True any duplicate); everything that can be refused is
+    refused before any device work.  Shuffling is a function of (seed, epoch)."""
+
+    def __init__(self, data, num_layers: int = 1, input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
+                 prefetch: int = 16, shuffle: bool = False, drop_last: bool = False, seed: int = 0, device="cuda"):
+        L, B = int(num_layers), int(batch_size)
+        if not 1 <= L <= _cabi.TG_MAX_HOPS:
+            raise ValueError("num_layers must be in 1..%d, got %r" % (_cabi.TG_MAX_HOPS, num_layers))
+        if B < 1:
+            raise ValueError("batch_size must be at least 1, got %r" % (batch_size,))
+        if int(prefetch) < 1:
+            raise ValueError("prefetch must be at least 1, got %r" % (prefetch,))
+        if _is_hetero(data):
+            raise ValueError("FullNeighborLoader takes a homogeneous graph (typed graphs are out of scope)")
+        N = _num_nodes(data)
+        if not 1 <= N <= 2 ** 31:
+            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
+        nodes = torch.arange(N) if input_nodes is None else input_nodes.detach().cpu().reshape(-1).to(torch.int64)
+        if nodes.numel() and (int(nodes.min()) < 0 or int(nodes.max()) >= N):
+            raise IndexError("input_nodes outside [0, %d)" % N)
+        if input_nodes is not None and nodes.numel():
+            # a frontier lists a node once: two equal seeds in one mini-batch would be two destinations with one column
+            batch_of = torch.zeros_like(nodes) if shuffle else torch.arange(nodes.numel()) // B
+            key = torch.sort(batch_of * N + nodes).values
+            if bool((key[1:] == key[:-1]).any()):
+                raise ValueError("input_nodes holds a node twice " + ("(shuffle=True: anywhere)" if shuffle else
+                                                                      "inside one mini-batch"))
+        self.data, self.num_layers, self.batch_size = data, L, B
+        self.prefetch, self.seed = int(prefetch), int(seed)
+        self.shuffle, self.drop_last = bool(shuffle), bool(drop_last)
+        self.device = torch.device(device)
+        self.n_nodes = N
+        self.input_nodes = nodes.to(self.device)
+        self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
+        E = int(data.edge_index.shape[1])
+        shadows = dict(indices32=self.row_indices.to(torch.int32), ptrs32=self.col_ptrs.to(torch.int32)) if E < 2 ** 31 else {}
+        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, **shadows)
+        self._node_attrs = [(k, v.to(self.device)) for k, v in _tensor_items(data) if _attr_kind(k, v, N, E) == "node"]
+        # the kept capacities per layer (distinct nodes, chunks per mini-batch): a guess from the mean degree that grows
+        mean = (E + N - 1) // N
+        self._node_cap = [min(_cabi.NS_FULL_MAX_NODES, B * (2 + 2 * mean))] * L
+        self._chunk_cap = [2 * B + self._node_cap[0] // 512] * L
+        self._ws = None
+        self.growths = 0
+        self.epoch = 0
+
+    def _layer(self, l: int, frontier: Tensor, ptr: List[int], first_batch: int):
+        """the pair over the launch's lists -> (host n_out, host m, the counted NsFull)"""
+        dev, G = self.device, len(ptr) - 1
+        node_ptr = torch.tensor(ptr, dtype=torch.int64, device=dev)
+        max_nodes = max(ptr[g + 1] - ptr[g] for g in range(G))
+        for attempt in (0, 1):
+            node_cap, chunk_cap = max(self._node_cap[l], max_nodes), max(self._chunk_cap[l], 1)
+            op = _cabi.NsFull(self._graph, self.n_nodes, max_nodes, node_cap, chunk_cap, G, dev, ws=self._ws)
+            self._ws = op.ws
+            op.count(frontier, node_ptr)
+            host = op.state.tolist()                      # the layer's ONE read-back (a second one after a growth)
+            n_out, m, chunks, status = host[:G], host[G:2 * G], host[2 * G:3 * G], host[-1] & 0xFFFFFFFF
+            _cabi.ns_full_status_check(status, type(self).__name__)
+            if not status & 1:
+                return n_out, m, op
+            for g in range(G):
+                n = ptr[g + 1] - ptr[g]
+                if m[g] >= 2 ** 31 or n + min(m[g], self.n_nodes) > _cabi.NS_FULL_MAX_NODES:
+                    raise RuntimeError("%s: layer %d of mini-batch %d has %d edges over %d nodes: past the limits of one "
+                                       "batch (2^31 edges, 2^30 nodes); use a smaller batch_size" %
+                                       (type(self).__name__, l, first_batch + g, m[g], n))
+            if attempt:
+                raise RuntimeError("%s: layer %d still refused after growing to the sizes it reported" % (type(self).__name__, l))
+            # what the launch needs, and a quarter more: the next launch's largest mini-batch is rarely the same size
+            need = max(ptr[g + 1] - ptr[g] + min(m[g], self.n_nodes) for g in range(G))
+            self._node_cap[l] = min(_cabi.NS_FULL_MAX_NODES, need + need // 4)
+            self._chunk_cap[l] = min(_cabi.NS_FULL_MAX_CHUNKS, max(chunks) + max(chunks) // 4)
+            self.growths += 1
+
+    def _launch(self, seeds: Tensor, first_batch: int) -> FullNeighborSuperBatch:
+        """seeds [G, width]: mini-batches first_batch .. first_batch + G - 1 of the run"""
+        dev = self.device
+        G, width = seeds.shape
+        o = dict(dtype=torch.int64, device=dev)
+        sb = FullNeighborSuperBatch()
+        sb.n_layers = self.num_layers
+        sb.input_nodes = frontier = seeds.reshape(-1).contiguous()
+        sb.seed_ptr = ptr = [g * width for g in range(G + 1)]
+        sb.layers = []
+        for l in range(self.num_layers):
+            n_out, m, op = self._layer(l, frontier, ptr, first_batch)
+            nptr, eptr = [0], [0]
+            for x, y in zip(n_out, m):
+                nptr.append(nptr[-1] + x)
+                eptr.append(eptr[-1] + y)
+            node_off = torch.cumsum(op.n_nodes, 0) - op.n_nodes
+            edge_off = torch.cumsum(op.n_edges, 0) - op.n_edges
+            n_id = torch.empty(nptr[-1], **o)
+            rc = torch.empty((2, eptr[-1]), **o)
+            offs = torch.empty(eptr[-1], **o)
+            op.emit(node_off, edge_off, n_id, rc[0], rc[1], offs)
+            sb.layers.append(dict(n_id=n_id, src_ptr=nptr, dst_ptr=ptr, edge_index=rc, e_id=self.perm[offs], edge_ptr=eptr))
+            frontier, ptr = n_id, nptr
+        sb.n_id, sb.node_ptr = frontier, ptr
+        sb.node_attrs = {k: _rows_of(v, frontier) for k, v in self._node_attrs}
+        return sb
+
+    def super_batches(self) -> Iterator[FullNeighborSuperBatch]:
+        """The epoch as launches of up to `prefetch` mini-batches."""
+        nodes = self.input_nodes
+        epoch = self.epoch                               # captured: a second iterator is the next epoch
+        self.epoch += 1
+        batch0 = epoch * len(self)
+        if self.shuffle:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(self.seed * 1000003 + epoch)
+            nodes = nodes[torch.randperm(nodes.numel(), device=self.device, generator=gen)]
+        for start, G, width in _epoch_plan(nodes.numel(), self.batch_size, self.prefetch, self.drop_last):
+            yield self._launch(nodes[start:start + G * width].reshape(G, width), batch0 + start // self.batch_size)
+
+    def __iter__(self) -> Iterator[FullNeighborBatch]:
         for sb in self.super_batches():
             yield from sb
 
