@@ -242,6 +242,179 @@ __global__ void __launch_bounds__(WIN_PART_THREADS) win_scatter8_tiled_kernel(co
     }
 }
 
+// The tiled pass with a CARRY per bucket: whole aligned 64-byte chunks only.  A bucket's items of one tile (~85 bytes at an
+// arbitrary 8-byte alignment) touch 2-3 chunks, one or two of them partly, and the rows' open destination lines (rows x
+// buckets x 128 B = 34 MB) do not wait in the L2s for the next tile to complete them.  Here the workgroup keeps, per
+// bucket, the items beyond the last 64-byte boundary of the DESTINATION ADDRESS (at most 7) in LDS for its next tile and
+// writes [cur, last boundary) only; after the row's last batch the carries are flushed.  The partial chunks left are one
+// at the head and one at the tail of each (row, bucket) run.
+// The write-out runs over SLOTS: bucket after bucket, a bucket's slots start at the phase of its destination inside a
+// chunk (the head of a run pads up to 7 slots once), so slot t goes to an address = t (mod 8 elements) and each aligned
+// group of 8 lanes of a store instruction covers one whole chunk.  Pad + carried slots of a bucket are at most 7.
+// A workgroup barrier that orders LDS only: __syncthreads() also waits for every global load and store of the wavefront
+// (one counter covers both on gfx9), which ends a prefetch at the next barrier and makes each tile wait for its stores.
+__device__ __forceinline__ void win_lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+constexpr int WIN_SC_CARRY = 8; // carry slots per bucket (at most 7 are held)
+constexpr int WIN_SC_CARRY_TILE = 4096; // items per tile (2 048, three workgroups per CU: slower, profiles/sort_chunks)
+__host__ __device__ inline size_t win_scatter8_carry_lds(int tile, int n_buckets) {
+    const size_t tables = (size_t)7 * n_buckets * sizeof(uint32_t) + ((size_t)tile + (size_t)(WIN_SC_CARRY - 1) * n_buckets) * sizeof(uint16_t);
+    return ((tables + 15) & ~(size_t)15) + ((size_t)tile + (size_t)WIN_SC_CARRY * n_buckets) * sizeof(WinItem8);
+}
+template <int TILE>
+__global__ void __launch_bounds__(WIN_PART_THREADS) win_scatter8_carry_kernel(const WinParams p) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ uint32_t wtot[WIN_PART_THREADS / 64];
+    const int nb = p.n_buckets, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t *cur = reinterpret_cast<uint32_t *>(smem); // first position of the bucket's run that is not written yet
+    uint32_t *ccnt = cur + nb;                          // items in the carry: they belong to cur .. cur + ccnt - 1
+    uint32_t *cnt = ccnt + nb;                          // the tile's items per bucket
+    uint32_t *lo = cnt + nb;                            // the bucket's first slot of the write-out
+    uint32_t *meta = lo + nb;                           // elements written out of this tile | carried items before it << 16
+    uint32_t *gb = meta + nb;                           // slot t goes to sorted[gb + t]
+    uint32_t *soff = gb + nb;                           // slot t behind the carried ones comes from sitem[soff + t]
+    uint16_t *skey = reinterpret_cast<uint16_t *>(soff + nb);
+    WinItem8 *sitem = reinterpret_cast<WinItem8 *>(
+        smem + ((((size_t)7 * nb * sizeof(uint32_t) + ((size_t)TILE + (size_t)(WIN_SC_CARRY - 1) * nb) * sizeof(uint16_t)) + 15) & ~(size_t)15));
+    WinItem8 *carry = sitem + TILE;
+    const WinItem8 *items = static_cast<const WinItem8 *>(p.items_in);
+    WinItem8 *sorted = static_cast<WinItem8 *>(p.items_sorted);
+    const uint32_t a0 = (uint32_t)(((uintptr_t)sorted >> 3) & 7u); // position i starts a chunk when (i + a0) % 8 == 0
+    const uint32_t *row = p.hist + (size_t)blockIdx.x * nb;
+    for (int i = tid; i < nb; i += blockDim.x) {
+        cur[i] = p.base[i] + row[i];
+        ccnt[i] = 0;
+        cnt[i] = 0;
+    }
+    constexpr int U = TILE / WIN_PART_THREADS;
+    // The tiles of the row's batches, one after the other; the NEXT tile's items and keys are loaded into registers while
+    // this one goes through LDS (the barriers order LDS only -- win_lds_barrier -- so the loads stay in flight across them:
+    // nothing in global memory is written and read again inside this kernel).  The frontier of the batch after the next is
+    // read a tile ahead as well, so that no load waits for another.
+    const int64_t b_end = p.b0 + p.n_batches;
+    auto frontier = [&](int64_t b) { // the frontier of the hop about to be gathered
+        if (b >= b_end) return (int64_t)0;
+        const WinState st = p.state[b];
+        return st.end - st.begin;
+    };
+    int64_t pb = p.b0 + blockIdx.x, pt0 = 0, pn = frontier(pb); // the next tile to load: batch, first item, the batch's items
+    int64_t ab = pb + gridDim.x, an = frontier(ab);             // the batch after it
+    WinItem8 nit[U];
+    uint32_t nkey[U];
+    int nnt;
+    auto fetch = [&]() {
+        while (pb < b_end && pt0 >= pn) { // the batch is done (or empty): on to the next
+            pb = ab;
+            pt0 = 0;
+            pn = an;
+            ab += gridDim.x;
+            an = frontier(ab);
+        }
+        nnt = pb < b_end ? (int)min((int64_t)TILE, pn - pt0) : 0;
+        const int64_t at = pb * p.item_pitch + pt0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = u * WIN_PART_THREADS + tid;
+            nkey[u] = 0xffffffffu;
+            nit[u] = WinItem8{0u, 0u};
+            if (j < nnt) {
+                nit[u] = items[at + j];
+                nkey[u] = p.item_keys[at + j]; // found once, by whoever counted the item
+            }
+        }
+        pt0 += TILE;
+    };
+    fetch();
+    win_lds_barrier(); // the cursors and the zeroed counters
+    while (nnt) {
+        {
+            WinItem8 it[U];
+            uint32_t key[U], rk[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                it[u] = nit[u];
+                key[u] = nkey[u];
+            }
+            fetch();
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (key[u] != 0xffffffffu) rk[u] = atomicAdd(&cnt[key[u]], 1u);
+            win_lds_barrier();
+            uint32_t n_slots;
+            { // per bucket (nb <= the workgroup's threads): what leaves now, where its slots start, what stays
+                uint32_t c = 0, cc = 0, wr = 0, n_out = 0, ph = 0;
+                if (tid < nb) {
+                    c = cnt[tid];
+                    cnt[tid] = 0; // for the next tile: its counting starts three barriers from here
+                    cc = ccnt[tid];
+                    wr = cur[tid];
+                    const uint32_t avail = cc + c, rem = (wr + avail + a0) & 7u; // rem: elements behind the run's last boundary
+                    n_out = avail > rem ? avail - rem : 0u;                      // 0: no boundary inside (wr, wr + avail]
+                    ph = n_out ? (wr + a0) & 7u : 0u;
+                }
+                const uint32_t n_new = n_out ? n_out - cc : 0u; // a write-out takes every carried item along
+                const uint32_t both = ((ph + n_out) << 16) | n_new; // slots (a multiple of 8) | the tile's own items written out
+                const uint32_t incl = wave_inclusive_scan(both);
+                if (lane == 63) wtot[wave] = incl;
+                win_lds_barrier();
+                uint32_t before = 0, all = 0;
+                for (int w = 0; w < WIN_PART_THREADS / 64; ++w) {
+                    if (w < wave) before += wtot[w];
+                    all += wtot[w];
+                }
+                n_slots = all >> 16;
+                if (tid < nb) {
+                    const uint32_t excl = before + incl - both, pad0 = excl >> 16, l = pad0 + ph;
+                    lo[tid] = l;
+                    meta[tid] = n_out | (cc << 16);
+                    gb[tid] = wr - l;
+                    soff[tid] = (excl & 0xffffu) - cc - l;
+                    cur[tid] = wr + n_out;
+                    ccnt[tid] = cc + c - n_out;
+                    if (n_out) {
+                        for (uint32_t i = 0; i < ph; ++i) skey[pad0 + i] = 0xffffu;
+                        for (uint32_t i = 0; i < cc; ++i) skey[l + i] = (uint16_t)tid;
+                    }
+                }
+            }
+            win_lds_barrier();
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (key[u] != 0xffffffffu) {
+                    const uint32_t m = meta[key[u]], q = (m >> 16) + rk[u]; // place in the bucket's stream: carried items first
+                    if (q < (m & 0xffffu)) {
+                        const uint32_t t = lo[key[u]] + q;
+                        sitem[soff[key[u]] + t] = it[u];
+                        skey[t] = (uint16_t)key[u];
+                    }
+                }
+            win_lds_barrier();
+            for (uint32_t t = tid; t < n_slots; t += WIN_PART_THREADS) {
+                const uint32_t k = skey[t];
+                if (k != 0xffffu) {
+                    const uint32_t q = t - lo[k];
+                    sorted[gb[k] + t] = q < (meta[k] >> 16) ? carry[k * WIN_SC_CARRY + q] : sitem[soff[k] + t];
+                }
+            }
+            win_lds_barrier();
+#pragma unroll
+            for (int u = 0; u < U; ++u) // what lies behind the last boundary waits in the carry (the old one has left or stays in front)
+                if (key[u] != 0xffffffffu) {
+                    const uint32_t m = meta[key[u]], q = (m >> 16) + rk[u];
+                    if (q >= (m & 0xffffu)) carry[key[u] * WIN_SC_CARRY + q - (m & 0xffffu)] = it[u];
+                }
+        }
+    }
+    win_lds_barrier();
+    for (int k = tid >> 3; k < nb; k += WIN_PART_THREADS >> 3) { // the tails: 8 lanes per bucket
+        const uint32_t j = (uint32_t)tid & 7u;
+        if (j < ccnt[k]) sorted[cur[k] + j] = carry[k * WIN_SC_CARRY + j];
+    }
+}
+
 // the histogram as a pass of its own (hops beyond the first: their items come from the emit kernel, which is not persistent)
 __global__ void __launch_bounds__(WIN_PART_THREADS) win_hist8_kernel(const WinParams p) {
     extern __shared__ __align__(16) unsigned char smem[];

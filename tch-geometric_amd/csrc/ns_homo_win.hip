@@ -1317,7 +1317,26 @@ static int win_run_staged(WinParams p, const tg_graph *csc, int64_t n_batches, c
             clk.mark("scans", h, stream);
             {
                 static const int tiled = win_env_int("TG_WIN_SCATTER_TILED", 1);
-                if (tiled && p.n_buckets <= WIN_PART_THREADS && win_scatter8_tiled_lds(p.n_buckets, p.n_windows) <= 64 * 1024)
+                // the tiled pass with per-bucket carries (whole 64-byte chunks only); 0: the plain tiled pass (A/B runs).
+                // 264 buckets: 69 KB of LDS, two workgroups per CU -- beyond the 64 KB a kernel gets unasked; where the device
+                // gives a workgroup less, the plain tiled pass runs
+                static const int carry = win_env_int("TG_WIN_SCATTER_CARRY", 1);
+                const size_t clds = win_scatter8_carry_lds(WIN_SC_CARRY_TILE, p.n_buckets);
+                const size_t ccap = std::max<size_t>(64 * 1024, std::min<size_t>((size_t)std::max(dl.per_block, 0), 128 * 1024));
+                if (tiled && carry && p.n_buckets <= WIN_PART_THREADS && clds <= ccap) {
+                    if (clds > 64 * 1024) {
+                        static int raised_on = -1; // per device
+                        int dev = 0;
+                        TG_HIP(hipGetDevice(&dev));
+                        if (raised_on != dev) {
+                            TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&win_scatter8_carry_kernel<WIN_SC_CARRY_TILE>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ccap));
+                            raised_on = dev;
+                        }
+                    }
+                    hipLaunchKernelGGL(win_scatter8_carry_kernel<WIN_SC_CARRY_TILE>, dim3((unsigned)p.n_rows), dim3(WIN_PART_THREADS), clds,
+                                       ps, p);
+                } else if (tiled && p.n_buckets <= WIN_PART_THREADS && win_scatter8_tiled_lds(p.n_buckets, p.n_windows) <= 64 * 1024)
                     hipLaunchKernelGGL(win_scatter8_tiled_kernel, dim3((unsigned)p.n_rows), dim3(WIN_PART_THREADS),
                                        win_scatter8_tiled_lds(p.n_buckets, p.n_windows), ps, p);
                 else
