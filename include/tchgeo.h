@@ -1542,6 +1542,64 @@ TG_API int tg_saint_coverage_add(const int64_t *nodes, int64_t pitch_nodes, cons
 TG_API int tg_saint_norm(const tg_graph *csc, const int64_t *node_count, const int64_t *edge_count, int64_t n_samples,
                          float *node_norm, float *edge_norm, void *stream);
 
+/* ---- GraphSAINT's node and edge samplers (PyG's GraphSAINTNodeSampler / GraphSAINTEdgeSampler) --------------------------
+ * Both write tg_saint_rw_out under tg_saint_rw_nodes' rules: G = n_batches mini-batches of B = batch_size slots, every
+ * visit has a position p < P, nodes[g] = the distinct visited ids ordered by the position of their first occurrence,
+ * counts[g * counts_stride] = their number n_unique, words past n_unique are not written, pitch_nodes >= P.
+ *   draws     slot i of mini-batch g takes ONE Philox block: w = draw(call key of (rng->seed, rng->call_id + g, tag), id = i,
+ *             d0 = 0, d1 = 0), lo = w0 | w1 << 32, hi = w2 | w3 << 32 (as tg_link_seeds splits them); every bounded pick is
+ *             floor(x * n / 2^64).  tag = TG_TAG_SAINT_NODE / TG_TAG_SAINT_EDGE.
+ * tg_saint_node_nodes: slot i picks the entry e = floor(lo * graph->n_edges / 2^64); its node indices[e] sits at position
+ *             i; P = B.  Given the CSC this picks a source with probability out-degree / E (PyG's law), given the CSR a
+ *             target with probability in-degree / E.  A value outside [0, id_bound) contributes nothing and raises bit 1
+ *             (value 2) of the caller-zeroed device word `status`.  graph->ptrs is not read.
+ * tg_saint_edge_nodes: slot i picks t = floor(lo * (n_cols + n_rows) / 2^64).
+ *               t < n_cols:  c = cols[t], k = floor(hi * deg_csc(c) / 2^64), source = csc.indices[csc.ptrs[c] + k], target = c
+ *               otherwise:   r = rows[t - n_cols], k = floor(hi * deg_csr(r) / 2^64), source = r,
+ *                            target = csr.indices[csr.ptrs[r] + k]
+ *             The source sits at position i, the target at position B + i (PyG's cat([source, target])); P = 2 B.
+ *   law       when cols / rows are exactly the non-empty columns of the CSC / rows of the CSR of one graph, the entry
+ *             (u -> v) is drawn with probability (1 / deg_in(v) + 1 / deg_out(u)) / (n_cols + n_rows): the paper's law
+ *             p_e ~ 1/deg(u) + 1/deg(v) as a mixture of "a uniform non-empty column, then a uniform entry of it" and the
+ *             same over rows -- no prefix sum or alias table over E.  Parallel entries count separately.  Draws are
+ *             INDEPENDENT, with replacement; PyG takes a Gumbel top-k (without replacement) over all E entries for every
+ *             mini-batch.  csr == NULL with n_rows == 0 is legal and gives the one-sided (column) law.
+ *   slots     a listed major outside its graph contributes nothing, never indexes ptrs and raises status bit 1 (value 2);
+ *             a listed major without entries contributes nothing and raises bit 2 (value 4); a drawn endpoint (either
+ *             one) >= id_bound raises bit 1 and the slot contributes NEITHER end.
+ * form: 0 auto, 1 LDS (one workgroup draws and dedups one mini-batch in LDS; nsu's table of 2^k >= 4P/3 slots of 8 bytes
+ * plus 2 bytes per position, sized by P so that small mini-batches share a CU; P <= 12 288; no workspace), 2 flat (any
+ * P <= 2^30; visit words and tables in `workspace`: bytes = n_batches * bytes_min runs all mini-batches at once, anything
+ * from bytes_min up runs them in rounds).  Both forms write identical words.  tg_saint_ne_form / _workspace_bytes speak in
+ * positions P (B, or 2 B for the edge sampler): lds_limit_bytes > 0 replaces the device's limit (no device is touched); a
+ * forced form asks no device either.
+ * Limits: ids below 2^31 (id_bound > 2^31: TG_ERR_UNSUPPORTED), P <= 2^30; ptrs32 / indices32 are used when given, with
+ * equal words.  Refused with TG_ERR_INVALID before any launch: null graph / in / rng / out / nodes / counts / status, null
+ * indices of a graph with entries, null ptrs of csc / csr, a list without its graph or null with entries, negative sizes,
+ * id_bound < 1, B < 0, n_edges == 0 (node) or n_cols + n_rows == 0 (edge) with B > 0, a short pitch, counts_stride < 1,
+ * an unknown form, a forced form 1 that does not fit, a short or misaligned (8 bytes) workspace.  G = 0 or B = 0 launches
+ * nothing.  The calls do not synchronise, allocate or read back. */
+#define TG_TAG_SAINT_NODE 16u
+#define TG_TAG_SAINT_EDGE 17u
+typedef struct {
+    const tg_graph *csc;   /* columns = targets: deg_csc(c) = in-degree                   */
+    const int64_t *cols;   /* device [n_cols]: the columns to draw from                   */
+    int64_t n_cols;
+    const tg_graph *csr;   /* rows = sources: deg_csr(r) = out-degree; NULL with n_rows 0 */
+    const int64_t *rows;   /* device [n_rows]                                             */
+    int64_t n_rows;
+} tg_saint_edge_in;
+
+TG_API int tg_saint_ne_form(int64_t positions, int64_t lds_limit_bytes, int32_t *form, int64_t *lds_bytes);
+TG_API int tg_saint_ne_workspace_bytes(int64_t n_batches, int64_t positions, int32_t form, int64_t *bytes,
+                                       int64_t *bytes_min /* one mini-batch */);
+TG_API int tg_saint_node_nodes(const tg_graph *graph, int64_t id_bound, int64_t n_batches, int64_t batch_size,
+                               const tg_rng *rng, const tg_saint_rw_out *out, int32_t *status, void *workspace,
+                               int64_t workspace_bytes, int32_t form, void *stream);
+TG_API int tg_saint_edge_nodes(const tg_saint_edge_in *in, int64_t id_bound, int64_t n_batches, int64_t batch_size,
+                               const tg_rng *rng, const tg_saint_rw_out *out, int32_t *status, void *workspace,
+                               int64_t workspace_bytes, int32_t form, void *stream);
+
 /* ---- PinSAGE's importance sampler: random-walk neighbours (DGL's RandomWalkNeighborSampler / PinSAGESampler) ---------------
  * tg_pinsage_hop: a flat hop over a frontier, shaped like tg_ns_hop_recent.  The neighbours of a frontier vertex are the
  * vertices that R = n_walks short random walks from it visit most often; the visit counts are the weights.

@@ -20,13 +20,13 @@
 // tg_saint_coverage_add / tg_saint_norm: the counters GraphSAINT pre-samples and the two normalisation vectors.
 #include <algorithm>
 
-#include "ns_unique.h"
 #include "rw_walk.h"
+#include "saint_dedup.h"
 
 namespace tg {
 
-constexpr uint32_t SRW_NONE = 0xFFFFFFFFu; // flat form's visit word of a position nobody visited (ids are < 2^31)
-constexpr int32_t SRW_STATUS_RANGE = 2;    // status bit 1: an id outside its table (as tg_ns_induced_count's)
+constexpr uint32_t SRW_NONE = SAINT_NONE;
+constexpr int32_t SRW_STATUS_RANGE = SAINT_STATUS_RANGE;
 constexpr int SRW_NORM_CHUNK = 1024;       // CSC offsets a wavefront normalises per chunk
 
 struct SrwArgs {
@@ -85,7 +85,8 @@ __global__ void __launch_bounds__(NSU_THREADS) srw_lds_kernel(const SrwArgs a) {
             }
         }
         __syncthreads();
-        // first occurrences, ranked in position order: a thread owns a contiguous run of positions
+        // first occurrences, ranked in position order: a thread owns a contiguous run of positions (saint_dedup.h's
+        // saint_lds_rank_store, kept in line here: this kernel's code is the one its measurements were taken on)
         const int per = (n + nt - 1) / nt; // <= NSU_MAX_PER_THREAD
         const int p0 = min(n, tid * per), p1 = min(n, p0 + per);
         uint32_t first = 0;
@@ -105,35 +106,13 @@ __global__ void __launch_bounds__(NSU_THREADS) srw_lds_kernel(const SrwArgs a) {
 }
 
 // ---- flat form -------------------------------------------------------------------------------------------------------
-struct SrwBatch {
-    nsu_k32 *keys;
-    uint32_t *vals, *slot, *tile_cnt, *visit;
-    __device__ __forceinline__ SrwBatch(const SrwArgs &a, int64_t b) {
-        unsigned char *base = a.ws + b * a.batch_bytes;
-        keys = reinterpret_cast<nsu_k32 *>(base);
-        vals = reinterpret_cast<uint32_t *>(base + a.vals_off);
-        slot = reinterpret_cast<uint32_t *>(base + a.slot_off);
-        tile_cnt = reinterpret_cast<uint32_t *>(base + a.tile_off);
-        visit = reinterpret_cast<uint32_t *>(base + a.visit_off);
-    }
-};
-
-__global__ void __launch_bounds__(NSU_TILE_THREADS) srw_clear_kernel(const SrwArgs a) {
-    const SrwBatch t(a, blockIdx.y);
-    const uint32_t cap = a.cap_mask + 1;
-    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += gridDim.x * blockDim.x) {
-        t.keys[s] = nsu_empty<nsu_k32>();
-        t.vals[s] = NSU_UNSEEN;
-    }
-}
-
 // one lane per walker of the round: the visit list of its mini-batch in position order
 __global__ void __launch_bounds__(NSU_TILE_THREADS) srw_walk_kernel(const SrwArgs a) {
     const WalkProbs pr = srw_probs();
     const int64_t total = a.n_batches * a.B;
     for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = w / a.B, i = w - b * a.B;
-        uint32_t *visit = SrwBatch(a, b).visit;
+        uint32_t *visit = SaintBatch(a, b).visit;
         int64_t prev = -1, cur = a.roots[w];
         if ((uint64_t)cur >= (uint64_t)a.n_major) { // never indexes ptrs
             atomicOr(a.status, SRW_STATUS_RANGE);
@@ -148,71 +127,6 @@ __global__ void __launch_bounds__(NSU_TILE_THREADS) srw_walk_kernel(const SrwArg
             if (!dead) dead = !walk_step(a.g, ck, (uint64_t)i, (uint32_t)l, pr, true, prev, cur);
         }
     }
-}
-
-__global__ void __launch_bounds__(NSU_TILE_THREADS) srw_insert_kernel(const SrwArgs a) {
-    const int64_t n = a.P;
-    const int64_t tile0 = (int64_t)blockIdx.x * NSU_TILE;
-    const SrwBatch t(a, blockIdx.y);
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k) {
-        const int64_t p = tile0 + k * NSU_TILE_THREADS + threadIdx.x;
-        if (p < n) {
-            const uint32_t v = t.visit[p];
-            uint32_t s = 0; // nobody's visit: slot 0's value is not this position
-            if (v != SRW_NONE) {
-                s = nsu_insert<nsu_k32>(t.keys, a.cap_mask, a.hash_shift, v);
-                atomicMin(&t.vals[s], (uint32_t)p);
-            }
-            t.slot[p] = s;
-        }
-    }
-}
-
-// flags the first occurrences of a tile in their slot words and counts them
-__global__ void __launch_bounds__(NSU_TILE_THREADS) srw_flag_kernel(const SrwArgs a) {
-    __shared__ uint32_t s_wave[NSU_TILE_THREADS / 64];
-    const int64_t n = a.P;
-    const SrwBatch t(a, blockIdx.y);
-    const int64_t p0 = (int64_t)blockIdx.x * NSU_TILE + (int64_t)threadIdx.x * NSU_PER;
-    uint32_t cnt = 0;
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k) {
-        const int64_t p = p0 + k;
-        if (p < n) {
-            const uint32_t s = t.slot[p];
-            if (t.vals[s] == (uint32_t)p) {
-                t.slot[p] = s | NSU_FLAG;
-                ++cnt;
-            }
-        }
-    }
-    uint32_t total;
-    nsu_scan(cnt, s_wave, &total);
-    if (threadIdx.x == 0) t.tile_cnt[blockIdx.x] = total;
-}
-
-// names the first occurrences of a tile: rank = first occurrences in the tiles before it + the scan inside it
-__global__ void __launch_bounds__(NSU_TILE_THREADS) srw_apply_kernel(const SrwArgs a) {
-    __shared__ uint32_t s_wave[NSU_TILE_THREADS / 64];
-    const int64_t b = blockIdx.y, n = a.P;
-    const int64_t tile0 = (int64_t)blockIdx.x * NSU_TILE;
-    const SrwBatch t(a, b);
-    uint32_t before = 0, base;
-    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += NSU_TILE_THREADS) before += t.tile_cnt[i];
-    nsu_scan(before, s_wave, &base);
-    const int64_t p0 = tile0 + (int64_t)threadIdx.x * NSU_PER;
-    uint32_t first = 0;
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k)
-        if (p0 + k < n && (t.slot[p0 + k] & NSU_FLAG)) first |= 1u << k;
-    uint32_t total;
-    uint32_t rank = base + nsu_scan((uint32_t)__popc(first), s_wave, &total);
-    int64_t *nodes = a.nodes + b * a.pitch;
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k)
-        if (first & (1u << k)) nodes[rank++] = (int64_t)t.keys[t.slot[p0 + k] & ~NSU_FLAG];
-    if (tile0 + NSU_TILE >= n && threadIdx.x == 0) a.counts[b * a.counts_stride] = (int64_t)(base + total);
 }
 
 // ---- coverage counters -------------------------------------------------------------------------------------------------
@@ -286,39 +200,20 @@ __global__ void __launch_bounds__(256) srw_edge_norm_kernel(const CsrView g, int
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-struct SrwPlan {
-    int64_t P;
-    NsuPlan nsu;
-    int64_t visit_off, batch_bytes; // flat form: a mini-batch's part of the workspace
-};
+typedef SaintPlan SrwPlan;
 
 static inline int srw_plan(int64_t B, int64_t T, const char *who, SrwPlan &pl) {
     TG_REQUIRE(B >= 0, "%s: batch_size = %lld is negative", who, (long long)B);
     TG_REQUIRE(T >= 1, "%s: walk_length = %lld, at least 1 expected", who, (long long)T);
     TG_REQUIRE(T < NSU_MAX_NODES && B <= NSU_MAX_NODES / (T + 1), "%s: batch_size * (walk_length + 1) = %lld * %lld above 2^30",
                who, (long long)B, (long long)(T + 1));
-    pl.P = B * (T + 1);
-    if (const int rc = nsu_plan(pl.P, 1, who, pl.nsu)) return rc; // ids below 2^31: 32-bit keys
-    pl.visit_off = pl.nsu.batch_bytes;
-    pl.batch_bytes = pl.visit_off + nsu_r256(pl.P * 4);
-    return TG_OK;
+    return saint_plan(B * (T + 1), who, pl); // ids below 2^31: 32-bit keys
 }
 
 static int srw_launch_lds(const SrwArgs &a, const SrwPlan &pl, hipStream_t stream) {
     const int64_t dyn = pl.nsu.lds_bytes - NSU_STATIC_LDS;
-    if (dyn > 64 * 1024) { // above the default limit of a launch (the caller checked that it fits the device's)
-        // raised once per device, to the most a request that fits can ask for: every thread sets the SAME value, so threads
-        // with different requests cannot lower each other's limit, and a race only sets it twice
-        static std::atomic<int64_t> raised[64]; // zero-initialised
-        int dev = 0;
-        TG_HIP(hipGetDevice(&dev));
-        const int64_t most = nsu_device_lds_limit() - NSU_STATIC_LDS; // >= dyn: nsu_fits held
-        if (dev < 0 || dev >= 64 || raised[dev] != most) {
-            TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(srw_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)most));
-            if (dev >= 0 && dev < 64) raised[dev] = most;
-        }
-    }
+    static std::atomic<int64_t> raised[64]; // zero-initialised
+    if (const int rc = saint_raise_lds(reinterpret_cast<const void *>(srw_lds_kernel), raised, dyn)) return rc;
     const unsigned grid = (unsigned)(a.n_batches < 16384 ? a.n_batches : 16384);
     hipLaunchKernelGGL(srw_lds_kernel, dim3(grid), dim3(pl.nsu.threads), (size_t)dyn, stream, a);
     TG_LAUNCH_CHECK();
@@ -326,20 +221,10 @@ static int srw_launch_lds(const SrwArgs &a, const SrwPlan &pl, hipStream_t strea
 }
 
 static int srw_launch_flat(const SrwArgs &a, const SrwPlan &pl, hipStream_t stream) {
-    const unsigned nb = (unsigned)a.n_batches, tiles = (unsigned)pl.nsu.n_node_tiles;
-    const dim3 block(NSU_TILE_THREADS);
-    const int64_t clear_blocks = (pl.nsu.table_cap + NSU_TILE_THREADS - 1) / NSU_TILE_THREADS;
-    hipLaunchKernelGGL(srw_clear_kernel, dim3((unsigned)(clear_blocks < 1024 ? clear_blocks : 1024), nb), block, 0, stream, a);
+    if (const int rc = saint_launch_clear(a, pl, stream)) return rc;
+    hipLaunchKernelGGL(srw_walk_kernel, dim3(grid_1d(a.n_batches * a.B, NSU_TILE_THREADS)), dim3(NSU_TILE_THREADS), 0, stream, a);
     TG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(srw_walk_kernel, dim3(grid_1d(a.n_batches * a.B, NSU_TILE_THREADS)), block, 0, stream, a);
-    TG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(srw_insert_kernel, dim3(tiles, nb), block, 0, stream, a);
-    TG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(srw_flag_kernel, dim3(tiles, nb), block, 0, stream, a);
-    TG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(srw_apply_kernel, dim3(tiles, nb), block, 0, stream, a);
-    TG_LAUNCH_CHECK();
-    return TG_OK;
+    return saint_launch_dedup(a, pl, stream);
 }
 
 } // namespace tg
@@ -424,14 +309,10 @@ extern "C" int tg_saint_rw_nodes(const tg_graph *csr, const int64_t *roots, int6
         a.nodes = out->nodes + b0 * out->pitch_nodes, a.counts = out->counts + b0 * out->counts_stride;
         a.pitch = out->pitch_nodes, a.counts_stride = out->counts_stride;
         a.n_batches = std::min(round, n_batches - b0);
-        a.B = batch_size, a.T = walk_length, a.P = pl.P;
+        a.B = batch_size, a.T = walk_length;
         a.seed = rng->seed, a.call_id = rng->call_id + (uint64_t)b0;
         a.status = status;
-        a.cap_mask = (uint32_t)(pl.nsu.table_cap - 1);
-        a.hash_shift = 32u - (uint32_t)__builtin_ctzll((unsigned long long)pl.nsu.table_cap);
-        a.ws = static_cast<unsigned char *>(workspace);
-        a.batch_bytes = pl.batch_bytes, a.vals_off = pl.nsu.vals_off, a.slot_off = pl.nsu.slot_off;
-        a.tile_off = pl.nsu.tile_off, a.visit_off = pl.visit_off;
+        saint_plan_args(pl, workspace, a);
         if (const int rc = lds ? srw_launch_lds(a, pl, stream) : srw_launch_flat(a, pl, stream)) return rc;
     }
     return TG_OK;

@@ -51,7 +51,8 @@ EXPORTS = ["tg_version", "tg_last_error", "tg_ns_homo_capacity", "tg_ns_homo_bat
            "tg_saint_coverage_add", "tg_saint_norm", "tg_ns_hop_labor_workspace_bytes", "tg_ns_hop_labor",
            "tg_ns_hop_labor_long_column", "tg_pinsage_hop_workspace_bytes", "tg_pinsage_hop",
            "tg_cluster_workspace_bytes", "tg_cluster_count", "tg_cluster_emit",
-           "tg_ns_full_workspace_bytes", "tg_ns_full_count", "tg_ns_full_emit"]
+           "tg_ns_full_workspace_bytes", "tg_ns_full_count", "tg_ns_full_emit",
+           "tg_saint_ne_form", "tg_saint_ne_workspace_bytes", "tg_saint_node_nodes", "tg_saint_edge_nodes"]
 
 
 class TgGraph(C.Structure):
@@ -1879,6 +1880,94 @@ def saint_norm(graph, node_count, edge_count, n_samples):
                             ptr(node_norm) if graph.n_major else None, ptr(edge_norm) if graph.n_edges else None,
                             stream_ptr(dev)))
     return node_norm, edge_norm
+
+
+class TgSaintEdgeIn(C.Structure):
+    _fields_ = [("csc", C.POINTER(TgGraph)), ("cols", C.c_void_p), ("n_cols", C.c_int64),
+                ("csr", C.POINTER(TgGraph)), ("rows", C.c_void_p), ("n_rows", C.c_int64)]
+
+
+def saint_ne_form(positions, lds_limit_bytes=0):
+    """-> (form, lds_bytes): the form an auto tg_saint_node_nodes / tg_saint_edge_nodes call of `positions` positions per
+    mini-batch takes (batch_size for the node sampler, 2 * batch_size for the edge sampler; 1 = one workgroup per
+    mini-batch with the table in LDS, 2 = flat through a workspace) and the LDS the LDS form asks for.  lds_limit_bytes > 0:
+    taken as the workgroup's limit, no device is touched; otherwise the current device is asked."""
+    form, nbytes = C.c_int32(-1), C.c_int64(0)
+    check(lib.tg_saint_ne_form(C.c_int64(positions), C.c_int64(lds_limit_bytes), C.byref(form), C.byref(nbytes)))
+    return form.value, nbytes.value
+
+
+def saint_ne_workspace_bytes(n_batches, positions, form=0):
+    """-> (bytes, bytes_min): the workspace of n_batches mini-batches of `positions` positions at once in this form (0: the
+    one auto takes on the current device; 0 bytes for the LDS form) and of one mini-batch of the flat form, the least a
+    flat call runs with."""
+    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
+    check(lib.tg_saint_ne_workspace_bytes(C.c_int64(n_batches), C.c_int64(positions), C.c_int32(form), C.byref(nbytes),
+                                          C.byref(bmin)))
+    return nbytes.value, bmin.value
+
+
+def _saint_ne_buffers(who, dev, G, P, form, ws, out, status):
+    """the output pair, the status word and the workspace of a tg_saint_node_nodes / tg_saint_edge_nodes call"""
+    if out is None:
+        out = (torch.empty((G, P), dtype=torch.int64, device=dev), torch.empty(G, dtype=torch.int64, device=dev))
+    nodes, counts = out
+    if nodes.dim() != 2 or nodes.shape[0] < G or nodes.stride(1) != 1 or counts.dim() != 1 or counts.numel() < G \
+            or nodes.dtype != torch.int64 or counts.dtype != torch.int64:
+        raise ValueError("%s: out must be (int64 nodes [>= n_batches, pitch], int64 counts [>= n_batches])" % who)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    need = saint_ne_workspace_bytes(G, P, form)[0]
+    if need and ws is None:
+        ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    o = TgSaintRwOut(nodes.data_ptr(), nodes.stride(0), counts.data_ptr(), counts.stride(0))
+    return nodes, counts, o, status, ws, C.c_int64(ws.numel() * ws.element_size() if ws is not None else 0)
+
+
+def saint_node_nodes(graph, batch_size, n_batches, seed, call_id, id_bound=None, form=0, ws=None, out=None, status=None):
+    """GraphSAINT's node sampler (tg_saint_node_nodes): G = n_batches mini-batches in one launch on the current stream ->
+    (nodes [G, pitch], counts [G]).  Slot i < batch_size of mini-batch g picks an entry of `graph` uniformly (call id
+    call_id + g) and visits indices[entry]: given the CSC a source with probability out-degree / E, given the CSR a target
+    with probability in-degree / E.  nodes[g, :counts[g]] = the distinct visited vertices, first visit first; words past
+    counts[g] are not written.  id_bound: ids are in [0, id_bound) (None: graph.n_major, a square graph); form, ws, out,
+    status as saint_rw_nodes (status bit 1, value 2 = a vertex outside [0, id_bound)).  `graph` is a graph_view: buffers
+    are allocated where its indices live."""
+    G, B = int(n_batches), int(batch_size)
+    dev = out[0].device if out is not None else graph._keep[1].device
+    nodes, counts, o, status, ws, ws_bytes = _saint_ne_buffers("saint_node_nodes", dev, G, B, form, ws, out, status)
+    rng = TgRng(seed, call_id)
+    check(lib.tg_saint_node_nodes(C.byref(graph), C.c_int64(graph.n_major if id_bound is None else id_bound), C.c_int64(G),
+                                  C.c_int64(B), C.byref(rng), C.byref(o), ptr(status), ptr(ws), ws_bytes, C.c_int32(form),
+                                  stream_ptr(dev)))
+    return nodes, counts
+
+
+def saint_edge_nodes(csc, cols, csr, rows, batch_size, n_batches, seed, call_id, id_bound=None, form=0, ws=None, out=None,
+                     status=None):
+    """GraphSAINT's edge sampler (tg_saint_edge_nodes): G = n_batches mini-batches of batch_size EDGES in one launch on the
+    current stream -> (nodes [G, pitch >= 2 * batch_size], counts [G]).  Slot i picks an entry of the concatenated lists
+    cols (columns of `csc`) | rows (rows of `csr`; csr = rows = None: columns only) and then a uniform entry of that column
+    / row; with the lists = the non-empty columns and rows of one graph the edge (u -> v) is drawn with probability
+    (1 / deg_in(v) + 1 / deg_out(u)) / (len(cols) + len(rows)).  Draws are independent, with replacement (PyG takes a
+    Gumbel top-k over all edges per mini-batch).  The source sits at position i, the target at batch_size + i;
+    nodes[g, :counts[g]] = the distinct ends, first position first.  status: bit 1 (value 2) = a listed major outside its
+    graph or an end >= id_bound (None: csc.n_major), bit 2 (value 4) = a listed major without entries; form, ws, out as
+    saint_rw_nodes."""
+    G, B = int(n_batches), int(batch_size)
+    for name, t in (("cols", cols), ("rows", rows)):
+        if t is not None and (t.dim() != 1 or t.dtype != torch.int64 or not t.is_contiguous()):
+            raise ValueError("saint_edge_nodes: %s must be a contiguous int64 vector" % name)
+    if (csr is None) != (rows is None):
+        raise ValueError("saint_edge_nodes: csr and rows go together")
+    dev = cols.device
+    nodes, counts, o, status, ws, ws_bytes = _saint_ne_buffers("saint_edge_nodes", dev, G, 2 * B, form, ws, out, status)
+    arg = TgSaintEdgeIn(C.pointer(csc), cols.data_ptr(), cols.numel(), C.pointer(csr) if csr is not None else None,
+                        rows.data_ptr() if rows is not None else None, rows.numel() if rows is not None else 0)
+    rng = TgRng(seed, call_id)
+    check(lib.tg_saint_edge_nodes(C.byref(arg), C.c_int64(csc.n_major if id_bound is None else id_bound), C.c_int64(G),
+                                  C.c_int64(B), C.byref(rng), C.byref(o), ptr(status), ptr(ws), ws_bytes, C.c_int32(form),
+                                  stream_ptr(dev)))
+    return nodes, counts
 
 
 class TgNsTypedIn(C.Structure):

@@ -23,7 +23,9 @@ rows; the temporal one also the windows' timestamps) of one tg_rw_skipgram / tg_
 `prefetch` mini-batches; nothing is read back.
 GraphSAINTRandomWalkLoader hands out subgraphs: the distinct nodes that short random walks from random roots visit
 (tg_saint_rw_nodes) with every edge of the graph between them (the induced pair), and with sample_coverage the two
-normalisation vectors of a pre-sample (tg_saint_coverage_add, tg_saint_norm).
+normalisation vectors of a pre-sample (tg_saint_coverage_add, tg_saint_norm).  GraphSAINTNodeLoader and GraphSAINTEdgeLoader
+are GraphSAINT's other two samplers on the same machinery: nodes drawn by degree (tg_saint_node_nodes) and the ends of
+edges drawn with probability ~ 1/deg(u) + 1/deg(v) (tg_saint_edge_nodes).
 PinSAGELoader hands out DGL-style blocks whose neighbours are the most visited nodes of short random walks with
 termination (tg_pinsage_hop), the visit counts as edge weights; a launch's frontiers are grown per mini-batch with the
 grouped dedup.
@@ -1823,38 +1825,24 @@ class HeteroLinkNeighborLoader(HeteroNeighborLoader):
             yield from self._emit(items[start:start + G * width].reshape(G, width), None, batch0 + start // B)
 
 
-SAINT_FIELDS = ("node_norm", "edge_norm")   # what GraphSAINTRandomWalkLoader(sample_coverage > 0) adds to a mini-batch
+SAINT_FIELDS = ("node_norm", "edge_norm")   # what a GraphSAINT loader with sample_coverage > 0 adds to a mini-batch
 SAINT_PRESAMPLE_CALL_ID0 = 1 << 62          # the pre-sample's call ids: a range no epoch reaches
 
 
-class GraphSAINTRandomWalkLoader(_Loader):
-    """GraphSAINT's random-walk sampler (PyG's GraphSAINTRandomWalkSampler) as a loader: a mini-batch is a SUBGRAPH -- the
-    distinct nodes that `walk_length`-step uniform walks from `batch_size` random roots visit, and every edge of the graph
-    between them.  An epoch is `num_steps` mini-batches; mini-batch j of epoch e has call id c = call_id0 + e * num_steps + j,
-    its roots are tg_seed_batches(seed, c, 1, batch_size, N) and its walks draw with (seed, c).  A launch takes `prefetch`
-    consecutive mini-batches (the epoch's last launch may be narrower): tg_seed_batches, tg_saint_rw_nodes (walks and the
-    first-occurrence dedup in one step, `form` as there), tg_ns_induced_count, ONE read-back of the node and edge counts
-    and the status words, tg_ns_induced_emit into flat arrays, tg_gather_rows per attribute -- all on the caller's stream.
-    The walks follow out-edges on a CSR built once with the device ingest; symmetric=True states that the graph is
-    symmetric and walks on the CSC the loader already holds.
+class _GraphSAINTLoader(_Loader):
+    """What GraphSAINT's three samplers share: everything but the step that makes a mini-batch's node list.  The argument
+    checks, the CSC, the attributes, the slab sets and their pool, a launch's read-back, the pre-sample with its two norms,
+    the super-batches.  A sampler supplies `_own_arguments` (its own checks; -> the positions P of a mini-batch and their
+    name in the refusal), `_prepare` (its graphs, once), `_workspace_bytes`, `_fill` (the node lists of mini-batches
+    call_id .. call_id + G - 1 into slab["nodes"] / slab["counts"], refusals into slab["status"]) and `_status_message`."""
 
-    Mini-batches are `MiniBatch` views of a `SuperBatch` (`super_batches()` hands those out): `n_id` (first visit first, so
-    the distinct roots lead), `edge_index` (row = source, col = target, numbered against n_id; ordered by target position,
-    then CSC offset), `e_id`, node and edge attributes; `batch_size` is the root count.
-
-    sample_coverage > 0: the constructor pre-samples whole launches (call ids from 1 << 62) until the node lists' sizes add
-    up to N * sample_coverage, counts how often every node and edge was sampled (tg_saint_coverage_add) and turns the
-    counts into GraphSAINT's two normalisation vectors (tg_saint_norm, n_samples = the mini-batches pre-sampled);
-    mini-batches then carry `node_norm` [num_nodes] and `edge_norm` [num_edges] like attributes.  A `data` that has node or
-    edge attributes of those names is refused."""
-
-    def __init__(self, data, batch_size: int, walk_length: int, num_steps: int, sample_coverage: int = 0, prefetch: int = 16,
-                 seed: int = 0, call_id0: int = 0, device="cuda", symmetric: bool = False, form: int = 0):
-        B, T, S = int(batch_size), int(walk_length), int(num_steps)
+    def __init__(self, data, batch_size: int, num_steps: int, sample_coverage: int, prefetch: int, seed: int, call_id0: int,
+                 device, form: int):
+        B, S = int(batch_size), int(num_steps)
         if B < 1:                            # everything that can be refused is refused before any device work
             raise ValueError("batch_size must be at least 1, got %r" % (batch_size,))
-        if T < 1:
-            raise ValueError("walk_length must be at least 1, got %r" % (walk_length,))
+        self.batch_size = B
+        positions, named = self._own_arguments()
         if S < 1:
             raise ValueError("num_steps must be at least 1, got %r" % (num_steps,))
         if int(sample_coverage) < 0:
@@ -1863,8 +1851,8 @@ class GraphSAINTRandomWalkLoader(_Loader):
             raise ValueError("prefetch must be at least 1, got %r" % (prefetch,))
         if int(form) not in (0, 1, 2):
             raise ValueError("form must be 0 (auto), 1 (LDS) or 2 (flat), got %r" % (form,))
-        if B * (T + 1) > 2 ** 30:
-            raise ValueError("batch_size * (walk_length + 1) = %d positions exceed 2^30" % (B * (T + 1)))
+        if positions > 2 ** 30:
+            raise ValueError("%s = %d positions exceed 2^30" % (named, positions))
         if not 0 <= int(call_id0) < SAINT_PRESAMPLE_CALL_ID0 // 2:
             raise ValueError("call_id0 must be in [0, 2^61), got %r" % (call_id0,))
         N, E = _num_nodes(data), int(data.edge_index.shape[1])
@@ -1874,21 +1862,14 @@ class GraphSAINTRandomWalkLoader(_Loader):
             for key, value in _tensor_items(data):   # the mini-batches' own node_norm / edge_norm would hide them
                 if key in SAINT_FIELDS and _attr_kind(key, value, N, E) in ("node", "edge"):
                     raise ValueError("a GraphSAINT loader's mini-batches carry their own `%s`: rename data.%s" % (key, key))
-        self.data, self.batch_size, self.walk_length, self.num_steps = data, B, T, S
+        self.data, self.num_steps = data, S
         self.sample_coverage, self.prefetch = int(sample_coverage), int(prefetch)
-        self.seed, self.call_id0, self.form, self.symmetric = int(seed), int(call_id0), int(form), bool(symmetric)
+        self.seed, self.call_id0, self.form = int(seed), int(call_id0), int(form)
         self.device = torch.device(device)
         self.n_nodes, self._n_edges = N, E
         self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
-        small = E < 2 ** 31
-        shadows = lambda ptrs, idx: dict(indices32=idx.to(torch.int32), ptrs32=ptrs.to(torch.int32)) if small else {}
-        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, **shadows(self.col_ptrs, self.row_indices))
-        if self.symmetric:                   # the caller's word: in-edges are out-edges
-            self._walk_graph = self._graph
-        else:                                # out-edges: the CSR, built once
-            ei = data.edge_index.to(self.device)
-            row_ptrs, col_indices, _ = _cabi.coo_to_csx(ei[0], ei[1], N, N, False)
-            self._walk_graph = _cabi.graph_view(row_ptrs, col_indices, **shadows(row_ptrs, col_indices))
+        self._graph = self._view(self.col_ptrs, self.row_indices)
+        self._prepare()
         self._node_attrs, self._edge_attrs = [], []
         for key, value in _tensor_items(data):
             kind = _attr_kind(key, value, N, E)
@@ -1896,7 +1877,7 @@ class GraphSAINTRandomWalkLoader(_Loader):
                 self._node_attrs.append((key, value.to(self.device)))
             elif kind == "edge":
                 self._edge_attrs.append((key, value.to(self.device)))
-        self.positions = _cabi.saint_rw_capacity(B, T)
+        self.positions = positions
         self._pool = []                      # slab sets of finished iterators (each live iterator owns its own)
         self.slab_allocations = 0            # slab sets made so far: a second epoch makes none
         self.epoch = 0
@@ -1905,12 +1886,23 @@ class GraphSAINTRandomWalkLoader(_Loader):
         if self.sample_coverage > 0:
             self._presample()
 
+    def _view(self, ptrs, indices):
+        """a graph view with the u32 shadows where they hold the same words"""
+        kw = dict(indices32=indices.to(torch.int32), ptrs32=ptrs.to(torch.int32)) if self._n_edges < 2 ** 31 else {}
+        return _cabi.graph_view(ptrs, indices, **kw)
+
+    def _out_graph(self):
+        """the CSR (out-edges), built once with the device ingest -> its view"""
+        ei = self.data.edge_index.to(self.device)
+        row_ptrs, col_indices, _ = _cabi.coo_to_csx(ei[0], ei[1], self.n_nodes, self.n_nodes, False)
+        return self._view(row_ptrs, col_indices)
+
     def __len__(self) -> int:
         return self.num_steps
 
     def _new_slab(self):
         """what a launch of up to `prefetch` mini-batches writes (an epoch's launches may be narrower; the pre-sample's are
-        always `prefetch` wide, so that is the size whatever num_steps is): the node slab, counts + the walk's status
+        always `prefetch` wide, so that is the size whatever num_steps is): the node slab, counts + the sampler's status
         word in one tensor, the induced pair's launch object (its counts, status and workspace), the flat form's workspace
         and the pinned image of everything the host reads back"""
         cap, dev = self.prefetch, self.device
@@ -1918,7 +1910,7 @@ class GraphSAINTRandomWalkLoader(_Loader):
         nodes = torch.empty((cap, self.positions), dtype=torch.int64, device=dev)
         state = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
         counts, status = state[:cap], state[-1:].view(torch.int32)[:1]
-        need = _cabi.saint_rw_workspace_bytes(cap, self.batch_size, self.walk_length, self.form)[0]
+        need = self._workspace_bytes(cap)
         ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev) if need else None
         ind = _cabi.NsInduced(self._graph, nodes, counts, 1, cap, self.n_nodes)
         host = torch.empty(state.numel() + ind.state.numel(), dtype=torch.int64).pin_memory()
@@ -1928,18 +1920,17 @@ class GraphSAINTRandomWalkLoader(_Loader):
         """mini-batches call_id .. call_id + G - 1 into the slab set -> (node counts, edge counts) as python lists, after the
         launch's one read-back; pass 2 of the induced pair has not run yet"""
         cap = self.prefetch
-        roots = _cabi.seed_batches(self.seed, call_id, G, self.batch_size, self.n_nodes, self.device)
         slab["state"][-1:].zero_()
-        _cabi.saint_rw_nodes(self._walk_graph, roots, self.walk_length, self.seed, call_id, form=self.form, ws=slab["ws"],
-                             out=(slab["nodes"], slab["counts"]), status=slab["status"])
+        self._fill(slab, call_id, G)
         ind = slab["ind"].count(G)
         host = slab["host"]
         host[:cap + 1].copy_(slab["state"], non_blocking=True)
         host[cap + 1:].copy_(ind.state, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         who = type(self).__name__
-        if int(host[cap:cap + 1].view(torch.int32)[0]):
-            raise RuntimeError("%s: a root outside the graph" % who)
+        status = int(host[cap:cap + 1].view(torch.int32)[0])
+        if status:
+            raise RuntimeError("%s: %s" % (who, self._status_message(status)))
         _cabi.induced_status_check(int(host[-1:].view(torch.int32)[0]), who)
         return host[:G].tolist(), host[cap + 1:cap + 1 + G].tolist()
 
@@ -2006,6 +1997,125 @@ class GraphSAINTRandomWalkLoader(_Loader):
     def __iter__(self) -> Iterator[MiniBatch]:
         for sb in self.super_batches():
             yield from sb
+
+
+class GraphSAINTRandomWalkLoader(_GraphSAINTLoader):
+    """GraphSAINT's random-walk sampler (PyG's GraphSAINTRandomWalkSampler) as a loader: a mini-batch is a SUBGRAPH -- the
+    distinct nodes that `walk_length`-step uniform walks from `batch_size` random roots visit, and every edge of the graph
+    between them.  An epoch is `num_steps` mini-batches; mini-batch j of epoch e has call id c = call_id0 + e * num_steps + j,
+    its roots are tg_seed_batches(seed, c, 1, batch_size, N) and its walks draw with (seed, c).  A launch takes `prefetch`
+    consecutive mini-batches (the epoch's last launch may be narrower): tg_seed_batches, tg_saint_rw_nodes (walks and the
+    first-occurrence dedup in one step, `form` as there), tg_ns_induced_count, ONE read-back of the node and edge counts
+    and the status words, tg_ns_induced_emit into flat arrays, tg_gather_rows per attribute -- all on the caller's stream.
+    The walks follow out-edges on a CSR built once with the device ingest; symmetric=True states that the graph is
+    symmetric and walks on the CSC the loader already holds.
+
+    Mini-batches are `MiniBatch` views of a `SuperBatch` (`super_batches()` hands those out): `n_id` (first visit first, so
+    the distinct roots lead), `edge_index` (row = source, col = target, numbered against n_id; ordered by target position,
+    then CSC offset), `e_id`, node and edge attributes; `batch_size` is the root count.
+
+    sample_coverage > 0: the constructor pre-samples whole launches (call ids from 1 << 62) until the node lists' sizes add
+    up to N * sample_coverage, counts how often every node and edge was sampled (tg_saint_coverage_add) and turns the
+    counts into GraphSAINT's two normalisation vectors (tg_saint_norm, n_samples = the mini-batches pre-sampled);
+    mini-batches then carry `node_norm` [num_nodes] and `edge_norm` [num_edges] like attributes.  A `data` that has node or
+    edge attributes of those names is refused."""
+
+    def __init__(self, data, batch_size: int, walk_length: int, num_steps: int, sample_coverage: int = 0, prefetch: int = 16,
+                 seed: int = 0, call_id0: int = 0, device="cuda", symmetric: bool = False, form: int = 0):
+        self.walk_length, self.symmetric = int(walk_length), bool(symmetric)
+        self._walk_length_given = walk_length
+        super().__init__(data, batch_size, num_steps, sample_coverage, prefetch, seed, call_id0, device, form)
+
+    def _own_arguments(self):
+        if self.walk_length < 1:
+            raise ValueError("walk_length must be at least 1, got %r" % (self._walk_length_given,))
+        return self.batch_size * (self.walk_length + 1), "batch_size * (walk_length + 1)"
+
+    def _prepare(self):
+        # symmetric: the caller's word that in-edges are out-edges
+        self._walk_graph = self._graph if self.symmetric else self._out_graph()
+
+    def _workspace_bytes(self, cap: int) -> int:
+        return _cabi.saint_rw_workspace_bytes(cap, self.batch_size, self.walk_length, self.form)[0]
+
+    def _fill(self, slab, call_id: int, G: int):
+        roots = _cabi.seed_batches(self.seed, call_id, G, self.batch_size, self.n_nodes, self.device)
+        _cabi.saint_rw_nodes(self._walk_graph, roots, self.walk_length, self.seed, call_id, form=self.form, ws=slab["ws"],
+                             out=(slab["nodes"], slab["counts"]), status=slab["status"])
+
+    def _status_message(self, status: int) -> str:
+        return "a root outside the graph"
+
+
+class GraphSAINTNodeLoader(_GraphSAINTLoader):
+    """GraphSAINT's node sampler (PyG's GraphSAINTNodeSampler) as a loader: a mini-batch is the subgraph induced by the
+    distinct nodes among `batch_size` draws, each draw a node with probability out-degree / E (the source of a uniform
+    edge: tg_saint_node_nodes on the CSC the loader holds; no CSR is needed).  Mini-batch j of epoch e has call id
+    call_id0 + e * num_steps + j and draws with (seed, that call id); the pre-sample's call ids start at 1 << 62.
+    Everything behind the node list -- launches of `prefetch` mini-batches, the induced pair, the one read-back, the
+    `MiniBatch` views, sample_coverage and the two norms -- is GraphSAINTRandomWalkLoader's.  A mini-batch's `batch_size`
+    is the draw count; `n_id` is in order of first draw."""
+
+    def __init__(self, data, batch_size: int, num_steps: int, sample_coverage: int = 0, prefetch: int = 16, seed: int = 0,
+                 call_id0: int = 0, device="cuda", form: int = 0):
+        super().__init__(data, batch_size, num_steps, sample_coverage, prefetch, seed, call_id0, device, form)
+
+    def _own_arguments(self):
+        return self.batch_size, "batch_size"
+
+    def _prepare(self):
+        if self._n_edges < 1:
+            raise ValueError("the node sampler draws the sources of edges: the graph has none")
+
+    def _workspace_bytes(self, cap: int) -> int:
+        return _cabi.saint_ne_workspace_bytes(cap, self.positions, self.form)[0]
+
+    def _fill(self, slab, call_id: int, G: int):
+        _cabi.saint_node_nodes(self._graph, self.batch_size, G, self.seed, call_id, id_bound=self.n_nodes, form=self.form,
+                               ws=slab["ws"], out=(slab["nodes"], slab["counts"]), status=slab["status"])
+
+    def _status_message(self, status: int) -> str:
+        return "a drawn node outside the graph"
+
+
+class GraphSAINTEdgeLoader(_GraphSAINTLoader):
+    """GraphSAINT's edge sampler (PyG's GraphSAINTEdgeSampler) as a loader: a mini-batch is the subgraph induced by the ends
+    of `batch_size` drawn EDGES.  An edge (u -> v) is drawn with probability proportional to 1 / deg_in(v) + 1 / deg_out(u),
+    the paper's minimum-variance law, as a mixture: a uniform entry of the list [non-empty columns of the CSC | non-empty
+    rows of the CSR], then a uniform entry of that column or row (tg_saint_edge_nodes) -- no table over E.  The draws are
+    independent, WITH replacement; PyG takes a Gumbel top-k over all E edges for every mini-batch, without replacement.
+    The CSR is built once with the device ingest and the two lists once with torch (diff(ptrs) > 0, nonzero);
+    symmetric=True states that the graph is symmetric and passes the CSC and its list for both sides.  Call ids, the
+    pre-sample, the norms and everything behind the node list are GraphSAINTRandomWalkLoader's.  A mini-batch's
+    `batch_size` is the number of edges drawn; `n_id` holds the distinct sources in order of first draw, then the targets
+    not among them."""
+
+    def __init__(self, data, batch_size: int, num_steps: int, sample_coverage: int = 0, prefetch: int = 16, seed: int = 0,
+                 call_id0: int = 0, device="cuda", symmetric: bool = False, form: int = 0):
+        self.symmetric = bool(symmetric)
+        super().__init__(data, batch_size, num_steps, sample_coverage, prefetch, seed, call_id0, device, form)
+
+    def _own_arguments(self):
+        return 2 * self.batch_size, "2 * batch_size"
+
+    def _prepare(self):
+        if self._n_edges < 1:
+            raise ValueError("the edge sampler draws edges: the graph has none")
+        nonempty = lambda ptrs: torch.nonzero(torch.diff(ptrs) > 0).view(-1)
+        self._out = self._graph if self.symmetric else self._out_graph()
+        self.cols = nonempty(self.col_ptrs)
+        self.rows = self.cols if self.symmetric else nonempty(self._out._keep[0])
+
+    def _workspace_bytes(self, cap: int) -> int:
+        return _cabi.saint_ne_workspace_bytes(cap, self.positions, self.form)[0]
+
+    def _fill(self, slab, call_id: int, G: int):
+        _cabi.saint_edge_nodes(self._graph, self.cols, self._out, self.rows, self.batch_size, G, self.seed, call_id,
+                               id_bound=self.n_nodes, form=self.form, ws=slab["ws"], out=(slab["nodes"], slab["counts"]),
+                               status=slab["status"])
+
+    def _status_message(self, status: int) -> str:
+        return "a drawn edge outside the graph" if status & 2 else "a listed column or row without entries"
 
 
 class _PinSAGESlabs:
