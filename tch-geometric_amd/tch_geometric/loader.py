@@ -12,6 +12,13 @@ under a backward temporal filter, uniformly or taking the most recent admitted e
 ShaDowKHopLoader is NeighborLoader with one subgraph per seed and every edge of the graph inside each (ShaDow-GNN's k-hop
 sampler): tg_ns_induced_grouped_count / _emit behind the grouped dedup.
 
+What the loaders share is written once.  _Loader: the length of an epoch, the walk over its launches (_epoch_launches: the
+epoch counter, the one shuffle rule, the launches of _epoch_plan) and iteration as the items of super_batches().
+_Indexable: a super-batch's len / index / iteration over one `_at(j)`.  SuperBatch: every optional field defaults to
+None, _set_flat takes a launch's flat arrays and gathers the attribute rows.  _BlockLoader with _Block / _BlockBatch /
+_BlockSuperBatch: the loaders of DGL-style blocks (PinSAGELoader, FullNeighborLoader), each with one per-layer hook.
+_PooledLoader: the loaders whose launches write into one pooled slab set (the GraphSAINT loaders, ClusterLoader).
+
 The typed-graph loaders (HeteroNeighborLoader, HGTLoader, BudgetLoader, NegativeLoader) are one program, _TypedLoader:
 `prefetch` mini-batches of one node type's seeds per launch of a batched operator, one read-back of the counts, every
 slab flattened and split per mini-batch, attributes gathered once per launch.  Each loader adds only its operator's
@@ -35,6 +42,7 @@ induced pair's hash table).
 FullNeighborLoader hands out blocks that hold EVERY in-edge of their destinations (layer-wise inference; PyG's
 num_neighbors=[-1]): tg_ns_full_count / tg_ns_full_emit, one read-back per layer and launch.
 """
+from itertools import accumulate
 from typing import Iterator, List, Optional
 
 import torch
@@ -46,10 +54,10 @@ from .transforms import (Graph, HeteroGraph, _attr_kind, _is_hetero, _num_nodes,
                          to_hetero_csc)
 
 
-def _checked_inputs(nodes: Tensor, n_nodes: int) -> Tensor:
-    """int64, flat, and inside [0, n_nodes): the kernels index `ptrs[w]` unchecked (the reference panics on such
-    an id, neighbor_sampling.rs:197)."""
-    nodes = nodes.reshape(-1).to(torch.int64)
+def _checked_inputs(nodes: Optional[Tensor], n_nodes: int, device=None) -> Tensor:
+    """The input nodes (None: all of them) on `device` (None: where they are): int64, flat, and inside [0, n_nodes) -- the
+    kernels index `ptrs[w]` unchecked (the reference panics on such an id, neighbor_sampling.rs:197)."""
+    nodes = torch.arange(n_nodes, device=device) if nodes is None else nodes.to(device=device).reshape(-1).to(torch.int64)
     if nodes.numel() and (int(nodes.min()) < 0 or int(nodes.max()) >= n_nodes):
         raise IndexError("input_nodes outside [0, %d)" % n_nodes)
     return nodes
@@ -67,15 +75,104 @@ def _epoch_plan(n: int, batch_size: int, prefetch: int, drop_last: bool):
     return plan
 
 
+def _ptr_list(counts) -> List[int]:
+    """Host-side counts -> their pointer list [0, c0, c0 + c1, ...]."""
+    return list(accumulate(counts, initial=0))
+
+
+def _at_least_1(name: str, value):
+    if int(value) < 1:
+        raise ValueError("%s must be at least 1, got %r" % (name, value))
+
+
+def _split_attrs(data, n_nodes: int, n_edges: int, device, edges: bool = True):
+    """(node_attrs, edge_attrs) of a homogeneous `data`: [(name, tensor on the device)] of the tensors with one row per
+    node and per edge; edges=False leaves the edge attributes where they are (an empty list)."""
+    node_attrs, edge_attrs = [], []
+    for key, value in _tensor_items(data):
+        kind = _attr_kind(key, value, n_nodes, n_edges)
+        if kind == "node":
+            node_attrs.append((key, value.to(device)))
+        elif kind == "edge" and edges:
+            edge_attrs.append((key, value.to(device)))
+    return node_attrs, edge_attrs
+
+
+def _shadowed_view(ptrs: Tensor, indices: Tensor, small: bool, **kw):
+    """A graph view with its u32 shadows (they halve the bytes per gathered line) where `small` says that
+    ids and offsets fit below 2^31."""
+    return _cabi.graph_view(ptrs, indices, indices32=indices.to(torch.int32) if small else None,
+                            ptrs32=ptrs.to(torch.int32) if small else None, **kw)
+
+
+def _refuse_reserved(data, fields, whose: str):
+    """A node or edge attribute of `data` named like a field the mini-batches carry themselves would be hidden by it."""
+    n_nodes, n_edges = _num_nodes(data), int(data.edge_index.shape[1])
+    for key, value in _tensor_items(data):
+        if key in fields and _attr_kind(key, value, n_nodes, n_edges) in ("node", "edge"):
+            raise ValueError("%s mini-batches carry their own `%s`: rename data.%s" % (whose, key, key))
+
+
+class _Indexable:
+    """A container of mini-batches: len, indexing (negative too) and iteration over one `_at(j)`."""
+    __slots__ = ()
+
+    def __len__(self):
+        return len(self.node_ptr) - 1
+
+    def __getitem__(self, j):
+        if j < 0:
+            j += len(self)
+        if not 0 <= j < len(self):
+            raise IndexError(j)
+        return self._at(j)
+
+    def __iter__(self):
+        return map(self._at, range(len(self)))
+
+
 class _Loader:
-    """What every loader here has: input_nodes, batch_size, drop_last -> the number of mini-batches of an epoch."""
+    """What every loader here has: input_nodes, batch_size, drop_last -> the number of mini-batches of an epoch; the walk
+    over an epoch's launches; mini-batches as the items of its super-batches."""
+    shuffle = False
 
     def __len__(self) -> int:
         n = self.input_nodes.numel()
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
+    def _epoch_launches(self, *inputs):
+        """The next epoch over `inputs` (flat tensors of one length, or None: the seeds and whatever is sliced alongside
+        them) as its launches: yields (the [G, width] rows of every input, the first mini-batch's number).  Every epoch
+        draws afresh, as the reference's global stream does (utils/random.rs:19-22): mini-batch j of epoch e is number
+        e * len(self) + j -- reproducible for a fixed (seed, epoch).  Under `shuffle` one permutation, a function of
+        (seed, epoch), orders all inputs."""
+        epoch = self.epoch                                      # captured: a second iterator is the next epoch
+        self.epoch += 1
+        batch0, B, n = epoch * len(self), self.batch_size, inputs[0].numel()
+        if self.shuffle:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(self.seed * 1000003 + epoch)
+            order = torch.randperm(n, device=self.device, generator=gen)
+            inputs = [None if t is None else t[order] for t in inputs]
+        for start, G, width in _epoch_plan(n, B, self.prefetch, self.drop_last):
+            yield tuple(None if t is None else t[start:start + G * width].reshape(G, width) for t in inputs), batch0 + start // B
 
-class SuperBatch:
+    def __iter__(self):
+        for sb in self.super_batches():
+            yield from sb
+
+    def _view(self, ptrs, indices):
+        """a graph view of a homogeneous `data`'s edges, with the u32 shadows where E < 2^31"""
+        return _shadowed_view(ptrs, indices, self._n_edges < 2 ** 31)
+
+    def _out_graph(self):
+        """the CSR (out-edges) of a homogeneous `data`, built with the device ingest -> its view"""
+        ei = self.data.edge_index.to(self.device)
+        row_ptrs, col_indices, _ = _cabi.coo_to_csx(ei[0], ei[1], self.n_nodes, self.n_nodes, False)
+        return self._view(row_ptrs, col_indices)
+
+
+class SuperBatch(_Indexable):
     """`prefetch` mini-batches sampled by ONE launch, as flat batch-major device tensors plus per-batch offsets -- the unit
     the loader really works in.  `n_id` [sum nodes], `edge_index` [2, sum edges] (batch-local numbering), `e_id`
     [sum edges] (COO edge ids of the source graph), one flat tensor per node / edge attribute, `node_ptr` / `edge_ptr`
@@ -90,6 +187,20 @@ class SuperBatch:
                  "layer_offsets", "layer_nodes", "layer_edges", "seed_counts", "batch_size", "call_id0", "n_hops", "_views",
                  "_index", "input_time", "node_time", "batch", "root_n_id")
 
+    def __init__(self):
+        """Nothing optional is there (n_hops: none) until the loader that fills the super-batch says so."""
+        self._e_id = self._views = self.layer_offsets = self.layer_nodes = self.layer_edges = self.seed_counts = None
+        self.input_time = self.node_time = self.batch = self.root_n_id = None
+        self.n_hops = 0
+
+    def _set_flat(self, n_id, edge_index, e_ptr, node_ptr, edge_ptr, perm, node_attrs, edge_attrs):
+        """The flat arrays of a launch with their pointer lists, and the attribute rows [(name, table)] gathered by them
+        (the edges' through e_id = perm[e_ptr]; the ids come from a sampler: no range read-back)."""
+        self.n_id, self.edge_index, self.node_ptr, self.edge_ptr = n_id, edge_index, node_ptr, edge_ptr
+        self._e_ptr, self._perm = e_ptr, perm
+        self.node_attrs = {k: _rows_of(v, n_id) for k, v in node_attrs}
+        self.edge_attrs = {k: _rows_of(v, self.e_id) for k, v in edge_attrs}
+
     @property
     def e_id(self):
         """COO edge ids of the sampled edges: a gather through the ingest permutation (one random 8-byte read per edge),
@@ -101,7 +212,7 @@ class SuperBatch:
     def views_of(self, j):
         """every tensor view of mini-batch j, cut by the host module in one call (BatchViews): (n_id, edge_index, node
         attributes..., edge attributes...); e_id is cut apart, when asked for"""
-        v = getattr(self, "_views", None)
+        v = self._views
         if v is None:
             names = ["n_id", "edge_index"] + list(self.node_attrs) + list(self.edge_attrs)
             bases = [self.n_id, self.edge_index] + list(self.node_attrs.values()) + list(self.edge_attrs.values())
@@ -111,19 +222,8 @@ class SuperBatch:
             v = self._views = _host.BatchViews(bases, dims, kinds, self.node_ptr, self.edge_ptr)
         return v.at(j)
 
-    def __len__(self):
-        return len(self.node_ptr) - 1
-
-    def __getitem__(self, j):
-        if j < 0:
-            j += len(self)
-        if not 0 <= j < len(self):
-            raise IndexError(j)
+    def _at(self, j):
         return MiniBatch(self, j)
-
-    def __iter__(self):
-        for j in range(len(self.node_ptr) - 1):
-            yield MiniBatch(self, j)
 
     @property
     def num_nodes(self):
@@ -317,10 +417,8 @@ class NeighborLoader(_Loader):
             raise ValueError("induced=True with disjoint subgraphs is out of scope: the induced edges are found per "
                              "mini-batch, not per subgraph")
         if self.disjoint:
-            for key, value in _tensor_items(data):   # the mini-batches' own `batch` would hide it
-                if key in DISJOINT_FIELDS and _attr_kind(key, value, _num_nodes(data), int(data.edge_index.shape[1])) in ("node", "edge"):
-                    raise ValueError("a disjoint loader's mini-batches carry their own `%s`: rename data.%s" % (key, key))
-        if self.temporal:                   # everything that can be refused is refused before any device work
+            _refuse_reserved(data, DISJOINT_FIELDS, "a disjoint loader's")
+        if self.temporal:                  # everything that can be refused is refused before any device work
             times = getattr(data, time_attr, None)
             n_edges = int(data.edge_index.shape[1])
             if not isinstance(times, Tensor) or times.dtype != torch.int64 or times.numel() != n_edges:
@@ -330,9 +428,7 @@ class NeighborLoader(_Loader):
                 raise ValueError("%s must be an int64 tensor with one entry per %s (%d)" % (self.TIME_ARG + (n_inputs,)))
             if temporal_strategy == "last" and any(int(k) > 64 for k in num_neighbors):
                 raise ValueError("temporal_strategy='last' takes num_neighbors up to 64")
-            for key, value in _tensor_items(data):   # the mini-batches' own input_time / node_time would hide them
-                if key in TIME_FIELDS and _attr_kind(key, value, _num_nodes(data), n_edges) in ("node", "edge"):
-                    raise ValueError("a temporal loader's mini-batches carry their own `%s`: rename data.%s" % (key, key))
+            _refuse_reserved(data, TIME_FIELDS, "a temporal loader's")
             self.time_window = (0, 2 ** 62) if time_window is None else (int(time_window[0]), int(time_window[1]))
         self.temporal_strategy = temporal_strategy
         self.induced = bool(induced)
@@ -350,10 +446,6 @@ class NeighborLoader(_Loader):
         self._unique_ws = None              # the dedup's tables (flat form), sized once for a full launch
         self.n_nodes = _num_nodes(data)
         self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
-        # u32 shadows halve the bytes per gathered line; ids and offsets fit below 2^31 here
-        small = self.n_nodes < 2 ** 31 and self.row_indices.numel() < 2 ** 31
-        self._idx32 = self.row_indices.to(torch.int32) if small else None
-        self._ptr32 = self.col_ptrs.to(torch.int32) if small else None
         # the longest column (one read-back) sets the stage slots' bit widths: without it they assume n_edges, and the
         # slots of a large graph come out two chunks wide, which the staged pipeline of many-batch launches refuses
         self.edge_time = self.input_time = None
@@ -361,19 +453,14 @@ class NeighborLoader(_Loader):
             times = getattr(data, time_attr).to(self.device).reshape(-1)
             self.edge_time = times[self.perm].contiguous() if times.numel() else times
             self.input_time = input_time.to(self.device).reshape(-1)
-        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, timestamps=self.edge_time, indices32=self._idx32,
-                                       ptrs32=self._ptr32, max_degree="auto")
-        self._time_ws = {}                  # temporal and labor launches: the workspace per launch shape (full / ragged), kept
-        nodes = torch.arange(self.n_nodes, device=self.device) if input_nodes is None else input_nodes.to(self.device)
-        self.input_nodes = _checked_inputs(nodes, self.n_nodes)
+        self._graph = _shadowed_view(self.col_ptrs, self.row_indices,
+                                     self.n_nodes < 2 ** 31 and self.row_indices.numel() < 2 ** 31,
+                                     timestamps=self.edge_time, max_degree="auto")
+        self._idx32, self._ptr32 = self._graph._keep[4:]
+        self._time_ws = {}               # temporal and labor launches: the workspace per launch shape (full / ragged), kept
+        self.input_nodes = _checked_inputs(input_nodes, self.n_nodes, self.device)
         self._n_edges = int(data.edge_index.shape[1])
-        self._node_attrs, self._edge_attrs = [], []
-        for key, value in _tensor_items(data):
-            kind = _attr_kind(key, value, self.n_nodes, self._n_edges)
-            if kind == "node":
-                self._node_attrs.append((key, value.to(self.device)))
-            elif kind == "edge":
-                self._edge_attrs.append((key, value.to(self.device)))
+        self._node_attrs, self._edge_attrs = _split_attrs(data, self.n_nodes, self._n_edges, self.device)
         self._pool = []                     # slab sets of finished iterators (each live iterator owns its own)
         self._ws = None
         self._side = None
@@ -533,7 +620,6 @@ class NeighborLoader(_Loader):
         else:
             n_id, edge_index, e_ptr = _cabi.ns_homo_compact(src, G, counts, stacked=True)   # copies: the slabs go back to the sampler
         sb = self._new_super_batch(slab, G)
-        sb.input_time = sb.node_time = sb.batch = sb.root_n_id = None
         total = sum(n_nodes)
         if self.disjoint:                    # the group slab trimmed like nodes (a copy: the slab goes back)
             sb.batch = _flat_rows(src.group[:G], src.counts[:G, 0], total)
@@ -548,24 +634,12 @@ class NeighborLoader(_Loader):
         free = torch.cuda.Event()
         free.record(cur)
         slab["free"] = free
-        rows_of = lambda table, index: _cabi.gather_rows(table, index)[0]   # ids come from the sampler: no range read-back
-        sb.n_id, sb.edge_index = n_id, edge_index
-        sb._e_id, sb._e_ptr, sb._perm = None, e_ptr, self.perm
-        sb.node_attrs = {k: rows_of(v, n_id) for k, v in self._node_attrs}
-        sb.edge_attrs = {k: rows_of(v, sb.e_id) for k, v in self._edge_attrs}
-        ptr_n, ptr_e, a, e = [0], [0], 0, 0
-        for x, y in zip(n_nodes, n_edges):
-            a += x
-            e += y
-            ptr_n.append(a)
-            ptr_e.append(e)
-        sb.node_ptr, sb.edge_ptr = ptr_n, ptr_e
-        sb.layer_offsets = slab["lo"][:G].tolist()
-        sb.layer_nodes = sb.seed_counts = sb.layer_edges = None
+        sb._set_flat(n_id, edge_index, e_ptr, _ptr_list(n_nodes), _ptr_list(n_edges), self.perm, self._node_attrs, self._edge_attrs)
         if self.induced:
             cap, H = slab["ind"].n_batches, len(self.fanout)
-            sb.layer_offsets = None
             sb.layer_edges = slab["ist"][cap:cap * (1 + H)].view(cap, H)[:G].tolist()
+        else:
+            sb.layer_offsets = slab["lo"][:G].tolist()
         if self.unique:
             H = len(self.fanout)
             sb.layer_nodes = slab["ln"][:G, :H].tolist()
@@ -592,23 +666,9 @@ class NeighborLoader(_Loader):
 
     def super_batches(self) -> Iterator[SuperBatch]:
         """The epoch as super-batches of up to `prefetch` mini-batches; the next one is sampled while this one is used."""
-        nodes = self.input_nodes
-        epoch = self.epoch                                      # captured: a second iterator is the next epoch
-        self.epoch += 1
-        B = self.batch_size
-        # every epoch draws afresh, as the reference's global stream does (utils/random.rs:19-22): mini-batch j of
-        # epoch e uses call id call_id0 + e * len(self) + j -- reproducible for a fixed (seed, epoch)
-        batch0 = epoch * len(self)
-        times = self.input_time
-        if self.shuffle:
-            gen = torch.Generator(device=self.device)
-            gen.manual_seed(self.seed * 1000003 + epoch)
-            order = torch.randperm(nodes.numel(), device=self.device, generator=gen)
-            nodes = nodes[order]
-            times = times[order] if times is not None else None
-        cut = lambda t, start, G, width: t[start:start + G * width].reshape(G, width)
-        work = [(cut(nodes, start, G, width), batch0 + start // B) + ((cut(times, start, G, width),) if times is not None else ())
-                for start, G, width in _epoch_plan(nodes.numel(), B, self.prefetch, self.drop_last)]
+        B = self.batch_size                                     # mini-batch j of epoch e uses call id call_id0 + e * len(self) + j
+        work = [(seeds, first_batch, times)
+                for (seeds, times), first_batch in self._epoch_launches(self.input_nodes, self.input_time)]
         # this iterator's own slabs (two iterators alive at once -- zip(loader, loader), a restart after an abandoned
         # epoch -- must not sample into each other's); they go back to the pool when the iterator ends or is dropped
         slabs = self._pool.pop() if self._pool else {}
@@ -625,10 +685,6 @@ class NeighborLoader(_Loader):
             if pending is not None:          # abandoned with a launch in flight: it still writes into these slabs
                 pending[4].synchronize()
             self._pool.append(slabs)
-
-    def __iter__(self) -> Iterator[MiniBatch]:
-        for sb in self.super_batches():
-            yield from sb
 
 
 def _flat_rows(slab: Tensor, lens: Tensor, total: int) -> Tensor:
@@ -674,9 +730,7 @@ class ShaDowKHopLoader(NeighborLoader):
             raise ValueError("temporal_strategy='last' takes num_neighbors up to 64")
         if chunk_cap is not None and not 1 <= int(chunk_cap) <= 2 ** 31:
             raise ValueError("chunk_cap must be in [1, 2^31], got %r" % (chunk_cap,))
-        for key, value in _tensor_items(data):       # the mini-batches' own root_n_id would hide it (`batch`: the parent's check)
-            if key in SHADOW_FIELDS and _attr_kind(key, value, _num_nodes(data), int(data.edge_index.shape[1])) in ("node", "edge"):
-                raise ValueError("a ShaDowKHopLoader's mini-batches carry their own `%s`: rename data.%s" % (key, key))
+        _refuse_reserved(data, SHADOW_FIELDS, "a ShaDowKHopLoader's")   # (`batch`: the parent's check)
         self.depth, self.num_neighbors = int(depth), int(num_neighbors)
         self.chunk_cap = int(chunk_cap) if chunk_cap is not None else 0   # 0: the launch object's default; grows on overflow
         super().__init__(data, [self.num_neighbors] * self.depth, input_nodes=input_nodes, batch_size=batch_size,
@@ -731,8 +785,7 @@ class _TypedLoader(_Loader):
         self._tix = {t: i for i, t in enumerate(self.node_types)}
         self._it = self._tix[input_type]
         n_in = _num_nodes(stores[self._it])
-        nodes = torch.arange(n_in, device=self.device) if input_nodes is None else input_nodes.to(self.device)
-        self.input_nodes = _checked_inputs(nodes, n_in)             # an input indexes the rows of its type unchecked
+        self.input_nodes = _checked_inputs(input_nodes, n_in, self.device)   # an input indexes the rows of its type unchecked
         self._node_attrs = [self._attrs_of(st, _num_nodes(st)) for st in stores]
         self._edge_attrs = [self._attrs_of(data[et], int(data[et].edge_index.shape[1])) if edge_attrs else []
                             for et in self.edge_types]
@@ -852,13 +905,8 @@ class _TypedLoader(_Loader):
             yield g
 
     def __iter__(self):
-        nodes, ts, B = self.input_nodes, self.input_ts, self.batch_size
-        batch0 = self.epoch * len(self)                             # fresh draws every epoch (see NeighborLoader)
-        self.epoch += 1
-        for start, G, width in _epoch_plan(nodes.numel(), B, self.prefetch, self.drop_last):
-            sl = slice(start, start + G * width)
-            yield from self._emit(nodes[sl].reshape(G, width), None if ts is None else ts[sl].reshape(G, width),
-                                  batch0 + start // B)
+        for (seeds, seeds_ts), first_batch in self._epoch_launches(self.input_nodes, self.input_ts):
+            yield from self._emit(seeds, seeds_ts, first_batch)
 
 
 class _TemporalInputs:
@@ -1139,7 +1187,7 @@ class SkipGramBatch:
         self.pos_rw, self.neg_rw, self.batch_size, self.call_id = pos_rw, neg_rw, batch_size, call_id
 
 
-class SkipGramSuperBatch:
+class SkipGramSuperBatch(_Indexable):
     """The mini-batches of ONE tg_rw_skipgram launch: `pos_rw` [G, nw * R * B, C], `neg_rw` [G, nw * R * K * B, C], batch-major,
     `batch_size`, `call_id0` (mini-batch g drew with call_id0 + g).  Iterating or indexing yields SkipGramBatch views."""
     __slots__ = ("pos_rw", "neg_rw", "batch_size", "call_id0")
@@ -1150,16 +1198,8 @@ class SkipGramSuperBatch:
     def __len__(self):
         return self.pos_rw.shape[0]
 
-    def __getitem__(self, g):
-        if g < 0:
-            g += len(self)
-        if not 0 <= g < len(self):
-            raise IndexError(g)
+    def _at(self, g):
         return SkipGramBatch(self.pos_rw[g], self.neg_rw[g], self.batch_size, self.call_id0 + g)
-
-    def __iter__(self):
-        for g in range(len(self)):
-            yield self[g]
 
 
 class Node2VecLoader(_Loader):
@@ -1185,18 +1225,29 @@ class Node2VecLoader(_Loader):
         # refuses a bad shape here, on the host (C > L, R < 1, K < 0, ...)
         self.cfg = _cabi.rw_skipgram_config(walk_length, context_size, walks_per_node, num_negative_samples, self.n_nodes,
                                             self.p, self.q)
+        self._batching(batch_size, drop_last, seed, call_id0)
+        self.form = int(form)
+        self.input_nodes = _checked_inputs(input_nodes, self.n_nodes)
+        pos_rows, neg_rows = _cabi.rw_skipgram_capacity(self.cfg, self.batch_size)
+        self._clamp_prefetch(prefetch, max_workspace_bytes, (pos_rows + neg_rows) * self.cfg.context_size * 8 +
+                             _cabi.rw_skipgram_workspace_bytes(self.cfg, 1, self.batch_size, self.n_nodes, self.form))
+        self._graph = self._edge_set = self._ws = None
+        self.epoch = 0
+
+    def _batching(self, batch_size, drop_last, seed, call_id0):
         self.batch_size, self.drop_last, self.seed, self.call_id0 = int(batch_size), drop_last, int(seed), int(call_id0)
         if self.batch_size < 1:
             raise ValueError("batch_size must be >= 1")
-        self.form = int(form)
-        nodes = torch.arange(self.n_nodes) if input_nodes is None else input_nodes
-        self.input_nodes = _checked_inputs(nodes, self.n_nodes)
-        pos_rows, neg_rows = _cabi.rw_skipgram_capacity(self.cfg, self.batch_size)
-        per_call = (pos_rows + neg_rows) * self.cfg.context_size * 8 + \
-            _cabi.rw_skipgram_workspace_bytes(self.cfg, 1, self.batch_size, self.n_nodes, self.form)
+
+    def _clamp_prefetch(self, prefetch, max_workspace_bytes, per_call: int):
+        """prefetch x the device memory of one mini-batch stays within max_workspace_bytes (at least one per launch)"""
         self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // max(per_call, 1)))
-        self._graph = self._edge_set = self._ws = None
-        self.epoch = 0
+
+    def _workspace(self, need: int):
+        """The kept workspace, grown to at least `need` bytes (None while no launch has needed one)."""
+        if need and (self._ws is None or self._ws.numel() * 8 < need):
+            self._ws = torch.empty(need // 8, dtype=torch.int64, device=self.device)
+        return self._ws
 
     def plan(self, epoch: int):
         """The launches of an epoch: [(start, n_batches, batch_width, first call id)] over input_nodes."""
@@ -1209,21 +1260,17 @@ class Node2VecLoader(_Loader):
             return
         self.input_nodes = self.input_nodes.to(self.device)
         self.row_ptrs, self.col_indices, _ = _host.to_csr(self.data.edge_index.to(self.device), self.n_nodes)
-        small = self.n_nodes < 2 ** 31 and self.col_indices.numel() < 2 ** 31
-        self._graph = _cabi.graph_view(self.row_ptrs, self.col_indices,
-                                       indices32=self.col_indices.to(torch.int32) if small else None,
-                                       ptrs32=self.row_ptrs.to(torch.int32) if small else None)
+        self._graph = _shadowed_view(self.row_ptrs, self.col_indices,
+                                     self.n_nodes < 2 ** 31 and self.col_indices.numel() < 2 ** 31)
         if not (self.p == 1.0 and self.q == 1.0) and self.n_nodes < 2 ** 32 - 1:
             self._edge_set = _cabi.edge_set(self._graph, self.device)
 
     def _launch(self, seeds: Tensor, call_id: int) -> SkipGramSuperBatch:
         c = self.cfg
-        need = _cabi.rw_skipgram_workspace_bytes(c, seeds.shape[0], seeds.shape[1], self.n_nodes, self.form)
-        if need and (self._ws is None or self._ws.numel() * 8 < need):
-            self._ws = torch.empty(need // 8, dtype=torch.int64, device=self.device)
+        ws = self._workspace(_cabi.rw_skipgram_workspace_bytes(c, seeds.shape[0], seeds.shape[1], self.n_nodes, self.form))
         pos, neg = _cabi.rw_skipgram(self._graph, seeds, c.walk_length, c.context_size, c.walks_per_node,
                                      c.num_negative_samples, self.p, self.q, self.seed, call_id, self.n_nodes,
-                                     edge_set=self._edge_set, form=self.form, ws=self._ws)
+                                     edge_set=self._edge_set, form=self.form, ws=ws)
         return SkipGramSuperBatch(pos, neg, seeds.shape[1], call_id)
 
     def super_batches(self) -> Iterator[SkipGramSuperBatch]:
@@ -1237,10 +1284,6 @@ class Node2VecLoader(_Loader):
     def _launch_inputs(self, start: int, G: int, width: int):
         """what _launch takes ahead of the call id: the [G, width] rows of every per-input tensor"""
         return (self.input_nodes[start:start + G * width].reshape(G, width).contiguous(),)
-
-    def __iter__(self) -> Iterator[SkipGramBatch]:
-        for sb in self.super_batches():
-            yield from sb
 
 
 class MetaPath2VecLoader(Node2VecLoader):
@@ -1285,20 +1328,16 @@ class MetaPath2VecLoader(Node2VecLoader):
         self.dummy_idx, self.num_embeddings, self.global_ids = total, total + 1, bool(global_ids)
         self._step_src, self._step_dst = [tix[et[0]] for et in self.metapath], [tix[et[2]] for et in self.metapath]
         self._n_edges = [int(data[et].edge_index.shape[1]) for et in self.metapath]
-        self.batch_size, self.drop_last, self.seed, self.call_id0 = int(batch_size), drop_last, int(seed), int(call_id0)
-        if self.batch_size < 1:
-            raise ValueError("batch_size must be >= 1")
+        self._batching(batch_size, drop_last, seed, call_id0)
         self.form = int(form)
         self._shape = (int(walk_length), int(context_size), int(walks_per_node), int(num_negative_samples))
         # sizes only: refuses a bad shape here, on the host (C > L, R < 1, K < 0, ...); _prepare puts the CSRs behind it
         self.cfg = self._config([_cabi.graph_sizing(self.type_count[s], e) for s, e in zip(self._step_src, self._n_edges)])
         n_in = self.type_count[self._step_src[0]]
-        nodes = torch.arange(n_in) if input_nodes is None else input_nodes
-        self.input_nodes = _checked_inputs(nodes, n_in)
+        self.input_nodes = _checked_inputs(input_nodes, n_in)
         pos_rows, neg_rows = _cabi.mp_skipgram_capacity(self.cfg, self.batch_size)
-        per_call = (pos_rows + neg_rows) * self.cfg.context_size * 8 + \
-            _cabi.mp_skipgram_workspace_bytes(self.cfg, 1, self.batch_size, self.form)
-        self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // max(per_call, 1)))
+        self._clamp_prefetch(prefetch, max_workspace_bytes, (pos_rows + neg_rows) * self.cfg.context_size * 8 +
+                             _cabi.mp_skipgram_workspace_bytes(self.cfg, 1, self.batch_size, self.form))
         self._graph = self._ws = None
         self.epoch = 0
 
@@ -1317,16 +1356,12 @@ class MetaPath2VecLoader(Node2VecLoader):
                 continue
             n_src, n_dst = self.type_count[s], self.type_count[d]
             ptrs, idx, _ = _host.to_csr(self.data[et].edge_index.to(self.device), (n_src, n_dst))
-            small = max(n_src, n_dst) < 2 ** 31 and idx.numel() < 2 ** 31
-            self._graph[et] = _cabi.graph_view(ptrs, idx, indices32=idx.to(torch.int32) if small else None,
-                                               ptrs32=ptrs.to(torch.int32) if small else None)
+            self._graph[et] = _shadowed_view(ptrs, idx, max(n_src, n_dst) < 2 ** 31 and idx.numel() < 2 ** 31)
         self.cfg = self._config([self._graph[et] for et in self.metapath])
 
     def _launch(self, seeds: Tensor, call_id: int) -> SkipGramSuperBatch:
-        need = _cabi.mp_skipgram_workspace_bytes(self.cfg, seeds.shape[0], seeds.shape[1], self.form)
-        if need and (self._ws is None or self._ws.numel() * 8 < need):
-            self._ws = torch.empty(need // 8, dtype=torch.int64, device=self.device)
-        pos, neg = _cabi.mp_skipgram(self.cfg, seeds, self.seed, call_id, form=self.form, ws=self._ws)
+        ws = self._workspace(_cabi.mp_skipgram_workspace_bytes(self.cfg, seeds.shape[0], seeds.shape[1], self.form))
+        pos, neg = _cabi.mp_skipgram(self.cfg, seeds, self.seed, call_id, form=self.form, ws=ws)
         return SkipGramSuperBatch(pos, neg, seeds.shape[1], call_id)
 
 
@@ -1341,7 +1376,7 @@ class TemporalSkipGramBatch:
         self.pos_rw, self.pos_ts, self.neg_rw, self.batch_size, self.call_id = pos_rw, pos_ts, neg_rw, batch_size, call_id
 
 
-class TemporalSkipGramSuperBatch:
+class TemporalSkipGramSuperBatch(_Indexable):
     """The mini-batches of ONE tg_tempo_skipgram launch: `pos_rw`, `pos_ts` (or None) [G, nw * R * B, C], `neg_rw` [G, nw * R *
     K * B, C], batch-major, `batch_size`, `call_id0` (mini-batch g drew with call_id0 + g).  Iterating or indexing yields
     TemporalSkipGramBatch views."""
@@ -1353,17 +1388,9 @@ class TemporalSkipGramSuperBatch:
     def __len__(self):
         return self.pos_rw.shape[0]
 
-    def __getitem__(self, g):
-        if g < 0:
-            g += len(self)
-        if not 0 <= g < len(self):
-            raise IndexError(g)
+    def _at(self, g):
         return TemporalSkipGramBatch(self.pos_rw[g], None if self.pos_ts is None else self.pos_ts[g], self.neg_rw[g],
                                      self.batch_size, self.call_id0 + g)
-
-    def __iter__(self):
-        for g in range(len(self)):
-            yield self[g]
 
 
 class TemporalWalkLoader(Node2VecLoader):
@@ -1394,10 +1421,8 @@ class TemporalWalkLoader(Node2VecLoader):
             raise ValueError("window = %r is empty: it is half open, window[0] < window[1]" % (window,))
         self.cfg = _cabi.tempo_skipgram_config(walk_length, context_size, self.window, walks_per_node, num_negative_samples,
                                                self.n_nodes)
-        self.batch_size, self.drop_last, self.seed, self.call_id0 = int(batch_size), drop_last, int(seed), int(call_id0)
-        if self.batch_size < 1:
-            raise ValueError("batch_size must be >= 1")
-        try:                                                         # the library's own refusals (C > L, R < 1, K < 0, too long ...)
+        self._batching(batch_size, drop_last, seed, call_id0)
+        try:                                                      # the library's own refusals (C > L, R < 1, K < 0, too long ...)
             pos_rows, neg_rows = _cabi.tempo_skipgram_capacity(self.cfg, self.batch_size)
             _cabi.tempo_skipgram_lds_bytes(self.cfg)
         except _cabi.TchGeoError as e:
@@ -1411,16 +1436,15 @@ class TemporalWalkLoader(Node2VecLoader):
         if node_timestamps is not None and node_timestamps.numel() != self.n_nodes:
             raise ValueError("node_timestamps must have one entry per node (%d), got %d" % (self.n_nodes, node_timestamps.numel()))
         self._edge_ts_in, self._node_ts_in = ets, node_timestamps
-        nodes = torch.arange(self.n_nodes) if input_nodes is None else input_nodes
-        self.input_nodes = _checked_inputs(nodes, self.n_nodes)
+        self.input_nodes = _checked_inputs(input_nodes, self.n_nodes)
         if input_timestamps is None:
             input_timestamps = torch.full((self.input_nodes.numel(),), -1, dtype=torch.int64)
         self.input_ts = input_timestamps.reshape(-1).to(torch.int64)
         if self.input_ts.numel() != self.input_nodes.numel():
             raise ValueError("input_timestamps must have one entry per input node")
         self.with_timestamps = bool(with_timestamps)
-        per_call = ((2 if self.with_timestamps else 1) * pos_rows + neg_rows) * self.cfg.context_size * 8
-        self.prefetch = max(1, min(int(prefetch), int(max_workspace_bytes) // max(per_call, 1)))
+        self._clamp_prefetch(prefetch, max_workspace_bytes,
+                             ((2 if self.with_timestamps else 1) * pos_rows + neg_rows) * self.cfg.context_size * 8)
         self._graph = None
         self.epoch = 0
 
@@ -1453,16 +1477,8 @@ class LinkSuperBatch(SuperBatch):
     __slots__ = ("neg_sampling", "edge_label_index", "edge_label", "src_index", "dst_pos_index", "dst_neg_index", "input_id",
                  "neg_unverified", "edge_label_time")
 
-    def __getitem__(self, j):
-        if j < 0:
-            j += len(self)
-        if not 0 <= j < len(self):
-            raise IndexError(j)
+    def _at(self, j):
         return LinkMiniBatch(self, j)
-
-    def __iter__(self):
-        for j in range(len(self.node_ptr) - 1):
-            yield LinkMiniBatch(self, j)
 
 
 def _row_of(name):
@@ -1726,9 +1742,7 @@ class HeteroLinkNeighborLoader(HeteroNeighborLoader):
         self._ta, self._tb, self.n_src, self.n_dst = self._tix[et[0]], self._tix[et[2]], n_src, n_dst
         self.same_type = self._ta == self._tb
         ptrs, idx = self.col_ptrs[rel_key(et)], self.row_indices[rel_key(et)]
-        small = max(n_src, n_dst) < 2 ** 31 and idx.numel() < 2 ** 31   # u32 shadows: half the bytes per look-up line
-        self._rel_graph = _cabi.graph_view(ptrs, idx, indices32=idx.to(torch.int32) if small else None,
-                                           ptrs32=ptrs.to(torch.int32) if small else None)
+        self._rel_graph = _shadowed_view(ptrs, idx, max(n_src, n_dst) < 2 ** 31 and idx.numel() < 2 ** 31)
         fits = max(n_src, n_dst) < 2 ** 32 - 1
         self._edge_set = _cabi.edge_set(self._rel_graph, dev) if edge_set and fits else None
         self._consts = {}
@@ -1813,42 +1827,67 @@ class HeteroLinkNeighborLoader(HeteroNeighborLoader):
             if self.edge_label is not None:
                 st.edge_label = link["label"][b]
 
-    def __iter__(self):
-        items, B = self.input_nodes, self.batch_size
-        epoch, batch0 = self.epoch, self.epoch * len(self)           # fresh draws every epoch
-        self.epoch += 1
-        if self.shuffle:
-            gen = torch.Generator(device=self.device)
-            gen.manual_seed(self.seed * 1000003 + epoch)
-            items = items[torch.randperm(items.numel(), device=self.device, generator=gen)]
-        for start, G, width in _epoch_plan(items.numel(), B, self.prefetch, self.drop_last):
-            yield from self._emit(items[start:start + G * width].reshape(G, width), None, batch0 + start // B)
-
 
 SAINT_FIELDS = ("node_norm", "edge_norm")   # what a GraphSAINT loader with sample_coverage > 0 adds to a mini-batch
 SAINT_PRESAMPLE_CALL_ID0 = 1 << 62          # the pre-sample's call ids: a range no epoch reaches
 
 
-class _GraphSAINTLoader(_Loader):
+class _PooledLoader(_Loader):
+    """Loaders whose launches all write into one slab set, on the caller's stream: a live iterator owns a set and gives it
+    back to `_pool` when it ends or is dropped, so a second epoch allocates nothing and two live iterators never share.
+    A loader supplies `_new_slab`, `_epoch_state` (what an epoch's launches share), `_launch` (mini-batches j .. j + G - 1
+    of that epoch into the slab set -> (call_id0 of the super-batch, node counts, edge counts) as the host reads them
+    back) and `_emit` (-> what SuperBatch._set_flat takes ahead of `perm`); `perm`, `_node_attrs` and `_edge_attrs` are its
+    own."""
+
+    def _init_pool(self):
+        self._pool = []                      # slab sets of finished iterators (each live iterator owns its own)
+        self.slab_allocations = 0            # slab sets made so far: a second epoch makes none
+        self.epoch = 0
+
+    def _take_slab(self):
+        if self._pool:
+            return self._pool.pop()
+        self.slab_allocations += 1
+        return self._new_slab()
+
+    def _finish(self, slab, G: int, call_id0: int, n_nodes, n_edges) -> SuperBatch:
+        sb = SuperBatch()
+        sb._set_flat(*self._emit(slab, G, n_nodes, n_edges), self.perm, self._node_attrs, self._edge_attrs)
+        sb.batch_size, sb.call_id0 = self.batch_size, call_id0
+        return sb
+
+    def super_batches(self) -> Iterator[SuperBatch]:
+        """The epoch as super-batches of up to `prefetch` mini-batches."""
+        epoch = self.epoch                   # captured: a second iterator is the next epoch
+        self.epoch += 1
+        state, n = self._epoch_state(epoch), len(self)
+        slab = self._take_slab()
+        try:
+            for j in range(0, n, self.prefetch):
+                G = min(self.prefetch, n - j)
+                yield self._finish(slab, G, *self._launch(slab, state, j, G))
+        finally:
+            self._pool.append(slab)
+
+
+class _GraphSAINTLoader(_PooledLoader):
     """What GraphSAINT's three samplers share: everything but the step that makes a mini-batch's node list.  The argument
-    checks, the CSC, the attributes, the slab sets and their pool, a launch's read-back, the pre-sample with its two norms,
-    the super-batches.  A sampler supplies `_own_arguments` (its own checks; -> the positions P of a mini-batch and their
+    checks, the CSC, the attributes, the slab sets, a launch's read-back, the pre-sample with its two norms.  A sampler
+    supplies `_own_arguments` (its own checks; -> the positions P of a mini-batch and their
     name in the refusal), `_prepare` (its graphs, once), `_workspace_bytes`, `_fill` (the node lists of mini-batches
     call_id .. call_id + G - 1 into slab["nodes"] / slab["counts"], refusals into slab["status"]) and `_status_message`."""
 
-    def __init__(self, data, batch_size: int, num_steps: int, sample_coverage: int, prefetch: int, seed: int, call_id0: int,
-                 device, form: int):
-        B, S = int(batch_size), int(num_steps)
-        if B < 1:                            # everything that can be refused is refused before any device work
-            raise ValueError("batch_size must be at least 1, got %r" % (batch_size,))
-        self.batch_size = B
+    def __init__(self, data, batch_size: int, num_steps: int, sample_coverage: int = 0, prefetch: int = 16, seed: int = 0,
+                 call_id0: int = 0, device="cuda", form: int = 0):
+        S = int(num_steps)
+        _at_least_1("batch_size", batch_size)    # everything that can be refused is refused before any device work
+        self.batch_size = int(batch_size)
         positions, named = self._own_arguments()
-        if S < 1:
-            raise ValueError("num_steps must be at least 1, got %r" % (num_steps,))
+        _at_least_1("num_steps", num_steps)
         if int(sample_coverage) < 0:
             raise ValueError("sample_coverage must not be negative, got %r" % (sample_coverage,))
-        if int(prefetch) < 1:
-            raise ValueError("prefetch must be at least 1, got %r" % (prefetch,))
+        _at_least_1("prefetch", prefetch)
         if int(form) not in (0, 1, 2):
             raise ValueError("form must be 0 (auto), 1 (LDS) or 2 (flat), got %r" % (form,))
         if positions > 2 ** 30:
@@ -1859,9 +1898,7 @@ class _GraphSAINTLoader(_Loader):
         if not 1 <= N <= 2 ** 31:
             raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
         if int(sample_coverage) > 0:
-            for key, value in _tensor_items(data):   # the mini-batches' own node_norm / edge_norm would hide them
-                if key in SAINT_FIELDS and _attr_kind(key, value, N, E) in ("node", "edge"):
-                    raise ValueError("a GraphSAINT loader's mini-batches carry their own `%s`: rename data.%s" % (key, key))
+            _refuse_reserved(data, SAINT_FIELDS, "a GraphSAINT loader's")
         self.data, self.num_steps = data, S
         self.sample_coverage, self.prefetch = int(sample_coverage), int(prefetch)
         self.seed, self.call_id0, self.form = int(seed), int(call_id0), int(form)
@@ -1870,35 +1907,19 @@ class _GraphSAINTLoader(_Loader):
         self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
         self._graph = self._view(self.col_ptrs, self.row_indices)
         self._prepare()
-        self._node_attrs, self._edge_attrs = [], []
-        for key, value in _tensor_items(data):
-            kind = _attr_kind(key, value, N, E)
-            if kind == "node":
-                self._node_attrs.append((key, value.to(self.device)))
-            elif kind == "edge":
-                self._edge_attrs.append((key, value.to(self.device)))
+        self._node_attrs, self._edge_attrs = _split_attrs(data, N, E, self.device)
         self.positions = positions
-        self._pool = []                      # slab sets of finished iterators (each live iterator owns its own)
-        self.slab_allocations = 0            # slab sets made so far: a second epoch makes none
-        self.epoch = 0
+        self._init_pool()
         self.node_norm = self.edge_norm = None
         self.presampled_launches = self.presampled_batches = 0
         if self.sample_coverage > 0:
             self._presample()
 
-    def _view(self, ptrs, indices):
-        """a graph view with the u32 shadows where they hold the same words"""
-        kw = dict(indices32=indices.to(torch.int32), ptrs32=ptrs.to(torch.int32)) if self._n_edges < 2 ** 31 else {}
-        return _cabi.graph_view(ptrs, indices, **kw)
-
-    def _out_graph(self):
-        """the CSR (out-edges), built once with the device ingest -> its view"""
-        ei = self.data.edge_index.to(self.device)
-        row_ptrs, col_indices, _ = _cabi.coo_to_csx(ei[0], ei[1], self.n_nodes, self.n_nodes, False)
-        return self._view(row_ptrs, col_indices)
-
     def __len__(self) -> int:
         return self.num_steps
+
+    def _workspace_bytes(self, cap: int) -> int:
+        return _cabi.saint_ne_workspace_bytes(cap, self.positions, self.form)[0]   # the node and the edge sampler's
 
     def _new_slab(self):
         """what a launch of up to `prefetch` mini-batches writes (an epoch's launches may be narrower; the pre-sample's are
@@ -1906,7 +1927,6 @@ class _GraphSAINTLoader(_Loader):
         word in one tensor, the induced pair's launch object (its counts, status and workspace), the flat form's workspace
         and the pinned image of everything the host reads back"""
         cap, dev = self.prefetch, self.device
-        self.slab_allocations += 1
         nodes = torch.empty((cap, self.positions), dtype=torch.int64, device=dev)
         state = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
         counts, status = state[:cap], state[-1:].view(torch.int32)[:1]
@@ -1916,10 +1936,13 @@ class _GraphSAINTLoader(_Loader):
         host = torch.empty(state.numel() + ind.state.numel(), dtype=torch.int64).pin_memory()
         return dict(nodes=nodes, state=state, counts=counts, status=status, ws=ws, ind=ind, host=host)
 
-    def _launch(self, slab, call_id: int, G: int):
-        """mini-batches call_id .. call_id + G - 1 into the slab set -> (node counts, edge counts) as python lists, after the
-        launch's one read-back; pass 2 of the induced pair has not run yet"""
-        cap = self.prefetch
+    def _epoch_state(self, epoch: int) -> int:
+        return self.call_id0 + epoch * self.num_steps            # the call id of the epoch's first mini-batch
+
+    def _launch(self, slab, first: int, j: int, G: int):
+        """mini-batches call_id = first + j .. call_id + G - 1 into the slab set -> (call_id, node counts, edge counts), the
+        counts as python lists after the launch's one read-back; pass 2 of the induced pair has not run yet"""
+        cap, call_id = self.prefetch, first + j
         slab["state"][-1:].zero_()
         self._fill(slab, call_id, G)
         ind = slab["ind"].count(G)
@@ -1932,7 +1955,7 @@ class _GraphSAINTLoader(_Loader):
         if status:
             raise RuntimeError("%s: %s" % (who, self._status_message(status)))
         _cabi.induced_status_check(int(host[-1:].view(torch.int32)[0]), who)
-        return host[:G].tolist(), host[cap + 1:cap + 1 + G].tolist()
+        return call_id, host[:G].tolist(), host[cap + 1:cap + 1 + G].tolist()
 
     def _presample(self):
         """whole launches under call ids from 1 << 62 until the node lists' sizes reach N * sample_coverage; their nodes
@@ -1941,10 +1964,10 @@ class _GraphSAINTLoader(_Loader):
         node_count = torch.zeros(self.n_nodes, dtype=torch.int64, device=dev)
         edge_count = torch.zeros(self._n_edges, dtype=torch.int64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        slab = self._new_slab()
+        slab = self._take_slab()
         covered, launches = 0, 0
         while covered < self.n_nodes * self.sample_coverage:
-            n_nodes, n_edges = self._launch(slab, SAINT_PRESAMPLE_CALL_ID0 + launches * G, G)
+            _, n_nodes, n_edges = self._launch(slab, SAINT_PRESAMPLE_CALL_ID0, launches * G, G)
             _, offsets, _ = _cabi.ns_induced_emit(slab["ind"], n_edges)
             _cabi.saint_coverage_add(slab["nodes"], slab["counts"], node_count, edge_count, edge_ids=offsets, status=status,
                                      n_batches=G)
@@ -1956,47 +1979,17 @@ class _GraphSAINTLoader(_Loader):
         if int(status.item()):
             raise RuntimeError("%s: an id outside the coverage tables" % type(self).__name__)
 
-    def _finish(self, slab, call_id: int, G: int, n_nodes, n_edges) -> SuperBatch:
+    def _emit(self, slab, G: int, n_nodes, n_edges):
         edge_index, e_ptr, _ = _cabi.ns_induced_emit(slab["ind"], n_edges)
-        total = sum(n_nodes)
-        n_id = _flat_rows(slab["nodes"][:G], slab["counts"][:G], total)   # copies: the slabs go back to the sampler
-        sb = SuperBatch()
-        sb.input_time = sb.node_time = sb.batch = sb.root_n_id = None
-        sb.n_id, sb.edge_index = n_id, edge_index
-        sb._e_id, sb._e_ptr, sb._perm = None, e_ptr, self.perm
-        sb.node_attrs = {k: _rows_of(v, n_id) for k, v in self._node_attrs}
-        sb.edge_attrs = {k: _rows_of(v, sb.e_id) for k, v in self._edge_attrs}
+        n_id = _flat_rows(slab["nodes"][:G], slab["counts"][:G], sum(n_nodes))   # copies: the slabs go back to the sampler
+        return n_id, edge_index, e_ptr, _ptr_list(n_nodes), _ptr_list(n_edges)
+
+    def _finish(self, slab, G: int, call_id: int, n_nodes, n_edges) -> SuperBatch:
+        sb = super()._finish(slab, G, call_id, n_nodes, n_edges)
         if self.node_norm is not None:       # like attributes: the view machinery cuts them per mini-batch
-            sb.node_attrs["node_norm"] = _rows_of(self.node_norm, n_id)
-            sb.edge_attrs["edge_norm"] = _rows_of(self.edge_norm, e_ptr)
-        ptr_n, ptr_e, a, e = [0], [0], 0, 0
-        for x, y in zip(n_nodes, n_edges):
-            a += x
-            e += y
-            ptr_n.append(a)
-            ptr_e.append(e)
-        sb.node_ptr, sb.edge_ptr = ptr_n, ptr_e
-        sb.layer_offsets = sb.layer_nodes = sb.layer_edges = sb.seed_counts = None
-        sb.batch_size, sb.call_id0, sb.n_hops = self.batch_size, call_id, 0
+            sb.node_attrs["node_norm"] = _rows_of(self.node_norm, sb.n_id)
+            sb.edge_attrs["edge_norm"] = _rows_of(self.edge_norm, sb._e_ptr)
         return sb
-
-    def super_batches(self) -> Iterator[SuperBatch]:
-        """The epoch as super-batches of up to `prefetch` mini-batches."""
-        epoch = self.epoch                   # captured: a second iterator is the next epoch
-        self.epoch += 1
-        first = self.call_id0 + epoch * self.num_steps
-        slab = self._pool.pop() if self._pool else self._new_slab()
-        try:
-            for j in range(0, self.num_steps, self.prefetch):
-                G = min(self.prefetch, self.num_steps - j)
-                n_nodes, n_edges = self._launch(slab, first + j, G)
-                yield self._finish(slab, first + j, G, n_nodes, n_edges)
-        finally:
-            self._pool.append(slab)
-
-    def __iter__(self) -> Iterator[MiniBatch]:
-        for sb in self.super_batches():
-            yield from sb
 
 
 class GraphSAINTRandomWalkLoader(_GraphSAINTLoader):
@@ -2056,19 +2049,12 @@ class GraphSAINTNodeLoader(_GraphSAINTLoader):
     `MiniBatch` views, sample_coverage and the two norms -- is GraphSAINTRandomWalkLoader's.  A mini-batch's `batch_size`
     is the draw count; `n_id` is in order of first draw."""
 
-    def __init__(self, data, batch_size: int, num_steps: int, sample_coverage: int = 0, prefetch: int = 16, seed: int = 0,
-                 call_id0: int = 0, device="cuda", form: int = 0):
-        super().__init__(data, batch_size, num_steps, sample_coverage, prefetch, seed, call_id0, device, form)
-
     def _own_arguments(self):
         return self.batch_size, "batch_size"
 
     def _prepare(self):
         if self._n_edges < 1:
             raise ValueError("the node sampler draws the sources of edges: the graph has none")
-
-    def _workspace_bytes(self, cap: int) -> int:
-        return _cabi.saint_ne_workspace_bytes(cap, self.positions, self.form)[0]
 
     def _fill(self, slab, call_id: int, G: int):
         _cabi.saint_node_nodes(self._graph, self.batch_size, G, self.seed, call_id, id_bound=self.n_nodes, form=self.form,
@@ -2106,9 +2092,6 @@ class GraphSAINTEdgeLoader(_GraphSAINTLoader):
         self.cols = nonempty(self.col_ptrs)
         self.rows = self.cols if self.symmetric else nonempty(self._out._keep[0])
 
-    def _workspace_bytes(self, cap: int) -> int:
-        return _cabi.saint_ne_workspace_bytes(cap, self.positions, self.form)[0]
-
     def _fill(self, slab, call_id: int, G: int):
         _cabi.saint_edge_nodes(self._graph, self.cols, self._out, self.rows, self.batch_size, G, self.seed, call_id,
                                id_bound=self.n_nodes, form=self.form, ws=slab["ws"], out=(slab["nodes"], slab["counts"]),
@@ -2116,6 +2099,123 @@ class GraphSAINTEdgeLoader(_GraphSAINTLoader):
 
     def _status_message(self, status: int) -> str:
         return "a drawn edge outside the graph" if status & 2 else "a listed column or row without entries"
+
+
+class _Block:
+    """One layer of a block mini-batch: `n_id` (the source nodes; its first `n_dst` entries are the destination nodes, the
+    previous frontier in order), `edge_index` [2, E] numbered against n_id, and one tensor [E] more under the name a subclass
+    declares (PAYLOAD, also its one slot): what `num_edges` counts."""
+    __slots__ = ("n_id", "n_dst", "edge_index")
+
+    def __init__(self, n_id, n_dst, edge_index, payload):
+        self.n_id, self.n_dst, self.edge_index = n_id, n_dst, edge_index
+        setattr(self, self.PAYLOAD, payload)
+
+    @property
+    def num_src_nodes(self):
+        return self.n_id.numel()
+
+    @property
+    def num_edges(self):
+        return getattr(self, self.PAYLOAD).numel()
+
+
+class _BlockBatch:
+    """Mini-batch j of a _BlockSuperBatch: `blocks` (of the subclass's BLOCK) outermost first as in DGL ([block_{L-1}, ...,
+    block_0]), `n_id` = the outermost block's source nodes, the node attributes of the data gathered by n_id, `batch_size`
+    and `input_nodes` (the seeds = the first `batch_size` entries of n_id); under CALL_ID also `call_id`, layer 0's."""
+    CALL_ID = False
+
+    def __init__(self, sb, j):
+        self.batch_size = sb.seed_ptr[j + 1] - sb.seed_ptr[j]
+        self.input_nodes = sb.input_nodes[sb.seed_ptr[j]:sb.seed_ptr[j + 1]]
+        if self.CALL_ID:
+            self.call_id = sb.call_id0 + j * sb.n_layers
+        self.blocks = []
+        for lay in reversed(sb.layers):
+            n0, n1 = lay["src_ptr"][j], lay["src_ptr"][j + 1]
+            e0, e1 = lay["edge_ptr"][j], lay["edge_ptr"][j + 1]
+            self.blocks.append(self.BLOCK(lay["n_id"][n0:n1], lay["dst_ptr"][j + 1] - lay["dst_ptr"][j],
+                                          lay["edge_index"][:, e0:e1], lay[self.BLOCK.PAYLOAD][e0:e1]))
+        self.n_id = self.blocks[0].n_id
+        n0, n1 = sb.node_ptr[j], sb.node_ptr[j + 1]
+        self._attrs = {k: v[n0:n1] for k, v in sb.node_attrs.items()}
+
+    @property
+    def num_nodes(self):
+        return self.n_id.numel()
+
+    def __getattr__(self, name):
+        attrs = self.__dict__.get("_attrs", {})
+        if name in attrs:
+            return attrs[name]
+        raise AttributeError(name)
+
+
+class _BlockSuperBatch(_Indexable):
+    """The mini-batches of ONE launch as flat batch-major device tensors with python pointer lists: `n_layers`, per layer l
+    `layers[l]` = dict(n_id, src_ptr, dst_ptr, edge_index (numbered inside each mini-batch), the payload, edge_ptr); `n_id` /
+    `node_ptr` of the last layer, `node_attrs` gathered once by it; `input_nodes` / `seed_ptr`.  Iterating or indexing
+    yields views of the subclass's BATCH."""
+
+    def _at(self, j):
+        return self.BATCH(self, j)
+
+
+class _BlockLoader(_Loader):
+    """What the loaders of DGL-style blocks share.  Distinct seeds per mini-batch, checked on the host; the CSC with its
+    shadows and the node attributes on the device; an epoch as launches of up to `prefetch` mini-batches, shuffled by
+    (seed, epoch); a launch as `n_layers` layers over the flat concatenation of its mini-batches' frontiers -- F_{l+1} = F_l
+    followed by what layer l adds -- with the node attributes gathered by F_L.  A loader supplies SUPER_BATCH, `_block`
+    (layer l of a launch -> its entry of `layers`) and, where the layers pass on more than the frontier, `_launch_state`."""
+
+    def __init__(self, data, n_layers: int, input_nodes, batch_size: int, prefetch: int, shuffle: bool, drop_last: bool,
+                 seed: int, device):
+        N, B = _num_nodes(data), int(batch_size)
+        if not 1 <= N <= 2 ** 31:
+            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
+        nodes = _checked_inputs(None if input_nodes is None else input_nodes.detach().cpu(), N)
+        if input_nodes is not None and nodes.numel():
+            # a frontier lists a node once: two equal seeds in one mini-batch would be two slots of F_0
+            batch_of = torch.zeros_like(nodes) if shuffle else torch.arange(nodes.numel()) // B
+            key = torch.sort(batch_of * N + nodes).values
+            if bool((key[1:] == key[:-1]).any()):
+                raise ValueError("input_nodes holds a node twice " + ("(shuffle=True: anywhere)" if shuffle else
+                                                                      "inside one mini-batch"))
+        self.data, self.n_layers, self.batch_size = data, n_layers, B
+        self.prefetch, self.seed = int(prefetch), int(seed)
+        self.shuffle, self.drop_last = bool(shuffle), bool(drop_last)
+        self.device = torch.device(device)
+        self.n_nodes, self._n_edges = N, int(data.edge_index.shape[1])
+        self.input_nodes = nodes.to(self.device)
+        self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
+        self._graph = self._view(self.col_ptrs, self.row_indices)
+        self._node_attrs = _split_attrs(data, N, self._n_edges, self.device, edges=False)[0]
+        self.epoch = 0
+
+    def _launch_state(self, sb, G: int, width: int, first_batch: int):
+        """What the layers of a launch pass on beside the frontier: handed to every `_block` of the launch."""
+
+    def _launch(self, seeds: Tensor, first_batch: int):
+        """seeds [G, width]: mini-batches first_batch .. first_batch + G - 1 of the run (epoch * len(self) + j)"""
+        G, width = seeds.shape
+        sb = self.SUPER_BATCH()
+        sb.n_layers = self.n_layers
+        sb.input_nodes = frontier = seeds.reshape(-1).contiguous()
+        sb.seed_ptr = ptr = [g * width for g in range(G + 1)]
+        state = self._launch_state(sb, G, width, first_batch)
+        sb.layers = []
+        for l in range(self.n_layers):
+            sb.layers.append(self._block(l, frontier, ptr, first_batch, state))
+            frontier, ptr = sb.layers[-1]["n_id"], sb.layers[-1]["src_ptr"]
+        sb.n_id, sb.node_ptr = frontier, ptr
+        sb.node_attrs = {k: _rows_of(v, frontier) for k, v in self._node_attrs}
+        return sb
+
+    def super_batches(self):
+        """The epoch as launches of up to `prefetch` mini-batches."""
+        for (seeds,), first_batch in self._epoch_launches(self.input_nodes):
+            yield self._launch(seeds, first_batch)
 
 
 class _PinSAGESlabs:
@@ -2135,76 +2235,25 @@ class _PinSAGESlabs:
     struct = _cabi.NsBatchedOut.struct
 
 
-class PinSAGEBlock:
-    """One layer of a PinSAGE mini-batch: `n_id` (the source nodes; its first `n_dst` entries are the destination nodes,
-    the previous frontier in order), `edge_index` [2, E] (row = position in n_id of the neighbour, col = position of the
-    destination) and `edge_weight` [E] int64, the visit counts."""
-    __slots__ = ("n_id", "n_dst", "edge_index", "edge_weight")
-
-    def __init__(self, n_id, n_dst, edge_index, edge_weight):
-        self.n_id, self.n_dst, self.edge_index, self.edge_weight = n_id, n_dst, edge_index, edge_weight
-
-    @property
-    def num_src_nodes(self):
-        return self.n_id.numel()
-
-    @property
-    def num_edges(self):
-        return self.edge_weight.numel()
+class PinSAGEBlock(_Block):
+    """One layer of a PinSAGE mini-batch: a _Block with `edge_index` [2, E] (row = position in n_id of the neighbour, col =
+    position of the destination) and `edge_weight` [E] int64, the visit counts."""
+    PAYLOAD = "edge_weight"
+    __slots__ = (PAYLOAD,)
 
 
-class PinSAGEBatch:
-    """Mini-batch j of a PinSAGESuperBatch: `blocks` outermost first as in DGL ([block_{L-1}, ..., block_0]), `n_id` = the
-    outermost block's source nodes, the node attributes of the data gathered by n_id, `input_nodes` (the seeds = the first
-    `batch_size` entries of n_id), `call_id` of layer 0."""
-
-    def __init__(self, sb, j):
-        self.batch_size = sb.seed_ptr[j + 1] - sb.seed_ptr[j]
-        self.input_nodes = sb.input_nodes[sb.seed_ptr[j]:sb.seed_ptr[j + 1]]
-        self.call_id = sb.call_id0 + j * sb.n_layers
-        self.blocks = []
-        for l in reversed(range(sb.n_layers)):
-            lay = sb.layers[l]
-            n0, n1 = lay["src_ptr"][j], lay["src_ptr"][j + 1]
-            e0, e1 = lay["edge_ptr"][j], lay["edge_ptr"][j + 1]
-            self.blocks.append(PinSAGEBlock(lay["n_id"][n0:n1], lay["dst_ptr"][j + 1] - lay["dst_ptr"][j],
-                                            lay["edge_index"][:, e0:e1], lay["edge_weight"][e0:e1]))
-        self.n_id = self.blocks[0].n_id
-        n0, n1 = sb.node_ptr[j], sb.node_ptr[j + 1]
-        self._attrs = {k: v[n0:n1] for k, v in sb.node_attrs.items()}
-
-    @property
-    def num_nodes(self):
-        return self.n_id.numel()
-
-    def __getattr__(self, name):
-        attrs = self.__dict__.get("_attrs", {})
-        if name in attrs:
-            return attrs[name]
-        raise AttributeError(name)
+class PinSAGEBatch(_BlockBatch):
+    """Mini-batch j of a PinSAGESuperBatch: a _BlockBatch of PinSAGEBlocks with the `call_id` of layer 0."""
+    BLOCK, CALL_ID = PinSAGEBlock, True
 
 
-class PinSAGESuperBatch:
-    """The mini-batches of ONE launch as flat batch-major device tensors: per layer l `layers[l]` = dict(n_id, src_ptr,
-    dst_ptr, edge_index (numbered inside each mini-batch), edge_weight, edge_ptr); `n_id` / `node_ptr` of the last layer,
-    `node_attrs` gathered once by it; `input_nodes` / `seed_ptr`; `call_id0` (layer 0 of mini-batch 0)."""
-
-    def __len__(self):
-        return len(self.node_ptr) - 1
-
-    def __getitem__(self, j):
-        if j < 0:
-            j += len(self)
-        if not 0 <= j < len(self):
-            raise IndexError(j)
-        return PinSAGEBatch(self, j)
-
-    def __iter__(self):
-        for j in range(len(self)):
-            yield PinSAGEBatch(self, j)
+class PinSAGESuperBatch(_BlockSuperBatch):
+    """A launch of PinSAGELoader: a _BlockSuperBatch whose layers carry `edge_weight`, with `call_id0` (layer 0 of
+    mini-batch 0)."""
+    BATCH = PinSAGEBatch
 
 
-class PinSAGELoader(_Loader):
+class PinSAGELoader(_BlockLoader):
     """PinSAGE's importance sampler (DGL's PinSAGESampler / RandomWalkNeighborSampler) as a loader: the neighbours of a
     node are the k_l nodes that `n_walks` random walks of up to `walk_length` steps from it visit most often (each walk
     ends before a step l >= 1 with probability `termination`), the visit counts are the edge weights
@@ -2233,194 +2282,86 @@ class PinSAGELoader(_Loader):
             raise ValueError("num_neighbors must name at least one layer")
         if any(not 1 <= k <= 64 for k in fanout):
             raise ValueError("num_neighbors must be in 1..64 per layer, got %r" % (list(num_neighbors),))
-        B, R, T = int(batch_size), int(n_walks), int(walk_length)
-        if B < 1:
-            raise ValueError("batch_size must be at least 1, got %r" % (batch_size,))
-        if R < 1:
-            raise ValueError("n_walks must be at least 1, got %r" % (n_walks,))
-        if T < 1:
-            raise ValueError("walk_length must be at least 1, got %r" % (walk_length,))
+        R, T = int(n_walks), int(walk_length)
+        _at_least_1("batch_size", batch_size)
+        _at_least_1("n_walks", n_walks)
+        _at_least_1("walk_length", walk_length)
         if R * T > _cabi.PINSAGE_MAX_VISITS:
             raise ValueError("n_walks * walk_length = %d visits per node exceed %d" % (R * T, _cabi.PINSAGE_MAX_VISITS))
         alpha = float(termination)
         if not 0.0 <= alpha < 1.0:                       # a NaN fails both comparisons
             raise ValueError("termination must be in [0, 1), got %r" % (termination,))
-        if int(prefetch) < 1:
-            raise ValueError("prefetch must be at least 1, got %r" % (prefetch,))
+        _at_least_1("prefetch", prefetch)
         if not 0 <= int(call_id0) < 2 ** 62:
             raise ValueError("call_id0 must be in [0, 2^62), got %r" % (call_id0,))
-        N = _num_nodes(data)
-        if not 1 <= N <= 2 ** 31:
-            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
-        nodes = torch.arange(N) if input_nodes is None else input_nodes.detach().cpu().reshape(-1).to(torch.int64)
-        if nodes.numel() and (int(nodes.min()) < 0 or int(nodes.max()) >= N):
-            raise IndexError("input_nodes outside [0, %d)" % N)
-        if input_nodes is not None and nodes.numel():
-            # a frontier lists a node once: two equal seeds in one mini-batch would be two slots of F_0
-            batch_of = torch.zeros_like(nodes) if shuffle else torch.arange(nodes.numel()) // B
-            key = torch.sort(batch_of * N + nodes).values
-            if bool((key[1:] == key[:-1]).any()):
-                raise ValueError("input_nodes holds a node twice " + ("(shuffle=True: anywhere)" if shuffle else
-                                                                      "inside one mini-batch"))
-        self.data, self.fanout, self.batch_size = data, fanout, B
+        super().__init__(data, len(fanout), input_nodes, batch_size, prefetch, shuffle, drop_last, seed, device)
+        self.fanout, self.call_id0 = fanout, int(call_id0)
         self.n_walks, self.walk_length, self.termination = R, T, alpha
-        self.prefetch, self.seed, self.call_id0 = int(prefetch), int(seed), int(call_id0)
-        self.shuffle, self.drop_last = bool(shuffle), bool(drop_last)
         self.symmetric, self.walk_out_edges = bool(symmetric), bool(walk_out_edges)
-        self.device = torch.device(device)
-        self.n_nodes = N
-        self.input_nodes = nodes.to(self.device)
-        self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
-        E = int(data.edge_index.shape[1])
-        small = E < 2 ** 31
-        shadows = lambda ptrs, idx: dict(indices32=idx.to(torch.int32), ptrs32=ptrs.to(torch.int32)) if small else {}
-        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, **shadows(self.col_ptrs, self.row_indices))
-        if self.walk_out_edges and not self.symmetric:   # out-edges: the CSR, built once
-            ei = data.edge_index.to(self.device)
-            row_ptrs, col_indices, _ = _cabi.coo_to_csx(ei[0], ei[1], N, N, False)
-            self._csr = (row_ptrs, col_indices)
-            self._walk_graph = _cabi.graph_view(row_ptrs, col_indices, **shadows(row_ptrs, col_indices))
-        else:
-            self._walk_graph = self._graph
-        self._node_attrs = [(k, v.to(self.device)) for k, v in _tensor_items(data) if _attr_kind(k, v, N, E) == "node"]
-        self.epoch = 0
+        # out-edges: the CSR, built once
+        self._walk_graph = self._out_graph() if self.walk_out_edges and not self.symmetric else self._graph
 
-    def _launch(self, seeds: Tensor, first_batch: int) -> PinSAGESuperBatch:
-        """seeds [G, width]: mini-batches first_batch .. first_batch + G - 1 of the run (epoch * len(self) + j)"""
-        dev, L = self.device, len(self.fanout)
-        G, width = seeds.shape
-        o = dict(dtype=torch.int64, device=dev)
+    SUPER_BATCH = PinSAGESuperBatch
+
+    def _launch_state(self, sb, G: int, width: int, first_batch: int):
+        sb.call_id0 = self.call_id0 + first_batch * self.n_layers
+        return {"group": torch.arange(G, device=self.device).repeat_interleave(width),   # the mini-batch of every frontier slot: ascending
+                "status": torch.zeros(1, dtype=torch.int32, device=self.device)}
+
+    def _block(self, l: int, frontier: Tensor, ptr: List[int], first_batch: int, state):
+        """the hop over the launch's frontiers, the grouped dedup and the relabel -> layer l; the next layer's groups go
+        into `state`"""
+        L, G, group, status = self.n_layers, len(ptr) - 1, state["group"], state["status"]
+        o = dict(dtype=torch.int64, device=self.device)
         arange = lambda n: torch.arange(n, **o)
-        sb = PinSAGESuperBatch()
-        sb.n_layers, sb.call_id0 = L, self.call_id0 + first_batch * L
-        sb.input_nodes = frontier = seeds.reshape(-1).contiguous()
-        sb.seed_ptr = ptr = [g * width for g in range(G + 1)]
-        group = arange(G).repeat_interleave(width)       # the mini-batch of every frontier slot: ascending
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-        sb.layers = []
-        for l, k in enumerate(self.fanout):
-            n = frontier.numel()
-            start = torch.tensor(ptr, **o)
-            local = arange(n) - start[group]             # the slot's index inside its own mini-batch's frontier
-            call_ids = (self.call_id0 + first_batch * L + l) + group * L
-            cnt, offsets, nbr, par, vis = _cabi.pinsage_hop(self._walk_graph, frontier, k, self.n_walks, self.walk_length,
-                                                            self.termination, self.seed, 0, call_ids=call_ids, ids=local,
-                                                            status=status)
-            slabs = _PinSAGESlabs(frontier, nbr, par, offsets[n])
-            u = _cabi.ns_homo_unique_grouped(slabs, 1, self.n_nodes, seed_group=group.to(torch.int32), n_groups=G)
-            cap = slabs.samples.shape[1]
-            g_of = torch.where(arange(cap) < u.counts[0, 0], u.group[0], torch.full((), G, **o))
-            sizes = torch.zeros(G + 1, **o).scatter_add_(0, g_of, torch.ones(cap, **o))
-            host = torch.cat([sizes[:G], offsets[start], status.to(torch.int64)]).tolist()   # the layer's ONE read-back
-            if host[-1]:
-                raise RuntimeError("%s: a frontier node outside the graph" % type(self).__name__)
-            n_next, eptr = host[:G], host[G:2 * G + 1]
-            nptr = [0]
-            for x in n_next:
-                nptr.append(nptr[-1] + x)
-            total, n_edges = nptr[-1], eptr[-1]
-            order = torch.sort(g_of, stable=True).indices[:total]     # grouped by mini-batch, first occurrence first
-            rank = torch.empty(cap, **o)
-            rank[order] = arange(total)
-            n_id, next_group = u.nodes[0][order], g_of[order]
-            next_start = torch.tensor(nptr, **o)
-            par_e, e_group = par[:n_edges], group[par[:n_edges]]
-            row = rank[u.inverse[0, n:n + n_edges]] - next_start[e_group]
-            col = par_e - start[e_group]
-            sb.layers.append(dict(n_id=n_id, src_ptr=nptr, dst_ptr=ptr, edge_index=torch.stack([row, col]),
-                                  edge_weight=vis[:n_edges].clone(), edge_ptr=eptr))
-            frontier, group, ptr = n_id, next_group, nptr
-        sb.n_id, sb.node_ptr = frontier, ptr
-        sb.node_attrs = {k: _rows_of(v, frontier) for k, v in self._node_attrs}
-        return sb
-
-    def super_batches(self) -> Iterator[PinSAGESuperBatch]:
-        """The epoch as launches of up to `prefetch` mini-batches."""
-        nodes = self.input_nodes
-        epoch = self.epoch                               # captured: a second iterator is the next epoch
-        self.epoch += 1
-        batch0 = epoch * len(self)
-        if self.shuffle:
-            gen = torch.Generator(device=self.device)
-            gen.manual_seed(self.seed * 1000003 + epoch)
-            nodes = nodes[torch.randperm(nodes.numel(), device=self.device, generator=gen)]
-        for start, G, width in _epoch_plan(nodes.numel(), self.batch_size, self.prefetch, self.drop_last):
-            yield self._launch(nodes[start:start + G * width].reshape(G, width), batch0 + start // self.batch_size)
-
-    def __iter__(self) -> Iterator[PinSAGEBatch]:
-        for sb in self.super_batches():
-            yield from sb
+        n = frontier.numel()
+        start = torch.tensor(ptr, **o)
+        local = arange(n) - start[group]                 # the slot's index inside its own mini-batch's frontier
+        call_ids = (self.call_id0 + first_batch * L + l) + group * L
+        cnt, offsets, nbr, par, vis = _cabi.pinsage_hop(self._walk_graph, frontier, self.fanout[l], self.n_walks,
+                                                        self.walk_length, self.termination, self.seed, 0, call_ids=call_ids,
+                                                        ids=local, status=status)
+        slabs = _PinSAGESlabs(frontier, nbr, par, offsets[n])
+        u = _cabi.ns_homo_unique_grouped(slabs, 1, self.n_nodes, seed_group=group.to(torch.int32), n_groups=G)
+        cap = slabs.samples.shape[1]
+        g_of = torch.where(arange(cap) < u.counts[0, 0], u.group[0], torch.full((), G, **o))
+        sizes = torch.zeros(G + 1, **o).scatter_add_(0, g_of, torch.ones(cap, **o))
+        host = torch.cat([sizes[:G], offsets[start], status.to(torch.int64)]).tolist()   # the layer's ONE read-back
+        if host[-1]:
+            raise RuntimeError("%s: a frontier node outside the graph" % type(self).__name__)
+        nptr, eptr = _ptr_list(host[:G]), host[G:2 * G + 1]
+        total, n_edges = nptr[-1], eptr[-1]
+        order = torch.sort(g_of, stable=True).indices[:total]     # grouped by mini-batch, first occurrence first
+        rank = torch.empty(cap, **o)
+        rank[order] = arange(total)
+        n_id, state["group"] = u.nodes[0][order], g_of[order]
+        next_start = torch.tensor(nptr, **o)
+        par_e, e_group = par[:n_edges], group[par[:n_edges]]
+        row = rank[u.inverse[0, n:n + n_edges]] - next_start[e_group]
+        col = par_e - start[e_group]
+        return dict(n_id=n_id, src_ptr=nptr, dst_ptr=ptr, edge_index=torch.stack([row, col]),
+                    edge_weight=vis[:n_edges].clone(), edge_ptr=eptr)
 
 
-class FullNeighborBlock:
-    """One layer of a full-neighbour mini-batch: `n_id` (the source nodes; its first `n_dst` entries are the destination
-    nodes, the previous frontier in order), `edge_index` [2, m] (row = position in n_id of the source, col = position of the
-    destination; EVERY in-edge of every destination, in (destination, CSC offset) order) and `e_id` [m], the edges' columns
-    in data.edge_index: data.edge_index[:, e_id] == n_id[edge_index]."""
-    __slots__ = ("n_id", "n_dst", "edge_index", "e_id")
-
-    def __init__(self, n_id, n_dst, edge_index, e_id):
-        self.n_id, self.n_dst, self.edge_index, self.e_id = n_id, n_dst, edge_index, e_id
-
-    @property
-    def num_src_nodes(self):
-        return self.n_id.numel()
-
-    @property
-    def num_edges(self):
-        return self.e_id.numel()
+class FullNeighborBlock(_Block):
+    """One layer of a full-neighbour mini-batch: a _Block with `edge_index` [2, m] (row = position in n_id of the source, col
+    = position of the destination; EVERY in-edge of every destination, in (destination, CSC offset) order) and `e_id` [m],
+    the edges' columns in data.edge_index: data.edge_index[:, e_id] == n_id[edge_index]."""
+    PAYLOAD = "e_id"
+    __slots__ = (PAYLOAD,)
 
 
-class FullNeighborBatch:
-    """Mini-batch j of a FullNeighborSuperBatch: `blocks` outermost first as in DGL ([block_{L-1}, ..., block_0]), `n_id` =
-    the outermost block's source nodes, the node attributes of the data gathered by n_id, `batch_size` and `input_nodes`
-    (the seeds = the first `batch_size` entries of n_id)."""
-
-    def __init__(self, sb, j):
-        self.batch_size = sb.seed_ptr[j + 1] - sb.seed_ptr[j]
-        self.input_nodes = sb.input_nodes[sb.seed_ptr[j]:sb.seed_ptr[j + 1]]
-        self.blocks = []
-        for lay in reversed(sb.layers):
-            n0, n1 = lay["src_ptr"][j], lay["src_ptr"][j + 1]
-            e0, e1 = lay["edge_ptr"][j], lay["edge_ptr"][j + 1]
-            self.blocks.append(FullNeighborBlock(lay["n_id"][n0:n1], lay["dst_ptr"][j + 1] - lay["dst_ptr"][j],
-                                                 lay["edge_index"][:, e0:e1], lay["e_id"][e0:e1]))
-        self.n_id = self.blocks[0].n_id
-        n0, n1 = sb.node_ptr[j], sb.node_ptr[j + 1]
-        self._attrs = {k: v[n0:n1] for k, v in sb.node_attrs.items()}
-
-    @property
-    def num_nodes(self):
-        return self.n_id.numel()
-
-    def __getattr__(self, name):
-        attrs = self.__dict__.get("_attrs", {})
-        if name in attrs:
-            return attrs[name]
-        raise AttributeError(name)
+class FullNeighborBatch(_BlockBatch):
+    """Mini-batch j of a FullNeighborSuperBatch: a _BlockBatch of FullNeighborBlocks (nothing is drawn: no call id)."""
+    BLOCK = FullNeighborBlock
 
 
-class FullNeighborSuperBatch:
-    """The mini-batches of ONE launch as flat batch-major device tensors with python pointer lists: per layer l `layers[l]` =
-    dict(n_id, src_ptr, dst_ptr, edge_index (numbered inside each mini-batch), e_id, edge_ptr); `n_id` / `node_ptr` of the
-    last layer, `node_attrs` gathered once by it; `input_nodes` / `seed_ptr`."""
-
-    def __len__(self):
-        return len(self.node_ptr) - 1
-
-    def __getitem__(self, j):
-        if j < 0:
-            j += len(self)
-        if not 0 <= j < len(self):
-            raise IndexError(j)
-        return FullNeighborBatch(self, j)
-
-    def __iter__(self):
-        for j in range(len(self)):
-            yield FullNeighborBatch(self, j)
+class FullNeighborSuperBatch(_BlockSuperBatch):
+    """A launch of FullNeighborLoader: a _BlockSuperBatch whose layers carry `e_id`."""
+    BATCH = FullNeighborBatch
 
 
-class FullNeighborLoader(_Loader):
+class FullNeighborLoader(_BlockLoader):
     """Every in-edge per layer: the loader of layer-wise inference (PyG's NeighborLoader(num_neighbors=[-1] * L), DGL's
     MultiLayerFullNeighborSampler(L)) over tg_ns_full_count / tg_ns_full_emit (csrc/ns_full.hip).  Nothing is sampled:
     a mini-batch is a function of the graph and its seeds.
@@ -2447,46 +2388,24 @@ class FullNeighborLoader(_Loader):
 
     def __init__(self, data, num_layers: int = 1, input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
                  prefetch: int = 16, shuffle: bool = False, drop_last: bool = False, seed: int = 0, device="cuda"):
-        L, B = int(num_layers), int(batch_size)
+        L = int(num_layers)
         if not 1 <= L <= _cabi.TG_MAX_HOPS:
             raise ValueError("num_layers must be in 1..%d, got %r" % (_cabi.TG_MAX_HOPS, num_layers))
-        if B < 1:
-            raise ValueError("batch_size must be at least 1, got %r" % (batch_size,))
-        if int(prefetch) < 1:
-            raise ValueError("prefetch must be at least 1, got %r" % (prefetch,))
+        _at_least_1("batch_size", batch_size)
+        _at_least_1("prefetch", prefetch)
         if _is_hetero(data):
             raise ValueError("FullNeighborLoader takes a homogeneous graph (typed graphs are out of scope)")
-        N = _num_nodes(data)
-        if not 1 <= N <= 2 ** 31:
-            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
-        nodes = torch.arange(N) if input_nodes is None else input_nodes.detach().cpu().reshape(-1).to(torch.int64)
-        if nodes.numel() and (int(nodes.min()) < 0 or int(nodes.max()) >= N):
-            raise IndexError("input_nodes outside [0, %d)" % N)
-        if input_nodes is not None and nodes.numel():
-            # a frontier lists a node once: two equal seeds in one mini-batch would be two destinations with one column
-            batch_of = torch.zeros_like(nodes) if shuffle else torch.arange(nodes.numel()) // B
-            key = torch.sort(batch_of * N + nodes).values
-            if bool((key[1:] == key[:-1]).any()):
-                raise ValueError("input_nodes holds a node twice " + ("(shuffle=True: anywhere)" if shuffle else
-                                                                      "inside one mini-batch"))
-        self.data, self.num_layers, self.batch_size = data, L, B
-        self.prefetch, self.seed = int(prefetch), int(seed)
-        self.shuffle, self.drop_last = bool(shuffle), bool(drop_last)
-        self.device = torch.device(device)
-        self.n_nodes = N
-        self.input_nodes = nodes.to(self.device)
-        self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
-        E = int(data.edge_index.shape[1])
-        shadows = dict(indices32=self.row_indices.to(torch.int32), ptrs32=self.col_ptrs.to(torch.int32)) if E < 2 ** 31 else {}
-        self._graph = _cabi.graph_view(self.col_ptrs, self.row_indices, **shadows)
-        self._node_attrs = [(k, v.to(self.device)) for k, v in _tensor_items(data) if _attr_kind(k, v, N, E) == "node"]
+        super().__init__(data, L, input_nodes, batch_size, prefetch, shuffle, drop_last, seed, device)
+        self.num_layers = L
+        N, E, B = self.n_nodes, self._n_edges, self.batch_size
         # the kept capacities per layer (distinct nodes, chunks per mini-batch): a guess from the mean degree that grows
         mean = (E + N - 1) // N
         self._node_cap = [min(_cabi.NS_FULL_MAX_NODES, B * (2 + 2 * mean))] * L
         self._chunk_cap = [2 * B + self._node_cap[0] // 512] * L
         self._ws = None
         self.growths = 0
-        self.epoch = 0
+
+    SUPER_BATCH = FullNeighborSuperBatch
 
     def _layer(self, l: int, frontier: Tensor, ptr: List[int], first_batch: int):
         """the pair over the launch's lists -> (host n_out, host m, the counted NsFull)"""
@@ -2517,50 +2436,17 @@ class FullNeighborLoader(_Loader):
             self._chunk_cap[l] = min(_cabi.NS_FULL_MAX_CHUNKS, max(chunks) + max(chunks) // 4)
             self.growths += 1
 
-    def _launch(self, seeds: Tensor, first_batch: int) -> FullNeighborSuperBatch:
-        """seeds [G, width]: mini-batches first_batch .. first_batch + G - 1 of the run"""
-        dev = self.device
-        G, width = seeds.shape
-        o = dict(dtype=torch.int64, device=dev)
-        sb = FullNeighborSuperBatch()
-        sb.n_layers = self.num_layers
-        sb.input_nodes = frontier = seeds.reshape(-1).contiguous()
-        sb.seed_ptr = ptr = [g * width for g in range(G + 1)]
-        sb.layers = []
-        for l in range(self.num_layers):
-            n_out, m, op = self._layer(l, frontier, ptr, first_batch)
-            nptr, eptr = [0], [0]
-            for x, y in zip(n_out, m):
-                nptr.append(nptr[-1] + x)
-                eptr.append(eptr[-1] + y)
-            node_off = torch.cumsum(op.n_nodes, 0) - op.n_nodes
-            edge_off = torch.cumsum(op.n_edges, 0) - op.n_edges
-            n_id = torch.empty(nptr[-1], **o)
-            rc = torch.empty((2, eptr[-1]), **o)
-            offs = torch.empty(eptr[-1], **o)
-            op.emit(node_off, edge_off, n_id, rc[0], rc[1], offs)
-            sb.layers.append(dict(n_id=n_id, src_ptr=nptr, dst_ptr=ptr, edge_index=rc, e_id=self.perm[offs], edge_ptr=eptr))
-            frontier, ptr = n_id, nptr
-        sb.n_id, sb.node_ptr = frontier, ptr
-        sb.node_attrs = {k: _rows_of(v, frontier) for k, v in self._node_attrs}
-        return sb
-
-    def super_batches(self) -> Iterator[FullNeighborSuperBatch]:
-        """The epoch as launches of up to `prefetch` mini-batches."""
-        nodes = self.input_nodes
-        epoch = self.epoch                               # captured: a second iterator is the next epoch
-        self.epoch += 1
-        batch0 = epoch * len(self)
-        if self.shuffle:
-            gen = torch.Generator(device=self.device)
-            gen.manual_seed(self.seed * 1000003 + epoch)
-            nodes = nodes[torch.randperm(nodes.numel(), device=self.device, generator=gen)]
-        for start, G, width in _epoch_plan(nodes.numel(), self.batch_size, self.prefetch, self.drop_last):
-            yield self._launch(nodes[start:start + G * width].reshape(G, width), batch0 + start // self.batch_size)
-
-    def __iter__(self) -> Iterator[FullNeighborBatch]:
-        for sb in self.super_batches():
-            yield from sb
+    def _block(self, l: int, frontier: Tensor, ptr: List[int], first_batch: int, state):
+        n_out, m, op = self._layer(l, frontier, ptr, first_batch)
+        o = dict(dtype=torch.int64, device=self.device)
+        nptr, eptr = _ptr_list(n_out), _ptr_list(m)
+        node_off = torch.cumsum(op.n_nodes, 0) - op.n_nodes
+        edge_off = torch.cumsum(op.n_edges, 0) - op.n_edges
+        n_id = torch.empty(nptr[-1], **o)
+        rc = torch.empty((2, eptr[-1]), **o)
+        offs = torch.empty(eptr[-1], **o)
+        op.emit(node_off, edge_off, n_id, rc[0], rc[1], offs)
+        return dict(n_id=n_id, src_ptr=nptr, dst_ptr=ptr, edge_index=rc, e_id=self.perm[offs], edge_ptr=eptr)
 
 
 def range_partition(num_nodes: int, num_parts: int) -> Tensor:
@@ -2624,21 +2510,14 @@ class ClusterData:
         self.partptr = _cabi.ind2ptr(sorted_part.contiguous(), P)
         ei = data.edge_index.to(dev)
         self.col_ptrs, self.row_indices, self.perm = _cabi.coo_to_csx(self.node_inv[ei[0]], self.node_inv[ei[1]], N, N, True)
-        shadows = dict(indices32=self.row_indices.to(torch.int32), ptrs32=self.col_ptrs.to(torch.int32)) if E < 2 ** 31 else {}
-        self.graph = _cabi.graph_view(self.col_ptrs, self.row_indices, **shadows)
-        self.node_attrs, self.edge_attrs = [], []
-        for key, value in _tensor_items(data):
-            kind = _attr_kind(key, value, N, E)
-            if kind == "node":
-                self.node_attrs.append((key, value.to(dev)))
-            elif kind == "edge":
-                self.edge_attrs.append((key, value.to(dev)))
+        self.graph = _shadowed_view(self.col_ptrs, self.row_indices, E < 2 ** 31)
+        self.node_attrs, self.edge_attrs = _split_attrs(data, N, E, dev)
 
     def __len__(self) -> int:
         return self.num_parts
 
 
-class ClusterLoader(_Loader):
+class ClusterLoader(_PooledLoader):
     """Cluster-GCN's mini-batches (PyG's ClusterLoader, DGL's ClusterGCNSampler) over a ClusterData: a mini-batch is the
     union of `batch_size` clusters with EVERY edge of the graph between its nodes, the between-cluster ones included.  An
     epoch visits every cluster once, in cluster_epoch_order(P, seed, epoch, shuffle); mini-batch j takes
@@ -2658,8 +2537,7 @@ class ClusterLoader(_Loader):
             raise ValueError("batch_size must be at least 1 cluster, got %r" % (batch_size,))
         if q > _cabi.CLUSTER_MAX_PARTS_PER_BATCH:
             raise ValueError("batch_size must be at most %d clusters, got %r" % (_cabi.CLUSTER_MAX_PARTS_PER_BATCH, batch_size))
-        if int(prefetch) < 1:
-            raise ValueError("prefetch must be at least 1, got %r" % (prefetch,))
+        _at_least_1("prefetch", prefetch)
         if not isinstance(cluster_data, ClusterData):
             raise ValueError("cluster_data must be a ClusterData, got %s" % type(cluster_data).__name__)
         cd = self.cluster_data = cluster_data
@@ -2669,24 +2547,25 @@ class ClusterLoader(_Loader):
         self.batch_size, self.shuffle, self.drop_last = q, bool(shuffle), bool(drop_last)
         self.prefetch, self.seed = int(prefetch), int(seed)
         self.input_nodes = torch.empty(cd.num_parts, dtype=torch.int8)   # _Loader.__len__: the inputs are the clusters
-        self._pool = []                      # slab sets of finished iterators (each live iterator owns its own)
-        self.slab_allocations = 0            # slab sets made so far: a second epoch makes none
-        self.epoch = 0
+        self.perm, self._node_attrs, self._edge_attrs = cd.perm, cd.node_attrs, cd.edge_attrs
+        self._init_pool()
 
     def _new_slab(self):
         """what a launch of up to `prefetch` mini-batches needs: the cluster lists and their lengths on the device, the
         pair's launch object (its counts, status and workspace) and the pinned images of what crosses the bus"""
         cap, q, dev, cd = self.prefetch, self.batch_size, self.device, self.cluster_data
-        self.slab_allocations += 1
         lists = torch.zeros(cap * q + cap, dtype=torch.int64, device=dev)   # lists and lengths: one upload
         clusters, n_clusters = lists[:cap * q].view(cap, q), lists[cap * q:]
         ind = _cabi.ClusterInduced(cd.graph, cd.partptr, clusters, n_clusters, cd.node_perm)
         return dict(lists=lists, ind=ind, host_lists=torch.zeros(cap * q + cap, dtype=torch.int64).pin_memory(),
                     host=torch.empty(ind.state.numel(), dtype=torch.int64).pin_memory())
 
+    def _epoch_state(self, epoch: int) -> Tensor:
+        return cluster_epoch_order(self.cluster_data.num_parts, self.seed, epoch, self.shuffle)
+
     def _launch(self, slab, order: Tensor, j0: int, G: int):
-        """mini-batches j0 .. j0 + G - 1 of the epoch -> (node counts, edge counts) as python lists, after the launch's one
-        read-back; pass 2 has not run yet"""
+        """mini-batches j0 .. j0 + G - 1 of the epoch -> (j0, node counts, edge counts), the counts as python lists after the
+        launch's one read-back; pass 2 has not run yet"""
         cap, q = self.prefetch, self.batch_size
         hl = slab["host_lists"]              # its last upload is behind the last launch's read-back
         hl.zero_()
@@ -2700,37 +2579,7 @@ class ClusterLoader(_Loader):
         host.copy_(ind.state, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         _cabi.cluster_status_check(int(host[-1:].view(torch.int32)[0]), type(self).__name__)
-        return host[:G].tolist(), host[cap:cap + G].tolist()
+        return j0, host[:G].tolist(), host[cap:cap + G].tolist()
 
-    def _finish(self, slab, j0: int, G: int, n_nodes, n_edges) -> SuperBatch:
-        cd = self.cluster_data
-        n_id, edge_index, e_ptr, ptr_n, ptr_e = slab["ind"].emit(n_nodes, n_edges)
-        sb = SuperBatch()
-        sb.input_time = sb.node_time = sb.batch = sb.root_n_id = None
-        sb.n_id, sb.edge_index = n_id, edge_index
-        sb._e_id, sb._e_ptr, sb._perm = None, e_ptr, cd.perm
-        sb.node_attrs = {k: _rows_of(v, n_id) for k, v in cd.node_attrs}
-        sb.edge_attrs = {k: _rows_of(v, sb.e_id) for k, v in cd.edge_attrs}
-        sb.node_ptr, sb.edge_ptr = ptr_n, ptr_e
-        sb.layer_offsets = sb.layer_nodes = sb.layer_edges = sb.seed_counts = None
-        sb.batch_size, sb.call_id0, sb.n_hops = self.batch_size, j0, 0
-        return sb
-
-    def super_batches(self) -> Iterator[SuperBatch]:
-        """The epoch as super-batches of up to `prefetch` mini-batches."""
-        epoch = self.epoch                   # captured: a second iterator is the next epoch
-        self.epoch += 1
-        order = cluster_epoch_order(self.cluster_data.num_parts, self.seed, epoch, self.shuffle)
-        n_mb = len(self)
-        slab = self._pool.pop() if self._pool else self._new_slab()
-        try:
-            for j0 in range(0, n_mb, self.prefetch):
-                G = min(self.prefetch, n_mb - j0)
-                n_nodes, n_edges = self._launch(slab, order, j0, G)
-                yield self._finish(slab, j0, G, n_nodes, n_edges)
-        finally:
-            self._pool.append(slab)
-
-    def __iter__(self) -> Iterator[MiniBatch]:
-        for sb in self.super_batches():
-            yield from sb
+    def _emit(self, slab, G: int, n_nodes, n_edges):
+        return slab["ind"].emit(n_nodes, n_edges)           # n_id, edge_index, e_ptr and the two pointer lists
