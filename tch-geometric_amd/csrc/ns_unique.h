@@ -1,6 +1,15 @@
-// What the node dedup operators share (ns_unique.hip: tg_ns_homo_unique, ns_unique_typed.hip: tg_ns_typed_unique): the
-// sizes, the open-addressing insert (atomicCAS claims the key; the caller's atomicMin of the position into the slot's value
-// leaves the id's first position there), the workgroup rank scan, and the host's LDS limit query.
+// What the node dedup operators share (ns_unique.hip: tg_ns_homo_unique and tg_ns_homo_unique_grouped, ns_unique_typed.hip:
+// tg_ns_typed_unique; saint_dedup.h and the induced, cluster and full-neighbor code take the sizes, the insert, the scans
+// and the plan): the sizes, the open-addressing insert (atomicCAS claims the key; the caller's atomicMin of the position
+// into the slot's value leaves the id's first position there), the workgroup rank scan, the flat form's clear, flag and
+// apply bodies as device function templates, the host's LDS limit query and raise, and the plan.
+//
+// The tile bodies take what differs from their caller: the view of a list's tables, what else to store for a first
+// occurrence, and they hand back the ranks for the caller's own counts (counts, layer_nodes, seed_counts).  The __global__
+// shells, their grids and their argument structs stay in the .hip files, so the code of a kernel does not depend on who
+// else includes this header.  The insert, the edge relabel and the LDS form are NOT here: as functions they compile to
+// other code than tg_ns_homo_unique's kernels had (the compiler simplifies a callee before it knows the caller's tile
+// origin), and those kernels are held to their instruction streams (tools/kernel_diff.py).
 #pragma once
 #include <atomic>
 
@@ -91,6 +100,70 @@ template <typename Lookup> __device__ __forceinline__ int64_t nsu_end(int64_t r,
     return (uint64_t)r < (uint64_t)n ? (int64_t)lookup(r) : -1;
 }
 
+// ---- flat form: the body of a block.  T is the caller's view of a list's part of the workspace: vals, slot, tile_cnt.
+// s0, stride: the thread's first slot and the grid's width, taken from blockDim / gridDim in the kernel itself
+template <typename K>
+__device__ __forceinline__ void nsu_clear_tile(K *keys, uint32_t *vals, uint32_t cap, uint32_t s0, uint32_t stride) {
+    for (uint32_t s = s0; s < cap; s += stride) {
+        keys[s] = nsu_empty<K>();
+        vals[s] = NSU_UNSEEN;
+    }
+}
+
+// flags the first occurrences of a tile in their slot words and counts them
+template <typename T>
+__device__ __forceinline__ void nsu_flag_tile(const T &t, int64_t n, int64_t tile0, uint32_t *s_wave) {
+    const int64_t p0 = tile0 + (int64_t)threadIdx.x * NSU_PER;
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int k = 0; k < NSU_PER; ++k) {
+        const int64_t p = p0 + k;
+        if (p < n) {
+            const uint32_t s = t.slot[p];
+            if (t.vals[s] == (uint32_t)p) {
+                t.slot[p] = s | NSU_FLAG;
+                ++cnt;
+            }
+        }
+    }
+    uint32_t total;
+    nsu_scan(cnt, s_wave, &total);
+    if (threadIdx.x == 0) t.tile_cnt[blockIdx.x] = total;
+}
+
+// names the first occurrences of a tile: local id = first occurrences in the tiles before it (base) + the scan inside it.
+// The thread owns positions [p0, p0 + NSU_PER), p0 = tile0 + threadIdx.x * NSU_PER: bit k of `first` says p0 + k is a first
+// occurrence, rank0 is the local id of the thread's first one, base + total = the first occurrences up to the end of the
+// tile.  store(rank, p): what else a first occurrence writes (nodes[rank] = samples[p] is written here).  The caller
+// writes its counts and marks from what comes back.
+struct NsuRanks {
+    uint32_t base, total, rank0, first;
+};
+template <typename T, typename Store>
+__device__ __forceinline__ NsuRanks nsu_apply_tile(const T &t, int64_t n, int64_t tile0, const int64_t *samples,
+                                                   int64_t *nodes, uint32_t *s_wave, Store store) {
+    NsuRanks r;
+    uint32_t before = 0;
+    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += NSU_TILE_THREADS) before += t.tile_cnt[i];
+    nsu_scan(before, s_wave, &r.base);
+    const int64_t p0 = tile0 + (int64_t)threadIdx.x * NSU_PER;
+    r.first = 0;
+#pragma unroll
+    for (int k = 0; k < NSU_PER; ++k)
+        if (p0 + k < n && (t.slot[p0 + k] & NSU_FLAG)) r.first |= 1u << k;
+    r.rank0 = r.base + nsu_scan((uint32_t)__popc(r.first), s_wave, &r.total);
+    uint32_t rank = r.rank0;
+#pragma unroll
+    for (int k = 0; k < NSU_PER; ++k) {
+        if (r.first & (1u << k)) {
+            t.vals[t.slot[p0 + k] & ~NSU_FLAG] = rank;
+            store(rank, p0 + k);
+            nodes[rank++] = samples[p0 + k];
+        }
+    }
+    return r;
+}
+
 static inline int64_t nsu_r256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 // LDS a workgroup may ask for on the current device (0: no device)
@@ -108,6 +181,20 @@ static inline int64_t nsu_device_lds_limit() {
     }
     if (dev >= 0 && dev < 64) cached[dev] = v;
     return v;
+}
+
+// the LDS form's request above the default limit of a launch (the plan keeps it below the device's): raised once per
+// device and kernel, whenever a launch asks for more than the last one set.  raised: the kernel instantiation's own 64
+// words, a function-local static of its launcher (zero-initialised; a race only sets the attribute twice).
+static inline int nsu_raise_lds(const void *kernel, std::atomic<int64_t> *raised, int64_t dyn) {
+    if (dyn <= 64 * 1024) return TG_OK;
+    int dev = 0;
+    TG_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || raised[dev] < dyn) {
+        TG_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+        if (dev >= 0 && dev < 64) raised[dev] = dyn;
+    }
+    return TG_OK;
 }
 
 // ---- host side: what a shape needs, which form it takes (tg_ns_induced_* sizes its tables by the same plan) -------------

@@ -1,5 +1,6 @@
 // Per-batch, per-type node dedup and relabel of the typed slabs of tg_ns_hetero_batched (tg_ns_typed_unique,
-// include/tchgeo.h): ns_unique.hip with a type dimension.
+// include/tchgeo.h): ns_unique.hip with a type dimension.  The insert, the scan, the LDS-limit raise and the flat form's clear,
+// flag and apply tile bodies are ns_unique.h's; the kernel shells, their grids over (tile, batch, type) and NstArgs are this file's.
 //
 // The rule, per batch b and node type t: nodes[t] = the distinct values of samples[t][:n] in order of FIRST occurrence,
 // inverse[t][p] = index of samples[t][p] in nodes[t]; per relation r: rows = inverse[rel_src[r]][rows], cols =
@@ -156,11 +157,7 @@ typedef NstTable<nsu_k32> NstWords;
 
 template <typename K> __device__ __forceinline__ void nst_clear(const NstArgs &a, const NstType &ty, int64_t b) {
     const NstTable<K> tb(a, ty, b);
-    const uint32_t cap = ty.cap_mask + 1;
-    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += gridDim.x * blockDim.x) {
-        tb.keys[s] = nsu_empty<K>();
-        tb.vals[s] = NSU_UNSEEN;
-    }
+    nsu_clear_tile<K>(tb.keys, tb.vals, ty.cap_mask + 1, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 __global__ void __launch_bounds__(NSU_TILE_THREADS) nst_clear_kernel(const NstArgs a) {
     const NstType &ty = a.t[blockIdx.z];
@@ -206,23 +203,7 @@ __global__ void __launch_bounds__(NSU_TILE_THREADS) nst_flag_kernel(const NstArg
     const int64_t n = nsu_clamp(a.counts[b * a.counts_stride + t], ty.pitch);
     const int64_t tile0 = (int64_t)blockIdx.x * NSU_TILE;
     if ((int)blockIdx.x >= ty.n_tiles || (tile0 >= n && blockIdx.x != 0)) return; // uniform
-    const NstWords tb(a, ty, b);
-    const int64_t p0 = tile0 + (int64_t)threadIdx.x * NSU_PER;
-    uint32_t cnt = 0;
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k) {
-        const int64_t p = p0 + k;
-        if (p < n) {
-            const uint32_t s = tb.slot[p];
-            if (tb.vals[s] == (uint32_t)p) {
-                tb.slot[p] = s | NSU_FLAG;
-                ++cnt;
-            }
-        }
-    }
-    uint32_t total;
-    nsu_scan(cnt, s_wave, &total);
-    if (threadIdx.x == 0) tb.tile_cnt[blockIdx.x] = total;
+    nsu_flag_tile(NstWords(a, ty, b), n, tile0, s_wave);
 }
 
 // names the first occurrences of a tile: local id = first occurrences in the tiles before it + the scan inside it
@@ -237,37 +218,19 @@ __global__ void __launch_bounds__(NSU_TILE_THREADS) nst_apply_kernel(const NstAr
     const int64_t n = nsu_clamp(a.counts[b * a.counts_stride + t], ty.pitch);
     const int64_t tile0 = (int64_t)blockIdx.x * NSU_TILE;
     if ((int)blockIdx.x >= ty.n_tiles || (tile0 >= n && blockIdx.x != 0)) return; // uniform
-    const NstWords tb(a, ty, b);
-    uint32_t before = 0, base;
-    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += NSU_TILE_THREADS) before += tb.tile_cnt[i];
-    nsu_scan(before, s_wave, &base);
+    const NsuRanks r = nsu_apply_tile(NstWords(a, ty, b), n, tile0, ty.samples + b * ty.pitch, ty.nodes + b * ty.pitch, s_wave,
+                                      [](uint32_t, int64_t) {});
     const int64_t p0 = tile0 + (int64_t)threadIdx.x * NSU_PER;
-    uint32_t first = 0;
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k)
-        if (p0 + k < n && (tb.slot[p0 + k] & NSU_FLAG)) first |= 1u << k;
-    uint32_t total;
-    const uint32_t rank0 = base + nsu_scan((uint32_t)__popc(first), s_wave, &total);
-    const int64_t *samples = ty.samples + b * ty.pitch;
-    int64_t *nodes = ty.nodes + b * ty.pitch;
-    uint32_t rank = rank0;
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k) {
-        if (first & (1u << k)) {
-            tb.vals[tb.slot[p0 + k] & ~NSU_FLAG] = rank;
-            nodes[rank++] = samples[p0 + k];
-        }
-    }
     const bool last = tile0 + NSU_TILE >= n; // the type's last tile in this batch (tile 0 of an empty list)
     if (a.seed_counts) {
         const int64_t L = nst_seed_bound(ty, n);
         if (L >= n) {
-            if (last && threadIdx.x == 0) a.seed_counts[b * a.n_types + t] = (int64_t)(base + total);
+            if (last && threadIdx.x == 0) a.seed_counts[b * a.n_types + t] = (int64_t)(r.base + r.total);
         } else if (L >= p0 && L < p0 + NSU_PER) {
-            a.seed_counts[b * a.n_types + t] = (int64_t)(rank0 + __popc(first & ((1u << (int)(L - p0)) - 1u)));
+            a.seed_counts[b * a.n_types + t] = (int64_t)(r.rank0 + __popc(r.first & ((1u << (int)(L - p0)) - 1u)));
         }
     }
-    if (last && threadIdx.x == 0) a.counts_u[b * a.counts_stride + t] = (int64_t)(base + total);
+    if (last && threadIdx.x == 0) a.counts_u[b * a.counts_stride + t] = (int64_t)(r.base + r.total);
 }
 
 __global__ void __launch_bounds__(NSU_TILE_THREADS) nst_inverse_kernel(const NstArgs a) {
@@ -368,16 +331,8 @@ static inline bool nst_fits(const NstPlan &pl, int64_t lds_limit) { return pl.ld
 
 static int nst_launch_lds(const NstArgs &a, const NstPlan &pl, hipStream_t stream) {
     const int64_t dyn = pl.lds_bytes - NSU_STATIC_LDS;
-    if (dyn > 64 * 1024) { // above the default limit of a launch: raise it once per device (the plan keeps it below the device's)
-        static std::atomic<int64_t> raised[64]; // zero-initialised; a race only sets the attribute twice
-        int dev = 0;
-        TG_HIP(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 64 || raised[dev] < dyn) {
-            TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(nst_lds_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-            if (dev >= 0 && dev < 64) raised[dev] = dyn;
-        }
-    }
+    static std::atomic<int64_t> raised[64];
+    if (const int rc = nsu_raise_lds(reinterpret_cast<const void *>(nst_lds_kernel), raised, dyn)) return rc;
     const unsigned grid = (unsigned)(a.n_batches < 16384 ? a.n_batches : 16384);
     hipLaunchKernelGGL(nst_lds_kernel, dim3(grid), dim3(pl.threads), (size_t)dyn, stream, a);
     TG_LAUNCH_CHECK();

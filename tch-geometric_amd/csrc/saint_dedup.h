@@ -50,11 +50,7 @@ struct SaintBatch {
 
 template <typename A> __global__ void __launch_bounds__(NSU_TILE_THREADS) saint_clear_kernel(const A a) {
     const SaintBatch t(a, blockIdx.y);
-    const uint32_t cap = a.cap_mask + 1;
-    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += gridDim.x * blockDim.x) {
-        t.keys[s] = nsu_empty<nsu_k32>();
-        t.vals[s] = NSU_UNSEEN;
-    }
+    nsu_clear_tile<nsu_k32>(t.keys, t.vals, a.cap_mask + 1, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 template <typename A> __global__ void __launch_bounds__(NSU_TILE_THREADS) saint_insert_kernel(const A a) {

@@ -47,7 +47,7 @@ loader the names stay the graph's own attributes).
 
 Disjoint mini-batches (PyG's disjoint=True: one subgraph per seed, the dedup key is (subgraph, node), `batch` [num_nodes]
 names every node's subgraph) come from loader.NeighborLoader(..., unique=True, disjoint=True), with or without times; a
-temporal NeighborLoader with unique=True and no disjoint=True raises ValueError (plain dedup would merge seed times).  The operator is tg_ns_homo_unique_grouped (csrc/ns_unique_grouped.hip):
+temporal NeighborLoader with unique=True and no disjoint=True raises ValueError (plain dedup would merge seed times).  The operator is tg_ns_homo_unique_grouped (csrc/ns_unique.hip):
 _cabi.ns_homo_unique_grouped(out, n_batches, id_bound, seed_group=None, n_groups=None, form=0, ws=None, in_place=False,
 result=None, with_inverse=True) -> an NsUniqueOut(..., with_group=True) whose `group` slab is the batch vector, with
 _cabi.ns_homo_unique_grouped_form(cap_nodes, id_bound, n_groups, lds_limit_bytes=0) -> (form, lds_bytes),

@@ -221,7 +221,7 @@ def unique_nodes(samples: Tensor, rows: Tensor, cols: Tensor, id_bound: Optional
     disjoint=True: the first n_seeds samples are the seeds, edge e made sample n_seeds + e from the earlier position
     cols[e] (what the sampler returns), every sample belongs to the group of the seed its parents lead to, and a node is
     listed once per GROUP that reaches it -> (nodes, rows_u, cols_u, inverse, batch), batch[u] the group of nodes[u]
-    (tg_ns_homo_unique_grouped, csrc/ns_unique_grouped.hip; forests of up to TG_MAX_HOPS hops)."""
+    (tg_ns_homo_unique_grouped, csrc/ns_unique.hip; forests of up to TG_MAX_HOPS hops)."""
     for t in (samples, rows, cols):
         if t.dtype != torch.int64:
             raise ValueError("Tensor must be a is of invalid type. Expected Int64 but got %s" % t.dtype)

@@ -250,6 +250,39 @@ def test_placed_duplicates():
         assert one["layer_nodes"][0, 0] == 1 and one["counts"][0, 0] == n - 3 - 3
 
 
+def run_plain(slabs, id_bound, form):
+    """tg_ns_homo_unique on the same slabs, outputs sentinel-filled as run()'s -> {field: host array} (no group)."""
+    from tch_geometric import _cabi
+    res = _cabi.NsUniqueOut(slabs)
+    for t in (res.nodes, res.inverse, res.rows, res.cols, res.counts, res.layer_nodes):
+        t.fill_(SENT)
+    _cabi.ns_homo_unique(slabs, slabs.n_batches, id_bound, form=form, result=res)
+    torch.cuda.synchronize()
+    return {k: getattr(res, k).cpu().numpy() for k in FIELDS if k != "group"}
+
+
+def test_one_group_equals_the_plain_dedup():
+    """The two operators are the two instantiations of one set of kernel templates: with every seed in ONE group the pair
+    key is the id, so tg_ns_homo_unique_grouped must give tg_ns_homo_unique's words -- both forms, both key widths.  Node
+    counts around the flat form's tile (NSU_TILE = 1 024) and up to five positions per thread of the LDS form."""
+    rs = np.random.default_rng(26)
+    counts = (3, 1023, 1024, 1025, 2049, 4097)
+    batches = [forest(rs, n, 8, 3, max(n // 4, 1)) for n in counts]
+    up = (1 << 33) - (1 << 10)                                                # ids just below 2^33: 64-bit keys
+    for id_bound, slabs in ((1 << 10, Slabs(batches, 8, 3)), (1 << 33, Slabs([(s + up, c, st) for s, c, st in batches], 8, 3))):
+        for form in (1, 2):
+            plain = run_plain(slabs, id_bound, form)
+            one = run(slabs, id_bound, [0] * 8, 1, form=form)
+            for k in plain:
+                assert np.array_equal(plain[k], one[k]), (id_bound, form, k)
+            for b, (s, cols, _) in enumerate(slabs.batches):
+                n, m, u = len(s), len(cols), int(plain["counts"][b, 0])
+                assert 0 < u <= max(n // 4, 1) and plain["counts"][b, 1] == m
+                assert (one["group"][b, :u] == 0).all() and (one["group"][b, u:] == SENT).all(), (id_bound, form, b)
+                assert (plain["nodes"][b, u:] == SENT).all() and (plain["inverse"][b, n:] == SENT).all(), (id_bound, form, b)
+                assert (plain["rows"][b, m:] == SENT).all() and (plain["cols"][b, m:] == SENT).all(), (id_bound, form, b)
+
+
 def test_wrapper_and_transform():
     """_cabi.ns_homo_unique_grouped allocates what it needs; transforms.unique_nodes(seed_group=...) on device tensors gives
     the five-tuple, and stays the four-tuple without the map."""
