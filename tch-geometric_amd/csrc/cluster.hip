@@ -7,7 +7,7 @@
 //     non-empty ranges, sorted by start, sit in LDS (start, end, base - start: 12 bytes a range, 12 KiB at most); a
 //     neighbour costs one binary search there and no global access besides its own word of `indices`;
 //   - no idle lanes: a cluster's columns are consecutive, so its CSC entries are ONE offset range [ptrs[lo], ptrs[hi]).
-//     It is cut into chunks of CL_CHUNK = 512 consecutive offsets that run across column boundaries; a wave takes 64
+//     It is cut into chunks of CS_CHUNK = 512 consecutive offsets that run across column boundaries; a wave takes 64
 //     consecutive offsets a step whatever the columns' lengths.  A hub column is still split over many chunks;
 //   - no node list: the positions are implied by the cluster list and are written once, by pass 2.
 //
@@ -21,26 +21,16 @@
 // Pass 1: plan (one workgroup per batch: ranges, base_k, the chunk prefix per cluster, the sort + dedup of (start, k),
 //   the bounds that raise the status bits) | scan: hits per chunk, summed per tile of chunks | chunk apply: the exclusive
 //   prefix over chunks in place, m_b.  Pass 2: nodes | scan again, a chunk's hits go to edge_off[b] + its prefix, ranked
-//   in lane order = offset order by ballot + popcount.  The cpref / ctile scheme and the units of 16 chunks with their
-//   look-ups in lanes 0..15 are ns_induced.hip's.
-#include <algorithm>
-
-#include "ns_unique.h"
+//   in lane order = offset order by ballot + popcount.  The chunk size, the cpref / ctile scheme and the units of up to
+//   16 chunks with their look-ups in lanes 0..15 are chunk_scan.h's; the unit shrinks by cs_short_fill.
+#include "chunk_scan.h"
 
 namespace tg {
 
-constexpr int CL_CHUNK = 512;                        // CSC offsets of a chunk (ns_induced.hip's, and why)
-constexpr int CL_UNIT = 16;                          // chunks a wave takes at once (fewer where chunks are few)
-constexpr int CL_THREADS = NSU_TILE_THREADS;         // 256
-constexpr int CL_TILE = NSU_TILE;                    // chunks of a prefix tile
 constexpr int CL_MAX_PARTS = TG_CLUSTER_MAX_PARTS_PER_BATCH;
-constexpr int CL_PER = CL_MAX_PARTS / CL_THREADS;    // list entries a plan thread owns
-constexpr int CL_HEADER = 256;                       // bytes: {chunks, n_b, list entries, table ranges} (0 on overflow)
-constexpr int64_t CL_MAX_CHUNKS = (int64_t)1 << 31;
-constexpr int64_t CL_GRID_Y = 32768;                 // batches per launch
-constexpr int CL_SCAN_BLOCKS = 2048;                 // of the fixed grid: 256 CUs x 8 workgroups of 4 waves
-static_assert(CL_TILE % CL_UNIT == 0, "a unit's chunks share a tile");
-static_assert(CL_MAX_PARTS % CL_THREADS == 0 && (CL_MAX_PARTS & (CL_MAX_PARTS - 1)) == 0, "the plan's sort is bitonic");
+constexpr int CL_PER = CL_MAX_PARTS / CS_THREADS;    // list entries a plan thread owns
+// the header's words: {chunks, n_b, list entries, table ranges} (0 on overflow)
+static_assert(CL_MAX_PARTS % CS_THREADS == 0 && (CL_MAX_PARTS & (CL_MAX_PARTS - 1)) == 0, "the plan's sort is bitonic");
 
 struct ClArgs {
     const int64_t *ptrs, *indices;
@@ -76,13 +66,9 @@ struct ClBatch {
     }
 };
 
-__device__ __forceinline__ int64_t cl_ptr(const ClArgs &a, int64_t v) {
-    return a.ptrs32 ? (int64_t)a.ptrs32[v] : a.ptrs[v];
-}
-
 // one workgroup per batch
-__global__ void __launch_bounds__(CL_THREADS) cl_plan_kernel(const ClArgs a) {
-    __shared__ unsigned long long s_wave[CL_THREADS / 64];
+__global__ void __launch_bounds__(CS_THREADS) cl_plan_kernel(const ClArgs a) {
+    __shared__ unsigned long long s_wave[CS_THREADS / 64];
     __shared__ unsigned long long s_key[CL_MAX_PARTS];
     __shared__ uint32_t s_size[CL_MAX_PARTS], s_base[CL_MAX_PARTS];
     const int64_t b = blockIdx.y;
@@ -90,7 +76,7 @@ __global__ void __launch_bounds__(CL_THREADS) cl_plan_kernel(const ClArgs a) {
     const int tid = threadIdx.x;
     const int q = (int)(a.n_clusters ? nsu_clamp(a.n_clusters[b], a.pitch) : a.pitch);
     const int64_t *list = a.clusters + b * a.pitch;
-    for (int64_t s = tid; s < a.chunk_tiles; s += CL_THREADS) t.ctile[s] = 0;
+    for (int64_t s = tid; s < a.chunk_tiles; s += CS_THREADS) t.ctile[s] = 0;
     int64_t lo[CL_PER], hi[CL_PER], e0[CL_PER], e1[CL_PER];
     unsigned long long nch[CL_PER], my_n = 0, my_c = 0;
     int bad = 0;
@@ -110,9 +96,9 @@ __global__ void __launch_bounds__(CL_THREADS) cl_plan_kernel(const ClArgs a) {
                 } else if (p1 > p0) {
                     lo[j] = p0, hi[j] = p1;
                     // a graph's ptrs are trusted to ascend inside [0, n_edges]; the clamp keeps `indices` in range anyway
-                    e0[j] = nsu_clamp(cl_ptr(a, p0), a.n_edges_graph);
-                    e1[j] = std::max(e0[j], nsu_clamp(cl_ptr(a, p1), a.n_edges_graph));
-                    nch[j] = (unsigned long long)((e1[j] - e0[j] + CL_CHUNK - 1) / CL_CHUNK);
+                    e0[j] = nsu_clamp(csc_ptr(a.ptrs, a.ptrs32, p0), a.n_edges_graph);
+                    e1[j] = std::max(e0[j], nsu_clamp(csc_ptr(a.ptrs, a.ptrs32, p1), a.n_edges_graph));
+                    nch[j] = (unsigned long long)((e1[j] - e0[j] + CS_CHUNK - 1) / CS_CHUNK);
                 }
             }
         }
@@ -154,7 +140,7 @@ __global__ void __launch_bounds__(CL_THREADS) cl_plan_kernel(const ClArgs a) {
     __syncthreads();
     for (int k2 = 2; k2 <= ns; k2 <<= 1) {
         for (int d = k2 >> 1; d > 0; d >>= 1) {
-            for (int i = tid; i < ns; i += CL_THREADS) {
+            for (int i = tid; i < ns; i += CS_THREADS) {
                 const int o = i ^ d;
                 if (o > i) {
                     const unsigned long long x = s_key[i], y = s_key[o];
@@ -192,8 +178,8 @@ __global__ void __launch_bounds__(CL_THREADS) cl_plan_kernel(const ClArgs a) {
 // the ends of columns vb + 1 .. vb + 64 relative to offset e_begin, one per lane, ascending in the lane; columns past the
 // cluster's last one read ptrs[hi], which is above every offset of the cluster.  Clamped so that an int holds it
 __device__ __forceinline__ int cl_ends(const ClArgs &a, long long vb, long long hi, long long e_begin, int lane) {
-    const long long d = cl_ptr(a, std::min<long long>(vb + 1 + lane, hi)) - e_begin;
-    return (int)std::max<long long>(-1, std::min<long long>(d, 2 * CL_CHUNK));
+    const long long d = csc_ptr(a.ptrs, a.ptrs32, std::min<long long>(vb + 1 + lane, hi)) - e_begin;
+    return (int)std::max<long long>(-1, std::min<long long>(d, 2 * CS_CHUNK));
 }
 
 // how many of the wavefront's 64 ascending words `rel` are <= t: an upper bound by lane exchanges.  Every lane calls it
@@ -207,20 +193,20 @@ __device__ __forceinline__ int cl_upper_bound(int rel, int t) {
 }
 
 // EMIT = false: hits per chunk (and their sum per tile of chunks); true: the hits themselves
-template <bool I32, bool EMIT> __global__ void __launch_bounds__(CL_THREADS) cl_scan_kernel(const ClArgs a) {
+template <bool I32, bool EMIT> __global__ void __launch_bounds__(CS_THREADS) cl_scan_kernel(const ClArgs a) {
     __shared__ uint32_t s_start[CL_MAX_PARTS], s_end[CL_MAX_PARTS], s_delta[CL_MAX_PARTS];
     const int64_t b = blockIdx.y;
     const ClBatch t(a, b);
     const unsigned long long n_chunks = t.hdr[0];
     if (n_chunks == 0) return; // uniform
     const int q = (int)t.hdr[2], n_tab = (int)t.hdr[3]; // chunks: n_tab >= 1
-    for (int i = threadIdx.x; i < n_tab; i += CL_THREADS) s_start[i] = t.t_start[i], s_end[i] = t.t_end[i], s_delta[i] = t.t_delta[i];
+    for (int i = threadIdx.x; i < n_tab; i += CS_THREADS) s_start[i] = t.t_start[i], s_end[i] = t.t_end[i], s_delta[i] = t.t_delta[i];
     __syncthreads();
     const uint32_t first = s_start[0], last = s_end[n_tab - 1]; // the table's span: most neighbours fall outside it
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int waves = CL_THREADS / 64;
-    int unit = CL_UNIT; // shorter units while the batch's wavefronts would not all get one: a small batch is latency, not work
-    while (unit > 1 && (n_chunks + unit - 1) / unit < (unsigned long long)gridDim.x * waves) unit >>= 1;
+    const int waves = CS_THREADS / 64;
+    int unit = CS_UNIT;
+    while (unit > 1 && cs_short_fill(n_chunks, unit, gridDim.x, waves)) unit >>= 1;
     const unsigned long long n_units = (n_chunks + unit - 1) / unit;
     const unsigned long long below = ((unsigned long long)1 << lane) - 1;
     const int64_t out0 = EMIT ? a.edge_off[b] : 0;
@@ -229,21 +215,16 @@ template <bool I32, bool EMIT> __global__ void __launch_bounds__(CL_THREADS) cl_
         long long my_e = 0, my_v = 0, my_hi = 0, my_i0 = 0;
         int my_len = 0;
         if (lane < unit && c < n_chunks) {
-            // the last list entry whose chunk prefix is <= c: cpk[0] = 0 <= c < n_chunks = cpk[q]; it has chunks
-            int k = 0, kh = q;
-            while (kh - k > 1) {
-                const int mid = (k + kh) >> 1;
-                if (t.cpk[mid] <= c) k = mid; else kh = mid;
-            }
-            my_e = t.e0[k] + (int64_t)(c - t.cpk[k]) * CL_CHUNK;
-            my_len = (int)std::min<int64_t>(CL_CHUNK, t.e1[k] - my_e);
+            const int k = cs_last_le(t.cpk, q, c); // the list entry: cpk[0] = 0 <= c < n_chunks = cpk[q]; it has chunks
+            my_e = t.e0[k] + (int64_t)(c - t.cpk[k]) * CS_CHUNK;
+            my_len = (int)std::min<int64_t>(CS_CHUNK, t.e1[k] - my_e);
             if (EMIT) { // pass 1 counts hits and needs no column
                 const int64_t lo = t.start[k], hi = lo + t.size[k];
                 // the chunk's first column: the last v in [lo, hi) with ptrs[v] <= my_e (ptrs[lo] <= my_e < ptrs[hi])
                 int64_t v = lo, vh = hi;
                 while (vh - v > 1) {
                     const int64_t mid = (v + vh) >> 1;
-                    if (cl_ptr(a, mid) <= my_e) v = mid; else vh = mid;
+                    if (csc_ptr(a.ptrs, a.ptrs32, mid) <= my_e) v = mid; else vh = mid;
                 }
                 my_v = v, my_hi = hi;
                 my_i0 = (long long)t.base[k] - lo; // position = column + my_i0
@@ -255,9 +236,9 @@ template <bool I32, bool EMIT> __global__ void __launch_bounds__(CL_THREADS) cl_
             if (cw >= n_chunks) break; // uniform
             const long long e_begin = __shfl(my_e, w);
             const int len = __shfl(my_len, w);
-            uint32_t nbr[CL_CHUNK / 64]; // the chunk's entries, all loads in flight at once
+            uint32_t nbr[CS_CHUNK / 64]; // the chunk's entries, all loads in flight at once
 #pragma unroll
-            for (int j = 0; j < CL_CHUNK / 64; ++j) {
+            for (int j = 0; j < CS_CHUNK / 64; ++j) {
                 const int o = j * 64 + lane;
                 nbr[j] = 0;
                 if (o < len) nbr[j] = I32 ? a.indices32[e_begin + o] : (uint32_t)a.indices[e_begin + o];
@@ -271,7 +252,7 @@ template <bool I32, bool EMIT> __global__ void __launch_bounds__(CL_THREADS) cl_
             const int64_t out = EMIT ? out0 + (int64_t)t.cpref[cw] : 0;
             uint32_t cnt = 0;
 #pragma unroll
-            for (int j = 0; j < CL_CHUNK / 64; ++j) {
+            for (int j = 0; j < CS_CHUNK / 64; ++j) {
                 if (j * 64 >= len) break; // uniform
                 const int o = j * 64 + lane;
                 uint32_t pos = NSU_UNSEEN;
@@ -309,43 +290,26 @@ template <bool I32, bool EMIT> __global__ void __launch_bounds__(CL_THREADS) cl_
                 unit_hits += cnt;
             }
         }
-        if (!EMIT && lane == 0 && unit_hits) atomicAdd(&t.ctile[u * unit / CL_TILE], unit_hits);
+        if (!EMIT) cs_unit_counted(t.ctile, u, unit, unit_hits, lane);
     }
 }
 
 // the exclusive prefix over a tile of chunks, in place; the last tile writes m_b
-__global__ void __launch_bounds__(CL_THREADS) cl_chunk_apply_kernel(const ClArgs a) {
-    __shared__ unsigned long long s_wave[CL_THREADS / 64];
+__global__ void __launch_bounds__(CS_THREADS) cl_chunk_apply_kernel(const ClArgs a) {
+    __shared__ unsigned long long s_wave[CS_THREADS / 64];
     const int64_t b = blockIdx.y;
     const ClBatch t(a, b);
     const unsigned long long n_chunks = t.hdr[0];
-    const unsigned long long tile0 = (unsigned long long)blockIdx.x * CL_TILE;
-    if (tile0 >= n_chunks && blockIdx.x != 0) return; // uniform
-    unsigned long long before = 0, base;
-    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += CL_THREADS) before += t.ctile[i];
-    nsu_scan64(before, s_wave, &base);
-    const unsigned long long c0 = tile0 + (unsigned long long)threadIdx.x * NSU_PER;
-    unsigned long long h[NSU_PER], mine = 0;
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k) {
-        h[k] = c0 + k < n_chunks ? t.cpref[c0 + k] : 0;
-        mine += h[k];
-    }
-    unsigned long long total;
-    unsigned long long run = base + nsu_scan64(mine, s_wave, &total);
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k) {
-        if (c0 + k < n_chunks) t.cpref[c0 + k] = run;
-        run += h[k];
-    }
-    if (tile0 + CL_TILE >= n_chunks && threadIdx.x == 0) { // the batch's last tile (tile 0 of a batch without chunks)
-        t.cpref[n_chunks] = base + total;
-        a.n_edges[b] = (int64_t)(base + total);
+    if (cs_tile_idle(n_chunks)) return;
+    const CsTile<unsigned long long> r = cs_chunk_apply_tile(t.cpref, t.ctile, n_chunks, s_wave);
+    if (r.last && threadIdx.x == 0) {
+        t.cpref[n_chunks] = r.base + r.total;
+        a.n_edges[b] = (int64_t)(r.base + r.total);
     }
 }
 
 // position i of the batch is vertex start_k + (i - base_k): the node list, written once
-__global__ void __launch_bounds__(CL_THREADS) cl_nodes_kernel(const ClArgs a) {
+__global__ void __launch_bounds__(CS_THREADS) cl_nodes_kernel(const ClArgs a) {
     const int64_t b = blockIdx.y;
     const ClBatch t(a, b);
     if (t.hdr[1] == 0) return;
@@ -353,7 +317,7 @@ __global__ void __launch_bounds__(CL_THREADS) cl_nodes_kernel(const ClArgs a) {
     int64_t *out = a.nodes + a.node_off[b];
     for (int k = blockIdx.x; k < q; k += gridDim.x) {
         const int64_t lo = t.start[k], n = t.size[k], base = t.base[k];
-        for (int64_t i = threadIdx.x; i < n; i += CL_THREADS) out[base + i] = a.node_ids ? a.node_ids[lo + i] : lo + i;
+        for (int64_t i = threadIdx.x; i < n; i += CS_THREADS) out[base + i] = a.node_ids ? a.node_ids[lo + i] : lo + i;
     }
 }
 
@@ -363,19 +327,14 @@ struct ClPlan {
 };
 
 static int cl_plan(const tg_graph *csc, int64_t n_parts, int64_t pitch, const char *who, ClPlan &pl) {
-    TG_REQUIRE(csc, "%s: null graph", who);
-    TG_REQUIRE(csc->n_major >= 0 && csc->n_edges >= 0, "%s: negative graph size (n_major = %lld, n_edges = %lld)", who,
-               (long long)csc->n_major, (long long)csc->n_edges);
+    TG_REQUIRE(pitch >= 0 && pitch <= CL_MAX_PARTS, "%s: pitch_parts = %lld outside [0, %d]", who, (long long)pitch, CL_MAX_PARTS);
+    // distinct clusters have disjoint offset ranges, the columns of cs_plan_chunks' default bound
+    if (const int rc = cs_plan_chunks(csc, pitch, 0, who, pl.chunk_bound, pl.chunk_tiles)) return rc;
     if (csc->n_major > ((int64_t)1 << 31))
         return fail(TG_ERR_UNSUPPORTED, "%s: n_major = %lld above 2^31: ranges and positions are 32-bit words", who,
                     (long long)csc->n_major);
     TG_REQUIRE(n_parts >= 0, "%s: n_parts = %lld is negative", who, (long long)n_parts);
-    TG_REQUIRE(pitch >= 0 && pitch <= CL_MAX_PARTS, "%s: pitch_parts = %lld outside [0, %d]", who, (long long)pitch, CL_MAX_PARTS);
-    // distinct clusters have disjoint offset ranges: every range ends in at most one ragged chunk
-    pl.chunk_bound = pitch + (csc->n_edges + CL_CHUNK - 1) / CL_CHUNK;
-    TG_REQUIRE(pl.chunk_bound <= CL_MAX_CHUNKS, "%s: %lld chunks per batch, at most 2^31 expected", who, (long long)pl.chunk_bound);
-    pl.chunk_tiles = pl.chunk_bound / CL_TILE + 1;
-    pl.e0_off = CL_HEADER;
+    pl.e0_off = CS_HEADER;
     pl.cpk_off = pl.e0_off + nsu_r256(2 * pitch * 8);
     pl.tab_off = pl.cpk_off + nsu_r256((4 * pitch + 1) * 4);
     pl.cpref_off = pl.tab_off + nsu_r256(3 * pitch * 4);
@@ -388,14 +347,8 @@ static int cl_plan(const tg_graph *csc, int64_t n_parts, int64_t pitch, const ch
 static int cl_common(const tg_graph *csc, const tg_cluster_in *in, int64_t n_batches, void *workspace, int64_t workspace_bytes,
                      const char *who, ClPlan &pl, ClArgs &a) {
     TG_REQUIRE(csc && in, "%s: null argument", who);
-    TG_REQUIRE(n_batches >= 0 && n_batches <= 0x7fffffff, "%s: n_batches = %lld outside [0, 2^31)", who, (long long)n_batches);
     if (const int rc = cl_plan(csc, in->n_parts, in->pitch_parts, who, pl)) return rc;
-    TG_REQUIRE(workspace_bytes >= 0, "%s: workspace_bytes = %lld is negative", who, (long long)workspace_bytes);
-    TG_REQUIRE(workspace && workspace_bytes / pl.batch_bytes >= n_batches,
-               "%s: workspace too small (%lld bytes, %lld batches of %lld expected)", who,
-               (long long)(workspace ? workspace_bytes : 0), (long long)n_batches, (long long)pl.batch_bytes);
-    TG_REQUIRE(((uintptr_t)workspace & 7u) == 0, "%s: workspace must be 8-byte aligned", who);
-    TG_REQUIRE(csc->ptrs && csc->indices, "%s: null ptrs / indices", who);
+    if (const int rc = cs_check_launch(csc, n_batches, pl.batch_bytes, workspace, workspace_bytes, who)) return rc;
     TG_REQUIRE(in->partptr, "%s: null partptr", who);
     TG_REQUIRE(in->clusters || in->pitch_parts == 0, "%s: null clusters", who);
     a = ClArgs{};
@@ -422,23 +375,15 @@ static ClArgs cl_at(const ClArgs &a0, int64_t b0) {
     return a;
 }
 
-static inline unsigned cl_scan_grid(int64_t nb) { return (unsigned)std::max<int64_t>(1, CL_SCAN_BLOCKS / nb); }
-
 } // namespace tg
 
 extern "C" int tg_cluster_workspace_bytes(const tg_graph *csc, int64_t n_parts, int64_t pitch_parts, int64_t n_batches,
                                           int64_t *bytes, int64_t *bytes_min) {
     using namespace tg;
     const char *who = "tg_cluster_workspace_bytes";
-    TG_REQUIRE(bytes && bytes_min, "%s: null output", who);
-    TG_REQUIRE(n_batches >= 0 && n_batches <= 0x7fffffff, "%s: n_batches = %lld outside [0, 2^31)", who, (long long)n_batches);
     ClPlan pl;
     if (const int rc = cl_plan(csc, n_parts, pitch_parts, who, pl)) return rc;
-    TG_REQUIRE(pl.batch_bytes <= INT64_MAX / std::max<int64_t>(1, n_batches), "%s: %lld batches of %lld bytes overflow int64",
-               who, (long long)n_batches, (long long)pl.batch_bytes);
-    *bytes_min = pl.batch_bytes;
-    *bytes = pl.batch_bytes * n_batches;
-    return TG_OK;
+    return cs_answer_bytes(pl.batch_bytes, n_batches, who, bytes, bytes_min);
 }
 
 extern "C" int tg_cluster_count(const tg_graph *csc, const tg_cluster_in *in, int64_t n_batches, int64_t *n_nodes,
@@ -451,22 +396,21 @@ extern "C" int tg_cluster_count(const tg_graph *csc, const tg_cluster_in *in, in
     TG_REQUIRE(n_nodes && n_edges && status, "%s: null n_nodes / n_edges / status", who);
     a0.n_nodes = n_nodes, a0.n_edges = n_edges, a0.status = status;
     hipStream_t stream = (hipStream_t)stream_;
-    const dim3 block(CL_THREADS);
-    for (int64_t b0 = 0; b0 < n_batches; b0 += CL_GRID_Y) {
+    const dim3 block(CS_THREADS);
+    return cs_rounds(n_batches, [&](int64_t b0, int64_t nb_) {
         const ClArgs a = cl_at(a0, b0);
-        const int64_t nb_ = std::min(CL_GRID_Y, n_batches - b0);
         const unsigned nb = (unsigned)nb_;
         hipLaunchKernelGGL(cl_plan_kernel, dim3(1, nb), block, 0, stream, a);
         TG_LAUNCH_CHECK();
         if (a.indices32)
-            hipLaunchKernelGGL((cl_scan_kernel<true, false>), dim3(cl_scan_grid(nb_), nb), block, 0, stream, a);
+            hipLaunchKernelGGL((cl_scan_kernel<true, false>), dim3(cs_scan_grid(nb_), nb), block, 0, stream, a);
         else
-            hipLaunchKernelGGL((cl_scan_kernel<false, false>), dim3(cl_scan_grid(nb_), nb), block, 0, stream, a);
+            hipLaunchKernelGGL((cl_scan_kernel<false, false>), dim3(cs_scan_grid(nb_), nb), block, 0, stream, a);
         TG_LAUNCH_CHECK();
         hipLaunchKernelGGL(cl_chunk_apply_kernel, dim3((unsigned)pl.chunk_tiles, nb), block, 0, stream, a);
         TG_LAUNCH_CHECK();
-    }
-    return TG_OK;
+        return (int)TG_OK;
+    });
 }
 
 extern "C" int tg_cluster_emit(const tg_graph *csc, const tg_cluster_in *in, int64_t n_batches, const int64_t *node_off,
@@ -481,21 +425,20 @@ extern "C" int tg_cluster_emit(const tg_graph *csc, const tg_cluster_in *in, int
     TG_REQUIRE(node_off || !nodes, "%s: nodes given without node_off", who);
     a0.node_off = node_off, a0.edge_off = edge_off, a0.nodes = nodes, a0.rows = rows, a0.cols = cols, a0.edge_index = edge_index;
     hipStream_t stream = (hipStream_t)stream_;
-    const dim3 block(CL_THREADS);
-    for (int64_t b0 = 0; b0 < n_batches; b0 += CL_GRID_Y) {
+    const dim3 block(CS_THREADS);
+    return cs_rounds(n_batches, [&](int64_t b0, int64_t nb_) {
         const ClArgs a = cl_at(a0, b0);
-        const int64_t nb_ = std::min(CL_GRID_Y, n_batches - b0);
         const unsigned nb = (unsigned)nb_;
         if (a.nodes && a.pitch > 0) {
-            const unsigned gx = (unsigned)std::min<int64_t>(a.pitch, std::max<int64_t>(1, CL_SCAN_BLOCKS / nb_));
+            const unsigned gx = (unsigned)std::min<int64_t>(a.pitch, std::max<int64_t>(1, CS_SCAN_BLOCKS / nb_));
             hipLaunchKernelGGL(cl_nodes_kernel, dim3(gx, nb), block, 0, stream, a);
             TG_LAUNCH_CHECK();
         }
         if (a.indices32)
-            hipLaunchKernelGGL((cl_scan_kernel<true, true>), dim3(cl_scan_grid(nb_), nb), block, 0, stream, a);
+            hipLaunchKernelGGL((cl_scan_kernel<true, true>), dim3(cs_scan_grid(nb_), nb), block, 0, stream, a);
         else
-            hipLaunchKernelGGL((cl_scan_kernel<false, true>), dim3(cl_scan_grid(nb_), nb), block, 0, stream, a);
+            hipLaunchKernelGGL((cl_scan_kernel<false, true>), dim3(cs_scan_grid(nb_), nb), block, 0, stream, a);
         TG_LAUNCH_CHECK();
-    }
-    return TG_OK;
+        return (int)TG_OK;
+    });
 }

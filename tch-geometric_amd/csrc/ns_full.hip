@@ -7,9 +7,9 @@
 // of first occurrence; row_k = the FIRST position of src_k in out_nodes.  The output is ragged and exact: pass 1 counts,
 // the caller allocates and passes two exclusive prefixes, pass 2 writes.
 //
-// Everything is ns_induced.hip's and ns_unique.h's machinery put together: columns are cut into chunks of 512 consecutive
-// CSC offsets (a hub column is many chunks all over the device), a wave takes a unit of up to 16 chunks whose look-ups run
-// in lanes 0..15, the batch's open-addressing table holds key = id, value = first position by atomicMin.  What is new is
+// Everything is chunk_scan.h's and ns_unique.h's machinery put together: columns are cut into chunks (a hub column is many
+// chunks all over the device), a wave takes a unit of chunks whose look-ups run in its first lanes (the unit shrinks by
+// cs_short_fill), the batch's open-addressing table holds key = id, value = first position by atomicMin.  What is new is
 // that the scan INSERTS: entry k of the batch's triple order inserts its source with value n + k, so after the insert pass
 // a slot's value is < n for a frontier node and n + (the first triple that names it) for a new one.
 //
@@ -25,21 +25,12 @@
 //   entry.  Pass 2 therefore consumes the workspace: a second emit needs a second count.
 // A position's column begin and the edges before it are kept in the workspace by the plan kernel, so the scans never touch
 // `nodes` or `ptrs` again: a chunk look-up is one binary search over the chunk prefix and three loads.
-#include <algorithm>
-
-#include "ns_unique.h"
+#include "chunk_scan.h"
 
 namespace tg {
 
-constexpr int NSF_CHUNK = 512;                         // CSC offsets of a chunk (ns_induced.hip's, and why)
-constexpr int NSF_UNIT = 16;                           // chunks a wave takes at once (fewer where chunks are few)
-constexpr int NSF_THREADS = NSU_TILE_THREADS;          // 256
-constexpr int NSF_TILE = NSU_TILE;                     // positions / chunks of a prefix tile
-constexpr int NSF_HEADER = 256;                        // bytes: {chunks of the batch (0 when refused), accepted}
-constexpr int64_t NSF_MAX_CHUNKS = (int64_t)1 << 31;   // of the bound
 constexpr uint64_t NSF_MAX_EDGES = (uint64_t)1 << 31;  // m_b below it: n + k fits the slot's 32-bit value
-constexpr int NSF_SCAN_BLOCKS = 2048;                  // of the fixed grid: 256 CUs x 8 workgroups of 4 waves
-static_assert(NSF_TILE % NSF_UNIT == 0, "a unit's chunks share a tile");
+// the header's words: {chunks of the batch (0 when refused), accepted}
 
 enum { NSF_INSERT = 0, NSF_FLAG = 1, NSF_NODES = 2, NSF_TRIPLES = 3 };
 
@@ -68,7 +59,7 @@ template <typename K> struct NsfBatch {
     __device__ __forceinline__ NsfBatch(const NsfArgs &a, int64_t b) {
         unsigned char *base = a.ws + b * a.batch_bytes;
         hdr = reinterpret_cast<unsigned long long *>(base);
-        keys = reinterpret_cast<K *>(base + NSF_HEADER);
+        keys = reinterpret_cast<K *>(base + CS_HEADER);
         vals = reinterpret_cast<uint32_t *>(base + a.vals_off);
         npref = reinterpret_cast<unsigned long long *>(base + a.npref_off); // [max_nodes + 1] chunks before a position
         epref = reinterpret_cast<unsigned long long *>(base + a.epref_off); // [max_nodes + 1] triples before a position
@@ -79,57 +70,25 @@ template <typename K> struct NsfBatch {
     }
 };
 
-__device__ __forceinline__ int64_t nsf_ptr(const NsfArgs &a, int64_t v) {
-    return a.ptrs32 ? (int64_t)a.ptrs32[v] : a.ptrs[v];
-}
-
 // batch b's frontier: nodes[base .. base + n)
 __device__ __forceinline__ int64_t nsf_list(const NsfArgs &a, int64_t b, int64_t *base) {
     *base = a.node_ptr[b];
     return nsu_clamp(a.node_ptr[b + 1] - *base, a.max_nodes);
 }
 
-// nsu_insert with the hash masked: a table of one slot (node_cap = 0) has a shift of 32
-template <typename K> __device__ __forceinline__ uint32_t nsf_insert(K *keys, uint32_t mask, uint32_t shift, K key) {
-    uint32_t s = nsu_hash(key, mask, shift & 31u) & mask;
-    for (uint32_t i = 0; i <= mask; ++i) {
-        const K prev = atomicCAS(&keys[s], nsu_empty<K>(), key);
-        if (prev == nsu_empty<K>() || prev == key) break;
-        s = (s + 1) & mask;
-    }
-    return s;
-}
-
-// the slot of `key`, NSU_UNSEEN where it has none; at most one pass over the table
-template <typename K> __device__ __forceinline__ uint32_t nsf_find(const K *keys, uint32_t mask, uint32_t shift, K key) {
-    uint32_t s = nsu_hash(key, mask, shift & 31u) & mask;
-    for (uint32_t i = 0; i <= mask; ++i) {
-        const K k = keys[s];
-        if (k == key) return s;
-        if (k == nsu_empty<K>()) break;
-        s = (s + 1) & mask;
-    }
-    return NSU_UNSEEN;
-}
-
-template <typename K> __global__ void __launch_bounds__(NSF_THREADS) nsf_clear_kernel(const NsfArgs a) {
+template <typename K> __global__ void __launch_bounds__(CS_THREADS) nsf_clear_kernel(const NsfArgs a) {
     const NsfBatch<K> t(a, blockIdx.y);
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t s = i0; s < a.table_cap; s += step) {
-        t.keys[s] = nsu_empty<K>();
-        t.vals[s] = NSU_UNSEEN;
-    }
-    for (int64_t s = i0; s < a.chunk_tiles; s += step) t.ctile[s] = 0;
-    if (i0 == 0) t.hdr[0] = t.hdr[1] = 0;
+    cs_clear<2>(t.keys, t.vals, a.table_cap, t.ctile, a.chunk_tiles, t.hdr, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                (int64_t)gridDim.x * blockDim.x);
 }
 
 // a tile of positions: the column, its chunks and entries, their exclusive prefixes inside the tile and the tile's sums
-template <typename K> __global__ void __launch_bounds__(NSF_THREADS) nsf_plan_kernel(const NsfArgs a) {
-    __shared__ unsigned long long s_wave[NSF_THREADS / 64];
+template <typename K> __global__ void __launch_bounds__(CS_THREADS) nsf_plan_kernel(const NsfArgs a) {
+    __shared__ unsigned long long s_wave[CS_THREADS / 64];
     const int64_t b = blockIdx.y;
     int64_t base;
     const int64_t n = nsf_list(a, b, &base);
-    const int64_t tile0 = (int64_t)blockIdx.x * NSF_TILE;
+    const int64_t tile0 = (int64_t)blockIdx.x * CS_TILE;
     if (tile0 >= n && blockIdx.x != 0) return; // uniform
     const NsfBatch<K> t(a, b);
     const int64_t p0 = tile0 + (int64_t)threadIdx.x * NSU_PER;
@@ -146,10 +105,10 @@ template <typename K> __global__ void __launch_bounds__(NSF_THREADS) nsf_plan_ke
                 outside = true;
             } else {
                 // a graph's ptrs are trusted to ascend inside [0, n_edges]; the clamp keeps `indices` in range anyway
-                e0 = nsu_clamp(nsf_ptr(a, v), a.n_edges_graph);
-                const int64_t e1 = std::max(e0, nsu_clamp(nsf_ptr(a, v + 1), a.n_edges_graph));
+                e0 = nsu_clamp(csc_ptr(a.ptrs, a.ptrs32, v), a.n_edges_graph);
+                const int64_t e1 = std::max(e0, nsu_clamp(csc_ptr(a.ptrs, a.ptrs32, v + 1), a.n_edges_graph));
                 d[k] = (unsigned long long)(e1 - e0);
-                c[k] = (d[k] + NSF_CHUNK - 1) / NSF_CHUNK;
+                c[k] = (d[k] + CS_CHUNK - 1) / CS_CHUNK;
             }
             t.col0[p] = e0;
         }
@@ -168,23 +127,24 @@ template <typename K> __global__ void __launch_bounds__(NSF_THREADS) nsf_plan_ke
 }
 
 // adds the sums of the tiles before; the last tile closes both prefixes and takes the capacity decision
-template <typename K> __global__ void __launch_bounds__(NSF_THREADS) nsf_node_apply_kernel(const NsfArgs a) {
-    __shared__ unsigned long long s_wave[NSF_THREADS / 64];
+template <typename K> __global__ void __launch_bounds__(CS_THREADS) nsf_node_apply_kernel(const NsfArgs a) {
+    __shared__ unsigned long long s_wave[CS_THREADS / 64];
     const int64_t b = blockIdx.y;
     int64_t base;
     const int64_t n = nsf_list(a, b, &base);
-    const int64_t tile0 = (int64_t)blockIdx.x * NSF_TILE;
+    const int64_t tile0 = (int64_t)blockIdx.x * CS_TILE;
     if (tile0 >= n && blockIdx.x != 0) return; // uniform
     const NsfBatch<K> t(a, b);
+    // the chunk and the triple sums of the tiles before, interleaved in ntile: one pass, so not cs_tiles_before twice
     unsigned long long before_c = 0, before_d = 0, base_c, base_d;
-    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += NSF_THREADS) before_c += t.ntile[2 * i], before_d += t.ntile[2 * i + 1];
+    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += CS_THREADS) before_c += t.ntile[2 * i], before_d += t.ntile[2 * i + 1];
     nsu_scan64(before_c, s_wave, &base_c);
     nsu_scan64(before_d, s_wave, &base_d);
     const int64_t p0 = tile0 + (int64_t)threadIdx.x * NSU_PER;
 #pragma unroll
     for (int k = 0; k < NSU_PER; ++k)
         if (p0 + k < n) t.npref[p0 + k] += base_c, t.epref[p0 + k] += base_d;
-    if (tile0 + NSF_TILE >= n && threadIdx.x == 0) { // the batch's last tile (tile 0 of an empty batch)
+    if (tile0 + CS_TILE >= n && threadIdx.x == 0) { // the batch's last tile (tile 0 of an empty batch)
         const unsigned long long n_chunks = base_c + t.ntile[2 * blockIdx.x], m = base_d + t.ntile[2 * blockIdx.x + 1];
         t.npref[n] = n_chunks, t.epref[n] = m;
         a.n_edges[b] = (int64_t)m;
@@ -200,7 +160,7 @@ template <typename K> __global__ void __launch_bounds__(NSF_THREADS) nsf_node_ap
 }
 
 // the four scans over the batch's chunks (the file's head comment)
-template <typename K, bool I32, int MODE> __global__ void __launch_bounds__(NSF_THREADS) nsf_scan_kernel(const NsfArgs a) {
+template <typename K, bool I32, int MODE> __global__ void __launch_bounds__(CS_THREADS) nsf_scan_kernel(const NsfArgs a) {
     const int64_t b = blockIdx.y;
     const NsfBatch<K> t(a, b);
     if (t.hdr[1] == 0) return; // refused: uniform
@@ -208,26 +168,24 @@ template <typename K, bool I32, int MODE> __global__ void __launch_bounds__(NSF_
     int64_t base;
     const int64_t n = nsf_list(a, b, &base);
     if (MODE == NSF_INSERT && n_chunks) { // the frontier: value = position (nobody looks a batch without triples up)
-        for (int64_t p = (int64_t)blockIdx.x * NSF_THREADS + threadIdx.x; p < n; p += (int64_t)gridDim.x * NSF_THREADS) {
+        for (int64_t p = (int64_t)blockIdx.x * CS_THREADS + threadIdx.x; p < n; p += (int64_t)gridDim.x * CS_THREADS) {
             const int64_t v = a.nodes[base + p];
             if ((uint64_t)v < (uint64_t)a.id_bound) { // any other word equals no source
-                const uint32_t s = nsf_insert<K>(t.keys, a.cap_mask, a.hash_shift, (K)v);
+                const uint32_t s = nsu_insert<K, true>(t.keys, a.cap_mask, a.hash_shift, (K)v);
                 atomicMin(&t.vals[s], (uint32_t)p);
             }
         }
     }
     if (MODE == NSF_NODES && a.nodes_out) {
         int64_t *out = a.nodes_out + a.node_off[b];
-        for (int64_t p = (int64_t)blockIdx.x * NSF_THREADS + threadIdx.x; p < n; p += (int64_t)gridDim.x * NSF_THREADS)
+        for (int64_t p = (int64_t)blockIdx.x * CS_THREADS + threadIdx.x; p < n; p += (int64_t)gridDim.x * CS_THREADS)
             out[p] = a.nodes[base + p];
     }
     if (n_chunks == 0) return; // uniform
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int waves = NSF_THREADS / 64;
-    // shorter units while the batch's wavefronts would not all get one: a loader-shaped batch (a thousand short columns,
-    // a chunk each) is latency, not work, and a chunk is a chain of dependent accesses (entry, key, value)
-    int unit = NSF_UNIT;
-    while (unit > 1 && (n_chunks + unit - 1) / unit < (unsigned long long)gridDim.x * waves) unit >>= 1;
+    const int waves = CS_THREADS / 64;
+    int unit = CS_UNIT;
+    while (unit > 1 && cs_short_fill(n_chunks, unit, gridDim.x, waves)) unit >>= 1;
     const unsigned long long n_units = (n_chunks + unit - 1) / unit;
     const unsigned long long below = ((unsigned long long)1 << lane) - 1;
     int64_t *nodes_out = MODE == NSF_NODES && a.nodes_out ? a.nodes_out + a.node_off[b] : nullptr;
@@ -237,18 +195,13 @@ template <typename K, bool I32, int MODE> __global__ void __launch_bounds__(NSF_
         long long my_i = 0, my_e0 = 0, my_k0 = 0;
         int my_len = 0;
         if (lane < unit && c < n_chunks) {
-            // the last position whose prefix is <= c: npref[0] = 0 <= c < n_chunks = npref[n]; it has chunks
-            int64_t lo = 0, hi = n;
-            while (hi - lo > 1) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (t.npref[mid] <= c) lo = mid; else hi = mid;
-            }
-            const long long rel = (long long)(c - t.npref[lo]) * NSF_CHUNK;
+            const int64_t lo = cs_last_le(t.npref, n, c); // npref[0] = 0 <= c < n_chunks = npref[n]; it has chunks
+            const long long rel = (long long)(c - t.npref[lo]) * CS_CHUNK;
             const long long k_lo = (long long)t.epref[lo];
             my_i = lo;
             my_e0 = t.col0[lo] + rel;
             my_k0 = k_lo + rel;
-            my_len = (int)std::min<long long>(NSF_CHUNK, (long long)t.epref[lo + 1] - my_k0);
+            my_len = (int)std::min<long long>(CS_CHUNK, (long long)t.epref[lo + 1] - my_k0);
         }
         uint32_t unit_new = 0;
         for (int q = 0; q < unit; ++q) {
@@ -268,12 +221,12 @@ template <typename K, bool I32, int MODE> __global__ void __launch_bounds__(NSF_
                 if (valid) src = I32 ? (int64_t)a.indices32[e] : a.indices[e];
                 if (MODE == NSF_INSERT) {
                     if (valid) {
-                        const uint32_t slot = nsf_insert<K>(t.keys, a.cap_mask, a.hash_shift, (K)src);
+                        const uint32_t slot = nsu_insert<K, true>(t.keys, a.cap_mask, a.hash_shift, (K)src);
                         atomicMin(&t.vals[slot], mark);
                     }
                 } else if (MODE == NSF_TRIPLES) {
                     if (valid) {
-                        const uint32_t slot = nsf_find<K>(t.keys, a.cap_mask, a.hash_shift, (K)src);
+                        const uint32_t slot = cs_find<false, true>(t.keys, t.vals, a.cap_mask, a.hash_shift, (K)src);
                         const int64_t o = out0 + k0 + s + lane;
                         a.rows[o] = slot != NSU_UNSEEN ? (int64_t)t.vals[slot] : -1;
                         a.cols[o] = i;
@@ -281,7 +234,7 @@ template <typename K, bool I32, int MODE> __global__ void __launch_bounds__(NSF_
                     }
                 } else {
                     uint32_t slot = NSU_UNSEEN;
-                    if (valid) slot = nsf_find<K>(t.keys, a.cap_mask, a.hash_shift, (K)src);
+                    if (valid) slot = cs_find<false, true>(t.keys, t.vals, a.cap_mask, a.hash_shift, (K)src);
                     const bool first = slot != NSU_UNSEEN && t.vals[slot] == mark;
                     const unsigned long long firsts = __ballot(first);
                     const uint32_t rank = cnt + (uint32_t)__popcll(firsts & below);
@@ -298,40 +251,23 @@ template <typename K, bool I32, int MODE> __global__ void __launch_bounds__(NSF_
                 unit_new += cnt;
             }
         }
-        if (MODE == NSF_FLAG && lane == 0 && unit_new) atomicAdd(&t.ctile[u * unit / NSF_TILE], unit_new);
+        if (MODE == NSF_FLAG) cs_unit_counted(t.ctile, u, unit, unit_new, lane);
     }
 }
 
 // the exclusive prefix over a tile of chunks, in place; the last tile writes n_out_b (0 for a refused batch)
-template <typename K> __global__ void __launch_bounds__(NSF_THREADS) nsf_chunk_apply_kernel(const NsfArgs a) {
-    __shared__ uint32_t s_wave[NSF_THREADS / 64];
+template <typename K> __global__ void __launch_bounds__(CS_THREADS) nsf_chunk_apply_kernel(const NsfArgs a) {
+    __shared__ uint32_t s_wave[CS_THREADS / 64];
     const int64_t b = blockIdx.y;
     const NsfBatch<K> t(a, b);
     const unsigned long long n_chunks = t.hdr[0];
-    const unsigned long long tile0 = (unsigned long long)blockIdx.x * NSF_TILE;
-    if (tile0 >= n_chunks && blockIdx.x != 0) return; // uniform
-    uint32_t before = 0, base;
-    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += NSF_THREADS) before += t.ctile[i];
-    nsu_scan(before, s_wave, &base);
-    const unsigned long long c0 = tile0 + (unsigned long long)threadIdx.x * NSU_PER;
-    uint32_t h[NSU_PER], mine = 0;
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k) {
-        h[k] = c0 + k < n_chunks ? t.cpref[c0 + k] : 0;
-        mine += h[k];
-    }
-    uint32_t total;
-    uint32_t run = base + nsu_scan(mine, s_wave, &total);
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k) {
-        if (c0 + k < n_chunks) t.cpref[c0 + k] = run;
-        run += h[k];
-    }
-    if (tile0 + NSF_TILE >= n_chunks && threadIdx.x == 0) { // the batch's last tile (tile 0 of a batch without chunks)
+    if (cs_tile_idle(n_chunks)) return;
+    const CsTile<uint32_t> r = cs_chunk_apply_tile(t.cpref, t.ctile, n_chunks, s_wave);
+    if (r.last && threadIdx.x == 0) {
         int64_t list;
         const int64_t n = nsf_list(a, b, &list);
-        t.cpref[n_chunks] = base + total;
-        a.n_nodes[b] = t.hdr[1] ? n + (int64_t)(base + total) : 0;
+        t.cpref[n_chunks] = r.base + r.total;
+        a.n_nodes[b] = t.hdr[1] ? n + (int64_t)(r.base + r.total) : 0;
     }
 }
 
@@ -342,27 +278,20 @@ struct NsfPlan {
     int64_t vals_off, npref_off, epref_off, col0_off, ntile_off, cpref_off, ctile_off, batch_bytes;
 };
 
-static int nsf_plan(const tg_graph *csc, const tg_ns_full_in *in, int64_t id_bound, int64_t n_batches, const char *who,
-                    NsfPlan &pl) {
+static int nsf_plan(const tg_graph *csc, const tg_ns_full_in *in, int64_t id_bound, const char *who, NsfPlan &pl) {
     TG_REQUIRE(csc && in, "%s: null argument", who);
-    TG_REQUIRE(n_batches >= 0 && n_batches <= 0x7fffffff, "%s: n_batches = %lld outside [0, 2^31)", who, (long long)n_batches);
-    TG_REQUIRE(csc->n_major >= 0 && csc->n_edges >= 0, "%s: negative graph size (n_major = %lld, n_edges = %lld)", who,
-               (long long)csc->n_major, (long long)csc->n_edges);
     TG_REQUIRE(in->max_nodes >= 0 && in->max_nodes <= NSU_MAX_NODES, "%s: max_nodes = %lld outside [0, 2^30]", who,
                (long long)in->max_nodes);
     TG_REQUIRE(in->node_cap >= in->max_nodes && in->node_cap <= NSU_MAX_NODES, "%s: node_cap = %lld outside [max_nodes = %lld, 2^30]",
                who, (long long)in->node_cap, (long long)in->max_nodes);
+    // a frontier of distinct nodes has disjoint columns, the ones of cs_plan_chunks' default bound
+    if (const int rc = cs_plan_chunks(csc, in->max_nodes, in->chunk_cap, who, pl.chunk_bound, pl.chunk_tiles)) return rc;
     if (const int rc = nsu_plan(in->node_cap, id_bound, who, pl.table)) return rc; // id_bound >= 1, the key width, the table
     TG_REQUIRE(id_bound >= csc->n_major, "%s: id_bound = %lld below n_major = %lld", who, (long long)id_bound,
                (long long)csc->n_major);
-    TG_REQUIRE(in->chunk_cap <= NSF_MAX_CHUNKS, "%s: chunk_cap = %lld, at most 2^31 expected", who, (long long)in->chunk_cap);
-    // a frontier of distinct nodes has disjoint columns: every column ends in at most one ragged chunk
-    pl.chunk_bound = in->chunk_cap > 0 ? in->chunk_cap : in->max_nodes + (csc->n_edges + NSF_CHUNK - 1) / NSF_CHUNK;
-    TG_REQUIRE(pl.chunk_bound <= NSF_MAX_CHUNKS, "%s: %lld chunks per batch, at most 2^31 expected", who, (long long)pl.chunk_bound);
     const int64_t pitch = in->max_nodes;
-    pl.node_tiles = pitch > 0 ? (pitch + NSF_TILE - 1) / NSF_TILE : 1;
-    pl.chunk_tiles = pl.chunk_bound / NSF_TILE + 1;
-    pl.vals_off = NSF_HEADER + nsu_r256(pl.table.table_cap * pl.table.key_bytes);
+    pl.node_tiles = pitch > 0 ? (pitch + CS_TILE - 1) / CS_TILE : 1;
+    pl.vals_off = CS_HEADER + nsu_r256(pl.table.table_cap * pl.table.key_bytes);
     pl.npref_off = pl.vals_off + nsu_r256(pl.table.table_cap * 4);
     pl.epref_off = pl.npref_off + nsu_r256((pitch + 1) * 8);
     pl.col0_off = pl.epref_off + nsu_r256((pitch + 1) * 8);
@@ -370,21 +299,16 @@ static int nsf_plan(const tg_graph *csc, const tg_ns_full_in *in, int64_t id_bou
     pl.cpref_off = pl.ntile_off + nsu_r256(pl.node_tiles * 16);
     pl.ctile_off = pl.cpref_off + nsu_r256((pl.chunk_bound + 1) * 4);
     pl.batch_bytes = pl.ctile_off + nsu_r256(pl.chunk_tiles * 4);
-    TG_REQUIRE(pl.batch_bytes <= INT64_MAX / std::max<int64_t>(1, n_batches), "%s: %lld batches of %lld bytes overflow int64", who,
-               (long long)n_batches, (long long)pl.batch_bytes);
     return TG_OK;
 }
 
 // what both passes check alike, and the kernel arguments of batch 0
 static int nsf_common(const tg_graph *csc, const tg_ns_full_in *in, int64_t n_batches, int64_t id_bound, void *workspace,
                       int64_t workspace_bytes, const char *who, NsfPlan &pl, NsfArgs &a) {
-    if (const int rc = nsf_plan(csc, in, id_bound, n_batches, who, pl)) return rc;
-    TG_REQUIRE(workspace_bytes >= 0, "%s: workspace_bytes = %lld is negative", who, (long long)workspace_bytes);
-    TG_REQUIRE(workspace && workspace_bytes / pl.batch_bytes >= n_batches,
-               "%s: workspace too small (%lld bytes, %lld batches of %lld expected)", who,
-               (long long)(workspace ? workspace_bytes : 0), (long long)n_batches, (long long)pl.batch_bytes);
-    TG_REQUIRE(((uintptr_t)workspace & 7u) == 0, "%s: workspace must be 8-byte aligned", who);
-    TG_REQUIRE(csc->ptrs && csc->indices, "%s: null ptrs / indices", who);
+    if (const int rc = nsf_plan(csc, in, id_bound, who, pl)) return rc;
+    if (n_batches >= 0 && n_batches <= 0x7fffffff) // the text this pair has always refused such a launch with
+        if (const int rc = cs_bytes_fit(pl.batch_bytes, n_batches, who)) return rc;
+    if (const int rc = cs_check_launch(csc, n_batches, pl.batch_bytes, workspace, workspace_bytes, who)) return rc;
     TG_REQUIRE(in->node_ptr, "%s: null node_ptr", who);
     TG_REQUIRE(in->nodes || in->max_nodes == 0, "%s: null nodes", who);
     a = NsfArgs{};
@@ -396,8 +320,7 @@ static int nsf_common(const tg_graph *csc, const tg_ns_full_in *in, int64_t n_ba
     a.batch_bytes = pl.batch_bytes, a.vals_off = pl.vals_off, a.npref_off = pl.npref_off, a.epref_off = pl.epref_off;
     a.col0_off = pl.col0_off, a.ntile_off = pl.ntile_off, a.cpref_off = pl.cpref_off, a.ctile_off = pl.ctile_off;
     a.chunk_bound = pl.chunk_bound, a.table_cap = pl.table.table_cap, a.chunk_tiles = pl.chunk_tiles;
-    a.cap_mask = (uint32_t)(pl.table.table_cap - 1);
-    a.hash_shift = 32u - (uint32_t)__builtin_ctzll((unsigned long long)pl.table.table_cap);
+    nsu_mask_shift(pl.table.table_cap, a.cap_mask, a.hash_shift);
     return TG_OK;
 }
 
@@ -413,10 +336,8 @@ static NsfArgs nsf_at(const NsfArgs &a0, int64_t b0) {
     return a;
 }
 
-static inline unsigned nsf_scan_grid(int64_t nb) { return (unsigned)std::max<int64_t>(1, NSF_SCAN_BLOCKS / nb); }
-
 template <typename K, int MODE> static int nsf_launch_scan(const NsfArgs &a, int64_t nb, hipStream_t stream) {
-    const dim3 grid(nsf_scan_grid(nb), (unsigned)nb), block(NSF_THREADS);
+    const dim3 grid(cs_scan_grid(nb), (unsigned)nb), block(CS_THREADS);
     if (a.indices32)
         hipLaunchKernelGGL((nsf_scan_kernel<K, true, MODE>), grid, block, 0, stream, a);
     else
@@ -426,11 +347,10 @@ template <typename K, int MODE> static int nsf_launch_scan(const NsfArgs &a, int
 }
 
 template <typename K> static int nsf_count(const NsfArgs &a0, const NsfPlan &pl, int64_t n_batches, hipStream_t stream) {
-    const dim3 block(NSF_THREADS);
-    const int64_t clear_blocks = (std::max(pl.table.table_cap, pl.chunk_tiles) + NSF_THREADS - 1) / NSF_THREADS;
-    for (int64_t b0 = 0; b0 < n_batches; b0 += NSU_ROUND_MAX) {
+    const dim3 block(CS_THREADS);
+    const int64_t clear_blocks = (std::max(pl.table.table_cap, pl.chunk_tiles) + CS_THREADS - 1) / CS_THREADS;
+    return cs_rounds(n_batches, [&](int64_t b0, int64_t nb_) {
         const NsfArgs a = nsf_at(a0, b0);
-        const int64_t nb_ = std::min(NSU_ROUND_MAX, n_batches - b0);
         const unsigned nb = (unsigned)nb_;
         hipLaunchKernelGGL(nsf_clear_kernel<K>, dim3((unsigned)std::min<int64_t>(clear_blocks, 1024), nb), block, 0, stream, a);
         TG_LAUNCH_CHECK();
@@ -442,18 +362,16 @@ template <typename K> static int nsf_count(const NsfArgs &a0, const NsfPlan &pl,
         if (const int rc = nsf_launch_scan<K, NSF_FLAG>(a, nb_, stream)) return rc;
         hipLaunchKernelGGL(nsf_chunk_apply_kernel<K>, dim3((unsigned)pl.chunk_tiles, nb), block, 0, stream, a);
         TG_LAUNCH_CHECK();
-    }
-    return TG_OK;
+        return (int)TG_OK;
+    });
 }
 
 template <typename K> static int nsf_emit(const NsfArgs &a0, int64_t n_batches, hipStream_t stream) {
-    for (int64_t b0 = 0; b0 < n_batches; b0 += NSU_ROUND_MAX) {
+    return cs_rounds(n_batches, [&](int64_t b0, int64_t nb) {
         const NsfArgs a = nsf_at(a0, b0);
-        const int64_t nb = std::min(NSU_ROUND_MAX, n_batches - b0);
         if (const int rc = nsf_launch_scan<K, NSF_NODES>(a, nb, stream)) return rc;
-        if (const int rc = nsf_launch_scan<K, NSF_TRIPLES>(a, nb, stream)) return rc;
-    }
-    return TG_OK;
+        return nsf_launch_scan<K, NSF_TRIPLES>(a, nb, stream);
+    });
 }
 
 } // namespace tg
@@ -462,12 +380,9 @@ extern "C" int tg_ns_full_workspace_bytes(const tg_graph *csc, const tg_ns_full_
                                           int64_t *bytes, int64_t *bytes_min) {
     using namespace tg;
     const char *who = "tg_ns_full_workspace_bytes";
-    TG_REQUIRE(bytes && bytes_min, "%s: null output", who);
     NsfPlan pl;
-    if (const int rc = nsf_plan(csc, in, id_bound, n_batches, who, pl)) return rc;
-    *bytes_min = pl.batch_bytes;
-    *bytes = pl.batch_bytes * n_batches;
-    return TG_OK;
+    if (const int rc = nsf_plan(csc, in, id_bound, who, pl)) return rc;
+    return cs_answer_bytes(pl.batch_bytes, n_batches, who, bytes, bytes_min);
 }
 
 extern "C" int tg_ns_full_count(const tg_graph *csc, const tg_ns_full_in *in, int64_t n_batches, int64_t id_bound,

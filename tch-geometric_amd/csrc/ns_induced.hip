@@ -9,22 +9,16 @@
 // fill the device batch by batch).  Per batch the workspace holds the open-addressing table of ns_unique.h (key = id,
 // value = first position by atomicMin), the node-chunk prefix, and one word per chunk.
 //
-// Columns are cut into chunks of NSI_CHUNK = 512 consecutive CSC offsets, the filtered hop's group size.  Why 512: a
-// chunk costs one search in the node-chunk prefix, one 8-byte word of workspace and one prefix element, so it should be
-// long enough that those vanish beside the scan (8 wave steps of 64 entries, each with a dependent random probe); and it
-// should be short enough that a hub spreads: a 10^5-entry column is 196 chunks = 13 wave units.  2 048 (the edge-set
-// segment) would quarter the per-chunk array (5.6 MB per loader-shaped batch on RMAT-24 at 512, beside the 1.4 MB node
-// prefix and the 2 MB table) but leaves a 10^5 hub to 4 wave units.
+// Columns are cut into chunks of CS_CHUNK consecutive CSC offsets; the chunk size, the count / prefix / emit scheme and
+// the unit walk are chunk_scan.h's.
 //
 // Pass 1: clear (table, tile sums, header) | insert + chunks per node, scanned inside a tile of positions | node apply
 //   (adds the tiles before; the batch's chunk total is compared with the bound HERE, before anything indexes the
 //   per-chunk array: overflow raises status bit 0 and the batch gets 0 chunks) | scan: hits per chunk | chunk apply (the
 //   exclusive prefix over chunks in place; its total is m_b, edge_marks read it at the marks' first chunks).
-// Pass 2: scan again, a chunk's hits go to edge_off[b] + its prefix, ranked in lane order = CSC-offset order by ballot +
-//   popcount, so a chunk's stores are consecutive addresses.  No hit mask is kept between the passes.
-// The scan kernels run a fixed grid and stride over the chunk count in the batch's header.  A wave takes a UNIT of 16
-// consecutive chunks (8, 4, 2, 1 where the batch has too few chunks to give a quarter of the grid's waves a unit): lanes 0..15 each search one chunk's node in the node-chunk prefix at once (17 dependent reads for
-// the loader's pitch, paid once per unit instead of once per chunk), then the wave walks the chunks, 64 entries a step.
+// Pass 2: scan again, a chunk's hits go to edge_off[b] + its prefix, so a chunk's stores are consecutive addresses.
+// A unit's look-up lanes each search one chunk's node in the node-chunk prefix (17 dependent reads for the loader's
+// pitch); the unit shrinks by cs_short_quarter.
 // The table of a loader-shaped batch (2^18 slots, 2 MB) does not stay in one XCD's 4 MiB L2 beside 15 others: probes are
 // Infinity Cache hits at best, and only wavefronts in flight hide them -- 8 waves per SIMD, no LDS, few registers.
 // An id outside [0, n_major) is a column of length 0, is not inserted and raises status bit 1.  Probe loops are capped at
@@ -38,22 +32,10 @@
 // chunk count goes to chunks[b], and the comparison still happens in the node apply kernel.  A group word outside
 // [0, n_groups) is a column of length 0, is not inserted and raises status bit 2.  The G = false instances are what the
 // ungrouped exports launch: no group word is read, no key is widened, no timestamp is looked at.
-#include <algorithm>
-
-#include "ns_unique.h"
+#include "chunk_scan.h"
 #include "tg_filter.h"
 
 namespace tg {
-
-constexpr int NSI_CHUNK = 512;                         // CSC offsets of a chunk
-constexpr int NSI_UNIT = 16;                           // chunks a wave takes at once (a power of two; fewer where chunks are few)
-constexpr int NSI_THREADS = NSU_TILE_THREADS;          // 256
-constexpr int NSI_TILE = NSU_TILE;                     // positions / chunks of a prefix tile: a thread owns NSU_PER consecutive ones
-constexpr int NSI_HEADER = 256;                        // bytes: {chunks of the batch (0 on overflow)}
-constexpr int64_t NSI_MAX_CHUNKS = (int64_t)1 << 31;   // of the bound
-constexpr int64_t NSI_GRID_Y = 32768;                  // batches per launch
-constexpr int NSI_SCAN_BLOCKS = 2048;                  // of the fixed grid: 256 CUs x 4 SIMDs x 8 waves in 4-wave workgroups
-static_assert(NSI_TILE % NSI_UNIT == 0, "a unit's chunks share a tile");
 
 struct NsiArgs {
     const int64_t *ptrs, *indices;
@@ -84,7 +66,7 @@ template <typename K> struct NsiBatch {
     __device__ __forceinline__ NsiBatch(const NsiArgs &a, int64_t b) {
         unsigned char *base = a.ws + b * a.batch_bytes;
         hdr = reinterpret_cast<unsigned long long *>(base);
-        keys = reinterpret_cast<K *>(base + NSI_HEADER);
+        keys = reinterpret_cast<K *>(base + CS_HEADER);
         vals = reinterpret_cast<uint32_t *>(base + a.vals_off);
         npref = reinterpret_cast<unsigned long long *>(base + a.npref_off); // [pitch + 1] chunks before a position
         ntile = reinterpret_cast<unsigned long long *>(base + a.ntile_off); // [node tiles]
@@ -93,40 +75,18 @@ template <typename K> struct NsiBatch {
     }
 };
 
-__device__ __forceinline__ int64_t nsi_ptr(const NsiArgs &a, int64_t v) {
-    return a.ptrs32 ? (int64_t)a.ptrs32[v] : a.ptrs[v];
-}
-
-// the first position of `key` in the batch's list, NSU_UNSEEN where it has none; at most one pass over the table
-template <typename K>
-__device__ __forceinline__ uint32_t nsi_find(const K *keys, const uint32_t *vals, uint32_t mask, uint32_t shift, K key) {
-    uint32_t s = nsu_hash(key, mask, shift);
-    for (uint32_t i = 0; i <= mask; ++i) {
-        const K k = keys[s];
-        if (k == key) return vals[s];
-        if (k == nsu_empty<K>()) break;
-        s = (s + 1) & mask;
-    }
-    return NSU_UNSEEN;
-}
-
-template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_clear_kernel(const NsiArgs a) {
+template <typename K> __global__ void __launch_bounds__(CS_THREADS) nsi_clear_kernel(const NsiArgs a) {
     const NsiBatch<K> t(a, blockIdx.y);
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t s = i0; s < a.table_cap; s += step) {
-        t.keys[s] = nsu_empty<K>();
-        t.vals[s] = NSU_UNSEEN;
-    }
-    for (int64_t s = i0; s < a.chunk_tiles; s += step) t.ctile[s] = 0;
-    if (i0 == 0) t.hdr[0] = 0;
+    cs_clear<1>(t.keys, t.vals, a.table_cap, t.ctile, a.chunk_tiles, t.hdr, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                (int64_t)gridDim.x * blockDim.x);
 }
 
 // a tile of positions: insert, chunks per position, their exclusive prefix inside the tile and the tile's sum
-template <typename K, bool G> __global__ void __launch_bounds__(NSI_THREADS) nsi_insert_kernel(const NsiArgs a) {
-    __shared__ unsigned long long s_wave[NSI_THREADS / 64];
+template <typename K, bool G> __global__ void __launch_bounds__(CS_THREADS) nsi_insert_kernel(const NsiArgs a) {
+    __shared__ unsigned long long s_wave[CS_THREADS / 64];
     const int64_t b = blockIdx.y;
     const int64_t n = nsu_clamp(a.counts[b * a.counts_stride], a.pitch);
-    const int64_t tile0 = (int64_t)blockIdx.x * NSI_TILE;
+    const int64_t tile0 = (int64_t)blockIdx.x * CS_TILE;
     if (tile0 >= n && blockIdx.x != 0) return; // uniform
     const NsiBatch<K> t(a, b);
     const int64_t *nodes = a.nodes + b * a.pitch;
@@ -153,8 +113,8 @@ template <typename K, bool G> __global__ void __launch_bounds__(NSI_THREADS) nsi
             } else if (grouped) {
                 const uint32_t s = nsu_insert<K>(t.keys, a.cap_mask, a.hash_shift, key);
                 atomicMin(&t.vals[s], (uint32_t)p);
-                const int64_t deg = nsi_ptr(a, v + 1) - nsi_ptr(a, v);
-                if (deg > 0) c[k] = (unsigned long long)((deg + NSI_CHUNK - 1) / NSI_CHUNK);
+                const int64_t deg = csc_ptr(a.ptrs, a.ptrs32, v + 1) - csc_ptr(a.ptrs, a.ptrs32, v);
+                if (deg > 0) c[k] = (unsigned long long)((deg + CS_CHUNK - 1) / CS_CHUNK);
             }
         }
         mine += c[k];
@@ -172,21 +132,19 @@ template <typename K, bool G> __global__ void __launch_bounds__(NSI_THREADS) nsi
 }
 
 // adds the chunks of the tiles before; the last tile closes the prefix and decides whether the batch fits the bound
-template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_node_apply_kernel(const NsiArgs a) {
-    __shared__ unsigned long long s_wave[NSI_THREADS / 64];
+template <typename K> __global__ void __launch_bounds__(CS_THREADS) nsi_node_apply_kernel(const NsiArgs a) {
+    __shared__ unsigned long long s_wave[CS_THREADS / 64];
     const int64_t b = blockIdx.y;
     const int64_t n = nsu_clamp(a.counts[b * a.counts_stride], a.pitch);
-    const int64_t tile0 = (int64_t)blockIdx.x * NSI_TILE;
+    const int64_t tile0 = (int64_t)blockIdx.x * CS_TILE;
     if (tile0 >= n && blockIdx.x != 0) return; // uniform
     const NsiBatch<K> t(a, b);
-    unsigned long long before = 0, base;
-    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += NSI_THREADS) before += t.ntile[i];
-    nsu_scan64(before, s_wave, &base);
+    const unsigned long long base = cs_tiles_before(t.ntile, s_wave);
     const int64_t p0 = tile0 + (int64_t)threadIdx.x * NSU_PER;
 #pragma unroll
     for (int k = 0; k < NSU_PER; ++k)
         if (p0 + k < n) t.npref[p0 + k] += base;
-    if (tile0 + NSI_TILE >= n && threadIdx.x == 0) { // the batch's last tile (tile 0 of an empty batch)
+    if (tile0 + CS_TILE >= n && threadIdx.x == 0) { // the batch's last tile (tile 0 of an empty batch)
         const unsigned long long total = base + t.ntile[blockIdx.x];
         t.npref[n] = total;
         if (a.chunks) a.chunks[b] = (int64_t)total;
@@ -201,7 +159,7 @@ template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_node_ap
 
 // EMIT = false: hits per chunk (and their sum per tile of chunks); true: the hits themselves
 template <typename K, bool I32, bool EMIT, bool G>
-__global__ void __launch_bounds__(NSI_THREADS) nsi_scan_kernel(const NsiArgs a) {
+__global__ void __launch_bounds__(CS_THREADS) nsi_scan_kernel(const NsiArgs a) {
     const int64_t b = blockIdx.y;
     const NsiBatch<K> t(a, b);
     const unsigned long long n_chunks = t.hdr[0];
@@ -209,10 +167,9 @@ __global__ void __launch_bounds__(NSI_THREADS) nsi_scan_kernel(const NsiArgs a) 
     const int64_t n = nsu_clamp(a.counts[b * a.counts_stride], a.pitch);
     const int64_t *nodes = a.nodes + b * a.pitch;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int waves = NSI_THREADS / 64;
-    // a batch with fewer units than a quarter of the grid's waves takes shorter units, so that a lone hub still spreads
-    int unit = NSI_UNIT;
-    while (unit > 1 && 4 * n_chunks < (unsigned long long)unit * gridDim.x * waves) unit >>= 1;
+    const int waves = CS_THREADS / 64;
+    int unit = CS_UNIT;
+    while (unit > 1 && cs_short_quarter(n_chunks, unit, gridDim.x, waves)) unit >>= 1;
     const unsigned long long n_units = (n_chunks + unit - 1) / unit;
     const unsigned long long below = ((unsigned long long)1 << lane) - 1;
     const int64_t out0 = EMIT ? a.edge_off[b] : 0;
@@ -222,17 +179,12 @@ __global__ void __launch_bounds__(NSI_THREADS) nsi_scan_kernel(const NsiArgs a) 
         int my_len = 0;
         uint32_t my_group = 0;
         if (lane < unit && c < n_chunks) {
-            // the last position whose prefix is <= c: npref[0] = 0 <= c < n_chunks = npref[n]
-            int64_t lo = 0, hi = n;
-            while (hi - lo > 1) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (t.npref[mid] <= c) lo = mid; else hi = mid;
-            }
-            const int64_t v = nodes[lo]; // in range: it has chunks
-            const int64_t col0 = nsi_ptr(a, v), col1 = nsi_ptr(a, v + 1);
+            const int64_t lo = cs_last_le(t.npref, n, c); // npref[0] = 0 <= c < n_chunks = npref[n]
+            const int64_t v = nodes[lo];                  // in range: it has chunks
+            const int64_t col0 = csc_ptr(a.ptrs, a.ptrs32, v), col1 = csc_ptr(a.ptrs, a.ptrs32, v + 1);
             my_i = lo;
-            my_e0 = col0 + (int64_t)(c - t.npref[lo]) * NSI_CHUNK;
-            my_len = (int)std::min<int64_t>(NSI_CHUNK, col1 - my_e0);
+            my_e0 = col0 + (int64_t)(c - t.npref[lo]) * CS_CHUNK;
+            my_len = (int)std::min<int64_t>(CS_CHUNK, col1 - my_e0);
             if (G) { // the position has chunks, so its group word is in range
                 my_group = (uint32_t)a.group[b * a.pitch + lo];
                 if (a.group_time) my_time = a.group_time[b * a.n_groups + my_group];
@@ -253,7 +205,7 @@ __global__ void __launch_bounds__(NSI_THREADS) nsi_scan_kernel(const NsiArgs a) 
                 uint32_t pos = NSU_UNSEEN;
                 if (s + lane < len) {
                     const K key = key0 + (I32 ? (K)a.indices32[e] : (K)a.indices[e]);
-                    pos = nsi_find<K>(t.keys, t.vals, a.cap_mask, a.hash_shift, key);
+                    pos = cs_find<true, false>(t.keys, t.vals, a.cap_mask, a.hash_shift, key); // the first position
                     if (G && pos != NSU_UNSEEN && a.group_time &&
                         !tg_filter_pass(TG_FILTER_RELATIVE, 0, a.win_lo, a.win_hi, time, a.timestamps[e]))
                         pos = NSU_UNSEEN;
@@ -272,42 +224,24 @@ __global__ void __launch_bounds__(NSI_THREADS) nsi_scan_kernel(const NsiArgs a) 
                 unit_hits += cnt;
             }
         }
-        if (!EMIT && lane == 0 && unit_hits) atomicAdd(&t.ctile[u * unit / NSI_TILE], unit_hits);
+        if (!EMIT) cs_unit_counted(t.ctile, u, unit, unit_hits, lane);
     }
 }
 
 // the exclusive prefix over a tile of chunks, in place; the last tile writes m_b; edge_marks read the prefix at the marks'
 // first chunks
-template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_chunk_apply_kernel(const NsiArgs a) {
-    __shared__ unsigned long long s_wave[NSI_THREADS / 64];
+template <typename K> __global__ void __launch_bounds__(CS_THREADS) nsi_chunk_apply_kernel(const NsiArgs a) {
+    __shared__ unsigned long long s_wave[CS_THREADS / 64];
     const int64_t b = blockIdx.y;
     const NsiBatch<K> t(a, b);
     const unsigned long long n_chunks = t.hdr[0];
-    const unsigned long long tile0 = (unsigned long long)blockIdx.x * NSI_TILE;
-    if (tile0 >= n_chunks && blockIdx.x != 0) return; // uniform
-    unsigned long long before = 0, base;
-    for (uint32_t i = threadIdx.x; i < blockIdx.x; i += NSI_THREADS) before += t.ctile[i];
-    nsu_scan64(before, s_wave, &base);
-    const unsigned long long c0 = tile0 + (unsigned long long)threadIdx.x * NSU_PER;
-    unsigned long long h[NSU_PER], mine = 0;
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k) {
-        h[k] = c0 + k < n_chunks ? t.cpref[c0 + k] : 0;
-        mine += h[k];
-    }
-    unsigned long long total;
-    unsigned long long run = base + nsu_scan64(mine, s_wave, &total);
+    if (cs_tile_idle(n_chunks)) return;
     unsigned long long pre[NSU_PER];
-#pragma unroll
-    for (int k = 0; k < NSU_PER; ++k) {
-        pre[k] = run;
-        if (c0 + k < n_chunks) t.cpref[c0 + k] = run;
-        run += h[k];
-    }
-    const bool last = tile0 + NSI_TILE >= n_chunks; // the batch's last tile (tile 0 of a batch without chunks)
-    if (last && threadIdx.x == 0) {
-        t.cpref[n_chunks] = base + total;
-        a.n_edges[b] = (int64_t)(base + total);
+    const CsTile<unsigned long long> r = cs_chunk_apply_tile(t.cpref, t.ctile, n_chunks, s_wave, pre);
+    const int64_t m_b = (int64_t)(r.base + r.total);
+    if (r.last && threadIdx.x == 0) {
+        t.cpref[n_chunks] = r.base + r.total;
+        a.n_edges[b] = m_b;
     }
     if (a.edge_marks) {
         const int64_t n = nsu_clamp(a.counts[b * a.counts_stride], a.pitch);
@@ -315,9 +249,9 @@ template <typename K> __global__ void __launch_bounds__(NSI_THREADS) nsi_chunk_a
             const int64_t L = nsu_clamp(a.node_marks[b * a.n_marks + m], n);
             const unsigned long long cs = n_chunks ? t.npref[L] : 0; // the first chunk of position L (n_chunks: none left)
             if (cs >= n_chunks) {
-                if (last && threadIdx.x == 0) a.edge_marks[b * a.n_marks + m] = (int64_t)(base + total);
-            } else if (cs >= c0 && cs < c0 + NSU_PER) {
-                a.edge_marks[b * a.n_marks + m] = (int64_t)pre[cs - c0];
+                if (r.last && threadIdx.x == 0) a.edge_marks[b * a.n_marks + m] = m_b;
+            } else if (cs >= r.c0 && cs < r.c0 + NSU_PER) {
+                a.edge_marks[b * a.n_marks + m] = (int64_t)pre[cs - r.c0];
             }
         }
     }
@@ -334,10 +268,10 @@ struct NsiPlan {
 // chunk_cap > 0 is the caller's capacity
 static int nsi_plan(const tg_graph *csc, int64_t pitch, int64_t id_bound, int64_t n_groups, int64_t chunk_cap, const char *who,
                     NsiPlan &pl) {
-    TG_REQUIRE(csc, "%s: null graph", who);
-    TG_REQUIRE(csc->n_major >= 0 && csc->n_edges >= 0, "%s: negative graph size (n_major = %lld, n_edges = %lld)", who,
-               (long long)csc->n_major, (long long)csc->n_edges);
     TG_REQUIRE(pitch >= 0 && pitch <= NSU_MAX_NODES, "%s: pitch_nodes = %lld outside [0, 2^30]", who, (long long)pitch);
+    // distinct nodes have disjoint columns, which is cs_plan_chunks' default bound.  A disjoint list has no such property;
+    // there it is only the default a caller may raise
+    if (const int rc = cs_plan_chunks(csc, pitch, chunk_cap, who, pl.chunk_bound, pl.chunk_tiles)) return rc;
     TG_REQUIRE(id_bound >= 1, "%s: id_bound = %lld, at least 1 expected", who, (long long)id_bound);
     int64_t key_bound = id_bound;
     if (n_groups) {
@@ -349,14 +283,8 @@ static int nsi_plan(const tg_graph *csc, int64_t pitch, int64_t id_bound, int64_
     if (const int rc = nsu_plan(pitch, key_bound, who, pl.table)) return rc; // the key width, the table
     TG_REQUIRE(id_bound >= csc->n_major, "%s: id_bound = %lld below n_major = %lld", who, (long long)id_bound,
                (long long)csc->n_major);
-    TG_REQUIRE(chunk_cap <= NSI_MAX_CHUNKS, "%s: chunk_cap = %lld, at most 2^31 expected", who, (long long)chunk_cap);
-    // distinct nodes have disjoint columns: every column ends in at most one ragged chunk.  A disjoint list has no such
-    // property; there this is only the default a caller may raise
-    pl.chunk_bound = chunk_cap > 0 ? chunk_cap : pitch + (csc->n_edges + NSI_CHUNK - 1) / NSI_CHUNK;
-    TG_REQUIRE(pl.chunk_bound <= NSI_MAX_CHUNKS, "%s: %lld chunks per batch, at most 2^31 expected", who, (long long)pl.chunk_bound);
-    pl.node_tiles = pitch > 0 ? (pitch + NSI_TILE - 1) / NSI_TILE : 1;
-    pl.chunk_tiles = pl.chunk_bound / NSI_TILE + 1;
-    pl.vals_off = NSI_HEADER + nsu_r256(pl.table.table_cap * pl.table.key_bytes);
+    pl.node_tiles = pitch > 0 ? (pitch + CS_TILE - 1) / CS_TILE : 1;
+    pl.vals_off = CS_HEADER + nsu_r256(pl.table.table_cap * pl.table.key_bytes);
     pl.npref_off = pl.vals_off + nsu_r256(pl.table.table_cap * 4);
     pl.ntile_off = pl.npref_off + nsu_r256((pitch + 1) * 8);
     pl.cpref_off = pl.ntile_off + nsu_r256(pl.node_tiles * 8);
@@ -369,7 +297,6 @@ static int nsi_plan(const tg_graph *csc, int64_t pitch, int64_t id_bound, int64_
 static int nsi_common(const tg_graph *csc, const tg_ns_induced_in *in, const tg_ns_induced_grouped_in *gin, int64_t n_batches,
                       int64_t id_bound, void *workspace, int64_t workspace_bytes, const char *who, NsiPlan &pl, NsiArgs &a) {
     TG_REQUIRE(csc && in, "%s: null argument", who);
-    TG_REQUIRE(n_batches >= 0 && n_batches <= 0x7fffffff, "%s: n_batches = %lld outside [0, 2^31)", who, (long long)n_batches);
     if (gin) TG_REQUIRE(gin->n_groups >= 1, "%s: n_groups = %lld, at least 1 expected", who, (long long)gin->n_groups);
     if (const int rc = nsi_plan(csc, in->pitch_nodes, id_bound, gin ? gin->n_groups : 0, gin ? gin->chunk_cap : 0, who, pl))
         return rc;
@@ -379,12 +306,7 @@ static int nsi_common(const tg_graph *csc, const tg_ns_induced_in *in, const tg_
     }
     TG_REQUIRE(in->counts_stride >= 1, "%s: counts_stride = %lld, at least 1 expected", who, (long long)in->counts_stride);
     TG_REQUIRE(in->n_marks >= 0 && in->n_marks <= TG_MAX_HOPS, "%s: n_marks = %d outside [0, %d]", who, in->n_marks, TG_MAX_HOPS);
-    TG_REQUIRE(workspace_bytes >= 0, "%s: workspace_bytes = %lld is negative", who, (long long)workspace_bytes);
-    TG_REQUIRE(workspace && workspace_bytes / pl.batch_bytes >= n_batches,
-               "%s: workspace too small (%lld bytes, %lld batches of %lld expected)", who,
-               (long long)(workspace ? workspace_bytes : 0), (long long)n_batches, (long long)pl.batch_bytes);
-    TG_REQUIRE(((uintptr_t)workspace & 7u) == 0, "%s: workspace must be 8-byte aligned", who);
-    TG_REQUIRE(csc->ptrs && csc->indices, "%s: null ptrs / indices", who);
+    if (const int rc = cs_check_launch(csc, n_batches, pl.batch_bytes, workspace, workspace_bytes, who)) return rc;
     TG_REQUIRE(in->nodes && in->counts, "%s: null nodes / counts", who);
     a = NsiArgs{};
     a.ptrs = csc->ptrs, a.indices = csc->indices, a.ptrs32 = csc->ptrs32, a.indices32 = csc->indices32;
@@ -395,8 +317,7 @@ static int nsi_common(const tg_graph *csc, const tg_ns_induced_in *in, const tg_
     a.batch_bytes = pl.batch_bytes, a.vals_off = pl.vals_off, a.npref_off = pl.npref_off, a.ntile_off = pl.ntile_off;
     a.cpref_off = pl.cpref_off, a.ctile_off = pl.ctile_off, a.chunk_bound = pl.chunk_bound;
     a.table_cap = pl.table.table_cap, a.chunk_tiles = pl.chunk_tiles;
-    a.cap_mask = (uint32_t)(pl.table.table_cap - 1);
-    a.hash_shift = 32u - (uint32_t)__builtin_ctzll((unsigned long long)pl.table.table_cap);
+    nsu_mask_shift(pl.table.table_cap, a.cap_mask, a.hash_shift);
     if (gin) {
         a.group = gin->group, a.group_time = gin->group_time, a.timestamps = csc->timestamps;
         a.n_groups = gin->n_groups, a.win_lo = gin->window_lo, a.win_hi = gin->window_hi;
@@ -429,12 +350,10 @@ static NsiArgs nsi_at(const NsiArgs &a0, int64_t b0) {
     return a;
 }
 
-static inline unsigned nsi_scan_grid(int64_t nb) { return (unsigned)std::max<int64_t>(1, NSI_SCAN_BLOCKS / nb); }
-
 template <typename K, bool G> static int nsi_launch_count(const NsiArgs &a, const NsiPlan &pl, int64_t nb_, hipStream_t stream) {
     const unsigned nb = (unsigned)nb_;
-    const dim3 block(NSI_THREADS);
-    const int64_t clear_blocks = (pl.table.table_cap + NSI_THREADS - 1) / NSI_THREADS;
+    const dim3 block(CS_THREADS);
+    const int64_t clear_blocks = (pl.table.table_cap + CS_THREADS - 1) / CS_THREADS;
     hipLaunchKernelGGL(nsi_clear_kernel<K>, dim3((unsigned)std::min<int64_t>(clear_blocks, 1024), nb), block, 0, stream, a);
     TG_LAUNCH_CHECK();
     hipLaunchKernelGGL((nsi_insert_kernel<K, G>), dim3((unsigned)pl.node_tiles, nb), block, 0, stream, a);
@@ -442,9 +361,9 @@ template <typename K, bool G> static int nsi_launch_count(const NsiArgs &a, cons
     hipLaunchKernelGGL(nsi_node_apply_kernel<K>, dim3((unsigned)pl.node_tiles, nb), block, 0, stream, a);
     TG_LAUNCH_CHECK();
     if (a.indices32)
-        hipLaunchKernelGGL((nsi_scan_kernel<K, true, false, G>), dim3(nsi_scan_grid(nb_), nb), block, 0, stream, a);
+        hipLaunchKernelGGL((nsi_scan_kernel<K, true, false, G>), dim3(cs_scan_grid(nb_), nb), block, 0, stream, a);
     else
-        hipLaunchKernelGGL((nsi_scan_kernel<K, false, false, G>), dim3(nsi_scan_grid(nb_), nb), block, 0, stream, a);
+        hipLaunchKernelGGL((nsi_scan_kernel<K, false, false, G>), dim3(cs_scan_grid(nb_), nb), block, 0, stream, a);
     TG_LAUNCH_CHECK();
     hipLaunchKernelGGL(nsi_chunk_apply_kernel<K>, dim3((unsigned)pl.chunk_tiles, nb), block, 0, stream, a);
     TG_LAUNCH_CHECK();
@@ -452,7 +371,7 @@ template <typename K, bool G> static int nsi_launch_count(const NsiArgs &a, cons
 }
 
 template <typename K, bool G> static int nsi_launch_emit(const NsiArgs &a, int64_t nb_, hipStream_t stream) {
-    const dim3 grid(nsi_scan_grid(nb_), (unsigned)nb_), block(NSI_THREADS);
+    const dim3 grid(cs_scan_grid(nb_), (unsigned)nb_), block(CS_THREADS);
     if (a.indices32)
         hipLaunchKernelGGL((nsi_scan_kernel<K, true, true, G>), grid, block, 0, stream, a);
     else
@@ -461,27 +380,20 @@ template <typename K, bool G> static int nsi_launch_emit(const NsiArgs &a, int64
     return TG_OK;
 }
 
-// pass 1 of either pair over launches of at most NSI_GRID_Y batches
+// the passes of either pair over launches of at most CS_ROUND_MAX batches
 template <bool G> static int nsi_count(const NsiArgs &a0, const NsiPlan &pl, int64_t n_batches, hipStream_t stream) {
-    for (int64_t b0 = 0; b0 < n_batches; b0 += NSI_GRID_Y) {
+    return cs_rounds(n_batches, [&](int64_t b0, int64_t nb) {
         const NsiArgs a = nsi_at(a0, b0);
-        const int64_t nb = std::min(NSI_GRID_Y, n_batches - b0);
-        if (const int rc = pl.table.key_bytes == 4 ? nsi_launch_count<nsu_k32, G>(a, pl, nb, stream)
-                                                   : nsi_launch_count<nsu_k64, G>(a, pl, nb, stream))
-            return rc;
-    }
-    return TG_OK;
+        return pl.table.key_bytes == 4 ? nsi_launch_count<nsu_k32, G>(a, pl, nb, stream)
+                                       : nsi_launch_count<nsu_k64, G>(a, pl, nb, stream);
+    });
 }
 
 template <bool G> static int nsi_emit(const NsiArgs &a0, const NsiPlan &pl, int64_t n_batches, hipStream_t stream) {
-    for (int64_t b0 = 0; b0 < n_batches; b0 += NSI_GRID_Y) {
+    return cs_rounds(n_batches, [&](int64_t b0, int64_t nb) {
         const NsiArgs a = nsi_at(a0, b0);
-        const int64_t nb = std::min(NSI_GRID_Y, n_batches - b0);
-        if (const int rc = pl.table.key_bytes == 4 ? nsi_launch_emit<nsu_k32, G>(a, nb, stream)
-                                                   : nsi_launch_emit<nsu_k64, G>(a, nb, stream))
-            return rc;
-    }
-    return TG_OK;
+        return pl.table.key_bytes == 4 ? nsi_launch_emit<nsu_k32, G>(a, nb, stream) : nsi_launch_emit<nsu_k64, G>(a, nb, stream);
+    });
 }
 
 } // namespace tg
@@ -490,13 +402,9 @@ extern "C" int tg_ns_induced_workspace_bytes(const tg_graph *csc, int64_t pitch_
                                              int64_t *bytes, int64_t *bytes_min) {
     using namespace tg;
     const char *who = "tg_ns_induced_workspace_bytes";
-    TG_REQUIRE(bytes && bytes_min, "%s: null output", who);
-    TG_REQUIRE(n_batches >= 0 && n_batches <= 0x7fffffff, "%s: n_batches = %lld outside [0, 2^31)", who, (long long)n_batches);
     NsiPlan pl;
     if (const int rc = nsi_plan(csc, pitch_nodes, id_bound, 0, 0, who, pl)) return rc;
-    *bytes_min = pl.batch_bytes;
-    *bytes = pl.batch_bytes * n_batches;
-    return TG_OK;
+    return cs_answer_bytes(pl.batch_bytes, n_batches, who, bytes, bytes_min);
 }
 
 extern "C" int tg_ns_induced_count(const tg_graph *csc, const tg_ns_induced_in *in, int64_t n_batches, int64_t id_bound,
@@ -531,14 +439,10 @@ extern "C" int tg_ns_induced_grouped_workspace_bytes(const tg_graph *csc, int64_
                                                      int64_t *bytes_min) {
     using namespace tg;
     const char *who = "tg_ns_induced_grouped_workspace_bytes";
-    TG_REQUIRE(bytes && bytes_min, "%s: null output", who);
-    TG_REQUIRE(n_batches >= 0 && n_batches <= 0x7fffffff, "%s: n_batches = %lld outside [0, 2^31)", who, (long long)n_batches);
     TG_REQUIRE(n_groups >= 1, "%s: n_groups = %lld, at least 1 expected", who, (long long)n_groups);
     NsiPlan pl;
     if (const int rc = nsi_plan(csc, pitch_nodes, id_bound, n_groups, chunk_cap, who, pl)) return rc;
-    *bytes_min = pl.batch_bytes;
-    *bytes = pl.batch_bytes * n_batches;
-    return TG_OK;
+    return cs_answer_bytes(pl.batch_bytes, n_batches, who, bytes, bytes_min);
 }
 
 extern "C" int tg_ns_induced_grouped_count(const tg_graph *csc, const tg_ns_induced_grouped_in *in, int64_t n_batches,

@@ -1,8 +1,11 @@
 // What the node dedup operators share (ns_unique.hip: tg_ns_homo_unique and tg_ns_homo_unique_grouped, ns_unique_typed.hip:
-// tg_ns_typed_unique; saint_dedup.h and the induced, cluster and full-neighbor code take the sizes, the insert, the scans
-// and the plan): the sizes, the open-addressing insert (atomicCAS claims the key; the caller's atomicMin of the position
-// into the slot's value leaves the id's first position there), the workgroup rank scan, the flat form's clear, flag and
-// apply bodies as device function templates, the host's LDS limit query and raise, and the plan.
+// tg_ns_typed_unique; saint_dedup.h takes the sizes, the insert, the scans and the plan, and so does chunk_scan.h for the
+// induced, cluster and full-neighbour pairs, which adds what those three share among themselves: the chunk sizes, the
+// find probe, the clear, the prefix over tiles of chunks, the unit rules and the host's checks, answer and round loop):
+// the sizes, the open-addressing insert (atomicCAS claims the key; the caller's atomicMin of the position into the slot's
+// value leaves the id's first position there; its masked variant came from ns_full.hip), the workgroup rank scan, the flat
+// form's clear, flag and apply bodies as device function templates, the host's LDS limit query and raise, the plan, and
+// the probe's mask and shift of a table capacity (nsu_mask_shift, once written out at five sites).
 //
 // The tile bodies take what differs from their caller: the view of a list's tables, what else to store for a first
 // occurrence, and they hand back the ranks for the caller's own counts (counts, layer_nodes, seed_counts).  The __global__
@@ -42,9 +45,11 @@ __device__ __forceinline__ uint32_t nsu_hash(nsu_k32 key, uint32_t mask, uint32_
 __device__ __forceinline__ uint32_t nsu_hash(nsu_k64 key, uint32_t mask, uint32_t shift) {
     return (uint32_t)map_hash((int64_t)key) & mask;
 }
-// claims (or finds) the slot of `key`; at most one pass over the table
-template <typename K> __device__ __forceinline__ uint32_t nsu_insert(K *keys, uint32_t mask, uint32_t shift, K key) {
-    uint32_t s = nsu_hash(key, mask, shift);
+// claims (or finds) the slot of `key`; at most one pass over the table.  MASKED: the hash is masked as well, for a table
+// that may have one slot (its shift is 32; the full-neighbour pair's node_cap = 0)
+template <typename K, bool MASKED = false>
+__device__ __forceinline__ uint32_t nsu_insert(K *keys, uint32_t mask, uint32_t shift, K key) {
+    uint32_t s = MASKED ? nsu_hash(key, mask, shift & 31u) & mask : nsu_hash(key, mask, shift);
     for (uint32_t i = 0; i <= mask; ++i) {
         const K prev = atomicCAS(&keys[s], nsu_empty<K>(), key);
         if (prev == nsu_empty<K>() || prev == key) break;
@@ -102,9 +107,10 @@ template <typename Lookup> __device__ __forceinline__ int64_t nsu_end(int64_t r,
 
 // ---- flat form: the body of a block.  T is the caller's view of a list's part of the workspace: vals, slot, tile_cnt.
 // s0, stride: the thread's first slot and the grid's width, taken from blockDim / gridDim in the kernel itself
-template <typename K>
-__device__ __forceinline__ void nsu_clear_tile(K *keys, uint32_t *vals, uint32_t cap, uint32_t s0, uint32_t stride) {
-    for (uint32_t s = s0; s < cap; s += stride) {
+// (I: the counters' type; chunk_scan.h's tables reach 2^31 slots and count in int64_t)
+template <typename K, typename I = uint32_t>
+__device__ __forceinline__ void nsu_clear_tile(K *keys, uint32_t *vals, I cap, I s0, I stride) {
+    for (I s = s0; s < cap; s += stride) {
         keys[s] = nsu_empty<K>();
         vals[s] = NSU_UNSEEN;
     }
@@ -220,6 +226,13 @@ static inline int nsu_plan(int64_t cap_nodes, int64_t id_bound, const char *who,
     pl.tile_off = pl.slot_off + nsu_r256(cap_nodes * 4);
     pl.batch_bytes = pl.tile_off + nsu_r256(pl.n_node_tiles * 4);
     return TG_OK;
+}
+
+// the probe's words for a table of table_cap slots (a power of two): slot = hash >> hash_shift for 32-bit keys, hash &
+// cap_mask for 64-bit ones, and cap_mask wraps the probe
+static inline void nsu_mask_shift(int64_t table_cap, uint32_t &cap_mask, uint32_t &hash_shift) {
+    cap_mask = (uint32_t)(table_cap - 1);
+    hash_shift = 32u - (uint32_t)__builtin_ctzll((unsigned long long)table_cap);
 }
 
 static inline bool nsu_fits(const NsuPlan &pl, int64_t lds_limit) { return pl.lds_ok && pl.lds_bytes <= lds_limit; }

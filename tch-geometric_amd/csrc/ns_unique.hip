@@ -411,8 +411,7 @@ static int nsu_run(const char *who, const tg_ns_out *in, int64_t n_batches, int6
         a.layer_nodes = out->layer_nodes ? out->layer_nodes + b0 * n_hops : nullptr;
         a.cap_nodes = in->cap_nodes, a.cap_edges = in->cap_edges, a.n_hops = n_hops;
         a.n_batches = std::min(round, n_batches - b0);
-        a.cap_mask = (uint32_t)(pl.table_cap - 1);
-        a.hash_shift = 32u - (uint32_t)__builtin_ctzll((unsigned long long)pl.table_cap);
+        nsu_mask_shift(pl.table_cap, a.cap_mask, a.hash_shift);
         a.ws = static_cast<unsigned char *>(workspace);
         a.batch_bytes = pl.batch_bytes, a.vals_off = pl.vals_off, a.slot_off = pl.slot_off, a.tile_off = pl.tile_off;
         a.n_node_tiles = (int32_t)pl.n_node_tiles, a.inv_tiles = a.inverse ? (int32_t)pl.n_node_tiles : 0;

@@ -447,8 +447,7 @@ extern "C" int tg_ns_typed_unique(const tg_ns_typed_in *in, int64_t n_batches, c
             any_inverse |= ty.inverse != nullptr;
             ty.pitch = pitch, ty.n_inputs = in->n_inputs ? in->n_inputs[t] : 0;
             ty.keys_off = pl.keys_off[t], ty.vals_off = pl.vals_off[t], ty.slot_off = pl.slot_off[t], ty.tile_off = pl.tile_off[t];
-            ty.cap_mask = (uint32_t)(pl.table_cap[t] - 1);
-            ty.hash_shift = 32u - (uint32_t)__builtin_ctzll((unsigned long long)pl.table_cap[t]);
+            nsu_mask_shift(pl.table_cap[t], ty.cap_mask, ty.hash_shift);
             ty.n_tiles = (int32_t)pl.n_tiles[t], ty.key64 = pl.key_bytes[t] == 8;
             ty.loc_off = (uint32_t)pl.loc_off[t];
         }

@@ -137,8 +137,7 @@ static inline int saint_plan(int64_t P, const char *who, SaintPlan &pl) {
 // the table's words of the launch arguments
 template <typename A> static inline void saint_plan_args(const SaintPlan &pl, void *workspace, A &a) {
     a.P = pl.P;
-    a.cap_mask = (uint32_t)(pl.nsu.table_cap - 1);
-    a.hash_shift = 32u - (uint32_t)__builtin_ctzll((unsigned long long)pl.nsu.table_cap);
+    nsu_mask_shift(pl.nsu.table_cap, a.cap_mask, a.hash_shift);
     a.ws = static_cast<unsigned char *>(workspace);
     a.batch_bytes = pl.batch_bytes, a.vals_off = pl.nsu.vals_off, a.slot_off = pl.nsu.slot_off;
     a.tile_off = pl.nsu.tile_off, a.visit_off = pl.visit_off;

@@ -122,6 +122,50 @@ def stream_ptr(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _two_i64(fn, *args):
+    """fn(*args, &a, &b) -> (a, b): the two int64 out-params of a size query (bytes, bytes_min)"""
+    a, b = C.c_int64(-1), C.c_int64(-1)
+    check(fn(*args, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def _host_prefix(counts):
+    """the exclusive prefix of host counts with the total behind it, as a python list"""
+    off = [0]
+    for m in counts:
+        off.append(off[-1] + int(m))
+    return off
+
+
+def _status_check(status, who, bits, mask=-1):
+    """raises where the status word of a count pass has a bit of `mask`, naming every raised bit of the table `bits`"""
+    if status & mask:
+        raise RuntimeError("%s: status %d (%s)" % (who, status, " and ".join(t for bit, t in bits if status & bit)))
+
+
+class _CountEmit:
+    """What the count / emit launch objects share: the workspace `ws` (an int64 tensor of an earlier launch, reused when
+    large enough), one int64 tensor `state` carved into the named fields with the status word behind them (a loader reads
+    everything back in one copy), and the zeroing of that word before pass 1."""
+
+    def _own(self, need, ws, device, fields, same_device=False):
+        if ws is None or ws.numel() * 8 < need or (same_device and ws.device != device):
+            ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=device)
+        self.ws = ws
+        self.state = torch.zeros(sum(words for _, words in fields) + 1, dtype=torch.int64, device=device)
+        o = 0
+        for name, words in fields:
+            setattr(self, name, self.state[o:o + words])
+            o += words
+        self.status = self.state[-1:].view(torch.int32)[:1]
+
+    def _begin_count(self):
+        self.state[-1:].zero_()
+
+    def _ws_args(self):
+        return ptr(self.ws), C.c_int64(self.ws.numel() * 8)
+
+
 def graph_max_degree(g, device):
     """The longest column (row) of a graph view, computed on the device (tg_graph_max_degree); one read-back."""
     out = torch.zeros(1, dtype=torch.int64, device=device)
@@ -1257,10 +1301,7 @@ def ns_homo_unique_form(cap_nodes, id_bound, lds_limit_bytes=0):
 def ns_homo_unique_workspace_bytes(cap_nodes, id_bound, n_batches):
     """-> (bytes, bytes_min): what an auto call wants for all batches at once (0 where it takes the LDS form) and the
     flat form's workspace of one batch (the least a flat call runs with, round by round)."""
-    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
-    check(lib.tg_ns_homo_unique_workspace_bytes(C.c_int64(cap_nodes), C.c_int64(id_bound), C.c_int64(n_batches),
-                                                C.byref(nbytes), C.byref(bmin)))
-    return nbytes.value, bmin.value
+    return _two_i64(lib.tg_ns_homo_unique_workspace_bytes, C.c_int64(cap_nodes), C.c_int64(id_bound), C.c_int64(n_batches))
 
 
 def ns_homo_unique_workspace(cap_nodes, id_bound, n_batches, device, form=0):
@@ -1348,10 +1389,8 @@ def ns_homo_unique_grouped_form(cap_nodes, id_bound, n_groups, lds_limit_bytes=0
 def ns_homo_unique_grouped_workspace_bytes(cap_nodes, id_bound, n_groups, n_batches):
     """-> (bytes, bytes_min) of tg_ns_homo_unique_grouped, as ns_homo_unique_workspace_bytes: a batch's part also holds a
     group word per position."""
-    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
-    check(lib.tg_ns_homo_unique_grouped_workspace_bytes(C.c_int64(cap_nodes), C.c_int64(id_bound), C.c_int64(n_groups),
-                                                        C.c_int64(n_batches), C.byref(nbytes), C.byref(bmin)))
-    return nbytes.value, bmin.value
+    return _two_i64(lib.tg_ns_homo_unique_grouped_workspace_bytes, C.c_int64(cap_nodes), C.c_int64(id_bound),
+                    C.c_int64(n_groups), C.c_int64(n_batches))
 
 
 def ns_homo_unique_grouped_workspace(cap_nodes, id_bound, n_groups, n_batches, device, form=0):
@@ -1399,61 +1438,62 @@ class TgNsInducedIn(C.Structure):
 def ns_induced_workspace_bytes(graph, pitch_nodes, id_bound, n_batches):
     """-> (bytes, bytes_min): the workspace of the induced pair for n_batches batches at once (n_batches * bytes_min) and
     for one batch; graph: a tg_graph view (only n_major and n_edges are read)."""
-    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
-    check(lib.tg_ns_induced_workspace_bytes(C.byref(graph), C.c_int64(pitch_nodes), C.c_int64(id_bound),
-                                            C.c_int64(n_batches), C.byref(nbytes), C.byref(bmin)))
-    return nbytes.value, bmin.value
+    return _two_i64(lib.tg_ns_induced_workspace_bytes, C.byref(graph), C.c_int64(pitch_nodes), C.c_int64(id_bound),
+                    C.c_int64(n_batches))
 
 
-class NsInduced:
+class NsInduced(_CountEmit):
     """The induced pair over the node slab `nodes` [>= n_batches, pitch] with n of batch b at
     counts.reshape(-1)[b * counts_stride]; node_marks: [n_batches, n_marks] positions or None.  Owns what the passes share:
     n_edges [n_batches], edge_marks [n_batches, n_marks], status [1] and the workspace (`ws`: an int64 tensor of an earlier
     launch of the same shape, reused when large enough).  count() then emit() run on the current stream; neither
     synchronises."""
+    _struct = TgNsInducedIn
 
     def __init__(self, graph, nodes, counts, counts_stride, n_batches, id_bound, node_marks=None, ws=None):
-        dev = nodes.device
+        self._slabs(graph, nodes, counts, counts_stride, n_batches, id_bound, node_marks)
+        self._carve(ns_induced_workspace_bytes(graph, self.struct.pitch_nodes, self.id_bound, self.n_batches)[0], ws)
+
+    def _slabs(self, graph, nodes, counts, counts_stride, n_batches, id_bound, node_marks):
         self.graph, self.n_batches, self.id_bound = graph, int(n_batches), int(id_bound)
         self.nodes, self.counts, self.node_marks = nodes, counts, node_marks
-        si = self.struct = TgNsInducedIn()
+        si = self.struct = self._struct()
         si.nodes, si.pitch_nodes = nodes.data_ptr(), nodes.shape[-1]
         si.counts, si.counts_stride = counts.data_ptr(), int(counts_stride)
         self.n_marks = 0 if node_marks is None else int(node_marks.shape[-1])
         si.node_marks, si.n_marks = (node_marks.data_ptr() if self.n_marks else None), self.n_marks
-        need = ns_induced_workspace_bytes(graph, si.pitch_nodes, self.id_bound, self.n_batches)[0]
-        if ws is None or ws.numel() * 8 < need:
-            ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
-        self.ws = ws
-        # n_edges, the marks and the status word in one tensor: a loader reads them back in one copy
-        self.state = torch.zeros(self.n_batches * (1 + self.n_marks) + 1, dtype=torch.int64, device=dev)
-        self.n_edges = self.state[:self.n_batches]
-        self.edge_marks = self.state[self.n_batches:self.n_batches * (1 + self.n_marks)].view(self.n_batches, self.n_marks)
-        self.status = self.state[-1:].view(torch.int32)[:1]
+
+    def _carve(self, need, ws, more=()):
+        # n_edges, the marks (and what a derived pair adds) and the status word in one tensor
+        nb, nm = self.n_batches, self.n_marks
+        self._own(need, ws, self.nodes.device, [("n_edges", nb), ("edge_marks", nb * nm)] + list(more))
+        self.edge_marks = self.edge_marks.view(nb, nm)
+
+    def _count(self, fn, stream, n_batches, *more):
+        # pass 1 of either pair; more: what the grouped entry point takes between edge_marks and status
+        self.live = self.n_batches if n_batches is None else int(n_batches)
+        self._begin_count()
+        check(fn(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live), C.c_int64(self.id_bound), ptr(self.n_edges),
+                 ptr(self.edge_marks) if self.n_marks else None, *more, ptr(self.status), *self._ws_args(), stream))
+        return self
+
+    def _emit(self, fn, stream, edge_off, rows, cols, edge_index):
+        check(fn(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live), C.c_int64(self.id_bound), ptr(edge_off),
+                 ptr(rows), ptr(cols), ptr(edge_index), *self._ws_args(), stream))
 
     def count(self, n_batches=None):
         """pass 1 over the first n_batches batches (all when None); emit() then runs the same ones"""
-        self.live = self.n_batches if n_batches is None else int(n_batches)
-        self.state[-1:].zero_()
-        check(lib.tg_ns_induced_count(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live),
-                                      C.c_int64(self.id_bound), ptr(self.n_edges), ptr(self.edge_marks) if self.n_marks else None,
-                                      ptr(self.status), ptr(self.ws), C.c_int64(self.ws.numel() * 8),
-                                      stream_ptr(self.nodes.device)))
-        return self
+        return self._count(lib.tg_ns_induced_count, stream_ptr(self.nodes.device), n_batches)
 
     def emit(self, edge_off, rows, cols, edge_index):
         """pass 2 into the caller's flat arrays; edge_off: device [n_batches], the exclusive prefix of n_edges"""
-        check(lib.tg_ns_induced_emit(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live),
-                                     C.c_int64(self.id_bound), ptr(edge_off), ptr(rows), ptr(cols), ptr(edge_index),
-                                     ptr(self.ws), C.c_int64(self.ws.numel() * 8), stream_ptr(self.nodes.device)))
+        self._emit(lib.tg_ns_induced_emit, stream_ptr(self.nodes.device), edge_off, rows, cols, edge_index)
 
 
 def induced_status_check(status, who):
     """the status word of tg_ns_induced_count after its read-back: non-zero raises"""
-    if status:
-        raise RuntimeError("%s: status %d (%s)" % (who, status, " and ".join(
-            t for bit, t in ((1, "a list with repeats exceeds the chunk bound"), (2, "a node id outside the graph"),
-                             (4, "a group word outside [0, n_groups)")) if status & bit)))
+    _status_check(status, who, ((1, "a list with repeats exceeds the chunk bound"), (2, "a node id outside the graph"),
+                                (4, "a group word outside [0, n_groups)")))
 
 
 CLUSTER_MAX_PARTS_PER_BATCH = 1024   # tchgeo.h TG_CLUSTER_MAX_PARTS_PER_BATCH
@@ -1467,13 +1507,11 @@ class TgClusterIn(C.Structure):
 def cluster_workspace_bytes(graph, n_parts, pitch_parts, n_batches):
     """-> (bytes, bytes_min): the workspace of the cluster pair for n_batches batches at once (n_batches * bytes_min) and
     for one batch; graph: a tg_graph view (only n_major and n_edges are read)."""
-    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
-    check(lib.tg_cluster_workspace_bytes(C.byref(graph), C.c_int64(n_parts), C.c_int64(pitch_parts), C.c_int64(n_batches),
-                                         C.byref(nbytes), C.byref(bmin)))
-    return nbytes.value, bmin.value
+    return _two_i64(lib.tg_cluster_workspace_bytes, C.byref(graph), C.c_int64(n_parts), C.c_int64(pitch_parts),
+                    C.c_int64(n_batches))
 
 
-class ClusterInduced:
+class ClusterInduced(_CountEmit):
     """The cluster pair (tg_cluster_count / tg_cluster_emit) over the cluster lists `clusters` [>= n_batches, pitch] of the
     partition `partptr` [n_parts + 1] of `graph` (a CSC whose clusters are id ranges); n_clusters: [>= n_batches] entries
     per batch or None (the pitch each); node_ids: [n_major] what `nodes` receives for a vertex, or None.  Owns what the
@@ -1501,24 +1539,17 @@ class ClusterInduced:
         si.clusters, si.pitch_parts = clusters.data_ptr(), int(clusters.shape[1])
         si.n_clusters = None if n_clusters is None else n_clusters.data_ptr()
         si.node_ids = None if node_ids is None else node_ids.data_ptr()
-        need = cluster_workspace_bytes(graph, si.n_parts, si.pitch_parts, self.n_batches)[0]
-        if ws is None or ws.numel() * 8 < need:
-            ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
-        self.ws = ws
-        self.state = torch.zeros(2 * self.n_batches + 1, dtype=torch.int64, device=dev)
-        self.n_nodes = self.state[:self.n_batches]
-        self.n_edges = self.state[self.n_batches:2 * self.n_batches]
-        self.status = self.state[-1:].view(torch.int32)[:1]
+        self._own(cluster_workspace_bytes(graph, si.n_parts, si.pitch_parts, self.n_batches)[0], ws, dev,
+                  [("n_nodes", self.n_batches), ("n_edges", self.n_batches)])
 
     def count(self, G=None):
         """pass 1 over the first G batches (all when None); emit() then runs the same ones"""
         self.live = self.n_batches if G is None else int(G)
         if not 0 <= self.live <= self.n_batches:
             raise ValueError("ClusterInduced.count: G = %d outside [0, %d]" % (self.live, self.n_batches))
-        self.state[-1:].zero_()
+        self._begin_count()
         check(lib.tg_cluster_count(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live), ptr(self.n_nodes),
-                                   ptr(self.n_edges), ptr(self.status), ptr(self.ws), C.c_int64(self.ws.numel() * 8),
-                                   stream_ptr(self.clusters.device)))
+                                   ptr(self.n_edges), ptr(self.status), *self._ws_args(), stream_ptr(self.clusters.device)))
         return self
 
     def emit_into(self, node_off, edge_off, nodes, rows, cols, edge_index):
@@ -1526,8 +1557,7 @@ class ClusterInduced:
         / n_edges; nodes may be None"""
         check(lib.tg_cluster_emit(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live), ptr(node_off),
                                   ptr(edge_off), None if nodes is None else ptr(nodes), ptr(rows), ptr(cols),
-                                  ptr(edge_index), ptr(self.ws), C.c_int64(self.ws.numel() * 8),
-                                  stream_ptr(self.clusters.device)))
+                                  ptr(edge_index), *self._ws_args(), stream_ptr(self.clusters.device)))
 
     def emit(self, n_nodes_host=None, n_edges_host=None, with_nodes=True):
         """pass 2 of a counted launch into exact flat arrays -> (nodes [sum n_b] or None, [2, M] rows over cols, edge_index
@@ -1539,10 +1569,7 @@ class ClusterInduced:
             cluster_status_check(int(state[-1:].view(torch.int32)[0]), "ClusterInduced.emit")
             n_nodes_host = state[:G].tolist()
             n_edges_host = state[self.n_batches:self.n_batches + G].tolist()
-        noff, eoff = [0], [0]
-        for n, m in zip(n_nodes_host, n_edges_host):
-            noff.append(noff[-1] + int(n))
-            eoff.append(eoff[-1] + int(m))
+        noff, eoff = _host_prefix(n_nodes_host), _host_prefix(n_edges_host)
         dev = self.clusters.device
         nodes = torch.empty(noff[-1], dtype=torch.int64, device=dev) if with_nodes else None
         rc = torch.empty((2, eoff[-1]), dtype=torch.int64, device=dev)
@@ -1556,11 +1583,9 @@ class ClusterInduced:
 
 def cluster_status_check(status, who):
     """the status word of tg_cluster_count after its read-back: non-zero raises"""
-    if status:
-        raise RuntimeError("%s: status %d (%s)" % (who, status, " and ".join(
-            t for bit, t in ((1, "a batch with repeated clusters exceeds the chunk bound, or has 2^31 nodes or more"),
-                             (2, "a cluster id outside [0, n_parts)"),
-                             (4, "a partptr pair that is inverted or leaves the graph")) if status & bit)))
+    _status_check(status, who, ((1, "a batch with repeated clusters exceeds the chunk bound, or has 2^31 nodes or more"),
+                                (2, "a cluster id outside [0, n_parts)"),
+                                (4, "a partptr pair that is inverted or leaves the graph")))
 
 
 class TgNsFullIn(C.Structure):
@@ -1598,13 +1623,10 @@ def ns_full_workspace_bytes(graph, id_bound, max_nodes, node_cap, chunk_cap, n_b
     """-> (bytes, bytes_min): the workspace of the full-neighbour pair for n_batches batches at once (n_batches * bytes_min)
     and for one batch; graph: a tg_graph view (only n_major and n_edges are read).  No device is touched."""
     si = TgNsFullIn(None, None, int(max_nodes), int(node_cap), int(chunk_cap))
-    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
-    check(lib.tg_ns_full_workspace_bytes(C.byref(graph), C.byref(si), int(id_bound), int(n_batches), C.byref(nbytes),
-                                         C.byref(bmin)))
-    return nbytes.value, bmin.value
+    return _two_i64(lib.tg_ns_full_workspace_bytes, C.byref(graph), C.byref(si), int(id_bound), int(n_batches))
 
 
-class NsFull:
+class NsFull(_CountEmit):
     """The full-neighbour pair (tg_ns_full_count / tg_ns_full_emit) for up to n_batches frontiers of at most max_nodes nodes
     each over `graph` (a CSC view): a table for node_cap distinct nodes and room for chunk_cap chunks per batch (<= 0: the
     bound of a frontier of distinct nodes).  Owns what the passes share: n_nodes, n_edges, chunks [n_batches each] and
@@ -1620,13 +1642,8 @@ class NsFull:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.struct = TgNsFullIn(None, None, self.max_nodes, self.node_cap, self.chunk_cap)
         need = ns_full_workspace_bytes(graph, self.id_bound, self.max_nodes, self.node_cap, self.chunk_cap, self.n_batches)[0]
-        if ws is None or ws.numel() * 8 < need or ws.device != self.device:
-            ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=self.device)
-        self.ws = ws
         G = self.n_batches
-        self.state = torch.zeros(3 * G + 1, dtype=torch.int64, device=self.device)
-        self.n_nodes, self.n_edges, self.chunks = self.state[:G], self.state[G:2 * G], self.state[2 * G:3 * G]
-        self.status = self.state[-1:].view(torch.int32)[:1]
+        self._own(need, ws, self.device, [("n_nodes", G), ("n_edges", G), ("chunks", G)], same_device=True)
         self.live = None
 
     def count(self, nodes, node_ptr):
@@ -1645,7 +1662,7 @@ class NsFull:
         self.struct.node_ptr = node_ptr.data_ptr()
         if self.max_nodes and not nodes.numel():
             self.struct.nodes = self.ws.data_ptr()       # never read: every list is empty
-        self.state[-1:].zero_()
+        self._begin_count()
         check(lib.tg_ns_full_count(C.byref(self.graph), C.byref(self.struct), live, self.id_bound, ptr(self.n_nodes),
                                    ptr(self.n_edges), ptr(self.chunks), ptr(self.status), ptr(self.ws), self.ws.numel() * 8,
                                    stream_ptr(self.device)))
@@ -1674,8 +1691,7 @@ class NsFull:
 def ns_full_status_check(status, who):
     """the status word of tg_ns_full_count after its read-back: bit 1 raises (bit 0, a refused batch, is the caller's to
     answer with a larger workspace)"""
-    if status & 2:
-        raise RuntimeError("%s: status %d (a frontier node outside the graph)" % (who, status))
+    _status_check(status, who, ((2, "a frontier node outside the graph"),), mask=2)
 
 
 class TgNsInducedGroupedIn(C.Structure):
@@ -1687,11 +1703,8 @@ class TgNsInducedGroupedIn(C.Structure):
 def ns_induced_grouped_workspace_bytes(graph, pitch_nodes, id_bound, n_groups, chunk_cap, n_batches):
     """-> (bytes, bytes_min) of the grouped induced pair: as ns_induced_workspace_bytes with the pair key's table and room
     for chunk_cap chunks per batch (<= 0: the ungrouped bound pitch_nodes + ceil(n_edges / 512)).  No device is touched."""
-    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
-    check(lib.tg_ns_induced_grouped_workspace_bytes(C.byref(graph), C.c_int64(pitch_nodes), C.c_int64(id_bound),
-                                                    C.c_int64(n_groups), C.c_int64(chunk_cap), C.c_int64(n_batches),
-                                                    C.byref(nbytes), C.byref(bmin)))
-    return nbytes.value, bmin.value
+    return _two_i64(lib.tg_ns_induced_grouped_workspace_bytes, C.byref(graph), C.c_int64(pitch_nodes), C.c_int64(id_bound),
+                    C.c_int64(n_groups), C.c_int64(chunk_cap), C.c_int64(n_batches))
 
 
 def ns_induced_default_chunk_cap(graph, pitch_nodes):
@@ -1699,24 +1712,20 @@ def ns_induced_default_chunk_cap(graph, pitch_nodes):
     return int(pitch_nodes) + (int(graph.n_edges) + 511) // 512
 
 
-class NsInducedGrouped:
+class NsInducedGrouped(NsInduced):
     """The grouped induced pair (tg_ns_induced_grouped_count / _emit) over `nodes` / `group` slabs [>= n_batches, pitch]:
     NsInduced with a group word per entry, n_groups groups per batch, optional group_time [n_batches, n_groups] with
     time_window = (lo, hi) (the graph view then carries timestamps), and chunk_cap chunks of workspace per batch (None: the
     ungrouped bound).  `state` holds n_edges [n_batches], edge_marks [n_batches, n_marks], chunks [n_batches] and the status
     word, so one copy reads everything back; a batch whose chunks exceed chunk_cap has status bit 0 and n_edges 0."""
+    _struct = TgNsInducedGroupedIn
 
     def __init__(self, graph, nodes, group, counts, counts_stride, n_batches, id_bound, n_groups, node_marks=None,
                  group_time=None, time_window=None, chunk_cap=None, ws=None):
-        dev = nodes.device
-        self.graph, self.n_batches, self.id_bound, self.n_groups = graph, int(n_batches), int(id_bound), int(n_groups)
-        self.nodes, self.group, self.counts, self.node_marks, self.group_time = nodes, group, counts, node_marks, group_time
-        si = self.struct = TgNsInducedGroupedIn()
-        si.nodes, si.group, si.pitch_nodes = nodes.data_ptr(), group.data_ptr(), nodes.shape[-1]
-        si.counts, si.counts_stride = counts.data_ptr(), int(counts_stride)
-        self.n_marks = 0 if node_marks is None else int(node_marks.shape[-1])
-        si.node_marks, si.n_marks = (node_marks.data_ptr() if self.n_marks else None), self.n_marks
-        si.n_groups = self.n_groups
+        self._slabs(graph, nodes, counts, counts_stride, n_batches, id_bound, node_marks)
+        self.n_groups, self.group, self.group_time = int(n_groups), group, group_time
+        si = self.struct
+        si.group, si.n_groups = group.data_ptr(), self.n_groups
         si.group_time = group_time.data_ptr() if group_time is not None else None
         if group_time is not None and time_window is None:
             raise ValueError("group_time comes with a time_window")
@@ -1725,32 +1734,15 @@ class NsInducedGrouped:
         si.chunk_cap = self.chunk_cap
         need = ns_induced_grouped_workspace_bytes(graph, si.pitch_nodes, self.id_bound, self.n_groups, self.chunk_cap,
                                                   self.n_batches)[0]
-        if ws is None or ws.numel() * 8 < need:
-            ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
-        self.ws = ws
-        nb, nm = self.n_batches, self.n_marks
-        self.state = torch.zeros(nb * (2 + nm) + 1, dtype=torch.int64, device=dev)
-        self.n_edges = self.state[:nb]
-        self.edge_marks = self.state[nb:nb * (1 + nm)].view(nb, nm)
-        self.chunks = self.state[nb * (1 + nm):nb * (2 + nm)]
-        self.status = self.state[-1:].view(torch.int32)[:1]
+        self._carve(need, ws, [("chunks", self.n_batches)])
 
     def count(self, n_batches=None):
         """pass 1 over the first n_batches batches (all when None); emit() then runs the same ones"""
-        self.live = self.n_batches if n_batches is None else int(n_batches)
-        self.state[-1:].zero_()
-        check(lib.tg_ns_induced_grouped_count(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live),
-                                              C.c_int64(self.id_bound), ptr(self.n_edges),
-                                              ptr(self.edge_marks) if self.n_marks else None, ptr(self.chunks),
-                                              ptr(self.status), ptr(self.ws), C.c_int64(self.ws.numel() * 8),
-                                              stream_ptr(self.nodes.device)))
-        return self
+        return self._count(lib.tg_ns_induced_grouped_count, stream_ptr(self.nodes.device), n_batches, ptr(self.chunks))
 
     def emit(self, edge_off, rows, cols, edge_index):
         """pass 2 into the caller's flat arrays; edge_off: device [n_batches], the exclusive prefix of n_edges"""
-        check(lib.tg_ns_induced_grouped_emit(C.byref(self.graph), C.byref(self.struct), C.c_int64(self.live),
-                                             C.c_int64(self.id_bound), ptr(edge_off), ptr(rows), ptr(cols), ptr(edge_index),
-                                             ptr(self.ws), C.c_int64(self.ws.numel() * 8), stream_ptr(self.nodes.device)))
+        self._emit(lib.tg_ns_induced_grouped_emit, stream_ptr(self.nodes.device), edge_off, rows, cols, edge_index)
 
     def chunks_of(self, state_host):
         """the chunk counts inside a host copy of `state`"""
@@ -1777,9 +1769,7 @@ def ns_induced_emit(launch, n_edges_host=None):
         state = launch.state.cpu()
         induced_status_check(int(state[-1:].view(torch.int32)[0]), "ns_induced_emit")
         n_edges_host = state[:launch.n_batches].tolist()
-    off = [0]
-    for m in n_edges_host:
-        off.append(off[-1] + int(m))
+    off = _host_prefix(n_edges_host)
     dev = launch.nodes.device
     rc = torch.empty((2, off[-1]), dtype=torch.int64, device=dev)
     eidx = torch.empty(off[-1], dtype=torch.int64, device=dev)
@@ -1813,10 +1803,8 @@ def saint_rw_form(batch_size, walk_length, lds_limit_bytes=0):
 def saint_rw_workspace_bytes(n_batches, batch_size, walk_length, form=0):
     """-> (bytes, bytes_min): the workspace of n_batches mini-batches at once in this form (0: the one auto takes on the
     current device; 0 bytes for the LDS form) and of one mini-batch of the flat form, the least a flat call runs with."""
-    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
-    check(lib.tg_saint_rw_workspace_bytes(C.c_int64(n_batches), C.c_int64(batch_size), C.c_int64(walk_length), C.c_int32(form),
-                                          C.byref(nbytes), C.byref(bmin)))
-    return nbytes.value, bmin.value
+    return _two_i64(lib.tg_saint_rw_workspace_bytes, C.c_int64(n_batches), C.c_int64(batch_size), C.c_int64(walk_length),
+                    C.c_int32(form))
 
 
 def saint_rw_nodes(graph, roots, walk_length, seed, call_id, form=0, ws=None, out=None, status=None):
@@ -1901,10 +1889,7 @@ def saint_ne_workspace_bytes(n_batches, positions, form=0):
     """-> (bytes, bytes_min): the workspace of n_batches mini-batches of `positions` positions at once in this form (0: the
     one auto takes on the current device; 0 bytes for the LDS form) and of one mini-batch of the flat form, the least a
     flat call runs with."""
-    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
-    check(lib.tg_saint_ne_workspace_bytes(C.c_int64(n_batches), C.c_int64(positions), C.c_int32(form), C.byref(nbytes),
-                                          C.byref(bmin)))
-    return nbytes.value, bmin.value
+    return _two_i64(lib.tg_saint_ne_workspace_bytes, C.c_int64(n_batches), C.c_int64(positions), C.c_int32(form))
 
 
 def _saint_ne_buffers(who, dev, G, P, form, ws, out, status):
@@ -1997,10 +1982,8 @@ def ns_typed_unique_form(pitch_nodes, id_bounds, lds_limit_bytes=0):
 def ns_typed_unique_workspace_bytes(pitch_nodes, id_bounds, n_batches):
     """-> (bytes, bytes_min): what an auto call wants for all batches at once (0 where it takes the LDS form) and the
     flat form's workspace of one batch (the least a flat call runs with, round by round)."""
-    nbytes, bmin = C.c_int64(-1), C.c_int64(-1)
-    check(lib.tg_ns_typed_unique_workspace_bytes(C.c_int32(len(pitch_nodes)), _i64(pitch_nodes), _i64(id_bounds),
-                                                 C.c_int64(n_batches), C.byref(nbytes), C.byref(bmin)))
-    return nbytes.value, bmin.value
+    return _two_i64(lib.tg_ns_typed_unique_workspace_bytes, C.c_int32(len(pitch_nodes)), _i64(pitch_nodes), _i64(id_bounds),
+                    C.c_int64(n_batches))
 
 
 class NsTypedUniqueOut:

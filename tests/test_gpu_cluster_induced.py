@@ -251,3 +251,40 @@ def test_more_batches_than_a_grid_round(wide):
     lists = lists_of(wide, 2, G, 9, distinct=16)
     lists[-1] = [1023, 0]
     assert run(wide, lists, 2, n_clusters=False) == 0
+
+
+LONG, LONGER, UNIT, UNIT1, SMALL = 0, 1, 2, 3, 4  # clusters whose offset ranges are 1 024, 1 025, 16, 17 chunks | short columns
+
+
+@pytest.fixture(scope="module")
+def seams():
+    """offset ranges at the seams of the chunk prefix, built on the device: 64 columns of 8 192 entries (1 024 * 512: the
+    range ends with a tile of chunks), the same with one entry more (a second tile of one chunk of one entry), 4 columns of
+    2 048 (16 chunks: one unit) and the same with one entry more; every range's last entry names a node of its cluster"""
+    n = 20000
+    sizes = [64, 64, 4, 4, 64, n - 200]
+    partptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    deg = torch.zeros(n, dtype=torch.int64, device=DEV)
+    deg[0:128], deg[127] = 8192, 8193
+    deg[128:136], deg[135] = 2048, 2049
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(31)
+    deg[136:200] = torch.randint(0, 9, (64,), device=DEV, generator=gen)
+    ptrs = torch.cat([torch.zeros(1, dtype=torch.int64, device=DEV), torch.cumsum(deg, 0)])
+    indices = torch.randint(0, n, (int(ptrs[-1]),), device=DEV, generator=gen)
+    ends = ptrs[torch.from_numpy(partptr[1:5]).to(DEV)] - 1
+    indices[ends] = torch.from_numpy(partptr[:4]).to(DEV)
+    fx = Fixture(partptr, ptrs.cpu().numpy(), indices.cpu().numpy())
+    span = fx.ptrs[partptr[1:5]] - fx.ptrs[partptr[:4]]
+    assert span.tolist() == [1024 * CHUNK, 1024 * CHUNK + 1, 16 * CHUNK, 16 * CHUNK + 1]
+    return fx
+
+
+@pytest.mark.parametrize("view", ["i64", "i32"])
+def test_ranges_at_the_tile_and_unit_seams(seams, view):
+    lists = [[LONG], [LONGER], [UNIT], [UNIT1], [UNIT1, SMALL, LONGER]]
+    assert [chunks_of(seams.partptr, l, seams.ptrs) for l in lists] == [1024, 1025, 16, 17, 17 + 1 + 1025]
+    assert run(seams, lists, 3, view=view) == 0
+    for l, c in zip(lists[:4], (LONG, LONGER, UNIT, UNIT1)):             # the hit in the range's last entry, its last chunk
+        nodes, rows, cols, eidx, _ = seams.rule(tuple(l), 3, None)
+        assert eidx[-1] == seams.ptrs[seams.partptr[c + 1]] - 1 and rows[-1] == 0 and cols[-1] == nodes.size - 1

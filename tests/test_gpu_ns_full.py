@@ -205,3 +205,34 @@ def test_against_the_induced_pair_over_out_nodes(K):
     assert int(ind.status.cpu()[0]) == 0
     mine = trip[:, trip[1] < nodes.size]                             # the induced triples whose column is a frontier position
     assert np.array_equal(mine, np.stack([rows, cols, e]))
+
+
+@pytest.fixture(scope="module")
+def seams():
+    """columns 0 .. 3 of 1 024 * 512, 1 024 * 512 + 1, 16 * 512 and 16 * 512 + 1 entries, built on the device: the chunk
+    prefix ends with a tile, has a second tile of one chunk of one entry, is one unit, is a unit and one chunk.  A column's
+    last entry is a source that it names nowhere else: a new node in its last chunk"""
+    from tch_geometric import _cabi
+    n = 3000
+    deg = [1024 * CHUNK, 1024 * CHUNK + 1, 16 * CHUNK, 16 * CHUNK + 1]
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(13)
+    di = torch.randint(4, n - 8, (sum(deg),), device=DEV, generator=gen)
+    dp = torch.full((n + 1,), sum(deg), dtype=torch.int64, device=DEV)
+    dp[:5] = torch.tensor([0] + np.cumsum(deg).tolist(), device=DEV)
+    di[dp[1:5] - 1] = torch.arange(n - 4, n, device=DEV)
+    plain = _cabi.graph_view(dp, di)
+    shadow = _cabi.graph_view(dp, di, indices32=di.to(torch.int32), ptrs32=dp.to(torch.int32))
+    return dict(cabi=_cabi, ptrs=dp.cpu().numpy(), indices=di.cpu().numpy(), plain=plain, shadow=shadow, cache={}, keep=(dp, di))
+
+
+@pytest.mark.parametrize("shadows", [True, False])
+def test_columns_at_the_tile_and_unit_seams(seams, shadows):
+    n = seams["ptrs"].size - 1
+    lists = [np.array([v], dtype=np.int64) for v in range(4)]
+    want, no = run(seams, lists, id_bound=n, shadows=shadows)
+    assert not any(no) and [w[4] for w in want] == [1024, 1025, 16, 17]
+    for v, w in enumerate(want):
+        assert w[0][-1] == n - 4 + v and w[1][-1] == w[0].size - 1           # the last entry's source is the last new node
+    want, no = run(seams, [np.array([3, 1, 2], dtype=np.int64)], id_bound=n, shadows=shadows)   # 17 + 1 025 + 16 chunks
+    assert not any(no) and want[0][4] == 17 + 1025 + 16

@@ -419,3 +419,29 @@ def test_transform_retries_past_the_default_capacity(star):
     for a, w in zip(got, grouped_induced_rule(nodes, group, g.hp, g.hi)):
         assert np.array_equal(a.cpu().numpy(), w)
     assert got[0].numel() == int((g.hi[:5000] == 7).sum()) > 0
+
+
+def test_hub_columns_of_1024_and_1025_chunks_in_two_groups():
+    """columns 0 and 1 of exactly 1 024 * 512 and 1 024 * 512 + 1 entries, each named by two groups: 2 048 chunks end with
+    the second tile of the chunk prefix, 2 050 leave two chunks (the second one entry long) in a third.  The second
+    group's hub starts at chunk 1 024 or 1 025, where a mark reads the prefix; both columns end in a member of every group"""
+    n, degs = 20000, [1024 * CHUNK, 1024 * CHUNK + 1]
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(17)
+    idx = torch.randint(2, n - 1, (sum(degs),), device=DEV, generator=gen)
+    idx[degs[0] - 1] = idx[sum(degs) - 1] = n - 1
+    ptrs = torch.full((n + 1,), sum(degs), dtype=torch.int64, device=DEV)
+    ptrs[0], ptrs[1] = 0, degs[0]
+    g = DeviceGraph(ptrs, idx)
+    rs = np.random.default_rng(18)
+    lists = [disjoint_list(rs, [np.concatenate([[hub, n - 1], rs.choice(np.arange(2, n - 1), 40, replace=False)])
+                                for _ in range(2)], shuffle=False) for hub in (0, 1)]
+    marks = np.array([[42, 84], [42, 43]])                                      # position 42: the second group's hub
+    out, mk, chunks, st = run(g, lists, 2, marks=marks)
+    assert st == 0 and chunks.tolist() == [2048, 2050] and all(s[42] == hub for hub, (s, _) in enumerate(lists))
+    check(g, lists, out, n_groups=2)
+    for b, (s, _) in enumerate(lists):
+        assert mk[b].tolist() == edges_before(out[b][1], marks[b], len(s))
+        last = out[b][:, out[b][2] == g.hp[b + 1] - 1]                          # the column's last entry, once per group
+        assert last[1].tolist() == [0, 42] and last[0].tolist() == [1, 43]
+        assert 0 < mk[b][0] < out[b].shape[1] and out[b].shape[1] > 1000

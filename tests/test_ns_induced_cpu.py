@@ -118,6 +118,35 @@ def test_workspace_sizes(cabi):
     assert lib.tg_ns_induced_workspace_bytes(C.byref(g), C.c_int64(64), C.c_int64(1 << 20), C.c_int64(1), None, C.byref(out)) == 1
 
 
+def _queries(cabi, g, pitch, n_batches):
+    return (lambda: cabi.ns_induced_workspace_bytes(g, pitch, 64, n_batches),
+            lambda: cabi.ns_induced_grouped_workspace_bytes(g, pitch, 64, 2, 0, n_batches))
+
+
+def test_workspace_bytes_refuse_an_int64_overflow(cabi):
+    """n_batches * bytes_min past 2^63 is refused by both induced queries (a batch of pitch 2^30 takes more than 2^33
+    bytes, 2^31 - 1 of them more than 2^64), not answered with a wrapped product; one such batch still has its answer"""
+    g = cabi.graph_sizing(64, 64)
+    for query in _queries(cabi, g, 1 << 30, 2 ** 31 - 1):
+        with pytest.raises(cabi.TchGeoError, match="overflow int64"):
+            query()
+    for query in _queries(cabi, g, 1 << 30, 1):
+        total, least = query()
+        assert total == least > 1 << 33
+
+
+# (n_major, n_edges, pitch_nodes, id_bound) -> bytes_min of one batch, as the build before the shared answer gave it
+BYTES_MIN_BEFORE = {(1 << 20, 1 << 24, 169984, 1 << 20): 5083136, (34, 156, 34, 34): 2304,
+                    (1 << 16, 1 << 20, 124, 1 << 40): 22272}
+
+
+@pytest.mark.parametrize("shape", sorted(BYTES_MIN_BEFORE))
+def test_workspace_bytes_min_is_unchanged(cabi, shape):
+    n_major, n_edges, pitch, id_bound = shape
+    g = cabi.graph_sizing(n_major, n_edges)
+    assert cabi.ns_induced_workspace_bytes(g, pitch, id_bound, 1) == (BYTES_MIN_BEFORE[shape],) * 2
+
+
 HOST = C.create_string_buffer(64)                          # stands in for device arrays; never read
 P = C.c_void_p(C.addressof(HOST))
 

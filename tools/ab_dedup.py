@@ -1,37 +1,23 @@
-"""A/B of library builds on the node dedup operators INSIDE one process, on the same slabs and workspaces (why one process:
-tools/ab_same_process.py): `python tools/ab_dedup.py parent.so parent.so new.so [--out FILE]` (paths relative to the repo
-root; "-" = the default build).  Three alternating rounds, HIP events, ms per call.  Cases, on RMAT-20 with 16 edges per
-node and seeds from seed_batches:
+"""A/B of library builds on the node dedup operators (the method and the command line: tools/ab_loop.py).  Cases, on RMAT-20
+with 16 edges per node and seeds from seed_batches:
   ns_homo_unique, ns_homo_unique_grouped (identity groups)   flat form: 16 batches x 1 024 seeds x [15, 10] (169 984
       positions, the loader's shape); LDS form: 2 048 batches x 128 seeds x [5, 3] (2 688 positions)
   ns_typed_unique   one sampled hetero launch, set up as tools/bench_hetero_unique_loader.py's `dedup` section (SHIFT > 0:
       a smaller graph), in its auto form and forced flat
-With the SAME build given first and second, the gap between those two medians is the noise floor of the run; every later
-build's median is held against the first build's median + twice that gap.  Prints one JSON object."""
-import ctypes as C
-import json
+Prints one JSON object."""
 import os
-import statistics
 import sys
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tch-geometric_amd"))
+import ab_loop  # noqa: E402
 from tch_geometric import _cabi  # noqa: E402
 from tch_geometric.loader import HeteroNeighborLoader  # noqa: E402
 from tch_geometric.transforms import HeteroGraph  # noqa: E402
 
 dev = torch.device("cuda:0")
-args = sys.argv[1:]
-out_path = args.pop(args.index("--out") + 1) if "--out" in args else None
-paths = [a for a in args if a != "--out"]
-default, libs = _cabi.lib, []
-for i, path in enumerate(paths):
-    h = default if path == "-" else C.CDLL(os.path.join(ROOT, path))
-    h.tg_version.restype = h.tg_last_error.restype = C.c_char_p
-    libs.append(("%d:%s" % (i, path), h))
-
 cases = {}                                                   # name -> a call that launches the operator once
 scale = 20
 n = 1 << scale
@@ -70,33 +56,4 @@ uniq = _cabi.NsTypedUniqueOut(hb, in_place=False, with_inverse=False)
 cases["ns_typed_unique/auto(form %d)" % auto] = lambda: _cabi.ns_typed_unique(hb, G, bounds, ws=tws, form=auto, result=uniq)
 cases["ns_typed_unique/flat"] = lambda: _cabi.ns_typed_unique(hb, G, bounds, ws=tws, form=2, result=uniq)
 
-ms = {c: {name: [] for name, _ in libs} for c in cases}
-for rnd in range(3):
-    for name, h in libs:
-        _cabi.lib = h
-        for c, call in cases.items():
-            for _ in range(3):
-                call()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(20):
-                call()
-            e1.record()
-            torch.cuda.synchronize()
-            ms[c][name].append(e0.elapsed_time(e1) / 20)
-_cabi.lib = default
-res = {}
-for c in cases:
-    med = {name: round(statistics.median(v), 5) for name, v in ms[c].items()}
-    entry = {"ms_per_call_median": med, "ms_per_call_rounds": {k: [round(x, 5) for x in v] for k, v in ms[c].items()}}
-    if len(libs) >= 3 and paths[0] == paths[1]:
-        (a, _), (b, _) = libs[0], libs[1]
-        gap = abs(med[a] - med[b])
-        entry["noise_floor_ms"] = round(gap, 5)
-        entry["verdict"] = {name: "ok" if med[name] <= med[a] + 2 * gap else "slower by %.5f ms" % (med[name] - med[a])
-                            for name, _ in libs[2:]}
-    res[c] = entry
-text = json.dumps(res, indent=1)
-print(text)
-if out_path:
-    open(out_path, "w").write(text + "\n")
+ab_loop.run(cases)
