@@ -10,7 +10,7 @@ from .tch_geometric import *  # noqa: F401,F403
 from .tch_geometric import (PanicException, backend_version, graph_cache_clear, graph_cache_info,  # noqa: F401
                             rng_state, seed, set_rng_state)
 from .loader import (ClusterData, ClusterLoader, FullNeighborLoader, GraphSAINTEdgeLoader, GraphSAINTNodeLoader,
-                     GraphSAINTRandomWalkLoader, HeteroLinkNeighborLoader,  # noqa: F401
+                     GraphSAINTRandomWalkLoader, HeteroLinkNeighborLoader, LADIESLoader,  # noqa: F401
                      LinkNeighborLoader, MetaPath2VecLoader, Node2VecLoader, PinSAGELoader, ShaDowKHopLoader,
                      TemporalWalkLoader, random_partition, range_partition)
 from .utils import (TEMPORAL_SAMPLE_DYNAMIC, TEMPORAL_SAMPLE_RELATIVE, TEMPORAL_SAMPLE_STATIC,  # noqa: F401

@@ -16,7 +16,7 @@ What the loaders share is written once.  _Loader: the length of an epoch, the wa
 epoch counter, the one shuffle rule, the launches of _epoch_plan) and iteration as the items of super_batches().
 _Indexable: a super-batch's len / index / iteration over one `_at(j)`.  SuperBatch: every optional field defaults to
 None, _set_flat takes a launch's flat arrays and gathers the attribute rows.  _BlockLoader with _Block / _BlockBatch /
-_BlockSuperBatch: the loaders of DGL-style blocks (PinSAGELoader, FullNeighborLoader), each with one per-layer hook.
+_BlockSuperBatch: the loaders of DGL-style blocks (PinSAGELoader, FullNeighborLoader, LADIESLoader), each with one per-layer hook.
 _PooledLoader: the loaders whose launches write into one pooled slab set (the GraphSAINT loaders, ClusterLoader).
 
 The typed-graph loaders (HeteroNeighborLoader, HGTLoader, BudgetLoader, NegativeLoader) are one program, _TypedLoader:
@@ -41,6 +41,8 @@ with every edge of the graph between its nodes (tg_cluster_count / tg_cluster_em
 induced pair's hash table).
 FullNeighborLoader hands out blocks that hold EVERY in-edge of their destinations (layer-wise inference; PyG's
 num_neighbors=[-1]): tg_ns_full_count / tg_ns_full_emit, one read-back per layer and launch.
+LADIESLoader hands out blocks of layer-wise importance sampling: one budget of drawn nodes per layer and mini-batch with
+rescaled edge weights (tg_ladies_count / tg_ladies_emit), on the same per-layer scheme.
 """
 from itertools import accumulate
 from typing import Iterator, List, Optional
@@ -2447,6 +2449,150 @@ class FullNeighborLoader(_BlockLoader):
         offs = torch.empty(eptr[-1], **o)
         op.emit(node_off, edge_off, n_id, rc[0], rc[1], offs)
         return dict(n_id=n_id, src_ptr=nptr, dst_ptr=ptr, edge_index=rc, e_id=self.perm[offs], edge_ptr=eptr)
+
+
+class LADIESBlock(_Block):
+    """One layer of a layer-wise mini-batch: a _Block with `edge_index` [2, m] (row = position in n_id of the source, col =
+    position of the destination; the in-edges whose source the layer drew, in (destination, CSC offset) order),
+    `edge_weight` [m] float32 (the rescaled adjacency entry: a destination's weighted sum is an unbiased estimate of its
+    full row) and `e_id` [m], the edges' columns in data.edge_index: data.edge_index[:, e_id] == n_id[edge_index]."""
+    PAYLOAD = "edge_weight"
+    __slots__ = (PAYLOAD, "e_id")
+
+
+class LADIESBatch(_BlockBatch):
+    """Mini-batch j of a LADIESSuperBatch: a _BlockBatch of LADIESBlocks with the `call_id` of layer 0; every block also
+    carries its slice of the layer's `e_id`."""
+    BLOCK, CALL_ID = LADIESBlock, True
+
+    def __init__(self, sb, j):
+        super().__init__(sb, j)
+        for blk, lay in zip(self.blocks, reversed(sb.layers)):
+            blk.e_id = lay["e_id"][lay["edge_ptr"][j]:lay["edge_ptr"][j + 1]]
+
+
+class LADIESSuperBatch(_BlockSuperBatch):
+    """A launch of LADIESLoader: a _BlockSuperBatch whose layers carry `edge_weight` and `e_id`, with `call_id0` (layer 0 of
+    mini-batch 0)."""
+    BATCH = LADIESBatch
+
+
+class LADIESLoader(_BlockLoader):
+    """Layer-wise importance sampling (FastGCN's estimator with LADIES' layer-dependent law, Zou et al. 2019) over
+    tg_ladies_count / tg_ladies_emit (csrc/ladies.hip): every layer draws ONE budget of num_samples[l] nodes for the whole
+    mini-batch, with replacement, a node's probability proportional to the squared norm of its column in the frontier's
+    rows of the normalised adjacency; the kept edges are rescaled so that the aggregation stays unbiased.  A block is
+    bounded by its budget where node-wise sampling grows by fanout^L.
+
+    Mini-batch j of the run (epoch * len(loader) + its number in the epoch) with distinct seeds F_0, for layer l = 0 .. L-1:
+    one pair of calls runs over the flat concatenation of the launch's frontiers F_l (one list per mini-batch) under call id
+    call_id0 + j * L + l -- a mini-batch does not depend on what else is in the launch.  F_{l+1} = F_l followed by the drawn
+    nodes that are not in it, ordered by their first drawing slot.  Block l (LADIESBlock) holds n_id = F_{l+1}, n_dst =
+    |F_l|, edge_index [2, m], edge_weight and e_id.  Without weight_attr the adjacency is the row-normalised one (every
+    in-edge of a destination of in-degree d weighs 1/d); weight_attr names a float tensor [E] of `data` with the caller's
+    entries (a normalised Laplacian's; values above 1 count as 1 in the draw's law, values <= 0 and NaN as 0), which
+    row_normalize=True first divides by their destination's sum (float64, index_add_).  A mini-batch (LADIESBatch) carries
+    `blocks` outermost first, `n_id` = F_L, the node attributes of `data` gathered by n_id, `batch_size`, `input_nodes`
+    and `call_id`; super_batches() hands out whole launches.
+
+    Host synchronisation: ONE read-back per layer and launch, between the two passes; the capacities grow as
+    FullNeighborLoader's do (`growths` counts the repeated first passes).  Duplicate input nodes inside one mini-batch are
+    refused in the constructor (with shuffle=True any duplicate); everything that can be refused is refused before any
+    device work.  Shuffling is a function of (seed, epoch)."""
+
+    def __init__(self, data, num_samples: List[int], input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
+                 prefetch: int = 16, shuffle: bool = True, drop_last: bool = False, seed: int = 0,
+                 weight_attr: Optional[str] = None, row_normalize: bool = False, device="cuda"):
+        from . import _cabi_ladies
+        budgets = [int(s) for s in num_samples]
+        if not budgets:
+            raise ValueError("num_samples must name at least one layer")
+        if any(not 1 <= s <= _cabi_ladies.LADIES_MAX_SAMPLES for s in budgets):
+            raise ValueError("num_samples must be in 1..%d per layer, got %r" % (_cabi_ladies.LADIES_MAX_SAMPLES, list(num_samples)))
+        _at_least_1("batch_size", batch_size)
+        _at_least_1("prefetch", prefetch)
+        if _is_hetero(data):
+            raise ValueError("LADIESLoader takes a homogeneous graph (typed graphs are out of scope)")
+        E = int(data.edge_index.shape[1])
+        weights = None
+        if weight_attr is not None:
+            weights = getattr(data, weight_attr, None)
+            if not isinstance(weights, Tensor):
+                raise ValueError("weight_attr: data has no tensor %r" % (weight_attr,))
+            if weights.dim() != 1 or weights.numel() != E or not weights.is_floating_point():
+                raise ValueError("weight_attr: data.%s must be a floating-point tensor of shape [%d], got %s %s" %
+                                 (weight_attr, E, weights.dtype, tuple(weights.shape)))
+        super().__init__(data, len(budgets), input_nodes, batch_size, prefetch, shuffle, drop_last, seed, device)
+        self._ops = _cabi_ladies
+        self.num_samples, self.call_id0 = budgets, 0
+        self.weight_attr, self.row_normalize = weight_attr, bool(row_normalize)
+        self.weights = self.col_sum = None
+        if weights is not None:
+            w = weights.to(self.device)[self.perm].to(torch.float64)           # CSC order
+            if self.row_normalize:
+                col = torch.repeat_interleave(torch.arange(self.n_nodes, device=self.device), self.col_ptrs[1:] - self.col_ptrs[:-1])
+                self.col_sum = torch.zeros(self.n_nodes, dtype=torch.float64, device=self.device).index_add_(0, col, w)
+                w = torch.where(self.col_sum[col] > 0, w / self.col_sum[col], torch.zeros_like(w))
+            self.weights = w.to(torch.float32).contiguous()
+        N, B, L = self.n_nodes, self.batch_size, self.n_layers
+        mean = (E + N - 1) // N
+        grown = [B]
+        for s in budgets:
+            grown.append(grown[-1] + s)                                       # a frontier's bound per layer
+        self._node_cap = [min(_cabi_ladies.LADIES_MAX_NODE_CAP, grown[l] * (2 + 2 * mean)) for l in range(L)]
+        self._chunk_cap = [2 * grown[l] + self._node_cap[l] // 512 for l in range(L)]
+        self._ws = None
+        self.growths = 0
+
+    SUPER_BATCH = LADIESSuperBatch
+
+    def _launch_state(self, sb, G: int, width: int, first_batch: int):
+        sb.call_id0 = self.call_id0 + first_batch * self.n_layers
+
+    def _layer(self, l: int, frontier: Tensor, ptr: List[int], first_batch: int):
+        """the count pass over the launch's lists -> (host n_out, host kept edges, the counted Ladies)"""
+        ops, dev, G, L, who = self._ops, self.device, len(ptr) - 1, self.n_layers, type(self).__name__
+        node_ptr = torch.tensor(ptr, dtype=torch.int64, device=dev)
+        max_nodes = max(ptr[g + 1] - ptr[g] for g in range(G))
+        if max_nodes > ops.LADIES_MAX_NODES:
+            raise RuntimeError("%s: layer %d has a frontier of %d nodes, more than 2^22" % (who, l, max_nodes))
+        for attempt in (0, 1):
+            node_cap, chunk_cap = max(self._node_cap[l], max_nodes), max(self._chunk_cap[l], 1)
+            op = ops.Ladies(self._graph, self.n_nodes, max_nodes, node_cap, chunk_cap, self.num_samples[l], G, dev,
+                            weights=self.weights, ws=self._ws)
+            self._ws = op.ws
+            op.count(frontier, node_ptr, self.seed, self.call_id0 + first_batch * L + l, call_stride=L)
+            host = op.state.tolist()                      # the layer's ONE read-back (a second one after a growth)
+            n_out, m, chunks, status = host[:G], host[G:2 * G], host[4 * G:5 * G], host[-1] & 0xFFFFFFFF
+            ops.ladies_status_check(status, who)
+            if not status & 1:
+                return n_out, m, op
+            for g in range(G):                            # a refused list reports ALL its triples in n_edges
+                n = ptr[g + 1] - ptr[g]
+                if not n_out[g] and (m[g] >= 2 ** 31 or n + min(m[g], self.n_nodes) > ops.LADIES_MAX_NODE_CAP):
+                    raise RuntimeError("%s: layer %d of mini-batch %d has %d edges over %d nodes: past the limits of one "
+                                       "batch (2^31 edges, 2^30 nodes); use a smaller batch_size" % (who, l, first_batch + g, m[g], n))
+            if attempt:
+                raise RuntimeError("%s: layer %d still refused after growing to the sizes it reported" % (who, l))
+            # what the refused lists need, and a quarter more: the next launch's largest mini-batch is rarely the same size
+            need = max([node_cap] + [ptr[g + 1] - ptr[g] + min(m[g], self.n_nodes) for g in range(G) if not n_out[g]])
+            self._node_cap[l] = min(ops.LADIES_MAX_NODE_CAP, need + need // 4)
+            self._chunk_cap[l] = min(ops.LADIES_MAX_CHUNKS, max(chunks) + max(chunks) // 4)
+            self.growths += 1
+
+    def _block(self, l: int, frontier: Tensor, ptr: List[int], first_batch: int, state):
+        n_out, m, op = self._layer(l, frontier, ptr, first_batch)
+        o = dict(dtype=torch.int64, device=self.device)
+        nptr, eptr = _ptr_list(n_out), _ptr_list(m)
+        node_off = torch.cumsum(op.n_nodes, 0) - op.n_nodes
+        edge_off = torch.cumsum(op.n_edges, 0) - op.n_edges
+        E = eptr[-1]                                      # a launch may keep no edge at all: the buffers still exist
+        n_id = torch.empty(max(nptr[-1], 1), **o)[:nptr[-1]]
+        rc = torch.empty((2, max(E, 1)), **o)[:, :E]
+        offs = torch.empty(max(E, 1), **o)[:E]
+        weight = torch.empty(max(E, 1), dtype=torch.float32, device=self.device)[:E]
+        op.emit(node_off, edge_off, n_id, None, None, rc[0], rc[1], offs, weight)
+        return dict(n_id=n_id, src_ptr=nptr, dst_ptr=ptr, edge_index=rc, edge_weight=weight, e_id=self.perm[offs], edge_ptr=eptr)
 
 
 def range_partition(num_nodes: int, num_parts: int) -> Tensor:
