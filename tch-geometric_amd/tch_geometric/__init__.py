@@ -13,5 +13,6 @@ from .loader import (ClusterData, ClusterLoader, FullNeighborLoader, GraphSAINTE
                      GraphSAINTRandomWalkLoader, HeteroLinkNeighborLoader, LADIESLoader,  # noqa: F401
                      LinkNeighborLoader, MetaPath2VecLoader, Node2VecLoader, PinSAGELoader, ShaDowKHopLoader,
                      TemporalWalkLoader, random_partition, range_partition)
+from .last_neighbor import LastNeighborLoader, TemporalEventLoader  # noqa: F401
 from .utils import (TEMPORAL_SAMPLE_DYNAMIC, TEMPORAL_SAMPLE_RELATIVE, TEMPORAL_SAMPLE_STATIC,  # noqa: F401
                     LaborEdgeSampler, RecentEdgeSampler, TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler)
