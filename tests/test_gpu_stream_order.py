@@ -399,7 +399,13 @@ def _plumbing_cases():
 # ------------------------------------------------------------------------------------------------ behind the forest
 def _sized(key, chain):
     """A chain whose flat outputs are sized by counts the host must know: make() runs it once on the default stream and
-    keeps the sizes, so that the measured run needs no read-back.  chain(inp, T, sizes) -> (outputs, sizes)."""
+    keeps the sizes of the REAL inputs, so that the measured run needs no read-back.  The sizes belong to the inputs: the
+    decoys give other counts, and pass 2 writes as many entries as ITS pass 1 counted, so flat arrays of the real inputs'
+    sizes are too short for a decoy run with more -- it then writes past their end, into whatever the allocator placed
+    there (the clones of `want`, where the layout has them there).  The reference runs are on the default stream and may
+    wait, so each reads its own counts back (sizes = None; the enqueue time printed for such a case includes that wait);
+    only the measured run, whose buffers are the arena's, takes the remembered ones.  chain(inp, T, sizes) -> (outputs,
+    sizes)."""
     def remember(make):
         def made(dev):
             real = make(dev)
@@ -407,7 +413,7 @@ def _sized(key, chain):
             torch.cuda.synchronize()
             return real
         return made
-    return remember, lambda inp, T: chain(inp, T, _cache[key])[0]
+    return remember, lambda inp, T: chain(inp, T, _cache[key] if getattr(T, "mode", None) == "replay" else None)[0]
 
 
 NB, B, FAN = 5, 33, [6, 3]
