@@ -43,6 +43,8 @@ FullNeighborLoader hands out blocks that hold EVERY in-edge of their destination
 num_neighbors=[-1]): tg_ns_full_count / tg_ns_full_emit, one read-back per layer and launch.
 LADIESLoader hands out blocks of layer-wise importance sampling: one budget of drawn nodes per layer and mini-batch with
 rescaled edge weights (tg_ladies_count / tg_ladies_emit), on the same per-layer scheme.
+PPRLoader hands out ShaDow-style subgraphs whose neighbourhoods are chosen by approximate personalised PageRank: the top-k
+of a forward push per seed (tg_ppr_topk), then the grouped induced pair, on the pooled scaffold.
 """
 from itertools import accumulate
 from typing import Iterator, List, Optional
@@ -2729,3 +2731,163 @@ class ClusterLoader(_PooledLoader):
 
     def _emit(self, slab, G: int, n_nodes, n_edges):
         return slab["ind"].emit(n_nodes, n_edges)           # n_id, edge_index, e_ptr and the two pointer lists
+
+
+PPR_FIELDS = ("ppr", "root_n_id", "batch")   # what PPRLoader adds to a mini-batch
+
+
+class PPRMiniBatch(MiniBatch):
+    """A PPRLoader mini-batch: MiniBatch with `ppr` [num_nodes] (float32: every node's estimate from its own seed), `batch`
+    [num_nodes] (the seed slot) and `root_n_id` [batch_size] (where every seed's own entry stands in n_id)."""
+    __slots__ = ()
+
+    def __getattr__(self, name):
+        if name in ("ppr", "root_n_id"):
+            sb, j = object.__getattribute__(self, "_sb"), object.__getattribute__(self, "_j")
+            if name == "root_n_id":
+                return sb.root_n_id[j, :sb.seed_counts[j]]
+            a = sb.node_ptr[j]
+            return sb.ppr.narrow(0, a, sb.node_ptr[j + 1] - a)
+        return super().__getattr__(name)
+
+
+class PPRSuperBatch(SuperBatch):
+    """SuperBatch of a PPRLoader launch: also `ppr` [sum nodes], `batch` [sum nodes], `root_n_id` [G, batch_size]"""
+    __slots__ = ("ppr",)
+
+    def _at(self, j):
+        return PPRMiniBatch(self, j)
+
+
+class PPRLoader(_PooledLoader):
+    """ShaDow-GNN's PPR sampler (the neighbourhood selector of PPRGo; PyG's get_ppr) as a loader: every seed gets the `k`
+    vertices of largest approximate personalised PageRank from it -- itself first -- and the mini-batch holds EVERY edge of
+    the graph inside each neighbourhood.  A launch takes `prefetch` consecutive mini-batches, all on the caller's stream:
+    tg_ppr_topk over the launch's seeds along the out-edges (forward push with restart `alpha` down to residual `eps` per
+    unit of degree, at most `max_rounds` synchronous rounds, at most `node_cap` touched vertices per seed; integer
+    arithmetic, so a mini-batch is a function of the graph, its seeds and these parameters), tg_compact_rows to the disjoint
+    (node, group = seed slot) lists, tg_ns_induced_grouped_count, ONE read-back of the sizes and the two status words,
+    tg_ns_induced_grouped_emit into exact flat arrays, tg_gather_rows per attribute.
+
+    Mini-batches carry `n_id`, `batch` (the seed slot of every node), `root_n_id` [batch_size], `ppr` (float32, the
+    estimate of every node from its own seed), `edge_index` / `e_id` / edge attributes of the per-seed induced edges (as
+    ShaDowKHopLoader's), node attributes and `batch_size`.  node_cap=None: min(num nodes, 1 + ceil(1 / (alpha * eps)), 2^20),
+    the bound of the push's volume, at least k.  A seed that touches more raises a RuntimeError naming node_cap.  chunk_cap:
+    as ShaDowKHopLoader's, grown on overflow.  Typed graphs and times are out of scope."""
+
+    def __init__(self, data, k: int, alpha: float = 0.15, eps: float = 1e-4, max_rounds: int = 64,
+                 node_cap: Optional[int] = None, input_nodes: Optional[Tensor] = None, batch_size: int = 1024,
+                 prefetch: int = 16, shuffle: bool = False, drop_last: bool = False, seed: int = 0, device="cuda",
+                 chunk_cap: Optional[int] = None):
+        from . import _cabi_ppr
+        _at_least_1("batch_size", batch_size)    # everything that can be refused is refused before any device work
+        _at_least_1("prefetch", prefetch)
+        if chunk_cap is not None and not 1 <= int(chunk_cap) <= 2 ** 31:
+            raise ValueError("chunk_cap must be in [1, 2^31], got %r" % (chunk_cap,))
+        N, E = _num_nodes(data), int(data.edge_index.shape[1])
+        if not 1 <= N <= 2 ** 31:
+            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
+        if node_cap is None:
+            volume = 1 + int(1.0 / (max(float(alpha), 2.0 ** -32) * max(float(eps), 2.0 ** -31)))
+            node_cap = max(int(k), min(N, volume, _cabi_ppr.PPR_MAX_CAP))
+        self.sizes = _cabi_ppr.PPR(k, node_cap, alpha, eps, max_rounds)
+        _refuse_reserved(data, PPR_FIELDS, "a PPRLoader's")
+        self.data, self.k, self.node_cap = data, self.sizes.k, self.sizes.node_cap
+        self.batch_size, self.prefetch = int(batch_size), int(prefetch)
+        self.shuffle, self.drop_last, self.seed = bool(shuffle), bool(drop_last), int(seed)
+        self.chunk_cap = int(chunk_cap) if chunk_cap is not None else 0   # 0: the launch object's default; grows on overflow
+        self.device = torch.device(device)
+        self.n_nodes, self._n_edges = N, E
+        self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
+        self._graph = self._view(self.col_ptrs, self.row_indices)       # the induced edges: columns
+        self._push_graph = self._out_graph()                            # the push: rows
+        self._node_attrs, self._edge_attrs = _split_attrs(data, N, E, self.device)
+        self.input_nodes = _checked_inputs(input_nodes, N, self.device)
+        self._init_pool()
+
+    def _new_slab(self):
+        """what a launch of up to `prefetch` mini-batches writes: tg_ppr_topk's rows for its cap * batch_size slots, the
+        slot -> (mini-batch, group) constants, the (node, group, score) slabs of pitch batch_size * k per mini-batch, the
+        grouped induced pair's launch object and the pinned image of what the host reads back"""
+        from . import _cabi_ppr
+        cap, B, K, dev = self.prefetch, self.batch_size, self.k, self.device
+        i64 = dict(dtype=torch.int64, device=dev)
+        slab = dict(seeds=torch.zeros(cap * B, **i64), count=torch.zeros(cap * B, **i64),
+                    rows=torch.empty((2, cap * B, K), **i64), status=torch.zeros(1, dtype=torch.int32, device=dev),
+                    lists=torch.empty((3, cap, B * K), **i64), counts_b=torch.zeros(cap, **i64),
+                    slot_group=(torch.arange(cap * B, device=dev) % B).reshape(-1, 1).expand(-1, K).contiguous(),
+                    row_base=(torch.arange(cap, device=dev) * (B * K)).reshape(-1, 1))
+        need = _cabi_ppr.PPR.workspace_bytes(cap * B, K, self.node_cap)[0]
+        slab["ws"] = torch.empty(need // 8 + 1, **i64) if need else None
+        slab["out"] = dict(count=slab["count"], nodes=slab["rows"][0], score=slab["rows"][1], weight=None,
+                           **{name: None for name in _cabi_ppr.DIAGNOSTICS})
+        slab["ind"] = _cabi.NsInducedGrouped(self._graph, slab["lists"][0], slab["lists"][1], slab["counts_b"], 1, cap,
+                                             self.n_nodes, B, chunk_cap=self.chunk_cap)
+        slab["host"] = torch.empty(cap + 1 + slab["ind"].state.numel(), dtype=torch.int64).pin_memory()
+        return slab
+
+    def _epoch_state(self, epoch: int):
+        nodes = self.input_nodes
+        if self.shuffle:                         # _Loader's one shuffle rule
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(self.seed * 1000003 + epoch)
+            nodes = nodes[torch.randperm(nodes.numel(), device=self.device, generator=gen)]
+        return nodes, epoch * len(self)
+
+    def _launch(self, slab, state, j: int, G: int):
+        """mini-batches j .. j + G - 1 of the epoch -> (their first number, node counts, edge counts), the counts as python
+        lists after the launch's one read-back; pass 2 of the induced pair has not run yet"""
+        from . import _cabi_ppr
+        nodes, batch0 = state
+        cap, B, K = self.prefetch, self.batch_size, self.k
+        seeds = nodes[j * B:(j + G) * B]
+        m = seeds.numel()
+        slab["widths"] = [min(B, m - g * B) for g in range(G)]
+        slab["seeds"][:m].copy_(seeds)
+        slab["count"].zero_()                    # the slots past m of a ragged mini-batch hold nothing
+        slab["status"].zero_()
+        _cabi_ppr.ppr_topk(self._push_graph, slab["seeds"][:m], self.sizes, None, out=slab["out"], status=slab["status"],
+                           ws=slab["ws"])
+        count = slab["count"].view(cap, B)
+        first = torch.cumsum(count, 1) - count   # where a slot's row starts inside its mini-batch's list
+        slab["first"] = first
+        torch.sum(count, 1, out=slab["counts_b"])
+        off = (first + slab["row_base"]).reshape(-1)
+        for dst, src in zip(slab["lists"], (slab["rows"][0], slab["slot_group"], slab["rows"][1])):
+            _cabi_ppr.compact_rows_at(src, slab["count"], off, m, dst)
+        ind = slab["ind"].count(G)
+        host = slab["host"]
+        host[:cap].copy_(slab["counts_b"], non_blocking=True)
+        host[cap:cap + 1].view(torch.int32)[:1].copy_(slab["status"], non_blocking=True)
+        host[cap + 1:].copy_(ind.state, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        who, ist = type(self).__name__, host[cap + 1:]
+        status = int(host[cap:cap + 1].view(torch.int32)[0])
+        if status & 1:
+            raise RuntimeError("%s: a seed's push touched more than node_cap = %d vertices; pass a larger node_cap (or a "
+                               "larger eps)" % (who, self.node_cap))
+        _cabi_ppr.ppr_status_check(status, who)
+        if int(ist[-1]) & 1:                     # a mini-batch needs more chunks than the workspace holds: the slow path
+            self.chunk_cap = max(self.chunk_cap, max(ind.chunks_of(ist)[:G]))
+            ind = slab["ind"] = ind.grown(self.chunk_cap)
+            ind.count(G)
+            ist.copy_(ind.state, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        _cabi.induced_status_check(int(ist[-1]) & 0xFFFFFFFF, who)
+        return batch0 + j, host[:G].tolist(), ist[:G].tolist()
+
+    def _emit(self, slab, G: int, n_nodes, n_edges):
+        edge_index, e_ptr, _ = _cabi.ns_induced_emit(slab["ind"], n_edges)
+        n_id = _flat_rows(slab["lists"][0][:G], slab["counts_b"][:G], sum(n_nodes))   # copies: the slabs go back
+        return n_id, edge_index, e_ptr, _ptr_list(n_nodes), _ptr_list(n_edges)
+
+    def _finish(self, slab, G: int, call_id0: int, n_nodes, n_edges) -> PPRSuperBatch:
+        sb = PPRSuperBatch()
+        sb._set_flat(*self._emit(slab, G, n_nodes, n_edges), self.perm, self._node_attrs, self._edge_attrs)
+        sb.batch_size, sb.call_id0, sb.seed_counts = self.batch_size, call_id0, slab["widths"]
+        total = sum(n_nodes)
+        sb.batch = _flat_rows(slab["lists"][1][:G], slab["counts_b"][:G], total)
+        # the weight word of tg_ppr_topk: one conversion of p, one exact scaling
+        sb.ppr = _flat_rows(slab["lists"][2][:G], slab["counts_b"][:G], total).to(torch.float32) * (2.0 ** -31)
+        sb.root_n_id = slab["first"][:G].clone()
+        return sb
