@@ -45,6 +45,8 @@ LADIESLoader hands out blocks of layer-wise importance sampling: one budget of d
 rescaled edge weights (tg_ladies_count / tg_ladies_emit), on the same per-layer scheme.
 PPRLoader hands out ShaDow-style subgraphs whose neighbourhoods are chosen by approximate personalised PageRank: the top-k
 of a forward push per seed (tg_ppr_topk), then the grouped induced pair, on the pooled scaffold.
+SEALLoader hands out one enclosing subgraph per candidate link with double-radius node labels (tg_seal_nodes), then the grouped
+induced pair, on the pooled scaffold.
 """
 from itertools import accumulate
 from typing import Iterator, List, Optional
@@ -2890,4 +2892,200 @@ class PPRLoader(_PooledLoader):
         # the weight word of tg_ppr_topk: one conversion of p, one exact scaling
         sb.ppr = _flat_rows(slab["lists"][2][:G], slab["counts_b"][:G], total).to(torch.float32) * (2.0 ** -31)
         sb.root_n_id = slab["first"][:G].clone()
+        return sb
+
+
+SEAL_FIELDS = ("z", "root_n_id", "batch", "target_edge", "edge_label", "edge_label_index")   # what SEALLoader adds
+
+
+class SEALMiniBatch(MiniBatch):
+    """A SEALLoader mini-batch: MiniBatch with `z` [num_nodes] (the double-radius label of every node inside its link's
+    subgraph), `batch` [num_nodes] (the link slot), `root_n_id` [batch_size, 2] (where every link's u and v stand in n_id),
+    `target_edge` [num_edges] (bool: both ends are the two roots of one link and differ -- the link itself, which the model
+    masks for positive links), `edge_label_index` [2, batch_size] (the links, original ids) and `edge_label` [batch_size] or
+    None."""
+    __slots__ = ()
+
+    def __getattr__(self, name):
+        if name not in SEAL_FIELDS or name == "batch":
+            return super().__getattr__(name)
+        sb, j = object.__getattribute__(self, "_sb"), object.__getattribute__(self, "_j")
+        width = sb.seed_counts[j]
+        if name == "z":
+            a = sb.node_ptr[j]
+            return sb.z.narrow(0, a, sb.node_ptr[j + 1] - a)
+        if name == "root_n_id":
+            return sb.root_n_id[j, :width]
+        if name == "edge_label_index":
+            return sb.edge_label_index[:, j, :width]
+        if name == "edge_label":
+            return None if sb.edge_label is None else sb.edge_label[j, :width]
+        # target_edge: elementwise over the mini-batch's edges, nothing is read back.  Both ends of an edge share a link slot
+        # (the grouped induced rule), and a slot's u and v are the first two entries of its part of n_id
+        first, (row, col) = sb.root_n_id[j, :, 0], self.edge_index
+        slot = self.batch
+        r, c = row - first[slot[row]], col - first[slot[col]]
+        target = (r < 2) & (c < 2) & (r != c)
+        self.__dict__[name] = target
+        return target
+
+
+class SEALSuperBatch(SuperBatch):
+    """SuperBatch of a SEALLoader launch: also `z` [sum nodes], `batch` [sum nodes], `root_n_id` [G, batch_size, 2],
+    `edge_label_index` [2, G, batch_size], `edge_label` [G, batch_size] or None (slots past a ragged mini-batch's width hold
+    nothing)"""
+    __slots__ = ("z", "edge_label", "edge_label_index")
+
+    def _at(self, j):
+        return SEALMiniBatch(self, j)
+
+
+class SEALLoader(_PooledLoader):
+    """SEAL (Zhang and Chen 2018; the labeling trick) as a loader: every candidate link (u, v) of `edge_label_index` [2, L]
+    gets its ENCLOSING SUBGRAPH -- every vertex within `num_hops` of u or of v along the in-edges (pass a symmetric graph
+    for SEAL's undirected subgraph), every edge of the graph between them -- and a double-radius node label `z` per vertex
+    from its distances to u and to v inside that subgraph, the link itself removed (z_max > 0 clamps the labels).  A launch
+    takes `prefetch` consecutive mini-batches, all on the caller's stream: tg_seal_nodes on the CSC view over the launch's
+    links, tg_compact_rows of nodes, link slot and z to the disjoint per-mini-batch lists, tg_ns_induced_grouped_count with
+    group = link slot, ONE read-back of the sizes and the two status words, tg_ns_induced_grouped_emit into exact flat
+    arrays, tg_gather_rows per attribute.  Everything is a function of the graph, the links and these parameters.
+
+    Mini-batches carry `n_id`, `batch` (the link slot of every node), `z`, `root_n_id` [batch_size, 2], `edge_index` /
+    `e_id` / edge attributes of the per-link induced edges, `target_edge`, `edge_label`, `edge_label_index`, node attributes
+    and `batch_size`.  Negative links are the caller's: put them into edge_label_index with edge_label 0.
+
+    The output rows of tg_seal_nodes have pitch `node_cap`, so a launch holds prefetch * batch_size * node_cap words per
+    array: that is why the defaults are small.  A link whose subgraph has more than `node_cap` vertices raises a
+    RuntimeError naming node_cap.  chunk_cap: as ShaDowKHopLoader's, grown on overflow.  Typed graphs, times and a per-hop
+    cap on new vertices are out of scope."""
+
+    def __init__(self, data, edge_label_index: Tensor, edge_label: Optional[Tensor] = None, num_hops: int = 1,
+                 node_cap: int = 1024, z_max: int = 0, batch_size: int = 32, prefetch: int = 4, shuffle: bool = False,
+                 drop_last: bool = False, seed: int = 0, device="cuda", chunk_cap: Optional[int] = None):
+        from . import _cabi_seal
+        _at_least_1("batch_size", batch_size)    # everything that can be refused is refused before any device work
+        _at_least_1("prefetch", prefetch)
+        if chunk_cap is not None and not 1 <= int(chunk_cap) <= 2 ** 31:
+            raise ValueError("chunk_cap must be in [1, 2^31], got %r" % (chunk_cap,))
+        if _is_hetero(data):
+            raise ValueError("SEALLoader takes a homogeneous graph (typed graphs are out of scope)")
+        N, E = _num_nodes(data), int(data.edge_index.shape[1])
+        if not 1 <= N <= 2 ** 31:
+            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
+        self.sizes = _cabi_seal.Seal(num_hops, node_cap, z_max)
+        eli = edge_label_index
+        if not isinstance(eli, Tensor) or eli.dtype != torch.int64 or eli.dim() != 2 or eli.shape[0] != 2:
+            raise ValueError("edge_label_index must be an int64 tensor of shape [2, L]")
+        L = int(eli.shape[1])
+        if L and (int(eli.min()) < 0 or int(eli.max()) >= N):
+            raise ValueError("edge_label_index outside [0, %d)" % N)
+        if L and bool((eli[0] == eli[1]).any()):
+            raise ValueError("edge_label_index holds a link from a vertex to itself")
+        if edge_label is not None and (not isinstance(edge_label, Tensor) or edge_label.shape != (L,)):
+            raise ValueError("edge_label must be a tensor of shape [%d]" % L)
+        _refuse_reserved(data, SEAL_FIELDS, "a SEALLoader's")
+        self.data, self.num_hops, self.node_cap, self.z_max = data, self.sizes.num_hops, self.sizes.node_cap, self.sizes.z_max
+        self.batch_size, self.prefetch = int(batch_size), int(prefetch)
+        self.shuffle, self.drop_last, self.seed = bool(shuffle), bool(drop_last), int(seed)
+        self.chunk_cap = int(chunk_cap) if chunk_cap is not None else 0   # 0: the launch object's default; grows on overflow
+        self.device = torch.device(device)
+        self.n_nodes, self._n_edges = N, E
+        self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
+        self._graph = self._view(self.col_ptrs, self.row_indices)       # the hops, the distances and the induced edges
+        self._node_attrs, self._edge_attrs = _split_attrs(data, N, E, self.device)
+        self.edge_label_index = eli.to(self.device).contiguous()
+        self.edge_label = None if edge_label is None else edge_label.to(self.device)
+        self.input_nodes = torch.arange(L, device=self.device)          # positions of the links: what an epoch is cut from
+        self._init_pool()
+
+    def _new_slab(self):
+        """what a launch of up to `prefetch` mini-batches writes: tg_seal_nodes' rows for its cap * batch_size slots, the
+        slot -> group constant, the (node, group, z) slabs of pitch batch_size * node_cap per mini-batch, the grouped induced
+        pair's launch object and the pinned image of what the host reads back"""
+        from . import _cabi_seal
+        cap, B, K, dev = self.prefetch, self.batch_size, self.node_cap, self.device
+        i64 = dict(dtype=torch.int64, device=dev)
+        slab = dict(links=torch.zeros((2, cap * B), **i64), count=torch.zeros(cap * B, **i64),
+                    rows=torch.empty((2, cap * B, K), **i64), status=torch.zeros(1, dtype=torch.int32, device=dev),
+                    lists=torch.empty((3, cap, B * K), **i64), counts_b=torch.zeros(cap, **i64),
+                    slot_group=(torch.arange(cap * B, device=dev) % B).reshape(-1, 1).expand(-1, K).contiguous(),
+                    row_base=(torch.arange(cap, device=dev) * (B * K)).reshape(-1, 1))
+        need = _cabi_seal.Seal.workspace_bytes(cap * B, K)[0]
+        slab["ws"] = torch.empty(need // 8 + 1, **i64) if need else None
+        slab["out"] = dict(count=slab["count"], nodes=slab["rows"][0], z=slab["rows"][1], du=None, dv=None, rounds=None)
+        slab["ind"] = _cabi.NsInducedGrouped(self._graph, slab["lists"][0], slab["lists"][1], slab["counts_b"], 1, cap,
+                                             self.n_nodes, B, chunk_cap=self.chunk_cap)
+        slab["host"] = torch.empty(cap + 1 + slab["ind"].state.numel(), dtype=torch.int64).pin_memory()
+        return slab
+
+    def _epoch_state(self, epoch: int):
+        order = self.input_nodes
+        if self.shuffle:                         # _Loader's one shuffle rule
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(self.seed * 1000003 + epoch)
+            order = torch.randperm(order.numel(), device=self.device, generator=gen)
+        return order, epoch * len(self)
+
+    def _launch(self, slab, state, j: int, G: int):
+        """mini-batches j .. j + G - 1 of the epoch -> (their first number, node counts, edge counts), the counts as python
+        lists after the launch's one read-back; pass 2 of the induced pair has not run yet"""
+        from . import _cabi_ppr, _cabi_seal
+        order, batch0 = state
+        cap, B = self.prefetch, self.batch_size
+        picked = order[j * B:(j + G) * B]
+        m = picked.numel()
+        slab["widths"] = [min(B, m - g * B) for g in range(G)]
+        slab["picked"] = picked
+        slab["links"][:, :m].copy_(self.edge_label_index[:, picked])
+        slab["count"].zero_()                    # the slots past m of a ragged mini-batch hold nothing
+        slab["status"].zero_()
+        _cabi_seal.seal_nodes(self._graph, slab["links"][0, :m], slab["links"][1, :m], self.sizes, out=slab["out"],
+                              status=slab["status"], ws=slab["ws"])
+        count = slab["count"].view(cap, B)
+        first = torch.cumsum(count, 1) - count   # where a slot's row starts inside its mini-batch's list
+        slab["first"] = first
+        torch.sum(count, 1, out=slab["counts_b"])
+        off = (first + slab["row_base"]).reshape(-1)
+        for dst, src in zip(slab["lists"], (slab["rows"][0], slab["slot_group"], slab["rows"][1])):
+            _cabi_ppr.compact_rows_at(src, slab["count"], off, m, dst)
+        ind = slab["ind"].count(G)
+        host = slab["host"]
+        host[:cap].copy_(slab["counts_b"], non_blocking=True)
+        host[cap:cap + 1].view(torch.int32)[:1].copy_(slab["status"], non_blocking=True)
+        host[cap + 1:].copy_(ind.state, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        who, ist = type(self).__name__, host[cap + 1:]
+        status = int(host[cap:cap + 1].view(torch.int32)[0])
+        if status & _cabi_seal.STATUS_CAP:
+            raise RuntimeError("%s: a link's enclosing subgraph has more than node_cap = %d vertices; pass a larger node_cap "
+                               "(or fewer hops)" % (who, self.node_cap))
+        _cabi_seal.seal_status_check(status, who)
+        if int(ist[-1]) & 1:                     # a mini-batch needs more chunks than the workspace holds: the slow path
+            self.chunk_cap = max(self.chunk_cap, max(ind.chunks_of(ist)[:G]))
+            ind = slab["ind"] = ind.grown(self.chunk_cap)
+            ind.count(G)
+            ist.copy_(ind.state, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        _cabi.induced_status_check(int(ist[-1]) & 0xFFFFFFFF, who)
+        return batch0 + j, host[:G].tolist(), ist[:G].tolist()
+
+    def _emit(self, slab, G: int, n_nodes, n_edges):
+        edge_index, e_ptr, _ = _cabi.ns_induced_emit(slab["ind"], n_edges)
+        n_id = _flat_rows(slab["lists"][0][:G], slab["counts_b"][:G], sum(n_nodes))   # copies: the slabs go back
+        return n_id, edge_index, e_ptr, _ptr_list(n_nodes), _ptr_list(n_edges)
+
+    def _finish(self, slab, G: int, call_id0: int, n_nodes, n_edges) -> SEALSuperBatch:
+        sb = SEALSuperBatch()
+        sb._set_flat(*self._emit(slab, G, n_nodes, n_edges), self.perm, self._node_attrs, self._edge_attrs)
+        sb.batch_size, sb.call_id0, sb.seed_counts = self.batch_size, call_id0, slab["widths"]
+        total, B = sum(n_nodes), self.batch_size
+        sb.batch = _flat_rows(slab["lists"][1][:G], slab["counts_b"][:G], total)
+        sb.z = _flat_rows(slab["lists"][2][:G], slab["counts_b"][:G], total)
+        first = slab["first"][:G]
+        sb.root_n_id = torch.stack([first, first + 1], 2)
+        picked = slab["picked"]
+        if picked.numel() < G * B:               # a ragged last mini-batch: its missing slots repeat the launch's first link
+            picked = torch.cat([picked, picked[:1].expand(G * B - picked.numel())])
+        sb.edge_label_index = self.edge_label_index[:, picked].view(2, G, B)
+        sb.edge_label = None if self.edge_label is None else self.edge_label[picked].view(G, B)
         return sb

@@ -73,7 +73,18 @@ lo <= T_seed - t <= hi) and root_n_id [batch_size].  The operators are tg_ns_ind
 node_marks=None, group_time=None, time_window=None, chunk_cap=None, ws=None) with count() / emit() / grown(chunk_cap) and
 _cabi.ns_induced_grouped_workspace_bytes(graph, pitch_nodes, id_bound, n_groups, chunk_cap, n_batches) -> (bytes,
 bytes_min); for one list transforms.induced_subgraph(nodes, col_ptrs, row_indices, id_bound=None, group=None,
-group_time=None, edge_time=None, time_window=None) -> (rows, cols, edge_index)."""
+group_time=None, edge_time=None, time_window=None) -> (rows, cols, edge_index).
+
+Subgraph-based link prediction (SEAL) mini-batches come from SEALLoader(data, edge_label_index, edge_label=None, num_hops=1,
+node_cap=1024, z_max=0, batch_size=32, prefetch=4, shuffle=False, drop_last=False, seed=0, device="cuda", chunk_cap=None)
+(exported by the package): per candidate link (u, v) every vertex within num_hops of u or of v along the in-edges, every
+edge between them and a double-radius node label.  Mini-batches carry n_id, batch (the link slot), z, root_n_id
+[batch_size, 2], edge_index / e_id / edge attributes, target_edge (bool per edge: the link itself), edge_label,
+edge_label_index (original ids), node attributes and batch_size; a link with more than node_cap vertices raises
+RuntimeError.  The operator is tg_seal_nodes (include/tchgeo_seal.h, csrc/seal.hip): _cabi_seal.seal_nodes(graph, src, dst,
+num_hops=1, node_cap=1024, z_max=0, form=0, ws=None, out=None, status=None, distances=True) -> dict(count, nodes, z, du,
+dv, rounds, status, ws), _cabi_seal.Seal.workspace_bytes(m, node_cap, form=0) -> (bytes, form taken) and
+_cabi_seal.seal_status_check(status, who)."""
 from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor
