@@ -44,3 +44,16 @@ def fake_hetero_dataset(num_node_types=3, num_edge_types=6, avg_num_nodes=1000, 
         data[(s, "e%d" % r, d)].edge_index = ei.to(device)
         data[(s, "e%d" % r, d)].timestamps = torch.randint(0, 100, (e,), generator=g).to(device)
     return data
+
+
+def fake_community_dataset(num_nodes=1000, communities=20, avg_degree=10, p_inside=0.9, channels=64, seed=0, device="cuda"):
+    """fake_dataset with planted communities (vertex v belongs to v % communities): an edge's target lies in its source's
+    community with probability p_inside, so that links have the local structure link heuristics look for"""
+    g = torch.Generator().manual_seed(seed)
+    e = num_nodes * avg_degree
+    src = torch.randint(0, num_nodes, (e,), generator=g)
+    inside = torch.randint(0, (num_nodes + communities - 1) // communities, (e,), generator=g) * communities + src % communities
+    dst = torch.where(torch.rand(e, generator=g) < p_inside, inside.clamp(max=num_nodes - 1),
+                      torch.randint(0, num_nodes, (e,), generator=g))
+    return Graph(edge_index=torch.stack([src, dst]).to(device), num_nodes=num_nodes,
+                 x=torch.randn(num_nodes, channels, generator=g).to(device))

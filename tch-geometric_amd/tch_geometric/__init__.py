@@ -9,7 +9,7 @@ from . import _cabi  # noqa: F401  (raises if lib/libtchgeo_hip.so is missing)
 from .tch_geometric import *  # noqa: F401,F403
 from .tch_geometric import (PanicException, backend_version, graph_cache_clear, graph_cache_info,  # noqa: F401
                             rng_state, seed, set_rng_state)
-from .loader import (ClusterData, ClusterLoader, FullNeighborLoader, GraphSAINTEdgeLoader, GraphSAINTNodeLoader,
+from .loader import (ClusterData, ClusterLoader, CommonNeighborLoader, FullNeighborLoader, GraphSAINTEdgeLoader, GraphSAINTNodeLoader,
                      GraphSAINTRandomWalkLoader, HeteroLinkNeighborLoader, LADIESLoader,  # noqa: F401
                      LinkNeighborLoader, MetaPath2VecLoader, Node2VecLoader, PinSAGELoader, PPRLoader, SEALLoader,
                      ShaDowKHopLoader, TemporalWalkLoader, random_partition, range_partition)

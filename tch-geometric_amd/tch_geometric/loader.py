@@ -47,6 +47,8 @@ PPRLoader hands out ShaDow-style subgraphs whose neighbourhoods are chosen by ap
 of a forward push per seed (tg_ppr_topk), then the grouped induced pair, on the pooled scaffold.
 SEALLoader hands out one enclosing subgraph per candidate link with double-radius node labels (tg_seal_nodes), then the grouped
 induced pair, on the pooled scaffold.
+CommonNeighborLoader hands out, per candidate link, the common neighbours of its two ends with their count, the ends' adjacency and
+the classical heuristics' scores (tg_cn_links), as ragged lists on the pooled scaffold; its mini-batches hold no edges.
 """
 from itertools import accumulate
 from typing import Iterator, List, Optional
@@ -3088,4 +3090,199 @@ class SEALLoader(_PooledLoader):
             picked = torch.cat([picked, picked[:1].expand(G * B - picked.numel())])
         sb.edge_label_index = self.edge_label_index[:, picked].view(2, G, B)
         sb.edge_label = None if self.edge_label is None else self.edge_label[picked].view(G, B)
+        return sb
+
+
+CN_SCORES = ("cn", "jaccard", "aa", "ra")   # the heuristics a CommonNeighborLoader knows
+
+
+class CommonNeighborMiniBatch:
+    """Mini-batch j of a CommonNeighborSuperBatch, built from views when asked for: `edge_label_index` [2, B] (original
+    ids), `edge_label` [B] or None, `cn_ptr` [B + 1] and `cn_index` [cn_ptr[-1]] (link i's common neighbours are
+    cn_index[cn_ptr[i]:cn_ptr[i + 1]], ascending, original ids), `cn_count` [B] (exact, also where the list is cut),
+    `adjacent` [B], `scores` (a dict of float32 [B]), the node attributes of the source graph gathered for cn_index,
+    `batch_size` and `call_id`."""
+    __slots__ = ("_sb", "_j", "__dict__")
+
+    def __init__(self, sb, j):
+        self._sb, self._j = sb, j
+
+    batch_size = property(lambda self: self._sb.seed_counts[self._j])
+    call_id = property(lambda self: self._sb.call_id0 + self._j)
+
+    def __getattr__(self, name):
+        sb, j = object.__getattribute__(self, "_sb"), object.__getattribute__(self, "_j")
+        width, a = sb.seed_counts[j], sb.node_ptr[j]
+        if name == "cn_index":
+            return sb.cn_index.narrow(0, a, sb.node_ptr[j + 1] - a)
+        if name in sb.node_attrs:
+            return sb.node_attrs[name].narrow(0, a, sb.node_ptr[j + 1] - a)
+        if name == "cn_ptr":
+            return sb.cn_ptr[j * sb.batch_size:j * sb.batch_size + width + 1] - a
+        if name == "edge_label_index":
+            return sb.edge_label_index[:, j, :width]
+        if name == "edge_label":
+            return None if sb.edge_label is None else sb.edge_label[j, :width]
+        if name in ("cn_count", "adjacent"):
+            return getattr(sb, name)[j, :width]
+        if name == "scores":
+            return {k: t[j, :width] for k, t in sb.scores.items()}
+        raise AttributeError(name)
+
+
+class CommonNeighborSuperBatch(_Indexable):
+    """The mini-batches of one CommonNeighborLoader launch as launch-wide tensors: `cn_index` [sum lists] with `cn_ptr`
+    [slots + 1] over the launch's slots, `cn_count` / `adjacent` / every score [G, batch_size], `edge_label_index`
+    [2, G, batch_size], `edge_label` [G, batch_size] or None, `node_attrs` (rows gathered for cn_index), `node_ptr` (python
+    list: where every mini-batch's part of cn_index begins) and `seed_counts` (the links of every mini-batch)."""
+    __slots__ = ("cn_index", "cn_ptr", "cn_count", "adjacent", "scores", "edge_label_index", "edge_label", "node_attrs",
+                 "node_ptr", "seed_counts", "batch_size", "call_id0")
+
+    def _at(self, j):
+        return CommonNeighborMiniBatch(self, j)
+
+
+class CommonNeighborLoader(_PooledLoader):
+    """The common neighbours of candidate links as a loader (the classical link heuristics; the per-link lists Neural Common
+    Neighbor, Neo-GNN and BUDDY take): every link (u, v) of `edge_label_index` [2, L] gets the vertices that stand in the
+    rows of both u and v along the in-edges (pass a symmetric graph for the undirected notion), u and v themselves left
+    out, parallel edges counted once.  A launch takes `prefetch` consecutive mini-batches, all on the caller's stream: ONE
+    tg_cn_links call over its links with the fixed-point tables of the asked-for sums, tg_compact_rows to one ragged list,
+    ONE read-back of the mini-batches' totals and the status word, tg_gather_rows per node attribute.
+
+    `scores`: any of "cn" (|C|), "jaccard" (|C| / |A(u) u A(v)| over the distinct neighbours with u and v left out; 0 where
+    that is empty), "aa" (Adamic-Adar, sum of 1 / log d(w)) and "ra" (resource allocation, sum of 1 / d(w)), d the distinct
+    degree; the two sums are exact integers in units of 2^-32 on the device and always run over all of C.  A list longer
+    than `cn_cap` raises a RuntimeError naming cn_cap unless truncate=True, which keeps its cn_cap smallest ids (cn_count
+    and the scores stay exact).  A link from a vertex to itself is allowed.  Typed graphs, two-hop common neighbours and
+    per-hop caps are out of scope."""
+
+    def __init__(self, data, edge_label_index: Tensor, edge_label: Optional[Tensor] = None, cn_cap: int = 256,
+                 scores=CN_SCORES, batch_size: int = 1024, prefetch: int = 4, shuffle: bool = False, drop_last: bool = False,
+                 seed: int = 0, device="cuda", truncate: bool = False):
+        from . import _cabi_cn
+        _at_least_1("batch_size", batch_size)    # everything that can be refused is refused before any device work
+        _at_least_1("prefetch", prefetch)
+        if _is_hetero(data):
+            raise ValueError("CommonNeighborLoader takes a homogeneous graph (typed graphs are out of scope)")
+        N, E = _num_nodes(data), int(data.edge_index.shape[1])
+        if not 1 <= N <= 2 ** 31:
+            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
+        self.scores = tuple(scores)
+        for name in self.scores:
+            if name not in CN_SCORES:
+                raise ValueError("unknown score %r (known: %s)" % (name, ", ".join(CN_SCORES)))
+        self._kinds = tuple(k for k in _cabi_cn.KINDS if k in self.scores)
+        self.sizes = _cabi_cn.CommonNeighbors(cn_cap, len(self._kinds))
+        eli = edge_label_index
+        if not isinstance(eli, Tensor) or eli.dtype != torch.int64 or eli.dim() != 2 or eli.shape[0] != 2:
+            raise ValueError("edge_label_index must be an int64 tensor of shape [2, L]")
+        L = int(eli.shape[1])
+        if L and (int(eli.min()) < 0 or int(eli.max()) >= N):
+            raise ValueError("edge_label_index outside [0, %d)" % N)
+        if edge_label is not None and (not isinstance(edge_label, Tensor) or edge_label.shape != (L,)):
+            raise ValueError("edge_label must be a tensor of shape [%d]" % L)
+        _refuse_reserved(data, ("cn_ptr", "cn_index", "cn_count", "adjacent", "scores", "edge_label", "edge_label_index"),
+                         "a CommonNeighborLoader's")
+        self.data, self.cn_cap, self.truncate = data, self.sizes.cn_cap, bool(truncate)
+        self.batch_size, self.prefetch = int(batch_size), int(prefetch)
+        self.shuffle, self.drop_last, self.seed = bool(shuffle), bool(drop_last), int(seed)
+        self.device = torch.device(device)
+        self.n_nodes, self._n_edges = N, E
+        self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
+        self._graph = self._view(self.col_ptrs, self.row_indices)
+        self._tables = _cabi_cn.cn_tables(self.col_ptrs, self.row_indices, self._kinds) if self._kinds else None
+        if "jaccard" in self.scores:             # |A(x) \ {x}|: the distinct degree without a self loop
+            col = torch.repeat_interleave(torch.arange(N, device=self.device), self.col_ptrs[1:] - self.col_ptrs[:-1])
+            loop = torch.zeros(N, dtype=torch.int64, device=self.device)
+            loop[col[self.row_indices == col]] = 1
+            self._degree = _cabi_cn.distinct_degree(self.col_ptrs, self.row_indices) - loop
+        self._node_attrs, _ = _split_attrs(data, N, E, self.device, edges=False)
+        self.edge_label_index = eli.to(self.device).contiguous()
+        self.edge_label = None if edge_label is None else edge_label.to(self.device)
+        self.input_nodes = torch.arange(L, device=self.device)          # positions of the links: what an epoch is cut from
+        self._init_pool()
+
+    def _new_slab(self):
+        """what a launch of up to `prefetch` mini-batches writes: tg_cn_links' words for its cap * batch_size slots, the
+        ragged list, the pointer over the slots and the pinned image of what the host reads back"""
+        from . import _cabi_cn
+        cap, B, K, T, dev = self.prefetch, self.batch_size, self.cn_cap, len(self._kinds), self.device
+        i64 = dict(dtype=torch.int64, device=dev)
+        slab = dict(links=torch.zeros((2, cap * B), **i64), status=torch.zeros(1, dtype=torch.int32, device=dev),
+                    flat=torch.empty(cap * B * K, **i64), ptr=torch.zeros(cap * B + 1, **i64),
+                    host=torch.empty(cap + 2, dtype=torch.int64).pin_memory())
+        slab["out"] = dict(count=torch.zeros(cap * B, **i64), cn=torch.empty((cap * B, K), **i64),
+                           adjacent=torch.zeros(cap * B, **i64), score=torch.zeros((cap * B, T), **i64) if T else None)
+        need = _cabi_cn.CommonNeighbors.workspace_bytes(cap * B)[0]
+        slab["ws"] = torch.empty(need // 4, dtype=torch.int32, device=dev)
+        return slab
+
+    def _epoch_state(self, epoch: int):
+        order = self.input_nodes
+        if self.shuffle:                         # _Loader's one shuffle rule
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(self.seed * 1000003 + epoch)
+            order = torch.randperm(order.numel(), device=self.device, generator=gen)
+        return order, epoch * len(self)
+
+    def _launch(self, slab, state, j: int, G: int):
+        """mini-batches j .. j + G - 1 of the epoch -> (their first number, where every mini-batch's list begins) after the
+        launch's one read-back"""
+        from . import _cabi_cn, _cabi_ppr
+        order, batch0 = state
+        cap, B, K = self.prefetch, self.batch_size, self.cn_cap
+        picked = order[j * B:(j + G) * B]
+        m = picked.numel()
+        slab["widths"], slab["picked"], slab["m"] = [min(B, m - g * B) for g in range(G)], picked, m
+        slab["links"][:, :m].copy_(self.edge_label_index[:, picked])
+        slab["status"].zero_()
+        out = slab["out"]
+        _cabi_cn.cn_links(self._graph, slab["links"][0, :m], slab["links"][1, :m], self.sizes, tables=self._tables, out=out,
+                          status=slab["status"], ws=slab["ws"])
+        lens = out["count"][:m].clamp(max=K)
+        ptr = slab["ptr"]
+        torch.cumsum(lens, 0, out=ptr[1:m + 1])
+        _cabi_ppr.compact_rows_at(out["cn"], lens, ptr[:m].contiguous(), m, slab["flat"])
+        host = slab["host"]
+        host[:G + 1].copy_(ptr[:m + 1:B] if m % B == 0 else torch.cat([ptr[:m:B], ptr[m:m + 1]]), non_blocking=True)
+        host[cap + 1:].view(torch.int32)[:1].copy_(slab["status"], non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        who, status = type(self).__name__, int(host[cap + 1:].view(torch.int32)[0])
+        if status & _cabi_cn.STATUS_CAP and not self.truncate:
+            raise RuntimeError("%s: a link has more than cn_cap = %d common neighbours; pass a larger cn_cap or "
+                               "truncate=True" % (who, K))
+        _cabi_cn.cn_status_check(status, who, mask=~_cabi_cn.STATUS_CAP)
+        return batch0 + j, host[:G + 1].tolist(), None
+
+    def _finish(self, slab, G: int, call_id0: int, node_ptr, _) -> CommonNeighborSuperBatch:
+        sb = CommonNeighborSuperBatch()
+        B, m, out, picked = self.batch_size, slab["m"], slab["out"], slab["picked"]
+        sb.batch_size, sb.call_id0, sb.seed_counts, sb.node_ptr = B, call_id0, slab["widths"], node_ptr
+        sb.cn_index = slab["flat"][:node_ptr[-1]].clone()    # copies: the slabs go back
+        sb.cn_ptr = slab["ptr"][:m + 1].clone()
+        sb.node_attrs = {k: _rows_of(v, sb.cn_index) for k, v in self._node_attrs}
+
+        def rows(t):                             # [m] -> [G, B]; a ragged last mini-batch's missing slots hold zeros
+            full = torch.zeros(G * B, dtype=t.dtype, device=t.device)
+            full[:m] = t[:m]
+            return full.view(G, B)
+        u, v = slab["links"][0, :m], slab["links"][1, :m]
+        count = out["count"][:m]
+        sb.cn_count, sb.adjacent = rows(count), rows(out["adjacent"])
+        sb.edge_label_index = torch.stack([rows(u), rows(v)])
+        sb.edge_label = None if self.edge_label is None else rows(self.edge_label[picked])
+        sb.scores = {}
+        for name in self.scores:
+            if name == "cn":
+                s = count.to(torch.float32)
+            elif name == "jaccard":
+                other = (u != v).to(torch.int64)             # a link's other end is left out of a row that holds it
+                adj = out["adjacent"][:m]
+                union = self._degree[u] - (adj & 1) * other + self._degree[v] - ((adj >> 1) & 1) * other - count
+                s = torch.where(union > 0, count.to(torch.float64) / union.clamp(min=1).to(torch.float64),
+                                torch.zeros((), dtype=torch.float64, device=self.device)).to(torch.float32)
+            else:                                            # the integer sums, scaled by the fixed-point unit
+                s = (out["score"][:m, self._kinds.index(name)].to(torch.float64) * 2.0 ** -32).to(torch.float32)
+            sb.scores[name] = rows(s)
         return sb

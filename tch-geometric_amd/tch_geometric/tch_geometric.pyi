@@ -84,7 +84,18 @@ edge_label_index (original ids), node attributes and batch_size; a link with mor
 RuntimeError.  The operator is tg_seal_nodes (include/tchgeo_seal.h, csrc/seal.hip): _cabi_seal.seal_nodes(graph, src, dst,
 num_hops=1, node_cap=1024, z_max=0, form=0, ws=None, out=None, status=None, distances=True) -> dict(count, nodes, z, du,
 dv, rounds, status, ws), _cabi_seal.Seal.workspace_bytes(m, node_cap, form=0) -> (bytes, form taken) and
-_cabi_seal.seal_status_check(status, who)."""
+_cabi_seal.seal_status_check(status, who).
+
+The common neighbours of candidate links come from CommonNeighborLoader(data, edge_label_index, edge_label=None, cn_cap=256,
+scores=("cn", "jaccard", "aa", "ra"), batch_size=1024, prefetch=4, shuffle=False, drop_last=False, seed=0, device="cuda",
+truncate=False) (exported by the package): per link (u, v) the distinct vertices that stand in the rows of both ends along the
+in-edges, u and v left out.  Mini-batches carry edge_label_index, edge_label, cn_ptr [B + 1], cn_index (original ids), cn_count,
+adjacent, scores (a dict of float32 [B]), the node attributes gathered for cn_index, batch_size and call_id; a list longer than
+cn_cap raises RuntimeError unless truncate=True.  The operator is tg_cn_links (include/tchgeo_cn.h, csrc/cn.hip):
+_cabi_cn.cn_links(graph, src, dst, cn_cap=256, tables=None, exclude_ends=True, form=0, wave_max=0, ws=None, out=None,
+status=None) -> dict(count, cn, adjacent, score, status, ws), _cabi_cn.CommonNeighbors.workspace_bytes(m, form=0) -> (bytes,
+form taken), _cabi_cn.cn_tables(ptrs, indices, kinds=("aa", "ra")) -> int32 [len(kinds), n] (uint32 words),
+_cabi_cn.distinct_degree(ptrs, indices) and _cabi_cn.cn_status_check(status, who)."""
 from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor
