@@ -49,6 +49,8 @@ SEALLoader hands out one enclosing subgraph per candidate link with double-radiu
 induced pair, on the pooled scaffold.
 CommonNeighborLoader hands out, per candidate link, the common neighbours of its two ends with their count, the ends' adjacency and
 the classical heuristics' scores (tg_cn_links), as ragged lists on the pooled scaffold; its mini-batches hold no edges.
+SketchData builds the MinHash / HyperLogLog sketches of every vertex's closed balls once (tg_sketch_init, tg_sketch_propagate);
+SubgraphSketchLoader hands out ELPH / BUDDY's structure features per candidate link (tg_sketch_links) on the pooled scaffold.
 """
 from itertools import accumulate
 from typing import Iterator, List, Optional
@@ -3285,4 +3287,158 @@ class CommonNeighborLoader(_PooledLoader):
             else:                                            # the integer sums, scaled by the fixed-point unit
                 s = (out["score"][:m, self._kinds.index(name)].to(torch.float64) * 2.0 ** -32).to(torch.float32)
             sb.scores[name] = rows(s)
+        return sb
+
+
+SKETCH_FIELDS = ("structure", "src_card", "dst_card", "match", "usum", "uzero", "nsum", "nzero")
+
+
+class SketchData:
+    """A graph with the subgraph sketches of its vertices (ELPH / BUDDY: Chamberlain et al., ICLR 2023), built once the way
+    ClusterData holds its partition: the CSC of `data` (pass a symmetric graph for the undirected notion), then
+    tg_sketch_init and `hops` tg_sketch_propagate calls into `sketch`, an int32 tensor [hops + 1, N, W] holding the uint32
+    words of include/tchgeo_sketch.h's row layout: hop l's row of x sketches the closed ball N_l(x)."""
+
+    def __init__(self, data, hops: int = 2, n_perm: int = 128, hll_p: int = 8, seed: int = 0, device="cuda", form: int = 0):
+        from . import _cabi_sketch
+        self.sizes = _cabi_sketch.Sketch(hops, n_perm, hll_p, seed, form)    # refuses before any device work
+        if _is_hetero(data):
+            raise ValueError("SketchData takes a homogeneous graph (typed graphs are out of scope)")
+        N, E = _num_nodes(data), int(data.edge_index.shape[1])
+        if not 1 <= N <= 2 ** 31:
+            raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
+        self.data, self.n_nodes, self.n_edges, self.device = data, N, E, torch.device(device)
+        self.hops, self.n_perm, self.hll_p, self.seed = self.sizes.hops, self.sizes.n_perm, self.sizes.hll_p, self.sizes.seed
+        self.col_ptrs, self.row_indices, self.perm = to_csc(data, self.device)
+        self.graph = _shadowed_view(self.col_ptrs, self.row_indices, E < 2 ** 31)
+        self.sketch, status = _cabi_sketch.sketch_build(self.graph, self.sizes, device=self.device)
+        _cabi_sketch.sketch_status_check(int(status.item()), type(self).__name__)
+
+    def cardinality(self, hop: int) -> Tensor:
+        """HyperLogLog's estimate of |N_hop(x)| for every vertex -> float32 [N]; hop in [0, hops]"""
+        from . import _cabi_sketch
+        if not 0 <= int(hop) <= self.hops:
+            raise ValueError("hop = %r outside [0, %d]" % (hop, self.hops))
+        parts = []
+        for rows in self.sketch[int(hop), :, self.n_perm:].split(1 << 16):                   # [<= 2^16, m_reg / 4] words
+            regs = rows.contiguous().view(torch.uint8).to(torch.int64)                       # [., m_reg] ranks
+            S = torch.bitwise_left_shift(torch.ones_like(regs), 33 - regs).sum(1)
+            parts.append(_cabi_sketch.cardinality(S, (regs == 0).sum(1), self.sizes.m_reg))
+        return torch.cat(parts)
+
+
+class SketchMiniBatch:
+    """Mini-batch j of a SketchSuperBatch as views: `edge_label_index` [2, B], `edge_label` [B] or None, `structure` float32
+    [B, h (h + 2)] (A row-major, then B of u, then B of v), `src_card` / `dst_card` float32 [B, h], the raw integers
+    `match` / `usum` / `uzero` [B, h, h] and `nsum` / `nzero` [B, 2, h], `batch_size` and `call_id`."""
+    __slots__ = ("_sb", "_j")
+
+    def __init__(self, sb, j):
+        self._sb, self._j = sb, j
+
+    batch_size = property(lambda self: self._sb.seed_counts[self._j])
+    call_id = property(lambda self: self._sb.call_id0 + self._j)
+
+    def __getattr__(self, name):
+        sb, j = object.__getattribute__(self, "_sb"), object.__getattribute__(self, "_j")
+        a, width = sb.node_ptr[j], sb.seed_counts[j]
+        if name == "edge_label_index":
+            return sb.edge_label_index[:, a:a + width]
+        if name == "edge_label":
+            return None if sb.edge_label is None else sb.edge_label[a:a + width]
+        if name in SKETCH_FIELDS:
+            return getattr(sb, name)[a:a + width]
+        raise AttributeError(name)
+
+
+class SketchSuperBatch(_Indexable):
+    """The mini-batches of one SubgraphSketchLoader launch as launch-wide tensors over its m links: the fields of
+    SketchMiniBatch with m in place of B, `node_ptr` (python list: where every mini-batch's links begin) and `seed_counts`."""
+    __slots__ = SKETCH_FIELDS + ("edge_label_index", "edge_label", "node_ptr", "seed_counts", "batch_size", "call_id0")
+
+    def _at(self, j):
+        return SketchMiniBatch(self, j)
+
+
+class SubgraphSketchLoader(_PooledLoader):
+    """ELPH / BUDDY's structure features of candidate links as a loader: every link (u, v) of `edge_label_index` [2, L] gets,
+    from the 2h sketch rows of its ends, the estimated numbers of vertices at distance exactly (a, b) from (u, v) and at
+    distance a from one end but beyond h from the other -- at a cost that depends on no degree.  A launch takes `prefetch`
+    consecutive mini-batches on the caller's stream: ONE tg_sketch_links call over its links, then elementwise torch on the
+    [m, h, h] integers (_cabi_sketch.structure_features); nothing is read back but the status word.  The balls are closed,
+    so u and v themselves are counted in the a = 1 or b = 1 bins.  Typed graphs are out of scope."""
+
+    def __init__(self, sketch_data: SketchData, edge_label_index: Tensor, edge_label: Optional[Tensor] = None,
+                 batch_size: int = 1024, shuffle: bool = False, drop_last: bool = False, prefetch: int = 4, seed: int = 0):
+        _at_least_1("batch_size", batch_size)    # everything that can be refused is refused before any device work
+        _at_least_1("prefetch", prefetch)
+        if not isinstance(sketch_data, SketchData):
+            raise ValueError("SubgraphSketchLoader takes a SketchData")
+        sd, eli = sketch_data, edge_label_index
+        if tuple(sd.sketch.shape) != (sd.sizes.hops + 1, sd.n_nodes, sd.sizes.row_words) or \
+                sd.sizes.key() != (sd.hops, sd.n_perm, sd.hll_p, sd.seed):
+            raise ValueError("the sketch was built with other parameters than the SketchData states")
+        if not isinstance(eli, Tensor) or eli.dtype != torch.int64 or eli.dim() != 2 or eli.shape[0] != 2:
+            raise ValueError("edge_label_index must be an int64 tensor of shape [2, L]")
+        L = int(eli.shape[1])
+        if L and (int(eli.min()) < 0 or int(eli.max()) >= sd.n_nodes):
+            raise ValueError("edge_label_index outside [0, %d)" % sd.n_nodes)
+        if edge_label is not None and (not isinstance(edge_label, Tensor) or edge_label.shape != (L,)):
+            raise ValueError("edge_label must be a tensor of shape [%d]" % L)
+        self.sketch_data, self.sizes, self.device = sd, sd.sizes, sd.device
+        self.batch_size, self.prefetch = int(batch_size), int(prefetch)
+        self.shuffle, self.drop_last, self.seed = bool(shuffle), bool(drop_last), int(seed)
+        self.edge_label_index = eli.to(self.device).contiguous()
+        self.edge_label = None if edge_label is None else edge_label.to(self.device)
+        self.input_nodes = torch.arange(L, device=self.device)          # positions of the links: what an epoch is cut from
+        self._init_pool()
+
+    def _new_slab(self):
+        """what a launch of up to `prefetch` mini-batches writes: its links, tg_sketch_links' integers, the status word and
+        its pinned image"""
+        m, h, dev = self.prefetch * self.batch_size, self.sizes.hops, self.device
+        i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+        out = dict(match=torch.empty((m, h, h), **i32), usum=torch.empty((m, h, h), **i64), uzero=torch.empty((m, h, h), **i32),
+                   nsum=torch.empty((m, 2, h), **i64), nzero=torch.empty((m, 2, h), **i32))
+        return dict(links=torch.zeros((2, m), **i64), out=out, status=torch.zeros(1, **i32),
+                    host=torch.empty(1, dtype=torch.int32).pin_memory())
+
+    def _epoch_state(self, epoch: int):
+        order = self.input_nodes
+        if self.shuffle:                         # _Loader's one shuffle rule
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(self.seed * 1000003 + epoch)
+            order = torch.randperm(order.numel(), device=self.device, generator=gen)
+        return order, epoch * len(self)
+
+    def _launch(self, slab, state, j: int, G: int):
+        from . import _cabi_sketch
+        order, batch0 = state
+        B = self.batch_size
+        picked = order[j * B:(j + G) * B]
+        m = picked.numel()
+        slab["picked"], slab["m"] = picked, m
+        slab["links"][:, :m].copy_(self.edge_label_index[:, picked])
+        slab["status"].zero_()
+        part = {k: t[:m] for k, t in slab["out"].items()}                # leading slices of contiguous tensors: contiguous
+        _cabi_sketch.sketch_links(self.sizes, self.sketch_data.sketch, slab["links"][0, :m], slab["links"][1, :m], out=part,
+                                  status=slab["status"])
+        slab["host"].copy_(slab["status"], non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        _cabi_sketch.sketch_status_check(int(slab["host"][0]), type(self).__name__)
+        return batch0 + j, [min(g * B, m) for g in range(G + 1)], None
+
+    def _finish(self, slab, G: int, call_id0: int, node_ptr, _) -> SketchSuperBatch:
+        from . import _cabi_sketch
+        sb = SketchSuperBatch()
+        m, picked = slab["m"], slab["picked"]
+        sb.batch_size, sb.call_id0, sb.node_ptr = self.batch_size, call_id0, node_ptr
+        sb.seed_counts = [b - a for a, b in zip(node_ptr[:-1], node_ptr[1:])]
+        raw = {k: t[:m].clone() for k, t in slab["out"].items()}         # copies: the slabs go back
+        for k, t in raw.items():
+            setattr(sb, k, t)
+        sb.structure, card = _cabi_sketch.structure_features(raw, self.sizes.n_perm, self.sizes.m_reg)
+        sb.src_card, sb.dst_card = card[:, 0], card[:, 1]
+        sb.edge_label_index = slab["links"][:, :m].clone()
+        sb.edge_label = None if self.edge_label is None else self.edge_label[picked]
         return sb

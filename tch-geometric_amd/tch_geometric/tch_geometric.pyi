@@ -95,7 +95,20 @@ cn_cap raises RuntimeError unless truncate=True.  The operator is tg_cn_links (i
 _cabi_cn.cn_links(graph, src, dst, cn_cap=256, tables=None, exclude_ends=True, form=0, wave_max=0, ws=None, out=None,
 status=None) -> dict(count, cn, adjacent, score, status, ws), _cabi_cn.CommonNeighbors.workspace_bytes(m, form=0) -> (bytes,
 form taken), _cabi_cn.cn_tables(ptrs, indices, kinds=("aa", "ra")) -> int32 [len(kinds), n] (uint32 words),
-_cabi_cn.distinct_degree(ptrs, indices) and _cabi_cn.cn_status_check(status, who)."""
+_cabi_cn.distinct_degree(ptrs, indices) and _cabi_cn.cn_status_check(status, who).
+
+Subgraph sketches (ELPH / BUDDY) come from SketchData(data, hops=2, n_perm=128, hll_p=8, seed=0, device="cuda") -- .sketch, an
+int32 tensor [hops + 1, N, n_perm + 2^hll_p / 4] of uint32 words, and .cardinality(hop) -> float32 [N] -- and
+SubgraphSketchLoader(sketch_data, edge_label_index, edge_label=None, batch_size=1024, shuffle=False, drop_last=False, prefetch=4,
+seed=0) (both exported by the package).  Mini-batches carry edge_label_index, edge_label, structure (float32 [B, h (h + 2)]: A
+row-major, then B of u, then B of v), src_card and dst_card [B, h], the raw integers match / usum / uzero [B, h, h] and nsum /
+nzero [B, 2, h], batch_size and call_id.  The operators are tg_sketch_init, tg_sketch_propagate and tg_sketch_links
+(include/tchgeo_sketch.h, csrc/sketch.hip): _cabi_sketch.Sketch(hops=2, n_perm=128, hll_p=8, seed=0, form=0, wave_max=0,
+group_max=0, split_seg=0) with .bytes(n) and .workspace_bytes(n, n_edges) -> (bytes, form taken), _cabi_sketch.sketch_build(view,
+hops, n_perm, hll_p, seed, form) -> (sketch, status), _cabi_sketch.sketch_init(sizes, hop0), _cabi_sketch.sketch_propagate(graph,
+sizes, prev, next, status, ws=None) -> ws, _cabi_sketch.sketch_links(sizes, sketch, src, dst, out=None, status=None) ->
+dict(match, usum, uzero, nsum, nzero, status), _cabi_sketch.cardinality(S, Z, m_reg), _cabi_sketch.structure_features(out,
+n_perm, m_reg) -> (structure, card [L, 2, h]) and _cabi_sketch.sketch_status_check(status, who)."""
 from typing import Dict, List, Optional, Tuple, Union
 
 from torch import Tensor
