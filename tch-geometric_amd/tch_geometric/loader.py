@@ -2960,12 +2960,19 @@ class SEALLoader(_PooledLoader):
 
     The output rows of tg_seal_nodes have pitch `node_cap`, so a launch holds prefetch * batch_size * node_cap words per
     array: that is why the defaults are small.  A link whose subgraph has more than `node_cap` vertices raises a
-    RuntimeError naming node_cap.  chunk_cap: as ShaDowKHopLoader's, grown on overflow.  Typed graphs, times and a per-hop
-    cap on new vertices are out of scope."""
+    RuntimeError naming node_cap.  chunk_cap: as ShaDowKHopLoader's, grown on overflow.
+
+    max_nodes_per_hop (an int or one int per hop, each in [0, 1024]; 0 leaves a hop uncapped) is SEAL-OGB's cap
+    (tg_seal_nodes_capped): a hop that meets more new vertices than its cap keeps a uniform random subset of that size and
+    the next hop expands only what was kept.  The draw is named by (`seed`, the link's position in edge_label_index, the
+    epoch when `resample`), so a link's subgraph does not depend on batch_size, prefetch, shuffling or its slot, and with
+    resample=False it is the same in every epoch.  When every hop is capped the rows have pitch min(node_cap, 2 + the sum
+    of the caps).  Typed graphs and times are out of scope."""
 
     def __init__(self, data, edge_label_index: Tensor, edge_label: Optional[Tensor] = None, num_hops: int = 1,
                  node_cap: int = 1024, z_max: int = 0, batch_size: int = 32, prefetch: int = 4, shuffle: bool = False,
-                 drop_last: bool = False, seed: int = 0, device="cuda", chunk_cap: Optional[int] = None):
+                 drop_last: bool = False, seed: int = 0, device="cuda", chunk_cap: Optional[int] = None,
+                 max_nodes_per_hop=None, resample: bool = True):
         from . import _cabi_seal
         _at_least_1("batch_size", batch_size)    # everything that can be refused is refused before any device work
         _at_least_1("prefetch", prefetch)
@@ -2977,6 +2984,12 @@ class SEALLoader(_PooledLoader):
         if not 1 <= N <= 2 ** 31:
             raise ValueError("the graph must have between 1 and 2^31 nodes, got %d" % N)
         self.sizes = _cabi_seal.Seal(num_hops, node_cap, z_max)
+        self.max_nodes_per_hop, self.resample = None, bool(resample)
+        if max_nodes_per_hop is not None:
+            from . import _cabi_seal_capped
+            self.max_nodes_per_hop = caps = _cabi_seal_capped.hop_caps(max_nodes_per_hop, self.sizes.num_hops)
+            if all(caps):                        # no subgraph passes 2 + the caps: rows of that pitch hold every one
+                self.sizes = _cabi_seal.Seal(num_hops, min(self.sizes.node_cap, 2 + sum(caps)), z_max)
         eli = edge_label_index
         if not isinstance(eli, Tensor) or eli.dtype != torch.int64 or eli.dim() != 2 or eli.shape[0] != 2:
             raise ValueError("edge_label_index must be an int64 tensor of shape [2, L]")
@@ -2988,7 +3001,7 @@ class SEALLoader(_PooledLoader):
         if edge_label is not None and (not isinstance(edge_label, Tensor) or edge_label.shape != (L,)):
             raise ValueError("edge_label must be a tensor of shape [%d]" % L)
         _refuse_reserved(data, SEAL_FIELDS, "a SEALLoader's")
-        self.data, self.num_hops, self.node_cap, self.z_max = data, self.sizes.num_hops, self.sizes.node_cap, self.sizes.z_max
+        self.data, self.num_hops, self.node_cap, self.z_max = data, self.sizes.num_hops, int(node_cap), self.sizes.z_max
         self.batch_size, self.prefetch = int(batch_size), int(prefetch)
         self.shuffle, self.drop_last, self.seed = bool(shuffle), bool(drop_last), int(seed)
         self.chunk_cap = int(chunk_cap) if chunk_cap is not None else 0   # 0: the launch object's default; grows on overflow
@@ -3007,7 +3020,7 @@ class SEALLoader(_PooledLoader):
         slot -> group constant, the (node, group, z) slabs of pitch batch_size * node_cap per mini-batch, the grouped induced
         pair's launch object and the pinned image of what the host reads back"""
         from . import _cabi_seal
-        cap, B, K, dev = self.prefetch, self.batch_size, self.node_cap, self.device
+        cap, B, K, dev = self.prefetch, self.batch_size, self.sizes.node_cap, self.device   # K: the rows' pitch
         i64 = dict(dtype=torch.int64, device=dev)
         slab = dict(links=torch.zeros((2, cap * B), **i64), count=torch.zeros(cap * B, **i64),
                     rows=torch.empty((2, cap * B, K), **i64), status=torch.zeros(1, dtype=torch.int32, device=dev),
@@ -3028,13 +3041,14 @@ class SEALLoader(_PooledLoader):
             gen = torch.Generator(device=self.device)
             gen.manual_seed(self.seed * 1000003 + epoch)
             order = torch.randperm(order.numel(), device=self.device, generator=gen)
-        return order, epoch * len(self)
+        # the third: what a capped launch adds to a link's position for its call id
+        return order, epoch * len(self), epoch * self.input_nodes.numel() if self.resample else 0
 
     def _launch(self, slab, state, j: int, G: int):
         """mini-batches j .. j + G - 1 of the epoch -> (their first number, node counts, edge counts), the counts as python
         lists after the launch's one read-back; pass 2 of the induced pair has not run yet"""
         from . import _cabi_ppr, _cabi_seal
-        order, batch0 = state
+        order, batch0, call_id0 = state
         cap, B = self.prefetch, self.batch_size
         picked = order[j * B:(j + G) * B]
         m = picked.numel()
@@ -3043,8 +3057,14 @@ class SEALLoader(_PooledLoader):
         slab["links"][:, :m].copy_(self.edge_label_index[:, picked])
         slab["count"].zero_()                    # the slots past m of a ragged mini-batch hold nothing
         slab["status"].zero_()
-        _cabi_seal.seal_nodes(self._graph, slab["links"][0, :m], slab["links"][1, :m], self.sizes, out=slab["out"],
-                              status=slab["status"], ws=slab["ws"])
+        if self.max_nodes_per_hop is None:
+            _cabi_seal.seal_nodes(self._graph, slab["links"][0, :m], slab["links"][1, :m], self.sizes, out=slab["out"],
+                                  status=slab["status"], ws=slab["ws"])
+        else:
+            from . import _cabi_seal_capped
+            _cabi_seal_capped.seal_nodes_capped(self._graph, slab["links"][0, :m], slab["links"][1, :m], self.sizes,
+                                                self.max_nodes_per_hop, self.seed, call_ids=(picked + call_id0).contiguous(),
+                                                out=slab["out"], status=slab["status"], ws=slab["ws"])
         count = slab["count"].view(cap, B)
         first = torch.cumsum(count, 1) - count   # where a slot's row starts inside its mini-batch's list
         slab["first"] = first

@@ -76,8 +76,10 @@ bytes_min); for one list transforms.induced_subgraph(nodes, col_ptrs, row_indice
 group_time=None, edge_time=None, time_window=None) -> (rows, cols, edge_index).
 
 Subgraph-based link prediction (SEAL) mini-batches come from SEALLoader(data, edge_label_index, edge_label=None, num_hops=1,
-node_cap=1024, z_max=0, batch_size=32, prefetch=4, shuffle=False, drop_last=False, seed=0, device="cuda", chunk_cap=None)
-(exported by the package): per candidate link (u, v) every vertex within num_hops of u or of v along the in-edges, every
+node_cap=1024, z_max=0, batch_size=32, prefetch=4, shuffle=False, drop_last=False, seed=0, device="cuda", chunk_cap=None,
+max_nodes_per_hop=None, resample=True) (exported by the package; max_nodes_per_hop: SEAL-OGB's cap per hop, tg_seal_nodes_capped,
+_cabi_seal_capped.seal_nodes_capped(graph, src, dst, sizes, max_per_hop, seed, call_ids=None, call_id0=0) -> seal_nodes' dict plus
+cut): per candidate link (u, v) every vertex within num_hops of u or of v along the in-edges, every
 edge between them and a double-radius node label.  Mini-batches carry n_id, batch (the link slot), z, root_n_id
 [batch_size, 2], edge_index / e_id / edge attributes, target_edge (bool per edge: the link itself), edge_label,
 edge_label_index (original ids), node attributes and batch_size; a link with more than node_cap vertices raises
