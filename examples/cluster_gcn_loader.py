@@ -1,17 +1,31 @@
 """Cluster-GCN-style training (PyG's ClusterData / ClusterLoader): the nodes are partitioned once, every step trains on the
-union of a few clusters with every edge of the graph between its nodes.  The partition here is range_partition, a stand-in
-that knows nothing about the edges: with a real partitioner (METIS through pymetis or torch-sparse, or a saved file) pass its
-cluster vector as `part` instead.  A two-layer GCN in plain torch, no torch_geometric."""
+union of a few clusters with every edge of the graph between its nodes.  The partition is range_partition by default, a
+stand-in that knows nothing about the edges; --partition lp runs lp_partition, balanced label propagation on the device, and
+prints the share of the edges the partition cuts before and after.  (METIS through pymetis or torch-sparse, or a saved file,
+can be passed as `part` just the same.)  A two-layer GCN in plain torch, no torch_geometric."""
+import argparse
+
 import torch
 import torch.nn.functional as F
 
 from _data import fake_dataset
-from tch_geometric import ClusterData, ClusterLoader, range_partition
+from tch_geometric import ClusterData, ClusterLoader, lp_partition, random_partition, range_partition
+
+args = argparse.ArgumentParser()
+args.add_argument("--partition", choices=("range", "random", "lp"), default="range")
+args = args.parse_args()
 
 data = fake_dataset()
 data.y = data.x[:, :10].argmax(1)            # labels a model can learn (the synthetic ones are noise)
 N, E = data.num_nodes, data.edge_index.shape[1]
-cluster_data = ClusterData(data, range_partition(N, 32), num_parts=32)
+ei = data.edge_index.cpu()
+cut_share = lambda part: (part[ei[0]] != part[ei[1]]).double().mean().item()
+part = random_partition(N, 32) if args.partition == "random" else range_partition(N, 32)
+if args.partition == "lp":
+    before = cut_share(part)
+    part = lp_partition(data.edge_index, N, 32, init=part).cpu()
+    print("lp_partition: cut share before %.4f, after %.4f" % (before, cut_share(part)))
+cluster_data = ClusterData(data, part, num_parts=32)
 loader = ClusterLoader(cluster_data, batch_size=4, shuffle=True, prefetch=4, seed=0)
 kept = sum(batch.num_edges for batch in loader)
 print("partition: %d clusters of about %d nodes, %d per mini-batch; an epoch keeps %d of %d edges (%.0f%%)"

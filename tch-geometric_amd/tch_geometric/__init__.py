@@ -12,8 +12,8 @@ from .tch_geometric import (PanicException, backend_version, graph_cache_clear, 
 from .loader import (ClusterData, ClusterLoader, CommonNeighborLoader, FullNeighborLoader, GraphSAINTEdgeLoader, GraphSAINTNodeLoader,
                      GraphSAINTRandomWalkLoader, HeteroLinkNeighborLoader, LADIESLoader,  # noqa: F401
                      LinkNeighborLoader, MetaPath2VecLoader, Node2VecLoader, PinSAGELoader, PPRLoader, SEALLoader,
-                     ShaDowKHopLoader, SketchData, SubgraphSketchLoader, TemporalWalkLoader, random_partition,
-                     range_partition)
+                     ShaDowKHopLoader, SketchData, SubgraphSketchLoader, TemporalWalkLoader, lp_partition,
+                     random_partition, range_partition)
 from .last_neighbor import LastNeighborLoader, TemporalEventLoader  # noqa: F401
 from .utils import (TEMPORAL_SAMPLE_DYNAMIC, TEMPORAL_SAMPLE_RELATIVE, TEMPORAL_SAMPLE_STATIC,  # noqa: F401
                     LaborEdgeSampler, RecentEdgeSampler, TemporalEdgeFilter, UniformEdgeSampler, WeightedEdgeSampler)

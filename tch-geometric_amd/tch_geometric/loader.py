@@ -38,7 +38,7 @@ termination (tg_pinsage_hop), the visit counts as edge weights; a launch's front
 grouped dedup.
 ClusterData / ClusterLoader hand out Cluster-GCN mini-batches: the union of `batch_size` clusters of a fixed node partition
 with every edge of the graph between its nodes (tg_cluster_count / tg_cluster_emit: a range table in LDS instead of the
-induced pair's hash table).
+induced pair's hash table).  lp_partition makes the partition: balanced label propagation (tg_lp_propose / tg_lp_commit).
 FullNeighborLoader hands out blocks that hold EVERY in-edge of their destinations (layer-wise inference; PyG's
 num_neighbors=[-1]): tg_ns_full_count / tg_ns_full_emit, one read-back per layer and launch.
 LADIESLoader hands out blocks of layer-wise importance sampling: one budget of drawn nodes per layer and mini-batch with
@@ -52,6 +52,7 @@ the classical heuristics' scores (tg_cn_links), as ragged lists on the pooled sc
 SketchData builds the MinHash / HyperLogLog sketches of every vertex's closed balls once (tg_sketch_init, tg_sketch_propagate);
 SubgraphSketchLoader hands out ELPH / BUDDY's structure features per candidate link (tg_sketch_links) on the pooled scaffold.
 """
+import math
 from itertools import accumulate
 from typing import Iterator, List, Optional
 
@@ -2622,6 +2623,63 @@ def random_partition(num_nodes: int, num_parts: int, seed: int = 0) -> Tensor:
     return torch.randint(0, P, (N,), generator=g, dtype=torch.int64)
 
 
+def lp_partition(edge_index: Tensor, num_nodes: int, num_parts: int, *, slack: float = 1.1, rounds: int = 30, seed: int = 0,
+                 init: Optional[Tensor] = None, symmetric: bool = True, device="cuda", return_stats: bool = False):
+    """part [N] (int64 on `device`): a balanced label-propagation partition, the partitioner ClusterData needs on machines
+    without METIS (the rule: include/tchgeo_lp.h).  Every round each node proposes the part most of its neighbours are in
+    (tg_lp_propose) and the proposals are admitted in order of gain while the target has room below cap = ceil(slack * N /
+    P) (tg_lp_commit).  The edge list is ingested on the device (both directions with symmetric=True), `init` defaults to
+    range_partition, all rounds run on the current stream and ONE read-back at the end fetches the per-round counters and the
+    status word.  A pure function of its arguments.  return_stats=True -> (part, dict(cut=[entries whose ends lay in two
+    parts at the start of round r], moved=[nodes admitted in round r], sizes=int64 [P] on the device, cap=cap))."""
+    from . import _cabi_lp as lp
+    N, P, R = int(num_nodes), int(num_parts), int(rounds)
+    if not isinstance(edge_index, Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
+        raise ValueError("lp_partition: edge_index must be an int64 tensor [2, E]")
+    if not 1 <= N < 2 ** 31:
+        raise ValueError("lp_partition: num_nodes = %d outside [1, 2^31)" % N)
+    if not 1 <= P <= lp.LP_MAX_PARTS:
+        raise ValueError("lp_partition: num_parts = %d outside [1, 2^20]" % P)
+    if not (slack >= 1.0 and slack < float("inf")):
+        raise ValueError("lp_partition: slack = %r must be a finite number >= 1" % (slack,))
+    if R < 0:
+        raise ValueError("lp_partition: rounds = %d is negative" % R)
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("lp_partition: seed = %r outside [0, 2^64)" % (seed,))
+    if init is None:
+        init = range_partition(N, P)
+    if not isinstance(init, Tensor) or init.dim() != 1 or init.numel() != N or init.is_floating_point() or init.dtype == torch.bool:
+        raise ValueError("lp_partition: init must be an integer tensor [num_nodes]")
+    E = int(edge_index.shape[1]) * (2 if symmetric else 1)
+    if E >= 2 ** 32:
+        raise ValueError("lp_partition: %d entries exceed the 2^32 - 1 the kernels take" % E)
+    dev = torch.device(device)
+    cap = max(1, math.ceil(slack * N / P))
+    ei = edge_index.to(dev)
+    row, col = (torch.cat([ei[0], ei[1]]), torch.cat([ei[1], ei[0]])) if symmetric else (ei[0], ei[1])
+    ptrs, indices, _ = _cabi.coo_to_csx(row, col, N, N, False)
+    graph = _shadowed_view(ptrs, indices, E < 2 ** 31)
+    label = init.to(dev, torch.int32).contiguous()
+    size = torch.empty(P, dtype=torch.int64, device=dev)
+    skey = torch.empty(N, dtype=torch.int64, device=dev)
+    state = torch.zeros(2 * R + 1, dtype=torch.int64, device=dev)    # cut [R], moved [R], the status word
+    status = state[2 * R:].view(torch.int32)[:1]
+    ws = lp.lp_workspace(N, P, dev)
+    lp.lp_sizes(label, P, size, status)
+    for r in range(R):
+        lp.lp_propose(graph, label, P, seed, r, skey, state[r:r + 1], status, ws)
+        lp.lp_commit(label, size, P, cap, skey, state[R + r:R + r + 1], status, ws)
+    host = state.cpu()                                               # the one read-back
+    word = int(host[2 * R]) & 0xFFFFFFFF
+    if word & lp.STATUS_LABEL:
+        raise ValueError("lp_partition: init holds part ids outside [0, %d)" % P)
+    lp.lp_status_check(word, "lp_partition")
+    part = label.to(torch.int64)
+    if not return_stats:
+        return part
+    return part, dict(cut=host[:R].tolist(), moved=host[R:2 * R].tolist(), sizes=size, cap=cap)
+
+
 def cluster_epoch_order(num_parts: int, seed: int, epoch: int, shuffle: bool = True) -> Tensor:
     """The order ClusterLoader visits the clusters in during epoch `epoch` (CPU int64 [P]): torch.randperm from a CPU
     generator seeded with (seed * 1000003 + epoch) mod 2^63, or arange without shuffle."""
@@ -2634,7 +2692,8 @@ def cluster_epoch_order(num_parts: int, seed: int, epoch: int, shuffle: bool = T
 
 class ClusterData:
     """A graph renumbered by a node partition (PyG's ClusterData without the partitioner): `part` [N] gives every node's
-    cluster in [0, num_parts) -- from METIS (pymetis, torch-sparse), a saved file, or range_partition / random_partition.
+    cluster in [0, num_parts) -- from lp_partition (balanced label propagation on the device: the partitioner that looks at
+    the edges), METIS (pymetis, torch-sparse), a saved file, or the stand-ins range_partition / random_partition.
     One-off setup on `device` with the plumbing that exists: a stable sort of `part` is `node_perm` (new id -> original id;
     `node_inv` the other way), tg_ind2ptr over the sorted cluster ids is `partptr` (cluster c = new ids [partptr[c],
     partptr[c+1])), the device ingest of the renumbered edge list gives the CSC (`col_ptrs`, `row_indices`) and `perm`
